@@ -9,9 +9,15 @@
 
 A step = zero_grad + forward + loss + backward (+ one flat gradient all-reduce when N>1) of the
 hand-written HIP path on a synthetic meta-batch that is already resident in HBM.  Rank 0 prints ONE
-JSON line; it also carries `roofline` (the dominant kernel, timed live with HIP events on its launch
-stream; `roofline.forward`: the training forward against the MFMA and the HBM roof) and `cpu_baseline`
-(the CPU oracle - a port of the reference arithmetic - on the host's physical cores, plus a 1-thread figure).
+JSON line.  A plain run sets up, warms up, times the K steps and prints that line, nothing more.
+With --full the line also carries `roofline` (the dominant kernel, timed live with HIP events on its
+launch stream; `roofline.forward`: the training forward against the MFMA and the HBM roof),
+`cpu_baseline` (the CPU oracle - a port of the reference arithmetic - on the host's physical cores, plus
+a 1-thread figure), `extras` (other timing legs and, for c3, the other BASELINE configs) and `eps`.
+
+    --dump-outputs DIR: after the timed steps, what the last one computed - the loss and every parameter's
+    gradient - as DIR/loss.npy and DIR/grad.<parameter>.npy (float32; a fixed, seeded sample of each array
+    when all of them together would exceed 64 MB).  The inputs are seeded: the same arguments give the same inputs.
 
     --workload c3 (default, BASELINE configs[2] = the headline metric) | c2 (configs[1]) | c5 (the per-GPU share of configs[4]:
     ANPMRShapeNet3D, Bayes-by-backprop ResNet encoder; eps drawn on the CPU generator by host threads, one step ahead)
@@ -799,7 +805,7 @@ def measure_other_configs(keys, steps, warmup, timeout_s=600):
                                                             "MLHOT_BENCH_SEQ", "MLHOT_BENCH_KERNELS", "MLHOT_BENCH_LAUNCHER", "MLHOT_FORCE_COLLECTIVES")}
     for key in keys:
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", key, "--steps", str(steps), "--warmup", str(warmup),
-               "--no-extras", "--no-cpu-baseline", "--no-configs"] + (["--shipped-cfg"] if key == "c5" else [])
+               "--full", "--no-extras", "--no-cpu-baseline", "--no-configs"] + (["--shipped-cfg"] if key == "c5" else [])
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout_s)
@@ -887,6 +893,28 @@ def timed_region(run, steps, warmup, world, device, sync=None, record=None):
     return elapsed, t_enqueue, out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loss, model):
+    """--dump-outputs: what a caller of the timed step receives after its last run - the loss and every parameter's gradient - as
+    out_dir/loss.npy and out_dir/grad.<parameter name>.npy in float32.  If all of them together exceed DUMP_LIMIT_BYTES, every array
+    is cut to the same fraction of its elements, taken at positions drawn from a generator seeded with 0 (the same positions in
+    every run) and written flat."""
+    import numpy as np
+    torch.cuda.synchronize()
+    arrays = {"loss": loss.detach()}
+    arrays.update({"grad." + n: p.grad.detach() for n, p in model.named_parameters() if p.grad is not None})
+    total = sum(t.numel() for t in arrays.values()) * 4
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.float().cpu()
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, a.numel() * DUMP_LIMIT_BYTES // total)
+            a = a.reshape(-1)[torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values]
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -952,8 +980,12 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline legs, the CPU baseline, the extras "
+                         "(c3: the other BASELINE configs, each in a child process) and the eps draw time")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss and gradients to DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--prof-steps", type=int, default=5)
+    ap.add_argument("--prof-steps", type=int, default=None, help="eager steps of the per-launch roofline leg (default: 5 with --full, else 0)")
     ap.add_argument("--steps-per-graph", type=int, default=5,
                     help="single-GPU vanilla workloads: this many consecutive steps are captured into ONE hipGraph (every step is still "
                          "zero_grad + forward + loss + backward on the resident batch; --steps of them are timed in all).  Between two graph "
@@ -985,6 +1017,8 @@ def main():
                          "default) or the same MT19937 stream continued on the GPU (mlhot_mt19937_normal)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="mlhot_set_option switches for A/B runs, e.g. c12_split=0")
     args = ap.parse_args()
+    if args.prof_steps is None:
+        args.prof_steps = 5 if args.full else 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: become one.  Nothing above touched the GPU (torch.cuda.device_count() does not initialise it on this image)
         have = torch.cuda.device_count()
@@ -1165,6 +1199,8 @@ def main():
     elapsed, t_enqueue, loss = timed_region(run, n_run, args.warmup // spg, world, device, sync=torch.cuda.synchronize,
                                             record=lambda i, k: ev[i][k].record())
     final_loss = loss.item()
+    if args.dump_outputs and rank == 0:                            # before any later leg runs a step of its own
+        dump_outputs(args.dump_outputs, loss, model)
     replay_collectives = [list(e) for e in bucket.issue_log]       # of the timed region's last step (the roofline leg below runs eager steps)
     step_ms = sorted(a.elapsed_time(b) / spg for a, b in ev)       # device time per step (events on the replaying stream, per graph launch / steps per graph)
     if eps is not None and eps._worker is not None:
@@ -1225,7 +1261,7 @@ def main():
                     "all_labels_tflops": {k: round(per_step[k] / (agg[k][1] / args.prof_steps * 1e-3) / 1e12, 1) for k in per_step}}
     # ---- the training forward alone, against both roofs ------------------------------------------------------
     fwd = None
-    if world == 1 and not args.no_graph:
+    if args.full and world == 1 and not args.no_graph:
         try:
             def fwd_only():
                 if eps is not None:
@@ -1242,9 +1278,9 @@ def main():
         roof["forward"] = fwd
     # ---- informational extras (SURVEY §8d "also report fwd-only and +Adam"), rank 0, single-GPU runs only -----------
     extras = None
-    if world == 1 and not args.no_extras and not args.no_graph and w["kind"] == "vanilla":
+    if args.full and world == 1 and not args.no_extras and not args.no_graph and w["kind"] == "vanilla":
         extras = measure_extras(w, device, loss_fn, (cx, qx, cy, qy), max(10, args.steps // 2))
-    if world == 1 and not args.no_extras and not args.no_graph and c5:
+    if args.full and world == 1 and not args.no_extras and not args.no_graph and c5:
         try:
             extras = {"variable_context": measure_variable_nc_3d(w, device, loss_fn, model, eps,
                                                                  lambda a, b_, c_, d_: fwd_bwd(batch=(a, c_, b_, d_)), max(10, args.steps // 2)),
@@ -1262,7 +1298,7 @@ def main():
             extras["shipped_cfg"] = {w["method"]: measure_shipped_cfg(w, device, loss_fn, max(10, args.steps // 2))}
         except Exception as e:  # noqa: BLE001 - extras must never break the bench line
             extras = dict(extras or {}, shipped_cfg={"error": f"{type(e).__name__}: {e}"})
-    if world == 1 and not mdist.force_collectives() and args.workload == "c3" and not args.no_extras and not args.no_configs and not args.no_graph:
+    if args.full and world == 1 and not mdist.force_collectives() and args.workload == "c3" and not args.no_extras and not args.no_configs and not args.no_graph:
         torch.cuda.synchronize()
         extras = dict(extras or {})
         extras["configs"] = measure_other_configs(("c2", "c5"), steps=20, warmup=5)
@@ -1316,7 +1352,10 @@ def main():
             # generator in the reference's draw order, bit-identical samples, the step then costs max(GPU, host draw); "device" = the same
             # MT19937 stream continued on the GPU (uniforms bit-identical, normals within 4 ulp)
             out["config"]["eps_source"] = eps.source
-        if eps is not None and eps.source == "host":
+        if eps is not None and not args.full:
+            if eps.source == "device":
+                eps.release()
+        elif eps is not None and eps.source == "host":
             d0 = time.perf_counter()
             eps.stage()
             from networks.bbb.eps import usable_cores
@@ -1341,7 +1380,7 @@ def main():
             eps.release()
         if extras:
             out["extras"] = extras
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(w)
         else:
             out["cpu_baseline"] = None

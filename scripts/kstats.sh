@@ -4,7 +4,7 @@ REPO=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$REPO/gpurun_out/kstats
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o s -- python3 $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --prof-steps 0 ${1:-} > $OUT/log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o s -- python3 $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --prof-steps 0 ${1:-} > $OUT/log 2>&1
 tail -1 $OUT/log | python3 -c "
 import json,sys
 try:

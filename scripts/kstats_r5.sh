@@ -4,7 +4,7 @@ REPO=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$REPO/gpurun_out/kstats_r5
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o stats -- python3 $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras "$@" > $OUT/run.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o stats -- python3 $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras "$@" > $OUT/run.log 2>&1
 python3 - "$OUT" <<'PY' | tee $REPO/gpurun_out/kstats_r5.txt
 import csv, glob, sys
 path = sorted(glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True))[0]

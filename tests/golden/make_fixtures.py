@@ -532,6 +532,22 @@ def run_ingest_case():
     print("ingest", {k: v.shape for k, v in out.items()})
 
 
+def run_cfg_case():
+    """Every YAML under the reference's cfg/, parsed as its train.py parses it (yaml.safe_load): relative path -> key/value dict,
+    the data test_boundary.py::test_every_reference_yaml_parses feeds to configs.config.Config."""
+    import glob
+    import yaml
+    root = os.path.join(REF, "cfg")
+    out = {}
+    for path in sorted(glob.glob(os.path.join(root, "**", "*.yaml"), recursive=True)):
+        with open(path, "rb") as fh:
+            out[os.path.relpath(path, root)] = yaml.safe_load(fh)
+    with open(os.path.join(OUT, "reference_cfgs.json"), "w") as fh:
+        json.dump(out, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("cfg", len(out))
+
+
 def main():
     assert os.path.isdir(REF), "the reference is only available in the build container"
     install_stubs()
@@ -570,6 +586,8 @@ def main():
         run_conv_embedding_case()
     if not only or "ingest" in only:
         run_ingest_case()
+    if not only or "cfg" in only:
+        run_cfg_case()
 
 
 if __name__ == "__main__":
