@@ -325,6 +325,62 @@ int mlhot_bbb_sample_multi_bwd(const mlhot_bbb_item* items, int n_items, const f
  * fp32 divide).  src: n_img*H*W*C bytes packed channel-last (4-byte aligned for the fast path), dst: n_img*C*H*W floats. */
 int mlhot_ingest_u8_nhwc(const uint8_t* src, float* dst, long n_img, int H, int W, int C, float div, void* stream);
 
+/* ---- device data augmentation fused into the batch ingest (DESIGN.md "Device augmentation") ----
+ * The reference's "data_aug" (config aug_list) runs an imgaug Sequential per image on the host inside get_batch
+ * (dataset/shapenet_1d.py:174-176, dataset/pascal_1d.py:116-118).  Here it runs on the staged bytes, one workgroup per image, with
+ * the divide of mlhot_ingest_u8_nhwc behind it.  Scope: C = 1, 1 <= H, W <= 128, the two single-channel sequences
+ *   shapenet_1d (dataset/shapenet_1d.py:34-72): CropAndPad, Affine, OneOf(Dropout, CoarseDropout)
+ *   pascal_1d   (utils/augment.py:83-122):      CropAndPad, GammaContrast, AverageBlur, Affine, OneOf(Dropout, CoarseDropout)
+ * Every step sits in Sometimes(0.5) and the Sequential has random_order=True; the host (mlhot/augment.py) draws all of it and
+ * hands the kernel one record per image.  The ops, restated from imgaug 0.4 / cv2 (bit-exact to this spec, not to imgaug):
+ *   CROP_PAD  CropAndPad(percent=(0, 0.05), pad_mode=ALL, pad_cval=(0, 255)), keep_size (shapenet_1d.py:50, augment.py:96):
+ *             pad[] = round(U(0, 0.05) * H or W) per side; np.pad on uint8 in `pad_mode` (MLHOT_PAD_*; constant_values and
+ *             linear_ramp's end_values = pad_cval); then cv2.resize INTER_CUBIC back to H x W: A = -0.75, half-pixel centres,
+ *             src = (float)((d + 0.5) * n_src / n_dst - 0.5), coefficients in fp32 rounded (half even) to 1/2048, replicated
+ *             border, sum rounded at 2^22 and saturated.  No pad on any side: no resize.
+ *   GAMMA     GammaContrast((0.5, 2.0)) (augment.py:98): luts[lut] = round(255 * (v / 255) ** g), built on the host in float64.
+ *   BLUR      AverageBlur(k=(1, 3)) (augment.py:102): k in {1, 2, 3}; k x k box mean, anchor k / 2 (k = 2: [x-1, x]),
+ *             BORDER_REFLECT_101, rounded half to even.
+ *   AFFINE    Affine(scale (0.8, 1.2) per axis, translate_percent (-0.1, 0.1) per axis, order [0, 1], cval (0, 255),
+ *             mode ALL) (shapenet_1d.py:52-58, augment.py:104-110) about the centre (W/2 - 0.5, H/2 - 0.5).  The inverse map in
+ *             1/65536 px: src_x = (aff_ax * x + aff_bx) / 2^16, src_y likewise.  order 0: nearest, (X + 2^15) >> 16; order 1:
+ *             cv2's fixed-point bilinear, coordinates (X + 2^10) >> 11 in 1/32 px, weights (32 - f) * (32 - g) * 32 etc. in
+ *             1/32768, sum rounded at 2^15.  aff_mode = MLHOT_BORDER_*: constant (aff_cval), edge = REPLICATE,
+ *             symmetric = REFLECT, reflect = REFLECT_101, wrap = WRAP.
+ *   DROPOUT   Dropout(p=(0.01, 0.1)) (shapenet_1d.py:62, augment.py:114): pixel i -> 0 when hash(i) < drop_thresh (= p * 2^32).
+ *   COARSE_DROPOUT  CoarseDropout(p=(0, 0.05), size_percent=(0.02, 0.25)) (shapenet_1d.py:63-66, augment.py:115-118): a
+ *             coarse_h x coarse_w mask (max(3, round(sp * H or W))), cell c dropped when hash(2^30 + c) < coarse_thresh, upscaled by
+ *             nearest neighbour (cell row = y * coarse_h / H).  per_channel has no effect at C = 1.
+ *   hash(item) = fmix32(key ^ item * 0x9E3779B1), key = fmix32 chained over (seed + 0x9E3779B9, counter, side, image)
+ *   (fmix32 = murmur3's 32-bit finaliser; all arithmetic mod 2^32).
+ * Record: op[0 .. n_steps) = the steps in this image's application order (OneOf already resolved to DROPOUT or COARSE_DROPOUT);
+ * a step runs when bit (1 << op) of `on` is set.  Out-of-range fields are clamped (never read or written out of bounds).
+ * Added within ABI 7 (a pure addition): the binding looks for the symbol and checks mlhot_augment_record_bytes() before its first
+ * call.                                                                                                                     */
+enum { MLHOT_AUG_CROP_PAD = 0, MLHOT_AUG_GAMMA = 1, MLHOT_AUG_BLUR = 2, MLHOT_AUG_AFFINE = 3, MLHOT_AUG_DROPOUT = 4,
+       MLHOT_AUG_COARSE_DROPOUT = 5 };
+/* numpy's ten pad modes (imgaug's pad_mode=ALL) */
+enum { MLHOT_PAD_CONSTANT = 0, MLHOT_PAD_EDGE = 1, MLHOT_PAD_LINEAR_RAMP = 2, MLHOT_PAD_MAXIMUM = 3, MLHOT_PAD_MEAN = 4,
+       MLHOT_PAD_MEDIAN = 5, MLHOT_PAD_MINIMUM = 6, MLHOT_PAD_REFLECT = 7, MLHOT_PAD_SYMMETRIC = 8, MLHOT_PAD_WRAP = 9 };
+/* imgaug Affine's modes = cv2 borders CONSTANT, REPLICATE, REFLECT, REFLECT_101, WRAP */
+enum { MLHOT_BORDER_CONSTANT = 0, MLHOT_BORDER_EDGE = 1, MLHOT_BORDER_SYMMETRIC = 2, MLHOT_BORDER_REFLECT = 3, MLHOT_BORDER_WRAP = 4 };
+typedef struct {
+  int32_t n_steps, op[7], on;
+  int32_t pad[4];                 /* top, right, bottom, left (px) */
+  int32_t pad_mode, pad_cval;
+  int32_t lut;                    /* row of `luts` (GAMMA) */
+  int32_t blur_k;
+  int32_t aff_order, aff_mode, aff_cval, aff_ax, aff_bx, aff_ay, aff_by;
+  uint32_t drop_thresh, coarse_thresh;
+  int32_t coarse_h, coarse_w;
+  uint32_t seed, counter, side, image;    /* hash inputs: stream seed, batch counter, 0 context / 1 target, image of the side */
+} mlhot_aug_record;               /* 128 bytes */
+size_t mlhot_augment_record_bytes(void);   /* sizeof(mlhot_aug_record): binding self-check */
+/* src: n_img * H * W bytes (C = 1); dst: n_img * H * W floats = augmented byte / div; rec: n_img records; luts: n_luts x 256
+ * bytes (may be NULL when n_luts = 0).  All device pointers; rec and luts are read on the device only. */
+int mlhot_augment_ingest_u8(const uint8_t* src, float* dst, long n_img, int H, int W, int C, float div,
+                            const mlhot_aug_record* rec, const uint8_t* luts, int n_luts, void* stream);
+
 /* ---- optimizer: torch.optim.Adam (train.py:52-56) as ONE launch over flat buffers -------------------
  * param / grad / exp_avg / exp_avg_sq: n floats each, laid out alike (e.g. mlhot_np_grads_flat_layout).
  * step >= 1 is the 1-based update count (bias correction); grad_scale multiplies the gradient first

@@ -15,6 +15,7 @@
 #include "np_vanilla.h"
 #include "conv_rt.h"
 #include "ingest.h"
+#include "augment.h"
 #include "bbb_multi.h"
 #include "mt_normal.h"
 #include "nt_xent.h"
@@ -589,6 +590,21 @@ int mlhot_ingest_u8_nhwc(const uint8_t* src, float* dst, long n_img, int H, int 
     return MLHOT_ERR_ARG;
   }
   return ingest::run(src, dst, n_img, H, W, C, div, (hipStream_t)stream);
+}
+
+// ---- batch ingest with the data augmentation of the 1D loaders (csrc/augment.h) -----------------------------------------
+size_t mlhot_augment_record_bytes(void) { return sizeof(mlhot_aug_record); }
+int mlhot_augment_ingest_u8(const uint8_t* src, float* dst, long n_img, int H, int W, int C, float div,
+                            const mlhot_aug_record* rec, const uint8_t* luts, int n_luts, void* stream) {
+  if (n_img < 0 || H <= 0 || W <= 0 || !(div > 0.f) || n_luts < 0 || (n_img > 0 && (!src || !dst || !rec)) || (n_luts > 0 && !luts)) {
+    set_error("augment_ingest_u8: bad argument");
+    return MLHOT_ERR_ARG;
+  }
+  if (C != 1 || H > aug::MAXD || W > aug::MAXD) {
+    set_error("augment_ingest_u8: C = 1 and H, W <= %d only (got C=%d H=%d W=%d)", aug::MAXD, C, H, W);
+    return MLHOT_ERR_UNSUPPORTED;
+  }
+  return aug::run(src, dst, n_img, H, W, div, rec, luts, n_luts, (hipStream_t)stream);
 }
 
 // ---- fused Adam over a flat parameter / gradient buffer ------------------------------------------------

@@ -1,0 +1,158 @@
+"""Device data augmentation ("DA") of the 1D loaders: the host half.
+
+The reference runs an imgaug Sequential per image on the host inside get_batch (dataset/shapenet_1d.py:174-176,
+dataset/pascal_1d.py:116-118).  Here the host only DRAWS: `Sampler` fills one parameter record per image (include/mlhot.h
+mlhot_aug_record) and the per-image gamma LUTs, vectorised with numpy, and the fused ingest kernel (csrc/augment.h) applies them to
+the staged bytes on the device.  The semantics are the spec in DESIGN.md "Device augmentation".
+
+    spec = AugmentSpec.for_task("shapenet_1d")
+    sampler = Sampler(spec, seed=config.seed, rank=rank)
+    table = sampler.batch(n_ctx_images, n_qry_images, H, W)     # one generate() per side, as the reference calls it
+    ingest.stage(xs_u8, xq_u8, ys, yq, augment=table)
+
+The sampler owns a numpy Generator seeded from (seed, rank): it never touches numpy's global generator, whose order of draws
+belongs to the reference's loaders.
+"""
+import numpy as np
+
+CROP_PAD, GAMMA, BLUR, AFFINE, DROPOUT, COARSE_DROPOUT = range(6)
+ONEOF = -1                  # a step whose op is drawn per image: DROPOUT or COARSE_DROPOUT
+N_PAD_MODES = 10            # np.pad: constant edge linear_ramp maximum mean median minimum reflect symmetric wrap
+N_AFFINE_MODES = 5          # constant edge symmetric reflect wrap
+RECORD_INTS = 32            # mlhot_aug_record
+
+# int32 field offsets of mlhot_aug_record
+F_N_STEPS, F_OP, F_ON, F_PAD, F_PAD_MODE, F_PAD_CVAL, F_LUT, F_BLUR_K = 0, 1, 8, 9, 13, 14, 15, 16
+F_AFF_ORDER, F_AFF_MODE, F_AFF_CVAL, F_AFF_AX, F_AFF_BX, F_AFF_AY, F_AFF_BY = 17, 18, 19, 20, 21, 22, 23
+F_DROP_THRESH, F_COARSE_THRESH, F_COARSE_H, F_COARSE_W = 24, 25, 26, 27
+F_SEED, F_COUNTER, F_SIDE, F_IMAGE = 28, 29, 30, 31
+
+
+class AugmentSpec:
+    """The step list of one loader's Sequential (each step in Sometimes(0.5), random_order=True)."""
+
+    SEQUENCES = {
+        "shapenet_1d": (CROP_PAD, AFFINE, ONEOF),                      # dataset/shapenet_1d.py:34-72 AugmenterShapeNet1D
+        "pascal_1d": (CROP_PAD, GAMMA, BLUR, AFFINE, ONEOF),           # utils/augment.py:83-122 PascalAugmenter
+    }
+
+    def __init__(self, task, steps):
+        self.task, self.steps = task, tuple(steps)
+
+    @classmethod
+    def for_task(cls, task):
+        if task not in cls.SEQUENCES:
+            raise NotImplementedError(
+                f"device augmentation covers the single-channel sequences {sorted(cls.SEQUENCES)}; task {task!r} uses the base "
+                "Augmenter (AddToBrightness, and segmentation maps for the distractor), which is not implemented on the device")
+        return cls(task, cls.SEQUENCES[task])
+
+
+class AugTable:
+    """The drawn parameters of one batch: records int32 [n_img, 32] (context images first, then targets) and luts uint8 [n, 256]."""
+
+    def __init__(self, records, luts):
+        self.records, self.luts = records, luts
+
+    @property
+    def n_img(self):
+        return self.records.shape[0]
+
+
+def gamma_luts(g):
+    """GammaContrast's per-image table (utils/augment.py:98), in float64: round(255 * (v / 255) ** g)."""
+    v = np.arange(256, dtype=np.float64) / 255.0
+    return np.clip(np.rint(255.0 * v[None, :] ** np.asarray(g, dtype=np.float64)[:, None]), 0, 255).astype(np.uint8)
+
+
+def affine_fixed(sx, sy, tx, ty, H, W):
+    """The inverse of imgaug's Affine (scale about the centre (W/2 - 0.5, H/2 - 0.5), then translate by tx * W, ty * H) in 1/65536 px:
+    src_x = (ax * x + bx) / 2^16.  Returns int32 arrays ax, bx, ay, by."""
+    cx, cy = W / 2.0 - 0.5, H / 2.0 - 0.5
+    ax = np.rint(65536.0 / sx)
+    bx = np.rint(65536.0 * (cx - (cx + tx * W) / sx))
+    ay = np.rint(65536.0 / sy)
+    by = np.rint(65536.0 * (cy - (cy + ty * H) / sy))
+    return [a.astype(np.int64).astype(np.int32) for a in (ax, bx, ay, by)]
+
+
+def _thresh(p):
+    """Bernoulli(p) as `hash < thresh` over uint32 hashes."""
+    return np.minimum(np.floor(np.asarray(p, dtype=np.float64) * 4294967296.0), 4294967295.0).astype(np.uint32)
+
+
+class Sampler:
+    def __init__(self, spec, seed=0, rank=0):
+        if not isinstance(spec, AugmentSpec):
+            spec = AugmentSpec.for_task(spec)
+        self.spec = spec
+        self.rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([int(seed) & 0xFFFFFFFF, int(rank)])))
+        self.hash_seed = int(np.random.SeedSequence([int(seed) & 0xFFFFFFFF, int(rank), 1]).generate_state(1, np.uint32)[0])
+        self.counter = 0            # batches drawn so far (a hash input of the dropouts)
+
+    def side(self, n, H, W, side, lut_base=0):
+        """One generate() call of the reference: n images of H x W.  -> (records int32 [n, 32], luts uint8 [k, 256])."""
+        rng, steps = self.rng, self.spec.steps
+        ns = len(steps)
+        perm = rng.permutation(ns)                                    # random_order: one order per call
+        on = rng.random((n, ns)) < 0.5                                # Sometimes(0.5) per image and step
+        coarse = rng.random(n) < 0.5                                  # OneOf: the second member (CoarseDropout) for these
+        pad = np.rint(rng.uniform(0.0, 0.05, (n, 4)) * np.array([H, W, H, W], dtype=np.float64)).astype(np.int32)
+        pad_mode = rng.integers(0, N_PAD_MODES, n)
+        pad_cval = rng.integers(0, 256, n)
+        gamma = rng.uniform(0.5, 2.0, n)
+        blur_k = rng.integers(1, 4, n)
+        scale = rng.uniform(0.8, 1.2, (n, 2))
+        trans = rng.uniform(-0.1, 0.1, (n, 2))
+        order = rng.integers(0, 2, n)
+        mode = rng.integers(0, N_AFFINE_MODES, n)
+        aff_cval = rng.integers(0, 256, n)
+        drop_p = rng.uniform(0.01, 0.1, n)
+        coarse_p = rng.uniform(0.0, 0.05, n)
+        size_p = rng.uniform(0.02, 0.25, n)
+
+        rec = np.zeros((n, RECORD_INTS), dtype=np.int32)
+        u = rec.view(np.uint32)
+        codes = np.array(steps, dtype=np.int32)[perm]
+        ops = np.broadcast_to(codes, (n, ns)).copy()
+        ops[ops == ONEOF] = np.broadcast_to(np.where(coarse, COARSE_DROPOUT, DROPOUT)[:, None], (n, ns))[ops == ONEOF]
+        rec[:, F_N_STEPS] = ns
+        rec[:, F_OP:F_OP + ns] = ops
+        rec[:, F_ON] = ((on[:, perm].astype(np.int32)) << ops).sum(axis=1)
+        rec[:, F_PAD:F_PAD + 4] = pad
+        rec[:, F_PAD_MODE], rec[:, F_PAD_CVAL] = pad_mode, pad_cval
+        rec[:, F_BLUR_K] = blur_k
+        rec[:, F_AFF_ORDER], rec[:, F_AFF_MODE], rec[:, F_AFF_CVAL] = order, mode, aff_cval
+        rec[:, F_AFF_AX], rec[:, F_AFF_BX], rec[:, F_AFF_AY], rec[:, F_AFF_BY] = affine_fixed(scale[:, 0], scale[:, 1], trans[:, 0],
+                                                                                              trans[:, 1], H, W)
+        u[:, F_DROP_THRESH], u[:, F_COARSE_THRESH] = _thresh(drop_p), _thresh(coarse_p)
+        rec[:, F_COARSE_H] = np.maximum(3, np.rint(size_p * H)).astype(np.int32)
+        rec[:, F_COARSE_W] = np.maximum(3, np.rint(size_p * W)).astype(np.int32)
+        u[:, F_SEED], u[:, F_COUNTER], u[:, F_SIDE] = self.hash_seed, self.counter & 0xFFFFFFFF, side
+        rec[:, F_IMAGE] = np.arange(n, dtype=np.int32)
+        rec[:, F_LUT] = -1
+        luts = np.zeros((0, 256), dtype=np.uint8)
+        if GAMMA in steps:
+            g_on = (rec[:, F_ON] >> GAMMA) & 1 == 1
+            rec[g_on, F_LUT] = lut_base + np.arange(int(g_on.sum()), dtype=np.int32)
+            luts = gamma_luts(gamma[g_on])
+        return rec, luts
+
+    def batch(self, n_ctx, n_qry, H, W):
+        """Both sides of one meta-batch (context = side 0, targets = side 1), each its own generate() call."""
+        rc, lc = self.side(n_ctx, H, W, 0)
+        rq, lq = self.side(n_qry, H, W, 1, lut_base=lc.shape[0])
+        self.counter += 1
+        return AugTable(np.concatenate([rc, rq]), np.concatenate([lc, lq]))
+
+
+def check_trainer_config(config, data):
+    """The trainer's switch (config.device_augment): None when off, else the Sampler.  Refuses what it cannot do."""
+    if not getattr(config, "device_augment", False) or "data_aug" not in (getattr(config, "aug_list", None) or []):
+        return None
+    spec = AugmentSpec.for_task(getattr(config, "task", None))
+    if getattr(data, "data_aug", False):
+        raise ValueError("config.device_augment: the loader still augments on the host (data.data_aug is True) - the batch would be "
+                         "augmented twice.  Build it with aug=[a for a in config.aug_list if a != 'data_aug'] (INTEGRATION.md)")
+    from .dist import rank as dist_rank
+    return Sampler(spec, seed=int(getattr(config, "seed", 0) or 0), rank=dist_rank())

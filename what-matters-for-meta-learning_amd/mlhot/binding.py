@@ -25,6 +25,9 @@ _f = C.c_void_p  # every device pointer travels as void*
 ABI_VERSION = 7     # include/mlhot.h MLHOT_ABI_VERSION (2: + nt_xent, mt19937_normal, the *_staged entries, trunk / skinny flat gradients; 3: + conv12_fwd / _bwd; 4: + np_vanilla_bwd_loss; 5: + mt19937_advance; 6: + host_f32_to_u8_exact; 7: + loss_plus_fwd / _bwd)
 
 
+AUG_RECORD_BYTES = 128   # include/mlhot.h mlhot_aug_record (checked against mlhot_augment_record_bytes() before the first augment call)
+
+
 class MlhotError(RuntimeError):
     pass
 
@@ -915,6 +918,41 @@ class MlhotLib:
             n_img *= v
         self.c.mlhot_ingest_u8_nhwc.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]
         self._rc(self.c.mlhot_ingest_u8_nhwc(_ptr(src), _ptr(out), n_img, H, W, Cc, float(div), _stream(src)), "mlhot_ingest_u8_nhwc")
+        return out
+
+    def augment_ingest_u8(self, src, records, luts=None, out=None, div=255.0):
+        """ingest_u8_nhwc with the 1D loaders' data augmentation in front (csrc/augment.h, include/mlhot.h mlhot_aug_record):
+        src uint8 [..., H, W, 1] -> fp32 [..., 1, H, W].  records: int32 [n_img, 32] (mlhot.augment.Sampler), luts: uint8
+        [n_luts, 256] or None; both on src's device."""
+        if src.dtype != torch.uint8 or src.dim() < 3:
+            raise MlhotError(f"augment_ingest_u8 expects a uint8 [..., H, W, C] tensor, got {src.dtype} {tuple(src.shape)}")
+        c = self.c
+        if not hasattr(c, "mlhot_augment_ingest_u8"):
+            raise MlhotError(f"augment_ingest_u8: {self.path} lacks mlhot_augment_ingest_u8 - rebuild with mlhot.build.build_product(force=True)")
+        c.mlhot_augment_record_bytes.restype = C.c_size_t
+        if c.mlhot_augment_record_bytes() != AUG_RECORD_BYTES:
+            raise MlhotError("mlhot: ABI struct size mismatch for mlhot_aug_record")
+        *lead, H, W, Cc = src.shape
+        n_img = 1
+        for v in lead:
+            n_img *= v
+        if records.dtype != torch.int32 or records.numel() != n_img * (AUG_RECORD_BYTES // 4) or records.device != src.device:
+            raise MlhotError(f"augment_ingest_u8: records must be int32 [{n_img}, {AUG_RECORD_BYTES // 4}] on {src.device}")
+        n_luts = 0
+        if luts is not None:
+            if luts.dtype != torch.uint8 or luts.dim() != 2 or luts.shape[1] != 256 or luts.device != src.device:
+                raise MlhotError("augment_ingest_u8: luts must be uint8 [n, 256] on the images' device")
+            n_luts = luts.shape[0]
+        _chk(src, out, records, luts)
+        shape = (*lead, Cc, H, W)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=src.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != src.device:
+            raise MlhotError(f"augment_ingest_u8: out must be fp32 {shape} on {src.device}")
+        c.mlhot_augment_ingest_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                              C.c_void_p, C.c_int, C.c_void_p]
+        self._rc(c.mlhot_augment_ingest_u8(_ptr(src), _ptr(out), n_img, H, W, Cc, float(div), _ptr(records),
+                                           _ptr(luts) if n_luts else None, n_luts, _stream(src)), "mlhot_augment_ingest_u8")
         return out
 
     # ---- fused Adam over flat buffers -------------------------------------------------------------

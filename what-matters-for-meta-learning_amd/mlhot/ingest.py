@@ -13,6 +13,9 @@ and `mlhot_ingest_u8_nhwc` does the divide + permute on the device (bit-identica
 
 `take()` writes into the same device tensors for every batch of the same shape, so a captured hipGraph of the step keeps
 reading valid addresses.  There is no CPU fallback: the device must be a ROCm GPU.
+
+`stage(..., augment=table)` (mlhot.augment.Sampler.batch): the batch's augmentation records and gamma LUTs ride in the same pinned
+slot and the same H2D copy, and take() expands it with mlhot_augment_ingest_u8 (csrc/augment.h) instead of mlhot_ingest_u8_nhwc.
 """
 import collections
 import threading
@@ -21,7 +24,7 @@ import numpy as np
 import torch
 
 from . import lib
-from .binding import MlhotError
+from .binding import AUG_RECORD_BYTES, MlhotError
 
 
 def _host(a, dtype):
@@ -39,20 +42,43 @@ def _layout(key):
     return n_img, n_lab, lab_off, lab_off + 4 * (n_lab[0] + n_lab[1])
 
 
+def _aug_layout(key, total):
+    """Behind the labels of an augmented slot: [records int32 [n, 32] | gamma LUTs uint8 [<= n, 256]], n = images of both sides."""
+    n = _n_images(key)
+    rec_off = (total + 15) // 16 * 16
+    lut_off = rec_off + AUG_RECORD_BYTES * n
+    return n, rec_off, lut_off, lut_off + 256 * n
+
+
+def _n_images(key):
+    return int(np.prod(key[0][:-3])) + int(np.prod(key[1][:-3]))
+
+
 class _Slot:
-    """One staging slot: ONE pinned host buffer + its device twin holding a whole batch (images as bytes, labels as fp32),
-    so a batch is one H2D copy."""
+    """One staging slot: ONE pinned host buffer + its device twin holding a whole batch (images as bytes, labels as fp32, and for an
+    augmented batch - key + ("aug",) - its records and LUTs), so a batch is one H2D copy."""
 
     def __init__(self, key, device):
         n_img, n_lab, lab_off, total = _layout(key)
+        lab_end = total
+        self.augmented = len(key) > 4
+        if self.augmented:
+            n_aug, rec_off, lut_off, total = _aug_layout(key, total)
         self.host = torch.empty(max(total, 16), dtype=torch.uint8).pin_memory()
         self.dev = torch.empty(max(total, 16), dtype=torch.uint8, device=device)
         hn = self.host.numpy()
         self.host_np = [hn[:n_img[0]].reshape(key[0]), hn[n_img[0]:n_img[0] + n_img[1]].reshape(key[1]),
                         hn[lab_off:lab_off + 4 * n_lab[0]].view(np.float32).reshape(key[2]),
-                        hn[lab_off + 4 * n_lab[0]:total].view(np.float32).reshape(key[3])]
+                        hn[lab_off + 4 * n_lab[0]:lab_end].view(np.float32).reshape(key[3])]
         self.dev_img = self.dev[:n_img[0] + n_img[1]]
-        self.dev_lab = self.dev[lab_off:total].view(torch.float32)
+        self.dev_lab = self.dev[lab_off:lab_end].view(torch.float32)
+        self.n_bytes = None                    # bytes to copy: None = the whole buffer
+        if self.augmented:
+            self.aug_rec_np = hn[rec_off:lut_off].view(np.int32).reshape(n_aug, AUG_RECORD_BYTES // 4)
+            self.aug_lut_np = hn[lut_off:total].reshape(n_aug, 256)
+            self.dev_rec = self.dev[rec_off:lut_off].view(torch.int32)
+            self.dev_lut = self.dev[lut_off:total].view(n_aug, 256)
+            self.lut_off, self.n_luts = lut_off, 0
         self.copied = torch.cuda.Event()       # H2D of this slot finished (host buffer reusable, device buffer readable)
         self.consumed = torch.cuda.Event()     # the kernels that read this slot's device buffer finished
         self.busy = False
@@ -100,25 +126,49 @@ class BatchIngest:
         slot.copied.synchronize()               # the previous H2D out of this pinned buffer is done (no-op when fresh)
         return slot
 
-    def stage(self, xs_u8, xq_u8, ys, yq):
-        """Queue one host batch: images uint8 [T,N,H,W,C] (channel-last), labels fp32 [T,N,L].  Returns a ticket."""
+    def stage(self, xs_u8, xq_u8, ys, yq, augment=None):
+        """Queue one host batch: images uint8 [T,N,H,W,C] (channel-last), labels fp32 [T,N,L].  Returns a ticket.  `augment`: an
+        mlhot.augment.AugTable for the context images then the targets (C = 1), or None."""
         src = [_host(xs_u8, torch.uint8), _host(xq_u8, torch.uint8), _host(ys, torch.float32), _host(yq, torch.float32)]
         if src[0].dim() != 5 or src[1].dim() != 5:
             raise MlhotError("BatchIngest: images must be [T, N, H, W, C]")
         key = tuple(tuple(t.shape) for t in src)
-        slot = self._free_slot(key)
+        slot = self._free_slot(self._slot_key(key, augment))
         for h, t in zip(slot.host_np, src):
             np.copyto(h, t.numpy())             # one thread on purpose: torch's copy_ wakes the whole OpenMP pool, whose
                                                 # spinning workers then starve the HIP runtime's helper threads
+        if augment is not None:
+            self._put_augment(slot, augment)
         return self._ship(key, slot)
 
-    def stage_filled(self, key, fill):
+    @staticmethod
+    def _slot_key(key, augment):
+        if augment is None:
+            return key
+        if key[0][-1] != 1 or key[1][-1] != 1:
+            raise MlhotError(f"BatchIngest: device augmentation needs single-channel images, got {key[0]} / {key[1]}")
+        if augment.n_img != _n_images(key):
+            raise MlhotError(f"BatchIngest: the augmentation table holds {augment.n_img} records for {_n_images(key)} images")
+        return key + ("aug",)
+
+    @staticmethod
+    def _put_augment(slot, augment):
+        np.copyto(slot.aug_rec_np, augment.records)
+        k = augment.luts.shape[0]
+        if k:
+            np.copyto(slot.aug_lut_np[:k], augment.luts)
+        slot.n_luts = k
+        slot.n_bytes = slot.lut_off + 256 * k   # the copy stops behind the LUTs in use
+
+    def stage_filled(self, key, fill, augment=None):
         """Queue a batch whose bytes the CALLER writes into the pinned staging buffers: `fill(host_np)` gets the slot's four numpy views
         ([ctx images u8 | qry images u8 | ctx labels f32 | qry labels f32], shaped like `key`) and returns True to ship the batch or
-        False to give the slot back (nothing is queued; returns None)."""
-        slot = self._free_slot(key)
+        False to give the slot back (nothing is queued; returns None).  `augment` as in stage()."""
+        slot = self._free_slot(self._slot_key(key, augment))
         try:
             ok = fill(slot.host_np)
+            if ok and augment is not None:
+                self._put_augment(slot, augment)
         except BaseException:
             slot.busy = False
             raise
@@ -130,7 +180,10 @@ class BatchIngest:
     def _ship(self, key, slot):
         with torch.cuda.stream(self.copy_stream):
             self.copy_stream.wait_event(slot.consumed)      # do not overwrite bytes an ingest kernel still reads
-            slot.dev.copy_(slot.host, non_blocking=True)
+            if slot.n_bytes is None:
+                slot.dev.copy_(slot.host, non_blocking=True)
+            else:
+                slot.dev[:slot.n_bytes].copy_(slot.host[:slot.n_bytes], non_blocking=True)
             slot.copied.record(self.copy_stream)
         with self._lock:
             self._queue.append((key, slot))
@@ -167,7 +220,9 @@ class BatchIngest:
             out = self._out[key] = _Out(key, self.device)
         L = lib()
         with torch.cuda.device(self.device):
-            if out.same_geometry:               # both image sets are one packed run of (H, W, C) images
+            if slot.augmented:
+                self._augment_into(L, key, slot, out)
+            elif out.same_geometry:             # both image sets are one packed run of (H, W, C) images
                 _, _, H, W, Cc = key[0]
                 L.ingest_u8_nhwc(slot.dev_img.view(-1, H, W, Cc), out=out.img.view(-1, Cc, H, W), div=self.div)
             else:
@@ -178,6 +233,16 @@ class BatchIngest:
         slot.consumed.record(cur)
         slot.busy = False
         return out.tensors
+
+    def _augment_into(self, L, key, slot, out):
+        luts = slot.dev_lut[:slot.n_luts] if slot.n_luts else None
+        if out.same_geometry:
+            _, _, H, W, Cc = key[0]
+            L.augment_ingest_u8(slot.dev_img.view(-1, H, W, Cc), slot.dev_rec, luts, out=out.img.view(-1, Cc, H, W), div=self.div)
+        else:
+            n0, r0 = out.n_img[0], int(np.prod(key[0][:-3]))
+            L.augment_ingest_u8(slot.dev_img[:n0].view(key[0]), slot.dev_rec[:r0 * 32], luts, out=out.tensors[0], div=self.div)
+            L.augment_ingest_u8(slot.dev_img[n0:].view(key[1]), slot.dev_rec[r0 * 32:], luts, out=out.tensors[1], div=self.div)
 
 
 class ExactU8Feed:
@@ -200,8 +265,10 @@ class ExactU8Feed:
         self.ok, self.refused_in_a_row = True, 0
         self.shipped, self.refused = 0, 0
 
-    def stage(self, host_batch):
-        if not self.ok:
+    def stage(self, host_batch, augment=None):
+        """`augment`: an mlhot.augment.AugTable for the batch's images (single-channel), or None; an augmented batch is always checked
+        (its caller has no other route for it)."""
+        if not self.ok and augment is None:
             return None
         xs, xq, ys, yq = host_batch
         for t in (xs, xq, ys, yq):
@@ -222,7 +289,7 @@ class ExactU8Feed:
             np.copyto(host_np[3], yq.numpy())
             return True
 
-        slot = self.ing.stage_filled(key, fill)
+        slot = self.ing.stage_filled(key, fill, augment=augment)
         if slot is None:
             return self._refuse()
         self.refused_in_a_row = 0

@@ -102,3 +102,64 @@ class SyntheticData:
         n_ctx = int(rng.randint(3, shot + 1)) if source == "train" else shot
         self._step += 1
         return get_batch_u8(self.task, tasks_per_batch, n_ctx, shot, seed=int(rng.randint(0, 2 ** 31 - 1)))
+
+
+def shape_images(n, H=128, W=128, seed=0):
+    """uint8 [n, H, W] images with visible structure for the augmentation to move: a horizontal gradient background and three
+    filled ellipses / rectangles of random size, place and grey level per image (no noise)."""
+    import numpy as np
+    rng = np.random.RandomState(seed)
+    y, x = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    img = np.broadcast_to(x[None] / max(W - 1, 1) * rng.uniform(20, 80, (n, 1, 1)), (n, H, W)).copy()
+    for _ in range(3):
+        cy, cx = rng.uniform(0.2, 0.8, (2, n, 1, 1)) * np.array([H, W]).reshape(2, 1, 1, 1)
+        ry, rx = rng.uniform(0.08, 0.3, (2, n, 1, 1)) * np.array([H, W]).reshape(2, 1, 1, 1)
+        level = rng.uniform(90, 255, (n, 1, 1))
+        ell = ((y[None] - cy) / ry) ** 2 + ((x[None] - cx) / rx) ** 2 <= 1.0
+        box = (np.abs(y[None] - cy) <= ry) & (np.abs(x[None] - cx) <= rx)
+        img = np.where(np.where(rng.rand(n, 1, 1) < 0.5, ell, box), level, img)
+    return np.rint(img).astype(np.uint8)
+
+
+class SyntheticShapesF32:
+    """A 1D-task loader (shapenet_1d / pascal_1d: one channel) over a fixed pool of structured images (`shape_images`), with the
+    reference's `get_batch` contract (fp32 [T, N, 1, H, W] = bytes / 255, the labels of `get_batch`); its fp32 batches take the
+    trainer's host-batch route (mlhot.ingest.ExactU8Feed).  It does not augment itself (`data_aug = False`): pair it with config.device_augment."""
+
+    data_aug = False
+
+    def __init__(self, task="shapenet_1d", seed=42, pool=256, H=128, W=128):
+        import numpy as np
+        self.task, self.test_counter = task, 0
+        self.pool = shape_images(pool, H, W, seed=seed)
+        self.rng = np.random.RandomState(seed)
+        self.val_rng, self.test_rng = np.random.RandomState(seed + 1), np.random.RandomState(seed + 2)
+
+    def gen_bg(self, config, data="all"):
+        pass
+
+    def _draw_u8(self, source, tasks_per_batch, shot):
+        import numpy as np
+        rng = {"train": self.rng, "validation": self.val_rng, "test": self.test_rng}[source]
+        n_ctx = int(rng.randint(3, shot + 1)) if source == "train" else shot
+        idx = rng.randint(0, self.pool.shape[0], (tasks_per_batch, n_ctx + shot))
+        imgs = self.pool[idx][..., None]                                       # [T, Nc + Nq, H, W, 1]
+        g = torch.Generator().manual_seed(int(rng.randint(0, 2 ** 31 - 1)))
+        if self.task == "shapenet_1d":              # [cos a, sin a, a], a ~ U[0, 2 pi), as get_batch's labels
+            a = torch.rand(tasks_per_batch, n_ctx + shot, 1, generator=g) * 2 * math.pi
+            y = torch.cat([torch.cos(a), torch.sin(a), a], dim=-1)
+        else:
+            y = torch.rand(tasks_per_batch, n_ctx + shot, 1, generator=g)
+        return (np.ascontiguousarray(imgs[:, :n_ctx]), np.ascontiguousarray(imgs[:, n_ctx:]), y[:, :n_ctx].contiguous(),
+                y[:, n_ctx:].contiguous())
+
+    def get_batch(self, source, tasks_per_batch, shot):
+        xs, xq, ys, yq = self._draw_u8(source, tasks_per_batch, shot)
+        return host_convert(xs), host_convert(xq), ys, yq
+
+
+class SyntheticShapes(SyntheticShapesF32):
+    """`SyntheticShapesF32` with `get_batch_u8`: the trainer reads it through mlhot.ingest.BatchIngest."""
+
+    def get_batch_u8(self, source, tasks_per_batch, shot):
+        return self._draw_u8(source, tasks_per_batch, shot)

@@ -55,10 +55,13 @@ class _HostPrefetch:
     pass) and the batch then crosses PCIe as 7.9 instead of 31.5 MB, expanded by the ingest kernel to the same fp32 bits.  A batch that
     holds anything else takes the fp32 route below, unchanged; the loader's contract is untouched either way."""
 
-    def __init__(self, device, u8=True, background=True):
+    def __init__(self, device, u8=True, background=True, augment=None):
         self.device = torch.device(device)
         self.stream = torch.cuda.Stream(self.device)
         self.u8 = None
+        self.augment = augment          # config.device_augment: an mlhot.augment.Sampler drawing on the worker, beside the byte conversion
+        if augment is not None and not u8:
+            raise ValueError("config.device_augment augments the staged bytes: it needs the byte route (config.host_u8 = True)")
         self.last_fixed = False         # did the last take() hand out the byte route's fixed per-shape device tensors?
         if u8:
             from mlhot.ingest import ExactU8Feed
@@ -73,8 +76,10 @@ class _HostPrefetch:
             from concurrent.futures import ThreadPoolExecutor
             self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="mlhot-host-batch")
 
-    def _stage_now(self, host_batch):
+    def _stage_now(self, host_batch, augment=False):
         with torch.cuda.device(self.device):
+            if augment and self.augment is not None:
+                return ("u8", self._stage_augmented(host_batch))
             if self.u8 is not None:
                 ticket = self.u8.stage(host_batch)
                 if ticket is not None:
@@ -85,10 +90,22 @@ class _HostPrefetch:
                 ev.record(self.stream)
             return ("f32", dev, ev)
 
-    def stage(self, host_batch):
+    def _stage_augmented(self, host_batch):
+        xs, xq = host_batch[0], host_batch[1]
+        if xs.dim() != 5 or xq.dim() != 5 or xs.shape[2] != 1 or xq.shape[2] != 1:
+            raise ValueError(f"config.device_augment: single-channel [T, N, 1, H, W] images only, got {tuple(xs.shape)} / {tuple(xq.shape)}")
+        (T, Nc, _, H, W), Nq = xs.shape, xq.shape[1]
+        table = self.augment.batch(T * Nc, T * Nq, H, W)
+        ticket = self.u8.stage(host_batch, augment=table)
+        if ticket is None:
+            raise ValueError("config.device_augment: a training batch is not exact bytes (every image element k / 255 for a byte k), so "
+                             "it cannot take the byte route the augmentation runs on; the loader must hand out un-normalised byte images")
+        return ticket
+
+    def stage(self, host_batch, augment=False):
         if self._pool is not None:
-            return ("later", self._pool.submit(self._stage_now, host_batch))
-        return self._stage_now(host_batch)
+            return ("later", self._pool.submit(self._stage_now, host_batch, augment))
+        return self._stage_now(host_batch, augment)
 
     def take(self, ticket):
         if ticket[0] == "later":
@@ -106,6 +123,10 @@ class _HostPrefetch:
 
 class ModelTrainer(BaseTrainer):
     def __init__(self, model, loss, optimizer, config, data):
+        # config.device_augment + "data_aug" in config.aug_list: the loader's image augmentation on the device (mlhot/augment.py);
+        # refused before anything else is set up when the task has no device sequence or the loader still augments itself
+        from mlhot.augment import check_trainer_config
+        self._augment = check_trainer_config(config, data)
         super().__init__(model=model, loss=loss, optimizer=optimizer, config=config)
         self.data = data
         # side stream: the RCCL kernels never sit in the compute queue; early bucket: models that know which gradients are complete
@@ -152,7 +173,10 @@ class ModelTrainer(BaseTrainer):
             self.ingest = BatchIngest(config.device)
         elif cuda and getattr(config, "host_prefetch", True):
             self._host_prefetch = _HostPrefetch(config.device, u8=bool(getattr(config, "host_u8", True)),
-                                                background=bool(getattr(config, "host_copy_thread", True)))
+                                                background=bool(getattr(config, "host_copy_thread", True)), augment=self._augment)
+        if self._augment is not None and self.ingest is None and self._host_prefetch is None:
+            raise ValueError("config.device_augment runs inside the device batch ingest: it needs a ROCm device and either a loader with "
+                             "get_batch_u8 (config.ingest_u8) or the host-batch byte route (config.host_prefetch, config.host_u8)")
 
     def _announce(self):
         """Once, at the start of train(): what the constructor promoted (nothing here is silent)."""
@@ -260,15 +284,21 @@ class ModelTrainer(BaseTrainer):
                 return tuple(t.to(dev) for t in draw(source))
             if source != "train":
                 return hp.take(hp.stage(draw(source)))
-            ticket = self._staged_q.popleft() if self._staged_q else hp.stage(draw("train"))
+            ticket = self._staged_q.popleft() if self._staged_q else hp.stage(draw("train"), augment=True)
             self._stage_later = int(self._prefetch)     # the next batches' (host-blocking) copies go out BEHIND this step's launch: _stage_next()
             batch = hp.take(ticket)
             self._fixed_batch = hp.last_fixed           # the byte route delivers every batch of a shape in the same device tensors
             return batch
 
         def stage(src):
-            return self.ingest.stage(*self.data.get_batch_u8(source=src, tasks_per_batch=self.config.tasks_per_batch,
-                                                             shot=self.config.max_ctx_num))
+            xs, xq, ys, yq = self.data.get_batch_u8(source=src, tasks_per_batch=self.config.tasks_per_batch, shot=self.config.max_ctx_num)
+            table = None
+            if src == "train" and self._augment is not None:          # the reference augments training batches only (shapenet_1d.py:174)
+                (T, Nc, H, W, Cc), Nq = xs.shape, xq.shape[1]
+                if Cc != 1 or xq.shape[-1] != 1:
+                    raise ValueError(f"config.device_augment: single-channel images only, got {tuple(xs.shape)}")
+                table = self._augment.batch(T * Nc, T * Nq, H, W)
+            return self.ingest.stage(xs, xq, ys, yq, augment=table)
         if source != "train":
             return self.ingest.take(stage(source))
         ticket, self._staged = (self._staged or stage("train")), None
@@ -286,7 +316,7 @@ class ModelTrainer(BaseTrainer):
                 ahead = 1       # Bayes-by-backprop models: batch k+2 would be drawn in front of step k+1's eps - one ahead keeps the reference's order on a shared generator
             while len(self._staged_q) < ahead:
                 self._staged_q.append(self._host_prefetch.stage(self.data.get_batch(source="train", tasks_per_batch=self.config.tasks_per_batch,
-                                                                                    shot=self.config.max_ctx_num)))
+                                                                                    shot=self.config.max_ctx_num), augment=True))
 
     def _seed(self, loss):
         """d loss / d loss = 1, allocated once: autograd's implicit seed is a fill kernel per iteration."""
