@@ -1,5 +1,5 @@
 """Where a promoted ModelTrainer iteration's wall time goes with VARIABLE context sizes (one hipGraph per size), c3's model:
-per-iteration wall clock and the host time inside _batch / graph replay / _stage_next / loss.item().  usage: python scripts/dev/trainer_iter_probe.py [fixed]"""
+per-iteration wall clock and the host time inside _batch / graph replay / _feed.stage_ahead / loss.item().  usage: python scripts/dev/trainer_iter_probe.py [fixed]"""
 import os, sys, time, types, tempfile
 import numpy as np
 import torch
@@ -58,7 +58,7 @@ with tempfile.TemporaryDirectory() as tmp:
                 acc[name] = acc.get(name, 0.0) + time.perf_counter() - t0
         return w
     tr._batch = timed("_batch", tr._batch)
-    tr._stage_next = timed("_stage_next", tr._stage_next)
+    tr._feed.stage_ahead = timed("_feed.stage_ahead", tr._feed.stage_ahead)
     tr._flush_loss = timed("_flush_loss (event wait + log)", tr._flush_loss)
     if tr._host_prefetch is not None:
         tr._host_prefetch.take = timed("prefetch.take (worker's future + stream wait)", tr._host_prefetch.take)

@@ -1754,7 +1754,7 @@ def test_trainer_trajectory_vs_oracle(gpulib, tmp_path, monkeypatch, optimizer, 
     tr = seen["trainer"]
     if optimizer == "torch_adam" and not unpromoted:      # the reference's sequence took the fast path by itself
         assert type(tr.optimizer).__name__ == "FlatAdam" and tr.optimizer.capturable and tr._graph_default and tr._host_prefetch is not None
-        assert [type(v).__name__ for v in tr._graphs.values()] == ["tuple"] and int(tr.optimizer.step_dev.item()) == 4
+        assert [isinstance(v, tuple) for v in tr._graphs.values()] == [True] and int(tr.optimizer.step_dev.item()) == 4
         sd = tr.optimizer.state_dict()                    # ... and its optimizer state reads back in torch.optim.Adam's layout
         ref = torch.optim.Adam(model.parameters(), lr=1e-3)
         ref.load_state_dict(sd)
@@ -1814,7 +1814,7 @@ def test_trainer_trajectory_vs_oracle_resnet_family(gpulib, tmp_path, monkeypatc
         tr = seen["trainer"]
         if promoted:        # the reference's sequence took the fast path by itself
             assert type(tr.optimizer).__name__ == "FlatAdam" and tr.optimizer.capturable and tr._graph_default
-            assert [type(v).__name__ for v in tr._graphs.values()] == ["tuple"] and int(tr.optimizer.step_dev.item()) == 4
+            assert [isinstance(v, tuple) for v in tr._graphs.values()] == [True] and int(tr.optimizer.step_dev.item()) == 4
             assert tr.optimizer.active < tr.optimizer.flat.numel()                      # resnet.fc.* parked behind the update
             assert all(p.untyped_storage().data_ptr() == tr.optimizer.flat.untyped_storage().data_ptr() for p in model.parameters())
             assert (tr._eps is not None and bool(tr._eps)) == mr
@@ -1903,11 +1903,12 @@ def test_batch_ingest_pipeline_matches_host_conversion(gpulib):
         BatchIngest("cpu")
 
 
-def test_host_batches_two_ahead_on_the_worker_thread_arrive_in_order_and_intact(gpulib):
-    """trainer._HostPrefetch as the trainer drives it since round 6: TWO batches staged ahead on the worker thread while the owner takes
-    the oldest (BatchIngest's slot choice and queue under a lock, three slots per shape).  300 batches of two alternating shapes, byte
-    images (the byte route) with every 7th batch off the byte grid (the fp32 route), each checked bit for bit against the host tensors
-    after the NEXT two have been put on their way."""
+@pytest.mark.parametrize("depth", [2, 4])
+def test_host_batches_two_ahead_on_the_worker_thread_arrive_in_order_and_intact(gpulib, depth):
+    """trainer._HostPrefetch as the trainer drives it since round 6: `depth` batches (config.host_prefetch_depth: the default 2, and 4)
+    staged ahead on the worker thread while the owner takes the oldest (BatchIngest's slot choice and queue under a lock, depth + 1
+    slots per shape).  300 batches of two alternating shapes, byte images (the byte route) with every 7th batch off the byte grid (the
+    fp32 route), each checked bit for bit against the host tensors after the NEXT `depth` have been put on their way."""
     import collections
     from mlhot import synth
     from trainer.model_trainer import _HostPrefetch
@@ -1921,15 +1922,15 @@ def test_host_batches_two_ahead_on_the_worker_thread_arrive_in_order_and_intact(
             xs.view(-1)[i] = 0.5001
         return xs, xq, torch.full((2, nc, 3), float(i)), torch.full((2, 5, 3), float(-i))
 
-    hp = _HostPrefetch(DEV)
+    hp = _HostPrefetch(DEV, depth=depth)
     try:
         q = collections.deque()
         n, routes = 300, collections.Counter()
-        for i in range(n + 2):
+        for i in range(n + depth):
             if i < n:
                 hb = host_batch(i)
                 q.append((hb, hp.stage(hb)))
-            if len(q) > 2 or i >= n:
+            if len(q) > depth or i >= n:
                 if not q:
                     break
                 hb, ticket = q.popleft()
@@ -1940,7 +1941,7 @@ def test_host_batches_two_ahead_on_the_worker_thread_arrive_in_order_and_intact(
                 for g, h in zip(got, hb):
                     assert g.shape == h.shape and torch.equal(g.cpu(), h)
         assert not q and routes["u8"] + routes["fp32"] == n and routes["fp32"] == len([i for i in range(n) if i % 7 == 3])
-        assert all(len(ring) <= 3 for ring in hp.u8.ing._slots.values())
+        assert all(len(ring) <= depth + 1 for ring in hp.u8.ing._slots.values())
     finally:
         hp._pool.shutdown(wait=True)
 
@@ -2136,8 +2137,8 @@ def test_graph_replayed_training_equals_eager_training(gpulib, tmp_path, monkeyp
         losses.append(seen)
         finals.append({k: v.clone() for k, v in model.state_dict().items()})
         if graph:
-            kinds = [type(v).__name__ for v in tr._graphs.values()]
-            assert "tuple" in kinds                     # context sizes 3..5 over 12 iterations: at least one shape was captured
+            kinds = [isinstance(v, tuple) for v in tr._graphs.values()]
+            assert True in kinds                        # context sizes 3..5 over 12 iterations: at least one shape was captured
         assert int(opt.step_dev.item()) == 12
         assert os.path.exists(tmp_path / f"g{int(graph)}" / "models" / "model_end_12.pt")
     assert losses[0] == losses[1]
@@ -2182,6 +2183,43 @@ def test_lagged_loss_log_reports_every_iteration_one_late(gpulib, tmp_path, monk
     assert ModelTrainer._lagged(types.SimpleNamespace(config=types.SimpleNamespace())) is True       # a config that does not say: late
     for k in finals[0]:
         assert torch.equal(finals[0][k], finals[1][k]), k
+
+
+def test_lagged_loss_log_does_not_depend_on_the_callers_iteration_numbers(gpulib, tmp_path, monkeypatch):
+    """A caller that drives `_train_iter` itself with a stride of two (it = 2, 4, 6, 8): the late log takes its two pinned buffers in
+    turn by its own count of calls, so every iteration is reported with ITS loss - the same (iteration, value) pairs as the read
+    behind every step on the same draws, the last one through the trainer's flush.  (Indexed by the parity of `it`, all four calls
+    shared one buffer and iteration 2 was reported with iteration 4's value.)"""
+    import types
+    from mlhot.optim import FlatAdam
+    from mlhot.synth import SyntheticData
+    from networks.ANPShapeNet1D import ANPShapeNet1D
+    from trainer.losses import LossFunc
+    from trainer.model_trainer import ModelTrainer
+    monkeypatch.chdir(tmp_path)
+    reports = []
+    for lag in (False, True):
+        cfg = types.SimpleNamespace(device=torch.device(DEV), seed=2578, img_size=[128, 128, 1], tasks_per_batch=2, input_dim=3,
+                                    output_dim=2, agg_mode="attention", img_agg="", dim_w=64, n_hidden_units_r=[100, 100], dim_r=64,
+                                    dim_z=64, task="shapenet_1d", iterations=100, val_freq=1000, val_iters=1, bg_gen_freq=1000, gen_bg=False,
+                                    max_ctx_num=5, beta=0, contrastive=False, graph_steps=True, log_every=1, lagged_loss_log=lag,
+                                    save_path=str(tmp_path / f"s{int(lag)}"), logger=None)
+        model = ANPShapeNet1D(cfg).to(cfg.device)
+        tr = ModelTrainer(model=model, loss=LossFunc("mse", "shapenet_1d"), optimizer=FlatAdam(model, lr=1e-3, ctx_num=5, test_num=5, capturable=True),
+                          config=cfg, data=SyntheticData())
+        seen = []
+        orig_report = tr._report
+        tr._report = lambda it, value, _o=orig_report, _s=seen: (_s.append((it, value)), _o(it, value))[1]
+        try:
+            for it in (2, 4, 6, 8):
+                tr._train_iter(it)
+            tr._flush_loss()
+        finally:
+            tr.close()
+        reports.append(seen)
+    print(f"[stride-2 late log] read behind the step {reports[0]}, one call late {reports[1]}")
+    assert [it for it, _ in reports[0]] == [2, 4, 6, 8] and len({v for _, v in reports[0]}) == 4
+    assert reports[1] == reports[0]
 
 
 def test_late_loss_read_stops_on_a_non_finite_loss_with_the_same_log_exit_code_and_files(gpulib, tmp_path, monkeypatch):

@@ -259,7 +259,7 @@ class ExactU8Feed:
     """
 
     def __init__(self, device, threads=None, div=255.0, give_up=3, slots=3):
-        self.ing = BatchIngest(device, slots=slots, div=div)      # three: two batches drawn ahead (trainer, host_prefetch_depth 2) + one on the spot
+        self.ing = BatchIngest(device, slots=slots, div=div)      # the trainer passes its own count: trainer.model_trainer._HostPrefetch (batches drawn ahead + one on the spot)
         self.div, self.give_up = float(div), int(give_up)
         self.threads = default_feed_threads() if threads is None else max(1, min(64, int(threads)))
         self.ok, self.refused_in_a_row = True, 0

@@ -29,21 +29,31 @@ maximum over the keys of the WHOLE meta-batch as in the reference's single-proce
 rank's shard - one scalar all-gather in the forward and one scalar all-reduce in the backward
 (mlhot.dist.StabiliserExchange, include/mlhot.h "strict sharded parity").  Eager iterations only: the exchange runs between
 two C calls, so it cannot sit inside a replayed hipGraph.
+
+Who owns what: `_Feed` the batches (the three routes, the training batches drawn ahead), `_LateLoss` the loss that is read one
+iteration late, `_Captured` one batch shape's hipGraph; ModelTrainer keeps the reference's loop and the order of its steps.
 """
 import collections
 import contextlib
 import math
 import os
 import sys
+import typing
 
 import torch
 
+from mlhot import ops
 from mlhot.dist import GradBucket, rank as dist_rank
+from mlhot.graphs import capture as capture_graph      # thread_local error mode, collector paused: see mlhot/graphs.py
 from mlhot.ops import add_scaled, loss_value_aside
 from trainer.base_trainer import BaseTrainer
 
 
-from mlhot.graphs import CAPTURE_MODE, capture as capture_graph      # thread_local error mode, collector paused: see mlhot/graphs.py
+def _depth(config):
+    """`config.host_prefetch_depth` (default 2): how many training batches may be drawn ahead of the one in use.  The one place that
+    reads it: train()'s look-ahead (`_clear_ahead`) and the byte route's staging slots (`_HostPrefetch`: depth + 1) follow from here."""
+    return max(1, int(getattr(config, "host_prefetch_depth", 2)))
+
 
 class _HostPrefetch:
     """fp32 host batches (the reference's loaders: dataset/shapenet_1d.py:189-196 -> utils/utils.py:26-30) to the device on a copy
@@ -55,7 +65,7 @@ class _HostPrefetch:
     pass) and the batch then crosses PCIe as 7.9 instead of 31.5 MB, expanded by the ingest kernel to the same fp32 bits.  A batch that
     holds anything else takes the fp32 route below, unchanged; the loader's contract is untouched either way."""
 
-    def __init__(self, device, u8=True, background=True, augment=None):
+    def __init__(self, device, u8=True, background=True, augment=None, depth=2):
         self.device = torch.device(device)
         self.stream = torch.cuda.Stream(self.device)
         self.u8 = None
@@ -65,7 +75,7 @@ class _HostPrefetch:
         self.last_fixed = False         # did the last take() hand out the byte route's fixed per-shape device tensors?
         if u8:
             from mlhot.ingest import ExactU8Feed
-            self.u8 = ExactU8Feed(self.device)
+            self.u8 = ExactU8Feed(self.device, slots=depth + 1)      # `depth` batches drawn ahead + the one staged and taken on the spot
         # Round 6: the copy itself runs on ONE worker thread.  Whichever route a batch takes, putting it on its way blocks the calling
         # thread for ~0.5 ms (the pageable fp32 copy: 0.60 ms; the byte conversion + its issue: 0.58 ms - measured inside this loop,
         # scripts/dev/trainer_iter_probe.py), and with the reference's `loss.item()` every iteration that time is SERIAL with the
@@ -121,6 +131,145 @@ class _HostPrefetch:
         return dev
 
 
+class _Feed:
+    """The trainer's batches, whichever way they reach the device: the byte ingest of a loader with `get_batch_u8` (`ingest`), host
+    batches through `_HostPrefetch` (`host`), or the reference's plain `.to(device)` (neither).  Owns the tickets of the training
+    batches that were drawn ahead; the draw order against the data source is the reference's (see ModelTrainer.train)."""
+
+    def __init__(self, config, data, augment):
+        self.config, self.data, self.augment = config, data, augment
+        self.ingest = self.host = None
+        cuda = torch.device(config.device).type == "cuda"
+        if hasattr(data, "get_batch_u8") and cuda and getattr(config, "ingest_u8", True):
+            from mlhot.ingest import BatchIngest
+            self.ingest = BatchIngest(config.device)
+        elif cuda and getattr(config, "host_prefetch", True):
+            self.host = _HostPrefetch(config.device, u8=bool(getattr(config, "host_u8", True)), background=bool(getattr(config, "host_copy_thread", True)),
+                                      augment=augment, depth=_depth(config))
+        if augment is not None and self.ingest is None and self.host is None:
+            raise ValueError("config.device_augment runs inside the device batch ingest: it needs a ROCm device and either a loader with "
+                             "get_batch_u8 (config.ingest_u8) or the host-batch byte route (config.host_prefetch, config.host_u8)")
+        self.ahead = collections.deque()        # tickets of the training batches drawn ahead, oldest first
+
+    @property
+    def fixed(self):
+        """Did the batch just handed out come in fixed per-shape device tensors?  The ingest's always do, the host route's byte batches
+        do (every batch of a shape in the same tensors), fp32 copies and the plain `.to(device)` do not."""
+        return self.ingest is not None or (self.host is not None and self.host.last_fixed)
+
+    def _draw(self, source, u8=False):
+        get = self.data.get_batch_u8 if u8 else self.data.get_batch
+        return get(source=source, tasks_per_batch=self.config.tasks_per_batch, shot=self.config.max_ctx_num)
+
+    def _stage(self, source):
+        """Draw one batch of `source` and put it on its way to the device; returns the ticket the route's take() wants."""
+        if self.ingest is None:
+            return self.host.stage(self._draw(source), augment=source == "train")
+        xs, xq, ys, yq = self._draw(source, u8=True)
+        table = None
+        if source == "train" and self.augment is not None:          # the reference augments training batches only (shapenet_1d.py:174)
+            (T, Nc, H, W, Cc), Nq = xs.shape, xq.shape[1]
+            if Cc != 1 or xq.shape[-1] != 1:
+                raise ValueError(f"config.device_augment: single-channel images only, got {tuple(xs.shape)}")
+            table = self.augment.batch(T * Nc, T * Nq, H, W)
+        return self.ingest.stage(xs, xq, ys, yq, augment=table)
+
+    def batch(self, source, ahead=0):
+        """One device batch of `source`; validation / test batches are staged and taken on the spot.  `ahead` (train()'s `_prefetch`):
+        may the next training batch be drawn right away?  The ingest then starts its copy as soon as this one is handed out, so it
+        overlaps with the step the caller is about to run; the host route's (host-blocking) copies go out BEHIND that step's
+        launch: stage_ahead()."""
+        route = self.host if self.ingest is None else self.ingest
+        if route is None:
+            return tuple(t.to(self.config.device) for t in self._draw(source))
+        if source != "train":
+            return route.take(self._stage(source))
+        batch = route.take(self.ahead.popleft() if self.ahead else self._stage("train"))
+        if self.ingest is not None and ahead:
+            self.ahead.append(self._stage("train"))
+        return batch
+
+    def stage_ahead(self, n):
+        """Host route: draw training batches until `n` are ahead and start their copies to the device - called right after the
+        current step has been enqueued, so the (pageable, host-blocking) copy runs beside the step instead of in front of it."""
+        while self.host is not None and len(self.ahead) < n:
+            self.ahead.append(self._stage("train"))
+
+    def drain(self):
+        """Nothing left in flight when the host route's worker goes; a later stage() copies on the caller's thread."""
+        if self.host is not None and self.host._pool is not None:
+            while self.ahead:
+                ticket = self.ahead.popleft()
+                if ticket[0] == "later":
+                    ticket[1].result()
+            self.host._pool.shutdown(wait=True)
+            self.host._pool = None
+
+
+class _LateLoss:
+    """`config.lagged_loss_log`: iteration k's loss leaves the device by an asynchronous copy into pinned memory queued behind its
+    graph and is read when iteration k + 1 has been launched.  Two buffers, taken in turn by this object's OWN count of calls (not
+    by the caller's iteration numbers): with at most one loss left pending behind a call, the buffer written next has been read."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.ring = None                        # [(pinned scalar, event)] * 2: pinned memory needs the device runtime, so the first push() allocates
+        self.calls = 0
+        self.pending = collections.deque()      # (it, buffer, event) of the losses that have not been read yet, oldest first
+
+    def push(self, it, loss):
+        if self.ring is None:
+            self.ring = [(torch.zeros((), dtype=torch.float32).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+        buf, ev = self.ring[self.calls & 1]
+        self.calls += 1
+        buf.copy_(loss, non_blocking=True)
+        ev.record(torch.cuda.current_stream(self.device))
+        self.pending.append((it, buf, ev))
+
+    def pop(self, report, keep=0):
+        """When more than `keep` losses are pending: read the oldest and return report(it, value); None otherwise."""
+        if len(self.pending) > keep:
+            it, buf, ev = self.pending.popleft()
+            ev.synchronize()
+            return report(it, float(buf))
+
+
+class _Captured(typing.NamedTuple):
+    """One batch shape's captured training iteration (ModelTrainer._graphs holds nothing, "warm" or one of these per shape)."""
+    graph: torch.cuda.CUDAGraph
+    loss: torch.Tensor          # the static device scalar every replay writes
+    grads: list                 # the gradient tensors THIS graph writes (its private pool), in the order of GradBucket.params
+    taps: list                  # [((owner, attribute), what the captured forward logged there)]: see _taps_aside
+
+    def replay(self, params):
+        self.graph.replay()
+        for p, g in zip(params, self.grads):        # a replay does not rebind p.grad, and another shape's graph or eager warm-up
+            p.grad = g                              # may have re-pointed it since
+        for (owner, name), log in self.taps:        # a replay runs no Python forward: hand a listener the graph's own saved
+            listener = getattr(owner, name)         # buffers, which now hold THIS iteration's routing
+            if listener is not None:
+                listener.extend(log)
+        return self.loss
+
+
+@contextlib.contextmanager
+def _taps_aside(model):
+    """The forward's test / diagnostic hooks - `mlhot.ops.saved_taps` and, the ResNet family's form of the same, a module's `tap_log` -
+    are None, or the list a listener put there to be handed every forward's saved buffers.  Around a capture the listeners are set
+    aside (nothing executes: there is nothing for them to hear) and put back afterwards; the captured forward logs into fresh lists
+    instead, which are yielded as _Captured.taps."""
+    hooks = [(ops, "saved_taps")] + [(m, "tap_log") for m in model.modules() if hasattr(m, "tap_log")]
+    listening = [getattr(owner, name) for owner, name in hooks]
+    taps = [(hook, []) for hook in hooks]
+    for (owner, name), log in taps:
+        setattr(owner, name, log)
+    try:
+        yield taps
+    finally:
+        for (owner, name), listener in zip(hooks, listening):
+            setattr(owner, name, listener)
+
+
 class ModelTrainer(BaseTrainer):
     def __init__(self, model, loss, optimizer, config, data):
         # config.device_augment + "data_aug" in config.aug_list: the loader's image augmentation on the device (mlhot/augment.py);
@@ -138,10 +287,11 @@ class ModelTrainer(BaseTrainer):
         if getattr(config, "strict_sharded_parity", False):
             if getattr(config, "graph_steps", False):
                 raise ValueError("config.strict_sharded_parity runs a collective between two C calls of the forward: not with config.graph_steps")
-            from mlhot import ops
             from mlhot.dist import StabiliserExchange
             ops.set_stabiliser_exchange(StabiliserExchange(dedicated_group=True))
         cuda = torch.device(config.device).type == "cuda"
+        self.replaced_optimizer = None      # the caller's torch.optim.Adam, when the flat update below took over from it
+        self._installed_arena = False       # did this trainer install the model's gradient arena?  (close() removes it again)
         # train.py:52-56's optimizer continued by the flat one-launch update
         if cuda and getattr(config, "promote_optimizer", True):
             from mlhot.optim import FlatAdam
@@ -161,27 +311,20 @@ class ModelTrainer(BaseTrainer):
                                    and not getattr(config, "strict_sharded_parity", False) and not getattr(config, "contrastive", False))
         else:
             self._graph_default = bool(config.graph_steps)
-        self.ingest, self._staged = None, None
-        self._staged_q = collections.deque()      # host-batch route: tickets of the training batches drawn ahead, oldest first
-        self._host_prefetch, self._fixed_batch = None, False
-        self._prefetch = False          # set per iteration by train(): may the NEXT training batch be drawn right away?  (an int: how many)
+        self._prefetch = 0              # set per iteration by train(): how many of the NEXT training batches may be drawn right away?
         self.rank0 = dist_rank() == 0   # files / logs / TensorBoard are rank 0's business (every rank holds the same weights)
-        self._graphs, self._static_in, self._side = {}, {}, None       # graph_steps: per batch shape
+        # graph_steps, per batch shape: nothing (not seen yet), "warm" (ran once, eagerly) or the _Captured graph; the fixed input tensors
+        self._graphs, self._static_in, self._side = {}, {}, None
+        self._captured_hyper, self.recaptures = None, 0     # the optimizer's scalars the graphs hold; how often their change dropped the graphs
+        self._one = None                # the backward's seed (see _step_body)
+        self._late = _LateLoss(config.device)
         self._eps = None                # graph_steps of a Bayes-by-backprop model: its eps draws staged per step (networks/bbb/eps.py)
-        if hasattr(data, "get_batch_u8") and cuda and getattr(config, "ingest_u8", True):
-            from mlhot.ingest import BatchIngest
-            self.ingest = BatchIngest(config.device)
-        elif cuda and getattr(config, "host_prefetch", True):
-            self._host_prefetch = _HostPrefetch(config.device, u8=bool(getattr(config, "host_u8", True)),
-                                                background=bool(getattr(config, "host_copy_thread", True)), augment=self._augment)
-        if self._augment is not None and self.ingest is None and self._host_prefetch is None:
-            raise ValueError("config.device_augment runs inside the device batch ingest: it needs a ROCm device and either a loader with "
-                             "get_batch_u8 (config.ingest_u8) or the host-batch byte route (config.host_prefetch, config.host_u8)")
+        self._feed = _Feed(config, data, self._augment)
+        self.ingest, self._host_prefetch = self._feed.ingest, self._feed.host      # which route the batches take (at most one is set)
 
     def _announce(self):
         """Once, at the start of train(): what the constructor promoted (nothing here is silent)."""
-        from mlhot.optim import FlatAdam
-        if isinstance(self.optimizer, FlatAdam) and getattr(self, "replaced_optimizer", None) is not None:
+        if self.replaced_optimizer is not None:
             self._log("mlhot: torch.optim.Adam continued by mlhot.optim.FlatAdam (one launch over the flat parameter buffer; same hyper-parameters, "
                       "moments and step count).  Checkpoint / schedule `trainer.optimizer`; the optimizer object passed in no longer steps.")
         if self._graph_default:
@@ -190,7 +333,7 @@ class ModelTrainer(BaseTrainer):
         if self._host_prefetch is not None:
             self._log("mlhot: host batches are copied on a copy stream behind the step" +
                       (" - as bytes when every image element is exactly k / 255 (checked per batch), as fp32 otherwise" if self._host_prefetch.u8 is not None else "")
-                      + f"; up to {max(1, int(getattr(self.config, 'host_prefetch_depth', 2)))} batches are drawn ahead where no validation round / background regeneration lies between")
+                      + f"; up to {_depth(self.config)} batches are drawn ahead where no validation round / background regeneration lies between")
         if self._graph_default and self._lagged():
             self._log("mlhot: every iteration's loss is logged and checked one iteration late (read behind the NEXT iteration's launch; flushed before "
                       "validation rounds, checkpoints and the end of training).  config.lagged_loss_log = False reads it right behind the step.")
@@ -198,26 +341,14 @@ class ModelTrainer(BaseTrainer):
     def close(self):
         """Undo the process-wide installs of the constructor (the gradient arena in mlhot.binding, the stabiliser exchange in mlhot.ops);
         train() calls it when it is done, a caller that only uses _train_iter calls it itself."""
-        if getattr(self, "_installed_arena", False):
+        if self._installed_arena:
             from mlhot import binding
             if binding.get_grad_arena() is self.model.__dict__.get("_arena"):
                 binding.set_grad_arena(None)
             self._installed_arena = False
         if getattr(self.config, "strict_sharded_parity", False):
-            from mlhot import ops
             ops.set_stabiliser_exchange(None)
-        hp = self._host_prefetch
-        if hp is not None and hp._pool is not None:
-            while self._staged_q:
-                staged = self._staged_q.popleft()
-                if staged[0] == "later":
-                    staged[1].result()                  # nothing left in flight when the worker goes
-            hp._pool.shutdown(wait=True)
-            hp._pool = None                             # a later stage() copies on the caller's thread
-
-    def _hyper(self):
-        g = self.optimizer.param_groups[0]
-        return (float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g.get("weight_decay", 0.0)))
+        self._feed.drain()
 
     def _log(self, msg):
         logger = getattr(self.config, "logger", None)
@@ -243,9 +374,8 @@ class ModelTrainer(BaseTrainer):
             # applied to every iteration in between, lets batch k+2 be drawn under step k.
             self._prefetch = self._clear_ahead(it)
             self._train_iter(it)
-            if getattr(self, "_loss_pending", None) is not None and (it % self.config.val_freq == 0 or it == self.iterations or it % 1000 == 0):
-                pending, self._loss_pending = self._loss_pending, None
-                self._flush_loss(pending)                               # lagged log: nothing stays behind a validation round, a checkpoint or the end
+            if it % self.config.val_freq == 0 or it == self.iterations or it % 1000 == 0:
+                self._flush_loss()          # lagged log: nothing stays behind a validation round, a checkpoint or the end
             if it % self.config.val_freq == 0:
                 self._validate_iter(it, source="validation")
                 if self.config.task != "pascal_1d":
@@ -262,9 +392,8 @@ class ModelTrainer(BaseTrainer):
         """How many of the training batches behind iteration `it`'s may be drawn now: batch it+j only if no validation round, end of
         training or background regeneration lies between iteration it and it+j (the reference's order of draws, train.py /
         model_trainer.py:59-70)."""
-        depth = max(1, int(getattr(self.config, "host_prefetch_depth", 2)))
         n = 0
-        for i in range(it, it + depth):
+        for i in range(it, it + _depth(self.config)):
             if i < self.iterations and i % self.config.val_freq != 0 and not ((i + 1) % self.config.bg_gen_freq == 0 and self.config.gen_bg):
                 n += 1
             else:
@@ -272,63 +401,14 @@ class ModelTrainer(BaseTrainer):
         return n
 
     def _batch(self, source):
-        """One device batch of `source`.  With the ingest path the NEXT training batch starts its host -> device copy as
-        soon as the current one is handed out (when train() allows it: see `_prefetch`), so it overlaps with the step the
-        caller is about to run; validation / test batches are staged and taken on the spot."""
-        if self.ingest is None:
-            def draw(src):
-                return self.data.get_batch(source=src, tasks_per_batch=self.config.tasks_per_batch, shot=self.config.max_ctx_num)
-            hp = self._host_prefetch
-            if hp is None:
-                dev = self.config.device
-                return tuple(t.to(dev) for t in draw(source))
-            if source != "train":
-                return hp.take(hp.stage(draw(source)))
-            ticket = self._staged_q.popleft() if self._staged_q else hp.stage(draw("train"), augment=True)
-            self._stage_later = int(self._prefetch)     # the next batches' (host-blocking) copies go out BEHIND this step's launch: _stage_next()
-            batch = hp.take(ticket)
-            self._fixed_batch = hp.last_fixed           # the byte route delivers every batch of a shape in the same device tensors
-            return batch
+        """One device batch of `source` (see _Feed.batch); a training batch takes train()'s `_prefetch` along."""
+        return self._feed.batch(source, ahead=self._prefetch)
 
-        def stage(src):
-            xs, xq, ys, yq = self.data.get_batch_u8(source=src, tasks_per_batch=self.config.tasks_per_batch, shot=self.config.max_ctx_num)
-            table = None
-            if src == "train" and self._augment is not None:          # the reference augments training batches only (shapenet_1d.py:174)
-                (T, Nc, H, W, Cc), Nq = xs.shape, xq.shape[1]
-                if Cc != 1 or xq.shape[-1] != 1:
-                    raise ValueError(f"config.device_augment: single-channel images only, got {tuple(xs.shape)}")
-                table = self._augment.batch(T * Nc, T * Nq, H, W)
-            return self.ingest.stage(xs, xq, ys, yq, augment=table)
-        if source != "train":
-            return self.ingest.take(stage(source))
-        ticket, self._staged = (self._staged or stage("train")), None
-        batch = self.ingest.take(ticket)
-        if self._prefetch:
-            self._staged = stage("train")
-        return batch
-
-    def _stage_next(self):
-        """Host-batch route: draw the next training batch and start its copy to the device - called right after the current
-        step has been enqueued, so the (pageable, host-blocking) copy runs beside the step instead of in front of it."""
-        if self._host_prefetch is not None and getattr(self, "_stage_later", 0):
-            ahead, self._stage_later = self._stage_later, 0
-            if self._eps is not None and self._eps is not False:
-                ahead = 1       # Bayes-by-backprop models: batch k+2 would be drawn in front of step k+1's eps - one ahead keeps the reference's order on a shared generator
-            while len(self._staged_q) < ahead:
-                self._staged_q.append(self._host_prefetch.stage(self.data.get_batch(source="train", tasks_per_batch=self.config.tasks_per_batch,
-                                                                                    shot=self.config.max_ctx_num), augment=True))
-
-    def _seed(self, loss):
-        """d loss / d loss = 1, allocated once: autograd's implicit seed is a fill kernel per iteration."""
-        s = getattr(self, "_one", None)
-        if s is None or s.device != loss.device or s.dtype != loss.dtype:
-            s = self._one = torch.ones((), device=loss.device, dtype=loss.dtype)
-        return s
-
-    # ---- graph-replayed training iterations -------------------------------------------------------------------
-    def _step_body(self, ctx_x, qry_x, ctx_y, qry_y, with_optimizer):
+    def _step_body(self, ctx_x, qry_x, ctx_y, qry_y, with_optimizer, arm=False):
+        """The reference's step (model_trainer.py:59-93), the one place it is written down: zero_grad -> forward -> loss + kl * beta
+        (+ the contrastive term) -> backward [-> optimizer step].  Eager and captured iterations both run this; returns the loss."""
         self.optimizer.zero_grad()
-        if getattr(self.config, "contrastive", False):
+        if getattr(self.config, "contrastive", False):       # FCL* models take the target labels and return the NT-Xent term
             pr_mu, pr_var, kl, contra_loss = self.model(ctx_x, ctx_y, qry_x, qry_y)
         else:
             pr_mu, pr_var, kl = self.model(ctx_x, ctx_y, qry_x)
@@ -336,10 +416,14 @@ class ModelTrainer(BaseTrainer):
         # config.loss_aside (default on): with the bare loss as the objective (no KL / contrastive term computes with its value) the value
         # is left to the model's first backward kernel (mlhot.ops.loss_value_aside) - it is read after the backward, below
         with loss_value_aside(enabled=self._bare_loss(kl, contra_loss)):
-            losses = self._objective(pr_mu, pr_var, qry_y, kl)
+            losses = self._objective(pr_mu, pr_var, qry_y, kl)        # loss + kl * beta (model_trainer.py:77-78)
             if contra_loss is not None:
                 losses = losses + contra_loss * self.config.contrastive_rate
-            losses.backward(gradient=self._seed(losses))
+            if arm:
+                self.bucket.arm()                                     # world > 1: the early bucket's all-reduce goes out from inside backward()
+            if self._one is None:
+                self._one = torch.ones_like(losses)                   # d loss / d loss = 1, allocated once: autograd's implicit seed is a fill kernel per iteration
+            losses.backward(gradient=self._one)
         if with_optimizer:
             self.optimizer.step()
         return losses.detach()
@@ -358,6 +442,7 @@ class ModelTrainer(BaseTrainer):
         return (bool(getattr(self.config, "loss_aside", True)) and contra_loss is None and not isinstance(kl, torch.Tensor)
                 and (not kl or not self.config.beta))
 
+    # ---- graph-replayed training iterations -------------------------------------------------------------------
     def _graph_train_iter(self, it):
         """One training iteration replayed from a hipGraph (see the module docstring).  Returns the device loss tensor."""
         if not getattr(self.optimizer, "capturable", False):
@@ -370,17 +455,18 @@ class ModelTrainer(BaseTrainer):
             self._side = torch.cuda.Stream(self.config.device)
         static = self._static_in.get(key)
         if static is None:                                           # fixed input addresses for this shape
-            static = self._static_in[key] = batch if (self.ingest is not None or self._fixed_batch) else tuple(t.clone() for t in batch)
+            static = self._static_in[key] = batch if self._feed.fixed else tuple(t.clone() for t in batch)
         if static[0].data_ptr() != batch[0].data_ptr():
             for d, t in zip(static, batch):
                 d.copy_(t)
         # lr / betas / eps / weight decay are scalar kernel arguments, frozen inside a captured graph: when a scheduler (or the caller)
         # changed them since the capture, every shape's graph is dropped - this iteration runs eagerly with the new values, the next
         # one captures again
-        hyper = self._hyper()
-        if getattr(self, "_captured_hyper", hyper) != hyper:
+        g = self.optimizer.param_groups[0]
+        hyper = (float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g.get("weight_decay", 0.0)))
+        if self._captured_hyper not in (None, hyper):
             self._graphs.clear()
-            self.recaptures = getattr(self, "recaptures", 0) + 1
+            self.recaptures += 1
         self._captured_hyper = hyper
         entry = self._graphs.get(key)
         cur = torch.cuda.current_stream(self.config.device)
@@ -395,38 +481,17 @@ class ModelTrainer(BaseTrainer):
             cur.wait_stream(self._side)
             self._graphs[key] = "warm"
         else:
-            from mlhot import ops
             if entry == "warm":                                      # second time: capture (nothing executes), then replay below
                 graph = torch.cuda.CUDAGraph()
                 self._side.wait_stream(cur)
-                taps, ops.saved_taps = ops.saved_taps, []            # the captured forward's saved buffers (test / diagnostic hook, see below)
-                loggers = [m for m in self.model.modules() if hasattr(m, "tap_log")]      # the ResNet family's form of the same hook
-                listening = [m.tap_log for m in loggers]
-                for m in loggers:
-                    m.tap_log = []
-                try:
-                    with staged, capture_graph(graph, self._side):
-                        static_loss = self._step_body(*static, with_optimizer=single)
-                finally:
-                    captured_taps, ops.saved_taps = ops.saved_taps, taps
-                    captured_logs = [m.tap_log for m in loggers]
-                    for m, log in zip(loggers, listening):
-                        m.tap_log = log
-                # the gradient tensors THIS graph writes (its private pool): a replay does not rebind p.grad, and another
-                # shape's graph or eager warm-up may have re-pointed it since
-                entry = self._graphs[key] = (graph, static_loss, [p.grad for p in self.bucket.params], captured_taps, (loggers, captured_logs))
-            entry[0].replay()
-            loss = entry[1]
-            for p, g in zip(self.bucket.params, entry[2]):
-                p.grad = g
-            if ops.saved_taps is not None:                          # a replay runs no Python forward: hand a listener the graph's own saved
-                ops.saved_taps.extend(entry[3])                      # buffers, which now hold THIS iteration's routing
-            for m, log in zip(*entry[4]):
-                if m.tap_log is not None:
-                    m.tap_log.extend(log)
+                with _taps_aside(self.model) as taps, staged, capture_graph(graph, self._side):
+                    static_loss = self._step_body(*static, with_optimizer=single)
+                entry = self._graphs[key] = _Captured(graph, static_loss, [p.grad for p in self.bucket.params], taps)
+            loss = entry.replay(self.bucket.params)
         if not single:
             self._sync_and_step()
-        self._stage_next()
+        # Bayes-by-backprop models: batch k+2 would be drawn in front of step k+1's eps - one ahead keeps the reference's order on a shared generator
+        self._feed.stage_ahead(self._prefetch if eps is None else min(self._prefetch, 1))
         if eps is not None and eps.shapes and self._prefetch:
             eps.prefetch()      # the next iteration's draws on host threads under this step - behind the next batch's draw, and only
         return loss             # when nothing else (a validation forward) touches the CPU generator in between
@@ -466,26 +531,12 @@ class ModelTrainer(BaseTrainer):
                 return self._lagged_log(it, loss)
             if it % every and it != self.iterations:
                 return None                                          # no host sync on this iteration
-            value = loss.item()
-            return self._report(it, value)
+            return self._report(it, loss.item())
         self.model.train()
-        self.optimizer.zero_grad()
-        ctx_x, qry_x, ctx_y, qry_y = self._batch("train")
-        contrastive = getattr(self.config, "contrastive", False)
-        if contrastive:                                   # FCL* models take the target labels and return the NT-Xent term
-            pr_mu, pr_var, kl, contra_loss = self.model(ctx_x, ctx_y, qry_x, qry_y)
-        else:
-            pr_mu, pr_var, kl = self.model(ctx_x, ctx_y, qry_x)
-        with loss_value_aside(enabled=self._bare_loss(kl, contra_loss if contrastive else None)):
-            losses = self._objective(pr_mu, pr_var, qry_y, kl)        # loss + kl * beta (model_trainer.py:77-78)
-            if contrastive:
-                losses = losses + contra_loss * self.config.contrastive_rate
-            self.bucket.arm()                                         # world > 1: the early bucket's all-reduce goes out from inside backward()
-            losses.backward(gradient=self._seed(losses))
+        loss = self._step_body(*self._batch("train"), with_optimizer=False, arm=True)
         self._sync_and_step()
-        self._stage_next()
-        value = losses.item()                                     # the iteration's only host sync
-        return self._report(it, value)
+        self._feed.stage_ahead(self._prefetch)
+        return self._report(it, loss.item())                     # the iteration's only host sync
 
     def _report(self, it, value):
         if self.writer is not None and self.rank0:
@@ -511,23 +562,13 @@ class ModelTrainer(BaseTrainer):
         asynchronous copy into pinned memory queued behind its graph; it is read, logged and checked when iteration k + 1 has been
         launched (a non-finite loss stops training one optimizer step later than the reference would), the last one when train()
         ends.  Returns the PREVIOUS iteration's loss (None for the first)."""
-        dev = torch.device(self.config.device)
-        ring = getattr(self, "_loss_ring", None)
-        if ring is None:
-            ring = self._loss_ring = [(torch.zeros((), dtype=torch.float32).pin_memory(), torch.cuda.Event()) for _ in range(2)]
-            self._loss_pending = None
-        buf, ev = ring[it & 1]
-        buf.copy_(loss, non_blocking=True)
-        ev.record(torch.cuda.current_stream(dev))
-        prev, self._loss_pending = self._loss_pending, (it, buf, ev)
-        if prev is None:
-            return None
-        return self._flush_loss(prev)
+        self._late.push(it, loss)
+        return self._flush_loss(keep=1)
 
-    def _flush_loss(self, pending):
-        it, buf, ev = pending
-        ev.synchronize()
-        return self._report(it, float(buf))
+    def _flush_loss(self, keep=0):
+        """Read, log and check the oldest pending loss when more than `keep` are pending (train(): the one that is left, before
+        everything that writes).  Returns its value, or None."""
+        return self._late.pop(self._report, keep)
 
     def _validate_iter(self, it, source):
         self.model.eval()
