@@ -43,8 +43,12 @@ const char* mlhot_last_error(void);
 
 /* Implementation switches for A/B tests (process-global, see Threading above): "conv2_tc" = 1 (default) runs the
  * weight-stationary conv2 kernels (csrc/conv_tc.h), 0 the generic implicit-GEMM problems; "tail_fused" = 1 (default) runs the
- * fused per-task tail kernels where they apply, "tail_spec" = bit mask of the six tail phases that use the kernels specialised
- * for the shipped dimensions (csrc/tail_spec.h; default 63 = all, 0 = the run-time-shaped csrc/tail_fused.h); "favor2" = 1
+ * fused per-task tail kernels where they apply, "tail_spec" = bit mask of what the fused tails run specialised for the shipped
+ * dimensions (csrc/tail_spec.h, cnp_spec.h; names in csrc/encoder.h enum TailSpec): 1 / 2 / 4 forward phases A / B / C, 8 / 16 / 32
+ * backward phases C' / B' / A' (the CNP tail's one forward / backward kernel: 1 / 8), 64 phase A also folds the encoder Linear's
+ * split-K partial results, 128 phase C' takes the loss's gradient itself when handed a loss descriptor, 512 phase B' as two
+ * workgroups per (task, head), 1024 / 2048 phases C' / A' as two workgroups per task, 4096 four instead of two, 256 unassigned;
+ * default 7935 = all, 0 = the run-time-shaped csrc/tail_fused.h / tail_cnp.h; "favor2" = 1
  * (default) the two-launch FAVOR+ kernels, 0 the operator chain; "materialize_a1" = 1 additionally stores the conv1 output
  * (debug / tests; the fused conv1+conv2 kernels never need it); "conv2_split" = 1 (default 0) runs the vanilla encoder's conv1 +
  * conv2 + pool forward with conv2 on the bf16 matrix pipe over exact hi / mid / lo splits of the fp32 operands (csrc/conv_split.h:

@@ -512,6 +512,23 @@ def test_model_edge_cases_vs_reference(gpulib, tail_impl, name):
     _run_case(gpulib, name)
 
 
+TAIL_SPEC_BITS = (1, 2, 4, 8, 16, 32, 64, 128, 512, 1024, 2048, 4096)       # csrc/encoder.h enum TailSpec (256 is unassigned)
+
+
+@pytest.mark.parametrize("bit", TAIL_SPEC_BITS)
+@pytest.mark.parametrize("name", ["s_anp_shapenet1d_ragged", "s_cnp_shapenet1d_max"])
+def test_model_with_one_tail_spec_bit_cleared(gpulib, name, bit):
+    """`tail_impl` visits 4 states of the route table (csrc/np_vanilla.h np_route); here every assigned bit of option tail_spec is
+    cleared on its own, on one whole-model case per fused family whose dims the specialised kernels accept, at the case's usual
+    tolerances (_run_case)."""
+    assert sum(TAIL_SPEC_BITS) == 7935
+    gpulib.set_option("tail_spec", 7935 & ~bit)
+    try:
+        _run_case(gpulib, name)
+    finally:
+        gpulib.set_option("tail_spec", 7935)
+
+
 def test_mid_size_case_takes_the_reference_gradient_branch(gpulib):
     """T = 2, 15 + 15 shots (60 images, 9.6 M routing decisions): no decision differs from the oracle's, so _run_case compares
     every gradient with the REFERENCE's own (the fixture) and not only with the routed oracle."""

@@ -25,6 +25,29 @@ namespace mlhot {
 // generic igemm problems are always available as the A/B reference of the specialised kernels.
 struct Options { int conv2_tc; int tail_fused; int materialize_a1; int dbg; int tail_spec; int conv2_split; int conv3_bwd_merged; };
 extern Options g_opt;
+// Option "tail_spec": which parts of a fused tail run the kernels specialised for the shipped dimensions (csrc/tail_spec.h,
+// cnp_spec.h) instead of the run-time-shaped ones (tail_fused.h, tail_cnp.h).  A clear bit is the A/B reference of a set one.  The
+// CNP tail is one kernel per direction: it reads FWD_A / BWD_C as "forward" / "backward", and ENC_FOLD, LOSS, BWD_C_WG2, WG4 with them.
+// np_route() (np_vanilla.h) is the only reader.
+enum TailSpec : int {
+  TAIL_SPEC_FWD_A = 1,         // forward phase A (transform_y, EncoderFC, K projection)
+  TAIL_SPEC_FWD_B = 2,         // forward phase B (V / Q projections, FAVOR+, the heads' _W shares)
+  TAIL_SPEC_FWD_C = 4,         // forward phase C (_W, r_to_z, decoder0)
+  TAIL_SPEC_BWD_C = 8,         // backward phase C'
+  TAIL_SPEC_BWD_B = 16,        // backward phase B'
+  TAIL_SPEC_BWD_A = 32,        // backward phase A'
+  TAIL_SPEC_ENC_FOLD = 64,     // phase A also folds the encoder Linear's split-K partial results
+  TAIL_SPEC_LOSS = 128,        // phase C' takes the loss's gradient itself when handed a loss descriptor
+                               // (256: unassigned)
+  TAIL_SPEC_BWD_B_SPLIT = 512, // phase B' as two workgroups per (task, head): query side | key / value side
+  TAIL_SPEC_BWD_C_WG2 = 1024,  // phase C' as two workgroups per task sharing the weight-gradient tiles
+  TAIL_SPEC_BWD_A_WG2 = 2048,  // phase A' likewise
+  TAIL_SPEC_WG4 = 4096,        // four workgroups instead of two, wherever one of the two bits above is set
+  TAIL_SPEC_DEFAULT = TAIL_SPEC_FWD_A | TAIL_SPEC_FWD_B | TAIL_SPEC_FWD_C | TAIL_SPEC_BWD_C | TAIL_SPEC_BWD_B | TAIL_SPEC_BWD_A |
+                      TAIL_SPEC_ENC_FOLD | TAIL_SPEC_LOSS | TAIL_SPEC_BWD_B_SPLIT | TAIL_SPEC_BWD_C_WG2 | TAIL_SPEC_BWD_A_WG2 |
+                      TAIL_SPEC_WG4,
+};
+static_assert(TAIL_SPEC_DEFAULT == 7935, "the numeric values are public: tests, scripts and MLHOT_OPTS pass numbers");
 constexpr int C2_GRID = 256;   // one persistent workgroup per CU
 
 struct EncSaved {

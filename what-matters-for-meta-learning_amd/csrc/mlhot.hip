@@ -32,7 +32,7 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-Options g_opt = {1, 1, 0, 0, 7935, 0, 1};
+Options g_opt = {1, 1, 0, 0, TAIL_SPEC_DEFAULT, 0, 1};
 int g_favor2 = 1;
 #ifndef MLHOT_HOSTSIM
 namespace rt { int g_trunk_fuse34 = 1, g_trunk_dual_dgrad = 1, g_trunk_wg_rows = 128; }
@@ -90,7 +90,7 @@ int mlhot_set_option(const char* name, int value) {
   if (!strcmp(name, "conv2_tc")) { g_opt.conv2_tc = value; return MLHOT_OK; }
   if (!strcmp(name, "conv2_split")) { g_opt.conv2_split = value; return MLHOT_OK; }
   if (!strcmp(name, "tail_fused")) { g_opt.tail_fused = value; return MLHOT_OK; }
-  if (!strcmp(name, "tail_spec")) { g_opt.tail_spec = value; return MLHOT_OK; }     // fused tail: bit mask of the phases that run the kernels specialised for the shipped dimensions (csrc/tail_spec.h; bits 1..32 = the six phases, 64 = phase A also folds the encoder Linear's split-K partial results, 128 = phase C' takes the loss's gradient itself when handed a loss descriptor, 512 = phase B' as two workgroups per (task, head): query side | key / value side, 1024 / 2048 = phases C' / A' as several workgroups per task sharing the weight-gradient tiles (two; four with 4096); default 7935 = all) instead of the run-time-shaped ones
+  if (!strcmp(name, "tail_spec")) { g_opt.tail_spec = value; return MLHOT_OK; }     // bit mask, enum TailSpec (encoder.h); default TAIL_SPEC_DEFAULT = 7935 = all
   if (!strcmp(name, "conv3_bwd_merged")) { g_opt.conv3_bwd_merged = value; return MLHOT_OK; }     // 0: two launches; 1: one launch, 128 + 128 workgroups; n > 1: n weight-gradient workgroups of 256
   if (!strcmp(name, "materialize_a1")) { g_opt.materialize_a1 = value; return MLHOT_OK; }
   if (!strcmp(name, "dbg")) { g_opt.dbg = value; return MLHOT_OK; }   // timing experiments only (results become wrong)
@@ -654,8 +654,8 @@ size_t mlhot_np_struct_bytes(int which) {
        : which == 3 ? sizeof(mlhot_chain_layer) : which == 4 ? sizeof(mlhot_chain_grads) : sizeof(mlhot_linear_job);
 }
 size_t mlhot_np_saved_bytes(const mlhot_np_dims* d) { return d ? np_saved_carve(*d, nullptr, 0).bytes : 0; }
-size_t mlhot_np_scratch_bytes(const mlhot_np_dims* d) { return d ? np_scratch_carve(*d, nullptr, 0).bytes : 0; }
-size_t mlhot_np_grads_flat_layout(const mlhot_np_dims* d, mlhot_np_grads* offsets) { return (d && offsets) ? np_grads_flat_layout(*d, *offsets) : 0; }
+size_t mlhot_np_scratch_bytes(const mlhot_np_dims* d) { return d ? np_scratch_carve(*d, np_route(*d), nullptr, 0).bytes : 0; }
+size_t mlhot_np_grads_flat_layout(const mlhot_np_dims* d, mlhot_np_grads* offsets) { return (d && offsets) ? np_grads_flat_layout(*d, np_route(*d), *offsets) : 0; }
 
 int mlhot_np_vanilla_fwd(const mlhot_np_dims* d, const mlhot_np_params* p, const float* ctx_x, const float* ctx_y,
                          const float* qry_x, float* mu, void* saved, void* scratch, size_t scratch_bytes, void* stream) {

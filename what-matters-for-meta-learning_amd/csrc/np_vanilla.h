@@ -17,6 +17,7 @@
 #include "cnp_spec.h"
 #include "linear_skinny.h"
 #include "favor2.h"
+#include <type_traits>
 
 namespace mlhot {
 
@@ -58,6 +59,130 @@ inline NpBuf np_saved_carve(const mlhot_np_dims& d, void* base, size_t cap) {
   return b;
 }
 
+#ifndef MLHOT_HOSTSIM
+// ---- the fused tails' dimension / parameter blocks (kernel arguments) -------------------------------
+inline tf::TailDims tail_dims(const mlhot_np_dims& d) {
+  return tf::TailDims{d.T, d.Nc, d.Nq, d.label_dim, d.y_dim, d.dim_w, d.dim_z, d.hidden[0], d.hidden[1], d.dec_hidden,
+                      d.out_tanh ? ACT_TANH : ACT_NONE, d.m_feat};
+}
+inline tf::TailParams tail_params(const mlhot_np_params& p) {
+  tf::TailParams q;
+  q.ty_w = p.ty_w; q.ty_b = p.ty_b;
+  for (int i = 0; i < 3; ++i) { q.er_w[i] = p.er_w[i]; q.er_b[i] = p.er_b[i]; q.dec_w[i] = p.dec_w[i]; q.dec_b[i] = p.dec_b[i]; }
+  q.r2z_w = p.r2z_w; q.r2z_b = p.r2z_b;
+  for (int i = 0; i < MLHOT_HEADS; ++i) {
+    q.wk_w[i] = p.wk_w[i]; q.wk_b[i] = p.wk_b[i]; q.wv_w[i] = p.wv_w[i]; q.wv_b[i] = p.wv_b[i];
+    q.wq_w[i] = p.wq_w[i]; q.wq_b[i] = p.wq_b[i];
+  }
+  q.wo_w = p.wo_w; q.wo_b = p.wo_b; q.proj = p.proj;
+  return q;
+}
+inline tf::CnpDims cnp_dims(const mlhot_np_dims& d) {
+  return tf::CnpDims{d.T, d.Nc, d.Nq, d.label_dim, d.y_dim, d.dim_w, d.dim_r, d.dim_z, d.hidden[0], d.hidden[1], d.dec_hidden,
+                     d.out_tanh ? ACT_TANH : ACT_NONE, d.agg_mode};
+}
+inline tf::CnpParams cnp_params(const mlhot_np_params& p) {
+  tf::CnpParams q;
+  q.ty_w = p.ty_w; q.ty_b = p.ty_b; q.r2z_w = p.r2z_w; q.r2z_b = p.r2z_b;
+  for (int i = 0; i < 3; ++i) { q.er_w[i] = p.er_w[i]; q.er_b[i] = p.er_b[i]; q.dec_w[i] = p.dec_w[i]; q.dec_b[i] = p.dec_b[i]; }
+  return q;
+}
+#endif
+
+// ---- the route: what runs between the encoder and the loss for these dims and these options -----------------
+// np_route() is the ONE place that reads the dims' limits and the options tail_fused / tail_spec / conv2_tc; np_forward, np_backward,
+// np_scratch_carve and np_grads_flat_layout take its answer and pass it down.
+enum class Tail { Generic, Attention, Cnp };   // the operator chain below | tail_fused.h + tail_spec.h | tail_cnp.h + cnp_spec.h
+struct NpRoute {
+  Tail family;
+  Tail slab;            // whose per-task gradient slab the scratch reserves: every two-hidden-layer model of that aggregation, whatever
+                        // the options and the shot counts (wider than `family`; mlhot_np_scratch_bytes has always reported it so)
+  // Which launches are the kernels specialised for the shipped dimensions (false: the run-time-shaped ones).  The CNP tail is one
+  // kernel per direction: fwd_A is its forward, bwd_C its backward, the other four stay false.
+  bool fwd_A, fwd_B, fwd_C, bwd_C, bwd_B, bwd_A;
+  bool enc_fold;        // the first forward kernel folds the encoder Linear's split-K partial results (the encoder skips its own fold)
+  bool loss_in_kernel;  // the first backward kernel takes a loss descriptor itself (otherwise np_backward materialises the gradient)
+  bool bwd_B_split;     // B' as two workgroups per (task, head): query side | key / value side
+  int bwd_C_wg, bwd_A_wg;   // workgroups per task of C' (the CNP backward) and A': 1, 2 or 4
+};
+inline NpRoute np_route(const mlhot_np_dims& d) {
+  NpRoute r{};
+  r.bwd_C_wg = r.bwd_A_wg = 1;
+#ifndef MLHOT_HOSTSIM      // the host simulation has the operator chain only
+  static_assert(ts::XK == el::F_KS, "the first forward kernel folds the encoder Linear's split-K factor");
+  const bool attn = d.agg_mode == MLHOT_AGG_ATTENTION, pooled = d.agg_mode == MLHOT_AGG_MEAN || d.agg_mode == MLHOT_AGG_MAX;
+  if (d.Nc > 0 && d.n_hidden == 2) r.slab = attn ? Tail::Attention : pooled ? Tail::Cnp : Tail::Generic;
+  const bool one_tile = g_opt.tail_fused && d.Nc >= 1 && d.Nc <= 16 && d.Nq <= 16 && d.n_hidden == 2;   // a task's rows fit one 16-row tile
+  int spec = 0;
+  if (one_tile && attn && d.dim_w % 64 == 0 && d.dim_r == d.dim_w && d.m_feat <= 4096 &&
+      (long long)d.T * d.Nc * MLHOT_HEADS < (1ll << 19)) {      // key arg-max positions are packed row * 4096 + col
+    r.family = Tail::Attention;
+    if (ts::applies(tail_dims(d))) spec = g_opt.tail_spec;
+  } else if (one_tile && pooled && d.dim_w % 16 == 0 && d.dim_r <= 128) {
+    r.family = Tail::Cnp;
+    if (ts::cnp_applies(cnp_dims(d)))
+      spec = g_opt.tail_spec & (TAIL_SPEC_FWD_A | TAIL_SPEC_BWD_C | TAIL_SPEC_ENC_FOLD | TAIL_SPEC_LOSS | TAIL_SPEC_BWD_C_WG2 | TAIL_SPEC_WG4);
+  }
+  r.fwd_A = spec & TAIL_SPEC_FWD_A; r.fwd_B = spec & TAIL_SPEC_FWD_B; r.fwd_C = spec & TAIL_SPEC_FWD_C;
+  r.bwd_C = spec & TAIL_SPEC_BWD_C; r.bwd_B = spec & TAIL_SPEC_BWD_B; r.bwd_A = spec & TAIL_SPEC_BWD_A;
+  r.enc_fold = r.fwd_A && (spec & TAIL_SPEC_ENC_FOLD) && g_opt.conv2_tc && d.dim_w == el::DW;
+  r.loss_in_kernel = r.bwd_C && (spec & TAIL_SPEC_LOSS);
+  r.bwd_B_split = r.bwd_B && (spec & TAIL_SPEC_BWD_B_SPLIT);
+  const int wg = (spec & TAIL_SPEC_WG4) ? 4 : 2;
+  if (r.bwd_C && (spec & TAIL_SPEC_BWD_C_WG2)) r.bwd_C_wg = wg;
+  if (r.bwd_A && (spec & TAIL_SPEC_BWD_A_WG2)) r.bwd_A_wg = wg;
+#endif
+  return r;
+}
+
+// ---- the parameter table: the tail's parameters in the order their gradients lie in a per-task slab ----------
+// The slab layouts the kernels index (tf::TailSlab / tf::CnpSlab), the slab reduce's segments and the flat gradient layout are all
+// derived from tail_table(); the contiguous one-launch reduce is correct because they are.
+struct TailParam {
+  size_t grad;    // offsetof(mlhot_np_grads, .): its gradient pointer (a head stack's: the first of MLHOT_HEADS consecutive ones)
+  size_t field;   // offsetof(tf::TailSlab, .): the field a kernel reads its slab offset from (tf::CnpSlab: the same place)
+  int len;        // floats (of one head)
+  int heads;      // 1, or MLHOT_HEADS: a head stack, its heads' blocks back to back
+  bool attn;      // attention models only
+  int off;        // slab offset in floats; every entry starts 4-float aligned
+};
+struct TailTable { TailParam p[2 * (MLHOT_MAX_HIDDEN + 1) + 18]; int n, total; };
+#ifndef MLHOT_HOSTSIM
+#define MLHOT_TAIL_ROW(f, i) offsetof(mlhot_np_grads, f) + (i) * sizeof(float*), offsetof(tf::TailSlab, f) + (i) * sizeof(int)
+#else
+#define MLHOT_TAIL_ROW(f, i) offsetof(mlhot_np_grads, f) + (i) * sizeof(float*), 0      // no slabs without the fused tails
+#endif
+inline TailTable tail_table(const mlhot_np_dims& d) {
+  const int dw = d.dim_w, dr = d.dim_r, dz = d.dim_z, dh = d.dec_hidden, H = MLHOT_HEADS;
+  TailTable t{};
+  auto row = [&](size_t grad, size_t field, int len, int heads = 1, bool attn = false) {
+    t.p[t.n++] = TailParam{grad, field, len, heads, attn, t.total};
+    t.total += (len * heads + 3) / 4 * 4;
+  };
+  row(MLHOT_TAIL_ROW(ty_w, 0), dw / 4 * d.label_dim); row(MLHOT_TAIL_ROW(ty_b, 0), dw / 4);
+  for (int i = 0, in = dw + dw / 4; i <= d.n_hidden; ++i) {          // EncoderFC: the hidden layers, then the one onto dim_r
+    const int out = i < d.n_hidden ? d.hidden[i] : dr;
+    row(MLHOT_TAIL_ROW(er_w, i), out * in); row(MLHOT_TAIL_ROW(er_b, i), out);
+    in = out;
+  }
+  row(MLHOT_TAIL_ROW(r2z_w, 0), dz * dr); row(MLHOT_TAIL_ROW(r2z_b, 0), dz);
+  row(MLHOT_TAIL_ROW(dec_w, 0), dh * (dw + dz)); row(MLHOT_TAIL_ROW(dec_b, 0), dh);
+  row(MLHOT_TAIL_ROW(dec_w, 1), dh * dh); row(MLHOT_TAIL_ROW(dec_b, 1), dh);
+  row(MLHOT_TAIL_ROW(dec_w, 2), d.y_dim * dh); row(MLHOT_TAIL_ROW(dec_b, 2), d.y_dim);
+  if (d.agg_mode == MLHOT_AGG_ATTENTION) {                           // (dim_r == dim_w)
+    row(MLHOT_TAIL_ROW(wk_w, 0), dw * dw, H, true); row(MLHOT_TAIL_ROW(wk_b, 0), dw, H, true);
+    row(MLHOT_TAIL_ROW(wv_w, 0), dw * dw, H, true); row(MLHOT_TAIL_ROW(wv_b, 0), dw, H, true);
+    row(MLHOT_TAIL_ROW(wq_w, 0), dw * dw, H, true); row(MLHOT_TAIL_ROW(wq_b, 0), dw, H, true);
+    row(MLHOT_TAIL_ROW(wo_w, 0), dw * H * dw, 1, true); row(MLHOT_TAIL_ROW(wo_b, 0), dw, 1, true);
+  }
+  return t;
+}
+#undef MLHOT_TAIL_ROW
+// entry `r`'s (head `h`'s) pointer in a gradient block
+inline float*& tail_grad(mlhot_np_grads& g, const TailParam& r, int h = 0) {
+  return reinterpret_cast<float**>(reinterpret_cast<char*>(&g) + r.grad)[h];
+}
+
 struct NpScratch {
   void* enc; size_t enc_bytes;
   float *d_dec_in, *dd1, *dd2, *d_cat_in, *dh[MLHOT_MAX_HIDDEN], *d_rs;
@@ -67,7 +192,7 @@ struct NpScratch {
   bool ok; size_t bytes;
 };
 
-inline NpScratch np_scratch_carve(const mlhot_np_dims& d, void* base, size_t cap) {
+inline NpScratch np_scratch_carve(const mlhot_np_dims& d, const NpRoute& rt, void* base, size_t cap) {
   Arena a(base, cap);
   NpScratch s{};
   const size_t Rc = (size_t)d.T * d.Nc, Rq = (size_t)d.T * d.Nq;
@@ -84,22 +209,11 @@ inline NpScratch np_scratch_carve(const mlhot_np_dims& d, void* base, size_t cap
     if (d.agg_mode == MLHOT_AGG_ATTENTION) {
       s.d_rr = a.take<float>(Rq * dw); s.d_merged = a.take<float>(Rq * H * dw);
       s.dqh = a.take<float>(Rq * H * dw); s.dkh = a.take<float>(Rc * H * dw); s.dvh = a.take<float>(Rc * H * dw);
-#ifndef MLHOT_HOSTSIM
-      if (d.n_hidden == 2) {
-        const tf::TailDims td{d.T, d.Nc, d.Nq, d.label_dim, d.y_dim, dw, d.dim_z, d.hidden[0], d.hidden[1], d.dec_hidden, 0, d.m_feat};
-        s.tail_slab = a.take<float>((size_t)d.T * tf::tail_slab_layout(td).total);
-      }
-#endif
     } else {
       s.dzt = a.take<float>((size_t)d.T * d.dim_z); s.dr = a.take<float>((size_t)d.T * d.dim_r);
       if (d.agg_mode == MLHOT_AGG_BACO) { s.d_mu_l = a.take<float>(Rc * d.dim_r); s.d_lv = a.take<float>(Rc * d.dim_r); }
-#ifndef MLHOT_HOSTSIM
-      if (d.n_hidden == 2 && d.agg_mode != MLHOT_AGG_BACO) {
-        const tf::CnpDims cd{d.T, d.Nc, d.Nq, d.label_dim, d.y_dim, dw, d.dim_r, d.dim_z, d.hidden[0], d.hidden[1], d.dec_hidden, 0, d.agg_mode};
-        s.tail_slab = a.take<float>((size_t)d.T * tf::cnp_slab_layout(cd).total);
-      }
-#endif
     }
+    if (rt.slab != Tail::Generic) s.tail_slab = a.take<float>((size_t)d.T * tail_table(d).total);
   }
   s.ok = a.ok; s.bytes = a.off + 256;
   return s;
@@ -157,123 +271,52 @@ inline int lin_wgrad(const float* dy, int lddy, const float* y, int ldy, int act
 }
 
 #ifndef MLHOT_HOSTSIM
-// ---- fused tail (csrc/tail_fused.h) ---------------------------------------------------------------
-inline bool tail_fused_applies(const mlhot_np_dims& d) {
-  return g_opt.tail_fused && d.agg_mode == MLHOT_AGG_ATTENTION && d.Nc >= 1 && d.Nc <= 16 && d.Nq <= 16 &&
-         d.n_hidden == 2 && d.dim_w % 64 == 0 && d.dim_r == d.dim_w && d.m_feat <= 4096 &&
-         (long long)d.T * d.Nc * MLHOT_HEADS < (1ll << 19);      // key arg-max positions are packed row * 4096 + col
-}
-inline tf::TailDims tail_dims(const mlhot_np_dims& d) {
-  return tf::TailDims{d.T, d.Nc, d.Nq, d.label_dim, d.y_dim, d.dim_w, d.dim_z, d.hidden[0], d.hidden[1], d.dec_hidden,
-                      d.out_tanh ? ACT_TANH : ACT_NONE, d.m_feat};
-}
-inline tf::TailParams tail_params(const mlhot_np_params& p) {
-  tf::TailParams q;
-  q.ty_w = p.ty_w; q.ty_b = p.ty_b;
-  for (int i = 0; i < 3; ++i) { q.er_w[i] = p.er_w[i]; q.er_b[i] = p.er_b[i]; q.dec_w[i] = p.dec_w[i]; q.dec_b[i] = p.dec_b[i]; }
-  q.r2z_w = p.r2z_w; q.r2z_b = p.r2z_b;
-  for (int i = 0; i < MLHOT_HEADS; ++i) {
-    q.wk_w[i] = p.wk_w[i]; q.wk_b[i] = p.wk_b[i]; q.wv_w[i] = p.wv_w[i]; q.wv_b[i] = p.wv_b[i];
-    q.wq_w[i] = p.wq_w[i]; q.wq_b[i] = p.wq_b[i];
-  }
-  q.wo_w = p.wo_w; q.wo_b = p.wo_b; q.proj = p.proj;
-  return q;
-}
-template <class K, class A>
-inline int tail_launch(K kernel, int grid, int block, size_t lds, const A& args, hipStream_t s, const char* what) {
+// ---- the fused tails' launches (kernels: tail_fused.h / tail_spec.h, tail_cnp.h / cnp_spec.h) -----------------------
+template <class K, class A, class... More>
+inline int tail_launch(K kernel, int grid, int block, size_t lds, const A& args, hipStream_t s, const char* what, const More&... more) {
   if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
     set_error("%s: %zu bytes of LDS refused", what, lds);
     return MLHOT_ERR_LAUNCH;
   }
   {
     ProfScope ps(what, s);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, s, args);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, s, args, more...);
   }
   return check_launch(what);
 }
-
-// does phase A of this forward run the specialised kernel (which can fold the encoder Linear's partial results itself)?
-inline bool tail_phaseA_folds(const mlhot_np_dims& d) {
-  static_assert(ts::XK == el::F_KS, "phase A folds the encoder Linear's split-K factor");
-  return tail_fused_applies(d) && ts::applies(tail_dims(d)) && (g_opt.tail_spec & 1) && (g_opt.tail_spec & 64) && g_opt.conv2_tc && d.dim_w == el::DW;
-}
-inline int tail_forward_fused(const mlhot_np_dims& d, const mlhot_np_params& p, const float* ctx_y, float* mu,
-                              const NpBuf& b, const NpScratch& sc, hipStream_t s, const Stage& st = Stage{}, const EncXFold& xf = EncXFold{nullptr, nullptr, 0, 0}) {
-  const tf::TailDims td = tail_dims(d);
-  const tf::TailParams tp = tail_params(p);
-  FavorDims f{d.T, MLHOT_HEADS, d.Nq, d.Nc, d.dim_w, d.m_feat};
-  FavorWs w = favor_carve(f, b.favor, b.favor_bytes);
-  if (!w.ok || !sc.d_merged) { set_error("tail_fused: workspace"); return MLHOT_ERR_WORKSPACE; }
-  // the kernels specialised for the shipped dimensions (csrc/tail_spec.h) where they apply; the option is a bit mask over the
-  // phases (1 / 2 / 4: forward A / B / C, 8 / 16 / 32: backward C / B / A; default 63 = all; per-phase A/B experiments)
-  const int spec = ts::applies(td) ? g_opt.tail_spec : 0;
-  tf::PhaseAArgs a{g_opt.dbg, td, tp, ctx_y, b.cat_in, b.h[0], b.h[1], b.rs, b.dec_in, b.kh, w.pc, w.max_k, w.arg_k, b.wot, xf.slab, xf.bias, xf.k, xf.n};
-  if (xf.slab != nullptr && !(spec & 1)) { set_error("tail_fused: the encoder left its fold to a phase A that cannot do it"); return MLHOT_ERR_ARG; }
-  if (st.first()) {
-    if (spec & 1) MLHOT_TRY(tail_launch(ts::phaseA_fwd_kernel, d.T + d.T * MLHOT_HEADS + (xf.slab != nullptr ? d.T : 0), 512, ts::phaseA_lds_bytes(), a, s, "tail.A"));
-    else MLHOT_TRY(tail_launch(tf::phaseA_fwd_kernel, d.T + d.T * MLHOT_HEADS, 512, tf::phaseA_lds_bytes(td), a, s, "tail.A"));
-  }
-  // strict sharded parity (stab_xchg.h): phase B folds the (task, head) shares (max_k, arg_k) into the batch-global key stabiliser
-  if (st.stage == 0) return sx::max_publish(w.max_k, d.T * MLHOT_HEADS, st.x, s);
-  if (st.stage == 1) MLHOT_TRY(sx::max_apply(w.max_k, w.arg_k, d.T * MLHOT_HEADS, st.x, s));
-  tf::PhaseBArgs bb{td, tp, b.dec_in, b.rs, b.qh, b.vh, b.kh, w.pc, w.max_k, w.arg_k, w.qf, w.kf, w.S, w.D, w.gmax, w.arg_q, w.gpos, b.merged, sc.d_merged, b.wot};   // sc.d_merged: forward scratch for the heads' _W shares
-  if (spec & 2) MLHOT_TRY(tail_launch(ts::phaseB_fwd_kernel, d.T * MLHOT_HEADS, 512, ts::phaseB_lds_bytes(), bb, s, "tail.B"));
-  else MLHOT_TRY(tail_launch(tf::phaseB_fwd_kernel, d.T * MLHOT_HEADS, 512, tf::phaseB_lds_bytes(td), bb, s, "tail.B"));
-  tf::PhaseCArgs c{td, tp, sc.d_merged, b.rr, b.dec_in, b.d1, b.d2, mu};
-  if (spec & 4) MLHOT_TRY(tail_launch(ts::phaseC_fwd_kernel, d.T, 512, ts::phaseC_lds_bytes(), c, s, "tail.C"));
-  else MLHOT_TRY(tail_launch(tf::phaseC_fwd_kernel, d.T, 512, tf::phaseC_lds_bytes(td), c, s, "tail.C"));
-  return MLHOT_OK;
+// launch(integral_constant<G>) with G = wg: picks a kernel template's instance for 1, 2 or 4 workgroups per task
+template <class F>
+inline int with_wg(int wg, F launch) {
+  if (wg == 4) return launch(std::integral_constant<int, 4>{});
+  if (wg == 2) return launch(std::integral_constant<int, 2>{});
+  return launch(std::integral_constant<int, 1>{});
 }
 
-// ---- fused CNP tail (csrc/tail_cnp.h) ---------------------------------------------------------------
-inline bool cnp_fused_applies(const mlhot_np_dims& d) {
-  return g_opt.tail_fused && (d.agg_mode == MLHOT_AGG_MEAN || d.agg_mode == MLHOT_AGG_MAX) && d.Nc >= 1 && d.Nc <= 16 &&
-         d.Nq <= 16 && d.n_hidden == 2 && d.dim_w % 16 == 0 && d.dim_r <= 128;
-}
-inline tf::CnpDims cnp_dims(const mlhot_np_dims& d) {
-  return tf::CnpDims{d.T, d.Nc, d.Nq, d.label_dim, d.y_dim, d.dim_w, d.dim_r, d.dim_z, d.hidden[0], d.hidden[1], d.dec_hidden,
-                     d.out_tanh ? ACT_TANH : ACT_NONE, d.agg_mode};
-}
-inline tf::CnpParams cnp_params(const mlhot_np_params& p) {
-  tf::CnpParams q;
-  q.ty_w = p.ty_w; q.ty_b = p.ty_b; q.r2z_w = p.r2z_w; q.r2z_b = p.r2z_b;
-  for (int i = 0; i < 3; ++i) { q.er_w[i] = p.er_w[i]; q.er_b[i] = p.er_b[i]; q.dec_w[i] = p.dec_w[i]; q.dec_b[i] = p.dec_b[i]; }
-  return q;
-}
-// the kernels specialised for the shipped CNP dimensions (csrc/cnp_spec.h) where they apply; option tail_spec bits as for the
-// attention tail: 1 forward, 8 backward, 64 the forward folds the encoder Linear's partial results, 128 the backward takes the loss's
-// gradient from a descriptor, 1024 / 4096 two / four workgroups per task in the backward
-inline bool cnp_spec_applies(const mlhot_np_dims& d) { return cnp_fused_applies(d) && ts::cnp_applies(cnp_dims(d)); }
-inline bool cnp_spec_folds(const mlhot_np_dims& d) {
-  return cnp_spec_applies(d) && (g_opt.tail_spec & 1) && (g_opt.tail_spec & 64) && g_opt.conv2_tc && d.dim_w == el::DW;
-}
-template <class K, class... A>
-inline int cnp_spec_launch(K kernel, int grid, size_t lds, hipStream_t s, const char* what, const A&... args) {
-  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-    set_error("%s: %zu bytes of LDS refused", what, lds);
-    return MLHOT_ERR_LAUNCH;
-  }
-  {
-    ProfScope ps(what, s);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, s, args...);
-  }
-  return check_launch(what);
-}
-inline int cnp_forward_fused(const mlhot_np_dims& d, const mlhot_np_params& p, const float* ctx_y, float* mu, const NpBuf& b, hipStream_t s,
-                             const EncXFold& xf = EncXFold{nullptr, nullptr, 0, 0}) {
-  const tf::CnpDims cd = cnp_dims(d);
-  tf::CnpFwdArgs a{cd, cnp_params(p), ctx_y, b.cat_in, b.h[0], b.h[1], b.rs, b.r, b.zt, b.dec_in, b.d1, b.d2, mu, b.amax};
-  if (ts::cnp_applies(cd) && (g_opt.tail_spec & 1))
-    return cnp_spec_launch(ts::cnp_fwd_kernel, d.T, ts::cnp_fwd_lds_bytes(), s, "tail.cnp", a, ts::CnpXFold{xf.slab, xf.bias, xf.k, xf.n});
-  if (xf.slab != nullptr) { set_error("cnp_fused: the encoder left its fold to a tail kernel that cannot do it"); return MLHOT_ERR_ARG; }
-  return tail_launch(tf::cnp_fwd_kernel, d.T, 512, tf::cnp_fwd_lds_bytes(cd), a, s, "tail.cnp");
+// the kernels' slab-offset block, filled from the parameter table
+template <class Slab>
+inline Slab slab_layout(const TailTable& t) {
+  static_assert(offsetof(tf::CnpSlab, ty_w) == offsetof(tf::TailSlab, ty_w) && offsetof(tf::CnpSlab, er_w) == offsetof(tf::TailSlab, er_w) &&
+                offsetof(tf::CnpSlab, er_b) == offsetof(tf::TailSlab, er_b) && offsetof(tf::CnpSlab, r2z_w) == offsetof(tf::TailSlab, r2z_w) &&
+                offsetof(tf::CnpSlab, dec_w) == offsetof(tf::TailSlab, dec_w) && offsetof(tf::CnpSlab, dec_b) == offsetof(tf::TailSlab, dec_b),
+                "TailParam::field serves both slab blocks");
+  Slab sl{};
+  for (int i = 0; i < t.n; ++i) *reinterpret_cast<int*>(reinterpret_cast<char*>(&sl) + t.p[i].field) = t.p[i].off;
+  sl.total = t.total;
+  return sl;
 }
 // Per-task slabs -> parameter gradients.  When the caller laid the gradient tensors out as ONE flat buffer in slab
 // order (mlhot_np_grads_flat_layout) the reduce is a single contiguous float4 sum; otherwise every element looks up
 // its destination segment.
 // `later`: where a contiguous sum may be parked instead of launched (the encoder backward that follows folds it into its own
 // final reduce launch).
-inline int tail_slab_reduce(tf::SlabReduce& r, hipStream_t s, PendingSum* later = nullptr) {
+inline int tail_slab_reduce(const TailTable& t, const mlhot_np_grads& g, int T, const float* slab, hipStream_t s, PendingSum* later) {
+  static_assert(16 + 6 * MLHOT_HEADS + 2 <= tf::MAX_SEG, "one segment per gradient tensor");
+  tf::SlabReduce r{};
+  for (int i = 0; i < t.n; ++i)
+    for (int h = 0; h < t.p[i].heads; ++h, ++r.nseg) {
+      r.dst[r.nseg] = reinterpret_cast<float* const*>(reinterpret_cast<const char*>(&g) + t.p[i].grad)[h]; r.off[r.nseg] = t.p[i].off + h * t.p[i].len; r.len[r.nseg] = t.p[i].len;
+    }
+  r.T = T; r.total = t.total; r.slab = slab;
   bool flat = r.nseg > 0 && r.off[0] == 0 && (reinterpret_cast<uintptr_t>(r.dst[0]) & 15) == 0 && (r.total & 3) == 0;
   for (int i = 1; flat && i < r.nseg; ++i) flat = r.dst[i] == r.dst[0] + r.off[i];
   if (flat && later != nullptr) {
@@ -288,153 +331,118 @@ inline int tail_slab_reduce(tf::SlabReduce& r, hipStream_t s, PendingSum* later 
   return check_launch("tail.bwd.reduce");
 }
 
-inline int cnp_backward_fused(const mlhot_np_dims& d, const mlhot_np_params& p, const float* ctx_y, const float* mu, const float* dmu,
-                              const mlhot_np_grads& g, const NpBuf& b, const NpScratch& sc, hipStream_t s, PendingSum* later,
-                              const LossDesc& loss = LossDesc{-1, nullptr, 0, nullptr, nullptr}) {
-  const tf::CnpDims cd = cnp_dims(d);
-  const tf::CnpSlab sl = tf::cnp_slab_layout(cd);
-  if (!sc.tail_slab) { set_error("cnp_fused: workspace"); return MLHOT_ERR_WORKSPACE; }
-  tf::CnpBwdArgs a{cd, cnp_params(p), sl, ctx_y, dmu, mu, b.d2, b.d1, b.dec_in, b.r, b.rs, b.h[1], b.h[0], b.cat_in, b.amax,
-                   sc.d_dec_in, sc.d_cat_in, sc.tail_slab};
-  if (ts::cnp_applies(cd) && (g_opt.tail_spec & 8)) {
-    const int gr = (g_opt.tail_spec & 1024) ? ((g_opt.tail_spec & 4096) ? 4 : 2) : 1;
-    const int lv = loss.value != nullptr ? 1 : 0;           // one workgroup more: the loss value
-    if (gr == 4) MLHOT_TRY(cnp_spec_launch(ts::cnp_bwd_kernel<4>, 4 * d.T + lv, ts::cnp_bwd_lds_bytes(), s, "tail.bwd.cnp", a, loss));
-    else if (gr == 2) MLHOT_TRY(cnp_spec_launch(ts::cnp_bwd_kernel<2>, 2 * d.T + lv, ts::cnp_bwd_lds_bytes(), s, "tail.bwd.cnp", a, loss));
-    else MLHOT_TRY(cnp_spec_launch(ts::cnp_bwd_kernel<1>, d.T + lv, ts::cnp_bwd_lds_bytes(), s, "tail.bwd.cnp", a, loss));
-  } else {
-    if (loss.kind >= 0) { set_error("cnp_fused: a loss descriptor reached a backward kernel that cannot take it"); return MLHOT_ERR_ARG; }
-    MLHOT_TRY(tail_launch(tf::cnp_bwd_kernel, d.T, 512, tf::cnp_bwd_lds_bytes(cd), a, s, "tail.bwd.cnp"));
-  }
-  tf::SlabReduce r{};
-  int ns = 0, maxlen = 0;
-  auto seg = [&](float* dst, int off, int len) { r.dst[ns] = dst; r.off[ns] = off; r.len[ns] = len; if (len > maxlen) maxlen = len; ++ns; };
-  const int dw = d.dim_w, ldc = dw + dw / 4, ldd = dw + d.dim_z;
-  seg(g.ty_w, sl.ty_w, dw / 4 * d.label_dim); seg(g.ty_b, sl.ty_b, dw / 4);
-  seg(g.er_w[0], sl.er_w[0], cd.h0 * ldc); seg(g.er_b[0], sl.er_b[0], cd.h0);
-  seg(g.er_w[1], sl.er_w[1], cd.h1 * cd.h0); seg(g.er_b[1], sl.er_b[1], cd.h1);
-  seg(g.er_w[2], sl.er_w[2], cd.dr * cd.h1); seg(g.er_b[2], sl.er_b[2], cd.dr);
-  seg(g.r2z_w, sl.r2z_w, d.dim_z * cd.dr); seg(g.r2z_b, sl.r2z_b, d.dim_z);
-  seg(g.dec_w[0], sl.dec_w[0], cd.dec_h * ldd); seg(g.dec_b[0], sl.dec_b[0], cd.dec_h);
-  seg(g.dec_w[1], sl.dec_w[1], cd.dec_h * cd.dec_h); seg(g.dec_b[1], sl.dec_b[1], cd.dec_h);
-  seg(g.dec_w[2], sl.dec_w[2], d.y_dim * cd.dec_h); seg(g.dec_b[2], sl.dec_b[2], d.y_dim);
-  r.nseg = ns; r.T = d.T; r.total = sl.total; r.slab = sc.tail_slab;
-  (void)maxlen;
-  return tail_slab_reduce(r, s, later);
+// ---- fused attention tail ---------------------------------------------------------------------------
+struct TailView { tf::TailDims td; tf::TailParams tp; FavorWs w; };   // what its forward and its backward both build their arguments from
+inline TailView tail_view(const mlhot_np_dims& d, const mlhot_np_params& p, const NpBuf& b) {
+  const FavorDims f{d.T, MLHOT_HEADS, d.Nq, d.Nc, d.dim_w, d.m_feat};
+  return TailView{tail_dims(d), tail_params(p), favor_carve(f, b.favor, b.favor_bytes)};
 }
-
-inline int tail_backward_fused(const mlhot_np_dims& d, const mlhot_np_params& p, const float* ctx_y, const float* mu,
+inline int tail_forward_fused(const mlhot_np_dims& d, const mlhot_np_params& p, const NpRoute& rt, const float* ctx_y, float* mu,
+                              const NpBuf& b, const NpScratch& sc, hipStream_t s, const Stage& st, const EncXFold& xf) {
+  const TailView v = tail_view(d, p, b);
+  const tf::TailDims& td = v.td; const tf::TailParams& tp = v.tp; const FavorWs& w = v.w;
+  const int TH = d.T * MLHOT_HEADS;
+  if (!w.ok || !sc.d_merged) { set_error("tail_fused: workspace"); return MLHOT_ERR_WORKSPACE; }
+  tf::PhaseAArgs a{g_opt.dbg, td, tp, ctx_y, b.cat_in, b.h[0], b.h[1], b.rs, b.dec_in, b.kh, w.pc, w.max_k, w.arg_k, b.wot, xf.slab, xf.bias, xf.k, xf.n};
+  if (xf.slab != nullptr && !rt.fwd_A) { set_error("tail_fused: the encoder left its fold to a phase A that cannot do it"); return MLHOT_ERR_ARG; }
+  if (st.first()) {
+    if (rt.fwd_A) MLHOT_TRY(tail_launch(ts::phaseA_fwd_kernel, d.T + TH + (xf.slab != nullptr ? d.T : 0), 512, ts::phaseA_lds_bytes(), a, s, "tail.A"));
+    else MLHOT_TRY(tail_launch(tf::phaseA_fwd_kernel, d.T + TH, 512, tf::phaseA_lds_bytes(td), a, s, "tail.A"));
+  }
+  // strict sharded parity (stab_xchg.h): phase B folds the (task, head) shares (max_k, arg_k) into the batch-global key stabiliser
+  if (st.stage == 0) return sx::max_publish(w.max_k, TH, st.x, s);
+  if (st.stage == 1) MLHOT_TRY(sx::max_apply(w.max_k, w.arg_k, TH, st.x, s));
+  tf::PhaseBArgs bb{td, tp, b.dec_in, b.rs, b.qh, b.vh, b.kh, w.pc, w.max_k, w.arg_k, w.qf, w.kf, w.S, w.D, w.gmax, w.arg_q, w.gpos, b.merged, sc.d_merged, b.wot};   // sc.d_merged: forward scratch for the heads' _W shares
+  if (rt.fwd_B) MLHOT_TRY(tail_launch(ts::phaseB_fwd_kernel, TH, 512, ts::phaseB_lds_bytes(), bb, s, "tail.B"));
+  else MLHOT_TRY(tail_launch(tf::phaseB_fwd_kernel, TH, 512, tf::phaseB_lds_bytes(td), bb, s, "tail.B"));
+  tf::PhaseCArgs c{td, tp, sc.d_merged, b.rr, b.dec_in, b.d1, b.d2, mu};
+  if (rt.fwd_C) MLHOT_TRY(tail_launch(ts::phaseC_fwd_kernel, d.T, 512, ts::phaseC_lds_bytes(), c, s, "tail.C"));
+  else MLHOT_TRY(tail_launch(tf::phaseC_fwd_kernel, d.T, 512, tf::phaseC_lds_bytes(td), c, s, "tail.C"));
+  return MLHOT_OK;
+}
+inline int tail_backward_fused(const mlhot_np_dims& d, const mlhot_np_params& p, const NpRoute& rt, const float* ctx_y, const float* mu,
                                const float* dmu, const mlhot_np_grads& g, const NpBuf& b, const NpScratch& sc, hipStream_t s,
-                               PendingSum* later, const Stage& st = Stage{}, const LossDesc& loss = LossDesc{-1, nullptr, 0, nullptr, nullptr}) {
-  const tf::TailDims td = tail_dims(d);
-  const tf::TailParams tp = tail_params(p);
-  const tf::TailSlab sl = tf::tail_slab_layout(td);
-  FavorDims f{d.T, MLHOT_HEADS, d.Nq, d.Nc, d.dim_w, d.m_feat};
-  FavorWs w = favor_carve(f, b.favor, b.favor_bytes);
+                               PendingSum* later, const Stage& st, const LossDesc& loss) {
+  const TailView v = tail_view(d, p, b);
+  const tf::TailDims& td = v.td; const tf::TailParams& tp = v.tp; const FavorWs& w = v.w;
+  const TailTable tab = tail_table(d);
+  const tf::TailSlab sl = slab_layout<tf::TailSlab>(tab);
+  const int TH = d.T * MLHOT_HEADS;
   if (!w.ok || !sc.tail_slab) { set_error("tail_fused: workspace"); return MLHOT_ERR_WORKSPACE; }
   float* part_k = w.rsum_k;   // [T*H]
   tf::PhaseCBwdArgs c{td, tp, sl, dmu, mu, b.d2, b.d1, b.dec_in, b.rr, sc.d_dec_in, sc.d_rr, sc.tail_slab, loss};
-  const int spec = ts::applies(td) ? g_opt.tail_spec : 0;
-  if (loss.kind >= 0 && !(spec & 8)) { set_error("tail_fused: a loss descriptor reached a phase C' that cannot take it"); return MLHOT_ERR_ARG; }
-  if (st.first()) {
-    const int lv = loss.value != nullptr ? 1 : 0;           // one workgroup more: the loss value
-    if ((spec & 8) && (spec & 1024) && (spec & 4096)) MLHOT_TRY(tail_launch(ts::phaseC_bwd_kernel<4>, 4 * d.T + lv, 512, ts::phaseC_bwd_lds_bytes(), c, s, "tail.bwd.C"));
-    else if ((spec & 8) && (spec & 1024)) MLHOT_TRY(tail_launch(ts::phaseC_bwd_kernel<2>, 2 * d.T + lv, 512, ts::phaseC_bwd_lds_bytes(), c, s, "tail.bwd.C"));
-    else if (spec & 8) MLHOT_TRY(tail_launch(ts::phaseC_bwd_kernel<1>, d.T + lv, 512, ts::phaseC_bwd_lds_bytes(), c, s, "tail.bwd.C"));
-    else MLHOT_TRY(tail_launch(tf::phaseC_bwd_kernel, d.T, 512, tf::phaseC_bwd_lds_bytes(td), c, s, "tail.bwd.C"));
-  }
+  if (loss.kind >= 0 && !rt.loss_in_kernel) { set_error("tail_fused: a loss descriptor reached a phase C' that cannot take it"); return MLHOT_ERR_ARG; }
   // sc.dqh / dkh / dvh double as the heads' input-gradient shares [T*H][N][dw] (same sizes)
   tf::PhaseBBwdArgs bb{td, tp, sl, b.qh, b.kh, b.vh, w.pc, w.qf, w.kf, w.S, w.D, b.merged, sc.d_rr, w.arg_q,
                        b.dec_in, b.cat_in, b.rs, b.wot, sc.dqh, sc.dkh, sc.dvh, part_k, sc.tail_slab};
   if (st.first()) {
-    if ((spec & 16) && (spec & 512)) MLHOT_TRY(tail_launch(ts::phaseB_bwd_kernel<true>, 2 * d.T * MLHOT_HEADS, 512, ts::phaseB_bwd_lds_bytes(), bb, s, "tail.bwd.B"));
-    else if (spec & 16) MLHOT_TRY(tail_launch(ts::phaseB_bwd_kernel<false>, d.T * MLHOT_HEADS, 512, ts::phaseB_bwd_lds_bytes(), bb, s, "tail.bwd.B"));
-    else MLHOT_TRY(tail_launch(tf::phaseB_bwd_kernel, d.T * MLHOT_HEADS, 512, tf::phaseB_bwd_lds_bytes(td), bb, s, "tail.bwd.B"));
+    const int lv = loss.value != nullptr ? 1 : 0;           // one workgroup more: the loss value
+    if (rt.bwd_C) MLHOT_TRY(with_wg(rt.bwd_C_wg, [&](auto G) { return tail_launch(ts::phaseC_bwd_kernel<decltype(G)::value>, G * d.T + lv, 512, ts::phaseC_bwd_lds_bytes(), c, s, "tail.bwd.C"); }));
+    else MLHOT_TRY(tail_launch(tf::phaseC_bwd_kernel, d.T, 512, tf::phaseC_bwd_lds_bytes(td), c, s, "tail.bwd.C"));
+    if (rt.bwd_B_split) MLHOT_TRY(tail_launch(ts::phaseB_bwd_kernel<true>, 2 * TH, 512, ts::phaseB_bwd_lds_bytes(), bb, s, "tail.bwd.B"));
+    else if (rt.bwd_B) MLHOT_TRY(tail_launch(ts::phaseB_bwd_kernel<false>, TH, 512, ts::phaseB_bwd_lds_bytes(), bb, s, "tail.bwd.B"));
+    else MLHOT_TRY(tail_launch(tf::phaseB_bwd_kernel, TH, 512, tf::phaseB_bwd_lds_bytes(td), bb, s, "tail.bwd.B"));
   }
   // strict sharded parity: phase A folds part_k into the stabiliser's gradient and routes it to the arg-max key's task
-  if (st.stage == 0) return sx::sum_publish(part_k, d.T * MLHOT_HEADS, st.x, s);
-  if (st.stage == 1) MLHOT_TRY(sx::sum_apply(part_k, d.T * MLHOT_HEADS, st.x, part_k, 1, s));
+  if (st.stage == 0) return sx::sum_publish(part_k, TH, st.x, s);
+  if (st.stage == 1) MLHOT_TRY(sx::sum_apply(part_k, TH, st.x, part_k, 1, s));
   tf::PhaseABwdArgs a{td, tp, sl, ctx_y, b.cat_in, b.h[0], b.h[1], sc.dqh, sc.dkh, sc.dvh, w.pc, part_k, w.gpos,
                       sc.d_dec_in, sc.d_cat_in, sc.tail_slab};
-  if ((spec & 32) && (spec & 2048) && (spec & 4096)) MLHOT_TRY(tail_launch(ts::phaseA_bwd_kernel<4>, 4 * d.T, 512, ts::phaseA_bwd_lds_bytes(), a, s, "tail.bwd.A"));
-  else if ((spec & 32) && (spec & 2048)) MLHOT_TRY(tail_launch(ts::phaseA_bwd_kernel<2>, 2 * d.T, 512, ts::phaseA_bwd_lds_bytes(), a, s, "tail.bwd.A"));
-  else if (spec & 32) MLHOT_TRY(tail_launch(ts::phaseA_bwd_kernel<1>, d.T, 512, ts::phaseA_bwd_lds_bytes(), a, s, "tail.bwd.A"));
+  if (rt.bwd_A) MLHOT_TRY(with_wg(rt.bwd_A_wg, [&](auto G) { return tail_launch(ts::phaseA_bwd_kernel<decltype(G)::value>, G * d.T, 512, ts::phaseA_bwd_lds_bytes(), a, s, "tail.bwd.A"); }));
   else MLHOT_TRY(tail_launch(tf::phaseA_bwd_kernel, d.T, 512, tf::phaseA_bwd_lds_bytes(td), a, s, "tail.bwd.A"));
-  // per-task slabs -> parameter gradients
-  tf::SlabReduce r{};
-  int ns = 0, maxlen = 0;
-  auto seg = [&](float* dst, int off, int len) { r.dst[ns] = dst; r.off[ns] = off; r.len[ns] = len; if (len > maxlen) maxlen = len; ++ns; };
-  const int dw = d.dim_w, ldc = dw + dw / 4, ldd = dw + d.dim_z;
-  seg(g.ty_w, sl.ty_w, dw / 4 * d.label_dim); seg(g.ty_b, sl.ty_b, dw / 4);
-  seg(g.er_w[0], sl.er_w[0], td.h0 * ldc); seg(g.er_b[0], sl.er_b[0], td.h0);
-  seg(g.er_w[1], sl.er_w[1], td.h1 * td.h0); seg(g.er_b[1], sl.er_b[1], td.h1);
-  seg(g.er_w[2], sl.er_w[2], dw * td.h1); seg(g.er_b[2], sl.er_b[2], dw);
-  seg(g.r2z_w, sl.r2z_w, d.dim_z * dw); seg(g.r2z_b, sl.r2z_b, d.dim_z);
-  seg(g.dec_w[0], sl.dec_w[0], td.dec_h * ldd); seg(g.dec_b[0], sl.dec_b[0], td.dec_h);
-  seg(g.dec_w[1], sl.dec_w[1], td.dec_h * td.dec_h); seg(g.dec_b[1], sl.dec_b[1], td.dec_h);
-  seg(g.dec_w[2], sl.dec_w[2], d.y_dim * td.dec_h); seg(g.dec_b[2], sl.dec_b[2], d.y_dim);
-  for (int i = 0; i < MLHOT_HEADS; ++i) {
-    seg(g.wk_w[i], sl.wk_w + i * dw * dw, dw * dw); seg(g.wk_b[i], sl.wk_b + i * dw, dw);
-    seg(g.wv_w[i], sl.wv_w + i * dw * dw, dw * dw); seg(g.wv_b[i], sl.wv_b + i * dw, dw);
-    seg(g.wq_w[i], sl.wq_w + i * dw * dw, dw * dw); seg(g.wq_b[i], sl.wq_b + i * dw, dw);
+  return tail_slab_reduce(tab, g, d.T, sc.tail_slab, s, later);
+}
+
+// ---- fused CNP tail: one kernel per direction ----------------------------------------------------------
+inline int cnp_forward_fused(const mlhot_np_dims& d, const mlhot_np_params& p, const NpRoute& rt, const float* ctx_y, float* mu,
+                             const NpBuf& b, hipStream_t s, const EncXFold& xf) {
+  const tf::CnpDims cd = cnp_dims(d);
+  tf::CnpFwdArgs a{cd, cnp_params(p), ctx_y, b.cat_in, b.h[0], b.h[1], b.rs, b.r, b.zt, b.dec_in, b.d1, b.d2, mu, b.amax};
+  if (rt.fwd_A) return tail_launch(ts::cnp_fwd_kernel, d.T, 512, ts::cnp_fwd_lds_bytes(), a, s, "tail.cnp", ts::CnpXFold{xf.slab, xf.bias, xf.k, xf.n});
+  if (xf.slab != nullptr) { set_error("cnp_fused: the encoder left its fold to a tail kernel that cannot do it"); return MLHOT_ERR_ARG; }
+  return tail_launch(tf::cnp_fwd_kernel, d.T, 512, tf::cnp_fwd_lds_bytes(cd), a, s, "tail.cnp");
+}
+inline int cnp_backward_fused(const mlhot_np_dims& d, const mlhot_np_params& p, const NpRoute& rt, const float* ctx_y, const float* mu,
+                              const float* dmu, const mlhot_np_grads& g, const NpBuf& b, const NpScratch& sc, hipStream_t s,
+                              PendingSum* later, const LossDesc& loss) {
+  const tf::CnpDims cd = cnp_dims(d);
+  const TailTable tab = tail_table(d);
+  if (!sc.tail_slab) { set_error("cnp_fused: workspace"); return MLHOT_ERR_WORKSPACE; }
+  tf::CnpBwdArgs a{cd, cnp_params(p), slab_layout<tf::CnpSlab>(tab), ctx_y, dmu, mu, b.d2, b.d1, b.dec_in, b.r, b.rs, b.h[1], b.h[0], b.cat_in, b.amax,
+                   sc.d_dec_in, sc.d_cat_in, sc.tail_slab};
+  if (rt.bwd_C) {
+    const int lv = loss.value != nullptr ? 1 : 0;           // one workgroup more: the loss value
+    MLHOT_TRY(with_wg(rt.bwd_C_wg, [&](auto G) { return tail_launch(ts::cnp_bwd_kernel<decltype(G)::value>, G * d.T + lv, 512, ts::cnp_bwd_lds_bytes(), a, s, "tail.bwd.cnp", loss); }));
+  } else {
+    if (loss.kind >= 0) { set_error("cnp_fused: a loss descriptor reached a backward kernel that cannot take it"); return MLHOT_ERR_ARG; }
+    MLHOT_TRY(tail_launch(tf::cnp_bwd_kernel, d.T, 512, tf::cnp_bwd_lds_bytes(cd), a, s, "tail.bwd.cnp"));
   }
-  seg(g.wo_w, sl.wo_w, dw * MLHOT_HEADS * dw); seg(g.wo_b, sl.wo_b, dw);
-  r.nseg = ns; r.T = d.T; r.total = sl.total; r.slab = sc.tail_slab;
-  (void)maxlen;
-  return tail_slab_reduce(r, s, later);
+  return tail_slab_reduce(tab, g, d.T, sc.tail_slab, s, later);
 }
 #endif
 
 // Layout of ONE flat gradient buffer: the fused tails' parameters at their slab offsets (so the per-task slabs reduce
 // with a single contiguous sum), everything else packed behind, 4-float aligned.  `o` receives BYTE offsets in its
 // pointer fields (fields of parameters the model does not have stay null); returns the buffer size in floats.
-inline size_t np_grads_flat_layout(const mlhot_np_dims& d, mlhot_np_grads& o) {
+inline size_t np_grads_flat_layout(const mlhot_np_dims& d, const NpRoute& rt, mlhot_np_grads& o) {
   memset(&o, 0, sizeof(o));
-  const int dw = d.dim_w, ldc = dw + dw / 4, ldd = dw + d.dim_z, H = MLHOT_HEADS;
-  const bool attn = d.agg_mode == MLHOT_AGG_ATTENTION, baco = d.agg_mode == MLHOT_AGG_BACO;
+  const int dw = d.dim_w;
   size_t next = 0;
   auto at = [](size_t off_floats) { return reinterpret_cast<float*>(off_floats * sizeof(float)); };
   auto take = [&](size_t n) { const size_t r = next; next += (n + 3) / 4 * 4; return at(r); };
-  bool tail_done = false;
-#ifndef MLHOT_HOSTSIM
-  if (d.Nc > 0 && tail_fused_applies(d)) {
-    const tf::TailSlab sl = tf::tail_slab_layout(tail_dims(d));
-    o.ty_w = at(sl.ty_w); o.ty_b = at(sl.ty_b);
-    for (int i = 0; i < 3; ++i) { o.er_w[i] = at(sl.er_w[i]); o.er_b[i] = at(sl.er_b[i]); o.dec_w[i] = at(sl.dec_w[i]); o.dec_b[i] = at(sl.dec_b[i]); }
-    o.r2z_w = at(sl.r2z_w); o.r2z_b = at(sl.r2z_b);
-    for (int h = 0; h < H; ++h) {
-      o.wk_w[h] = at(sl.wk_w + (size_t)h * dw * dw); o.wk_b[h] = at(sl.wk_b + (size_t)h * dw);
-      o.wv_w[h] = at(sl.wv_w + (size_t)h * dw * dw); o.wv_b[h] = at(sl.wv_b + (size_t)h * dw);
-      o.wq_w[h] = at(sl.wq_w + (size_t)h * dw * dw); o.wq_b[h] = at(sl.wq_b + (size_t)h * dw);
-    }
-    o.wo_w = at(sl.wo_w); o.wo_b = at(sl.wo_b);
-    next = sl.total; tail_done = true;
-  } else if (d.Nc > 0 && cnp_fused_applies(d)) {
-    const tf::CnpSlab sl = tf::cnp_slab_layout(cnp_dims(d));
-    o.ty_w = at(sl.ty_w); o.ty_b = at(sl.ty_b);
-    for (int i = 0; i < 3; ++i) { o.er_w[i] = at(sl.er_w[i]); o.er_b[i] = at(sl.er_b[i]); o.dec_w[i] = at(sl.dec_w[i]); o.dec_b[i] = at(sl.dec_b[i]); }
-    o.r2z_w = at(sl.r2z_w); o.r2z_b = at(sl.r2z_b);
-    next = sl.total; tail_done = true;
+  const TailTable t = tail_table(d);
+  const TailParam* const end = t.p + t.n;
+  if (rt.family != Tail::Generic) {
+    for (const TailParam* r = t.p; r != end; ++r)
+      for (int h = 0; h < r->heads; ++h) tail_grad(o, *r, h) = at(r->off + (size_t)h * r->len);
+    next = t.total;
+  } else {      // the table's order, except that the head stacks lie head by head: k, v, q of head 0, of head 1, ...
+    for (const TailParam* r = t.p; r != end; ++r) if (!r->attn) tail_grad(o, *r) = take(r->len);
+    for (int h = 0; h < MLHOT_HEADS; ++h)
+      for (const TailParam* r = t.p; r != end; ++r) if (r->heads > 1) tail_grad(o, *r, h) = take(r->len);
+    for (const TailParam* r = t.p; r != end; ++r) if (r->attn && r->heads == 1) tail_grad(o, *r) = take(r->len);
   }
-#endif
-  if (!tail_done) {
-    o.ty_w = take((size_t)dw / 4 * d.label_dim); o.ty_b = take(dw / 4);
-    int in = ldc;
-    for (int i = 0; i < d.n_hidden; ++i) { o.er_w[i] = take((size_t)d.hidden[i] * in); o.er_b[i] = take(d.hidden[i]); in = d.hidden[i]; }
-    o.er_w[d.n_hidden] = take((size_t)d.dim_r * in); o.er_b[d.n_hidden] = take(d.dim_r);
-    o.r2z_w = take((size_t)d.dim_z * d.dim_r); o.r2z_b = take(d.dim_z);
-    o.dec_w[0] = take((size_t)d.dec_hidden * ldd); o.dec_b[0] = take(d.dec_hidden);
-    o.dec_w[1] = take((size_t)d.dec_hidden * d.dec_hidden); o.dec_b[1] = take(d.dec_hidden);
-    o.dec_w[2] = take((size_t)d.y_dim * d.dec_hidden); o.dec_b[2] = take(d.y_dim);
-    if (attn) {
-      for (int h = 0; h < H; ++h) {
-        o.wk_w[h] = take((size_t)dw * dw); o.wk_b[h] = take(dw); o.wv_w[h] = take((size_t)dw * dw); o.wv_b[h] = take(dw);
-        o.wq_w[h] = take((size_t)dw * dw); o.wq_b[h] = take(dw);
-      }
-      o.wo_w = take((size_t)dw * H * dw); o.wo_b = take(dw);
-    }
-  }
-  if (baco) {
+  if (d.agg_mode == MLHOT_AGG_BACO) {
     o.mu_w = take((size_t)d.dim_r * d.dim_r); o.mu_b = take(d.dim_r); o.var_w = take((size_t)d.dim_r * d.dim_r); o.var_b = take(d.dim_r);
   }
   o.enc.w1 = take(32 * 9); o.enc.b1 = take(32); o.enc.w2 = take(48 * 288); o.enc.b2 = take(48);
@@ -448,31 +456,25 @@ inline int np_forward(const mlhot_np_dims& d, const mlhot_np_params& p, const fl
   MLHOT_TRY(np_check_dims(d));
   MLHOT_TRY(stage_check(st, "np_vanilla_fwd"));
   NpBuf b = np_saved_carve(d, saved, (size_t)-1 / 2);
-  NpScratch sc = np_scratch_carve(d, scratch, scratch_bytes);
+  const NpRoute rt = np_route(d);
+  NpScratch sc = np_scratch_carve(d, rt, scratch, scratch_bytes);
   if (!sc.ok) { set_error("np_vanilla_fwd: scratch too small (%zu < %zu)", scratch_bytes, sc.bytes); return MLHOT_ERR_WORKSPACE; }
   const int Rc = d.T * d.Nc, Rq = d.T * d.Nq, dw = d.dim_w, H = MLHOT_HEADS;
   const int ldc = dw + dw / 4, ldd = dw + d.dim_z;
 
   // E1 on [context | target] images in one pass; rows land in cat_in / dec_in
-#ifndef MLHOT_HOSTSIM
-  const bool fused = tail_fused_applies(d);
-#else
-  const bool fused = false;
-#endif
-  if (st.staged() && !fused) {      // the staged pass is built on the fused attention tail's launch boundaries
+  if (st.staged() && rt.family != Tail::Attention) {      // the staged pass is built on the fused attention tail's launch boundaries
     set_error("np_vanilla_fwd: staged passes need the fused attention tail (attention aggregation, Nc, Nq <= 16, option tail_fused)");
     return MLHOT_ERR_UNSUPPORTED;
   }
-#ifndef MLHOT_HOSTSIM
   EncXFold xf{nullptr, nullptr, 0, 0};
-  const bool cnp_folds = !fused && cnp_spec_folds(d);
   if (st.first()) MLHOT_TRY(enc_forward(ctx_x, Rc, qry_x, Rq, p.enc, dw, Rows2{b.cat_in, ldc, Rc, b.dec_in, ldd}, b.enc, sc.enc, sc.enc_bytes, s,
-                                        (fused && tail_phaseA_folds(d)) || cnp_folds ? &xf : nullptr));
-  if (fused) return tail_forward_fused(d, p, ctx_y, mu, b, sc, s, st, xf);
-  if (cnp_fused_applies(d)) return cnp_forward_fused(d, p, ctx_y, mu, b, s, xf);
-#else
-  if (st.first()) MLHOT_TRY(enc_forward(ctx_x, Rc, qry_x, Rq, p.enc, dw, Rows2{b.cat_in, ldc, Rc, b.dec_in, ldd}, b.enc, sc.enc, sc.enc_bytes, s));
+                                        rt.enc_fold ? &xf : nullptr));
+#ifndef MLHOT_HOSTSIM
+  if (rt.family == Tail::Attention) return tail_forward_fused(d, p, rt, ctx_y, mu, b, sc, s, st, xf);
+  if (rt.family == Tail::Cnp) return cnp_forward_fused(d, p, rt, ctx_y, mu, b, s, xf);
 #endif
+
 
   if (d.Nc > 0) {
     MLHOT_TRY(lin_fwd(ctx_y, d.label_dim, wb1(p.ty_w, p.ty_b, dw / 4), b.cat_in + dw, ldc, Rc, d.label_dim, dw / 4, ACT_NONE, s, "np.transform_y"));
@@ -519,7 +521,8 @@ inline int np_backward(const mlhot_np_dims& d, const mlhot_np_params& p, const f
   MLHOT_TRY(np_check_dims(d));
   MLHOT_TRY(stage_check(st, "np_vanilla_bwd"));
   NpBuf b = np_saved_carve(d, (void*)saved, (size_t)-1 / 2);
-  NpScratch sc = np_scratch_carve(d, scratch, scratch_bytes);
+  const NpRoute rt = np_route(d);
+  NpScratch sc = np_scratch_carve(d, rt, scratch, scratch_bytes);
   if (!sc.ok) { set_error("np_vanilla_bwd: scratch too small (%zu < %zu)", scratch_bytes, sc.bytes); return MLHOT_ERR_WORKSPACE; }
   const int Rc = d.T * d.Nc, Rq = d.T * d.Nq, dw = d.dim_w, H = MLHOT_HEADS, dh = d.dec_hidden;
   const int ldc = dw + dw / 4, ldd = dw + d.dim_z;
@@ -530,10 +533,7 @@ inline int np_backward(const mlhot_np_dims& d, const mlhot_np_params& p, const f
   LossDesc in_kernel{-1, nullptr, 0, nullptr, nullptr};
   if (loss != nullptr) {
     if (st.staged()) { set_error("np_vanilla_bwd: the staged pass takes dmu, not a loss descriptor"); return MLHOT_ERR_UNSUPPORTED; }
-#ifndef MLHOT_HOSTSIM
-    if (tail_fused_applies(d) && ts::applies(tail_dims(d)) && (g_opt.tail_spec & 8) && (g_opt.tail_spec & 128)) in_kernel = *loss;
-    if (!tail_fused_applies(d) && cnp_spec_applies(d) && (g_opt.tail_spec & 8) && (g_opt.tail_spec & 128)) in_kernel = *loss;
-#endif
+    if (rt.loss_in_kernel) in_kernel = *loss;
     if (in_kernel.kind < 0) {
       // (the loss VALUE, when the caller left that to this call as well: the launch mlhot_loss_fwd would have made)
       if (loss->value != nullptr) MLHOT_TRY(run_reduce1(LossRed{loss->kind, d.y_dim, loss->gt_dim, Rq, mu, loss->gt, loss->value}, Rq, s, "loss_fwd"));
@@ -541,15 +541,15 @@ inline int np_backward(const mlhot_np_dims& d, const mlhot_np_params& p, const f
       dmu = sc.dmu_tmp;
     }
   } else if (dmu == nullptr) { set_error("np_vanilla_bwd: null dmu"); return MLHOT_ERR_ARG; }
-#ifndef MLHOT_HOSTSIM
-  if (st.staged() && !tail_fused_applies(d)) {
+  if (st.staged() && rt.family != Tail::Attention) {
     set_error("np_vanilla_bwd: staged passes need the fused attention tail (attention aggregation, Nc, Nq <= 16, option tail_fused)");
     return MLHOT_ERR_UNSUPPORTED;
   }
-  if (tail_fused_applies(d) || cnp_fused_applies(d)) {
+#ifndef MLHOT_HOSTSIM
+  if (rt.family != Tail::Generic) {
     PendingSum tail_sum{};       // the tail's per-task slabs: summed by the encoder backward's final reduce launch when contiguous
-    if (tail_fused_applies(d)) MLHOT_TRY(tail_backward_fused(d, p, ctx_y, mu, dmu, g, b, sc, s, &tail_sum, st, in_kernel));
-    else MLHOT_TRY(cnp_backward_fused(d, p, ctx_y, mu, dmu, g, b, sc, s, &tail_sum, in_kernel));
+    if (rt.family == Tail::Attention) MLHOT_TRY(tail_backward_fused(d, p, rt, ctx_y, mu, dmu, g, b, sc, s, &tail_sum, st, in_kernel));
+    else MLHOT_TRY(cnp_backward_fused(d, p, rt, ctx_y, mu, dmu, g, b, sc, s, &tail_sum, in_kernel));
     if (st.stage == 0) return MLHOT_OK;
     return enc_backward(ctx_x, Rc, qry_x, Rq, p.enc, dw, Rows2{sc.d_cat_in, ldc, Rc, sc.d_dec_in, ldd}, b.enc, g.enc, sc.enc, sc.enc_bytes, s,
                         &tail_sum);

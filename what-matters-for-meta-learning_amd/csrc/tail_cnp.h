@@ -17,22 +17,6 @@ struct CnpDims { int T, Nc, Nq, label_dim, y_dim, dw, dr, dz, h0, h1, dec_h, out
 struct CnpParams { const float *ty_w, *ty_b, *er_w[3], *er_b[3], *r2z_w, *r2z_b, *dec_w[3], *dec_b[3]; };
 struct CnpSlab { int ty_w, ty_b, er_w[3], er_b[3], r2z_w, r2z_b, dec_w[3], dec_b[3], total; };
 
-__host__ inline CnpSlab cnp_slab_layout(const CnpDims& d) {
-  CnpSlab s; int o = 0;
-  auto take = [&](int n) { int r = o; o += (n + 3) / 4 * 4; return r; };
-  const int ldc = d.dw + d.dw / 4, ldd = d.dw + d.dz;
-  s.ty_w = take(d.dw / 4 * d.label_dim); s.ty_b = take(d.dw / 4);
-  s.er_w[0] = take(d.h0 * ldc); s.er_b[0] = take(d.h0);
-  s.er_w[1] = take(d.h1 * d.h0); s.er_b[1] = take(d.h1);
-  s.er_w[2] = take(d.dr * d.h1); s.er_b[2] = take(d.dr);
-  s.r2z_w = take(d.dz * d.dr); s.r2z_b = take(d.dz);
-  s.dec_w[0] = take(d.dec_h * ldd); s.dec_b[0] = take(d.dec_h);
-  s.dec_w[1] = take(d.dec_h * d.dec_h); s.dec_b[1] = take(d.dec_h);
-  s.dec_w[2] = take(d.y_dim * d.dec_h); s.dec_b[2] = take(d.y_dim);
-  s.total = o;
-  return s;
-}
-
 struct CnpFwdArgs {
   CnpDims d; CnpParams p;
   const float* ctx_y;

@@ -1007,29 +1007,10 @@ __device__ __forceinline__ void lds_actgrad(lptr g, int ldg_, lcptr y, int ldy, 
     for (int c = lane; c < width; c += 64) g[r * ldg_ + c] *= act_grad_from_out(act, y[r * ldy + c]);
 }
 
-// per-task gradient slab: offsets (floats) of every tail parameter, in reduce order
+// per-task gradient slab: offsets (floats) of every tail parameter (filled from np_vanilla.h's parameter table)
 struct TailSlab {
   int ty_w, ty_b, er_w[3], er_b[3], r2z_w, r2z_b, dec_w[3], dec_b[3], wk_w, wk_b, wv_w, wv_b, wq_w, wq_b, wo_w, wo_b, total;
 };
-__host__ inline TailSlab tail_slab_layout(const TailDims& d) {
-  TailSlab s; int o = 0;
-  auto take = [&](int n) { int r = o; o += (n + 3) / 4 * 4; return r; };
-  const int ldc = d.dw + d.dw / 4, ldd = d.dw + d.dz;
-  s.ty_w = take(d.dw / 4 * d.label_dim); s.ty_b = take(d.dw / 4);
-  s.er_w[0] = take(d.h0 * ldc); s.er_b[0] = take(d.h0);
-  s.er_w[1] = take(d.h1 * d.h0); s.er_b[1] = take(d.h1);
-  s.er_w[2] = take(d.dw * d.h1); s.er_b[2] = take(d.dw);
-  s.r2z_w = take(d.dz * d.dw); s.r2z_b = take(d.dz);
-  s.dec_w[0] = take(d.dec_h * ldd); s.dec_b[0] = take(d.dec_h);
-  s.dec_w[1] = take(d.dec_h * d.dec_h); s.dec_b[1] = take(d.dec_h);
-  s.dec_w[2] = take(d.y_dim * d.dec_h); s.dec_b[2] = take(d.y_dim);
-  s.wk_w = take(H * d.dw * d.dw); s.wk_b = take(H * d.dw);
-  s.wv_w = take(H * d.dw * d.dw); s.wv_b = take(H * d.dw);
-  s.wq_w = take(H * d.dw * d.dw); s.wq_b = take(H * d.dw);
-  s.wo_w = take(d.dw * H * d.dw); s.wo_b = take(d.dw);
-  s.total = o;
-  return s;
-}
 
 // ==================================================================================================
 // phase C backward, one workgroup per task: decoder0, r_to_z and _W backward.
