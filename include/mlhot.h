@@ -219,6 +219,21 @@ int mlhot_favor_bwd(const float* q, const float* k, const float* v, const float*
                     int T, int H, int Nq, int Nc, int d, int m, const float* out, const float* dout,
                     float* dq, float* dk, float* dv, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- every context prefix of one batch, forward only (the evaluator's loss-versus-context-size sweep) -------------------
+ * Row k-1 of an output is what the plain operator returns for the first k shots of every task, k = 1..Nc.
+ * mlhot_agg_prefix_fwd: rs[T,Nc,R] (and lv for baco) -> r[Nc,T,R], sigma_z[Nc,T,R] (may be NULL); one pass over rs, the
+ * operations of mlhot_agg_fwd in the same order.
+ * mlhot_favor_prefix_fwd: out[Nc,T,Nq,d*H] in the merged order of mlhot_favor_fwd.  The batch-global key stabiliser of prefix
+ * k is the maximum over the first k shots of every task only (fast_attention.py:96-97 on a batch of k shots).  Shapes (favor2.h's):
+ * Nq, Nc <= 32, d % 16 == 0, d <= 256, 16 <= m <= 1536; mlhot_favor_prefix_ws_bytes returns 0 and the call MLHOT_ERR_UNSUPPORTED for others
+ * (callers loop mlhot_favor_fwd over the prefixes).  Added within ABI 7: bindings look the symbols up. */
+int mlhot_agg_prefix_fwd(int mode, const float* rs, const float* lv, int T, int Nc, int R,
+                         float* r, float* sigma_z, void* stream);
+size_t mlhot_favor_prefix_ws_bytes(int T, int H, int Nq, int Nc, int d, int m);
+int mlhot_favor_prefix_fwd(const float* q, const float* k, const float* v, const float* proj,
+                           int T, int H, int Nq, int Nc, int d, int m, float* out,
+                           void* ws, size_t ws_bytes, void* stream);
+
 /* ---- strict sharded parity of the key stabiliser -------------------------
  * fast_attention.py:96-97 takes torch.max over the keys of the WHOLE batch.  When a caller shards the meta-batch over
  * ranks, each rank's launch sequence can be run in two halves around the caller's own collectives on `xchg`

@@ -11,6 +11,7 @@
 #include "ops_direct.h"
 #include "favor.h"
 #include "favor2.h"
+#include "prefix.h"
 #include "encoder.h"
 #include "np_vanilla.h"
 #include "conv_rt.h"
@@ -276,6 +277,12 @@ int mlhot_agg_bwd(int mode, const float* rs, const float* lv, const float* r, co
   return run_foreach(AggBwd{mode, Nc, R, rs, lv, r, sigma_z, amax, dr, drs, dlv}, (size_t)T * R, (hipStream_t)stream, "agg_bwd");
 }
 
+// every context prefix 1..Nc in one pass (csrc/prefix.h): row k-1 of r / sigma_z is mlhot_agg_fwd's result for rs[:, :k]
+int mlhot_agg_prefix_fwd(int mode, const float* rs, const float* lv, int T, int Nc, int R, float* r, float* sigma_z, void* stream) {
+  if (mode < 0 || mode > 2 || T <= 0 || Nc <= 0 || R <= 0 || !rs || !r || (mode == 2 && !lv)) { set_error("agg_prefix_fwd: bad argument"); return MLHOT_ERR_ARG; }
+  return run_foreach(AggPrefixFwd{mode, T, Nc, R, rs, lv, r, sigma_z}, (size_t)T * R, (hipStream_t)stream, "agg_prefix_fwd");
+}
+
 // ---- FAVOR+ -----------------------------------------------------------------------------------
 size_t mlhot_favor_ws_bytes(int T, int H, int Nq, int Nc, int d, int m) {
   return favor_ws_need(FavorDims{T, H, Nq, Nc, d, m});
@@ -290,6 +297,24 @@ int mlhot_favor_bwd(const float* q, const float* k, const float* v, const float*
                     size_t ws_bytes, void* stream) {
   if (T <= 0 || H <= 0 || Nq <= 0 || Nc <= 0 || d <= 0 || m <= 0) { set_error("favor_bwd: bad argument"); return MLHOT_ERR_ARG; }
   return favor_bwd_any(FavorDims{T, H, Nq, Nc, d, m}, q, k, v, proj, out, dout, dq, dk, dv, ws, ws_bytes, (hipStream_t)stream);
+}
+// every context prefix 1..Nc in three launches (csrc/prefix.h): out[k-1] is mlhot_favor_fwd's result for the first k keys / values
+size_t mlhot_favor_prefix_ws_bytes(int T, int H, int Nq, int Nc, int d, int m) {
+#ifndef MLHOT_HOSTSIM
+  if (T <= 0 || H <= 0 || Nq <= 0 || Nc <= 0 || d <= 0 || m <= 0) return 0;
+  return fp::ws_need(FavorDims{T, H, Nq, Nc, d, m});
+#else
+  (void)T; (void)H; (void)Nq; (void)Nc; (void)d; (void)m; return 0;
+#endif
+}
+int mlhot_favor_prefix_fwd(const float* q, const float* k, const float* v, const float* proj, int T, int H, int Nq, int Nc,
+                           int d, int m, float* out, void* ws, size_t ws_bytes, void* stream) {
+  if (T <= 0 || H <= 0 || Nq <= 0 || Nc <= 0 || d <= 0 || m <= 0 || !q || !k || !v || !proj || !out) { set_error("favor_prefix_fwd: bad argument"); return MLHOT_ERR_ARG; }
+#ifndef MLHOT_HOSTSIM
+  return fp::forward(FavorDims{T, H, Nq, Nc, d, m}, q, k, v, proj, out, ws, ws_bytes, (hipStream_t)stream);
+#else
+  (void)ws; (void)ws_bytes; (void)stream; set_error("favor_prefix_fwd: GPU build only"); return MLHOT_ERR_UNSUPPORTED;
+#endif
 }
 // Staged passes (strict sharded parity of the key stabiliser, csrc/stab_xchg.h): stage 0 runs up to the rank-local scalar and
 // publishes it in xchg, stage 1 takes the batch-wide scalar from xchg and runs the rest.

@@ -8,7 +8,8 @@ validation split and, except for pascal_1d, on the test split, then writes `val_
 MI355X side: every batch runs the forward-only HIP path (one C call); the per-batch losses stay on the device and are
 fetched once per sweep point (the reference syncs twice per point as well, but copies every batch synchronously);
 a data source with `get_batch_u8` is read through mlhot.ingest.BatchIngest with the next batch's uint8 copy in flight
-while the current forward runs.  `refine()` (model_evaluator.py:33-93) feeds `None` contexts, which the CNP / ANP
+while the current forward runs.  `config.prefix_sweep` (off by default) evaluates every context size from ONE forward per
+batch at max_ctx_num (`_sweep_prefixes`; DESIGN.md "prefix sweep").  `refine()` (model_evaluator.py:33-93) feeds `None` contexts, which the CNP / ANP
 plugins of the reference do not accept either (ANPShapeNet1D.py:127) - it belongs to the SingleTask baselines and is out
 of scope here.
 """
@@ -40,6 +41,9 @@ class ModelEvaluator(BaseEvaluator):
     def _sweep(self, sources):
         """Context sizes 1..max_ctx_num, the sources interleaved per size in the reference's order (model_evaluator.py:103-110:
         its loaders may draw from numpy's global generator, so the order of the calls is part of the contract)."""
+        mode = getattr(self.config, "prefix_sweep", False)
+        if mode:
+            return self._sweep_prefixes(sources, mode)
         res = {src: ([], []) for src in sources}
         for ctx_num in range(1, self.config.max_ctx_num + 1):
             for src in sources:
@@ -111,6 +115,86 @@ class ModelEvaluator(BaseEvaluator):
         self._log(f"{source} loss: {loss:.4f}")
         self._log(f"{source} std: {std:.4f}")
         return loss, std
+
+    # ---- prefix sweep (config.prefix_sweep): every context size from ONE forward per batch ------------------------------
+    def _reset(self, source):
+        """What the plain sweep does in front of every sweep point: the loader's counter and the source's generator."""
+        self.data.test_counter = 0
+        rng = getattr(self.data, "test_rng" if source == "test" else "val_rng", None)
+        if rng is not None:
+            rng.seed(42)
+
+    def _draw(self, source, shot):
+        """One batch as the loader hands it over, on the host: bytes when it is read through the u8 ingest."""
+        get = self.data.get_batch_u8 if self.ingest is not None else self.data.get_batch
+        return get(source=source, tasks_per_batch=self.config.tasks_per_batch, shot=shot)
+
+    def _prefix_property(self, source):
+        """Does the loader's sweep have the structure the prefix sweep computes?  After the usual reset, the batch at context
+        size 1 must be the first shot of the batch at max_ctx_num, with the same targets and labels (the reference's eval-mode
+        ShapeNet3D / Distractor loaders: their draws do not depend on `shot`)."""
+        def same(a, b):
+            a, b = np.asarray(a), np.asarray(b)
+            return a.shape == b.shape and np.array_equal(a, b)
+        self._reset(source)
+        cx1, qx1, cy1, qy1 = self._draw(source, 1)
+        self._reset(source)
+        cxk, qxk, cyk, qyk = self._draw(source, self.config.max_ctx_num)
+        return (np.asarray(cx1).shape[1] == 1 and same(cx1, np.asarray(cxk)[:, :1]) and same(cy1, np.asarray(cyk)[:, :1])
+                and same(qx1, qxk) and same(qy1, qyk))
+
+    def _sweep_prefixes(self, sources, mode):
+        """The sweep of `_sweep` with ONE forward per batch: per source `val_iters` batches at shot = max_ctx_num through
+        `model.forward_prefixes` (every ResNet pass once; networks/_resnet_np.py), the test-mode loss per context size."""
+        if mode is not True and mode != "paired":
+            raise ValueError(f"config.prefix_sweep must be False, True or 'paired', got {mode!r}")
+        if not hasattr(self.model, "forward_prefixes"):
+            raise ValueError(f"config.prefix_sweep: {type(self.model).__name__} has no forward_prefixes (the ResNet-encoder family has: "
+                             "ANP, CondNeuralProcess, ANPDistractor, CNPDistractor, FCL*)")
+        res = {}
+        for src in sources:
+            if self._prefix_property(src):
+                self._log(f"prefix sweep ({src}): the loader's batch at context size k is the first k shots of its batch at "
+                          f"{self.config.max_ctx_num} with the same targets - the sweep reproduces the reference's draws")
+            elif mode == "paired":
+                self._log(f"prefix sweep ({src}, paired): same tasks at every context size, not the reference's draws")
+            else:
+                raise ValueError(f"config.prefix_sweep: the loader's {src} batch at context size 1 is not a prefix of its batch at "
+                                 f"{self.config.max_ctx_num} (a train-mode loader, the 1D loaders, draws from numpy's global generator): "
+                                 "the plain sweep evaluates other tasks per context size.  prefix_sweep = 'paired' evaluates the "
+                                 "same tasks at every context size instead")
+            res[src] = self._validate_prefixes(src)
+        return res
+
+    def _validate_prefixes(self, source):
+        """Mean and std of the test-mode loss over config.val_iters batches for every context size 1..max_ctx_num: ([K], [K])."""
+        self.model.eval()
+        self._reset(source)
+        n, K = self.config.val_iters, self.config.max_ctx_num
+        rows = []
+        with torch.no_grad():
+            def stage():
+                return self.ingest.stage(*self.data.get_batch_u8(source=source, tasks_per_batch=self.config.tasks_per_batch, shot=K))
+            ticket = stage() if self.ingest is not None and n > 0 else None
+            for i in range(n):
+                if self.ingest is None:
+                    ctx_x, qry_x, ctx_y, qry_y = self._host_batch(source, K)
+                else:
+                    ctx_x, qry_x, ctx_y, qry_y = self.ingest.take(ticket)
+                mu = self.model.forward_prefixes(ctx_x, ctx_y, qry_x)
+                rows.append(torch.stack([self.loss.calc_loss(mu[k], None, qry_y, test=True).view(()) for k in range(K)]))
+                if self.ingest is not None and i + 1 < n:
+                    ticket = stage()                       # next batch's copy overlaps with this forward
+            vals = torch.stack(rows)                       # [val_iters, K]: column k-1 = the plain sweep's `vals` at context size k
+            cols = [vals[:, k].contiguous() for k in range(K)]
+            loss = torch.stack([c.mean() for c in cols])
+            std = torch.stack([c.std() if n > 1 else c.new_full((), float("nan")) for c in cols])
+            both = torch.stack([loss, std]).cpu()          # the one fetch of this source
+        losses, stds = both[0].tolist(), both[1].tolist()
+        for lo, sd in zip(losses, stds):
+            self._log(f"{source} loss: {lo:.4f}")
+            self._log(f"{source} std: {sd:.4f}")
+        return losses, stds
 
     def _plot(self, val, test):
         try:

@@ -821,7 +821,66 @@ class MlhotLib:
                                       _ptr(drs), _ptr(dlv), _stream(rs)), "mlhot_agg_bwd")
         return drs, dlv
 
+    def agg_prefix_fwd(self, mode, rs, lv=None, want_sigma=False):
+        """rs [T,Nc,R] (baco: + lv) -> r [Nc,T,R] (and sigma_z [Nc,T,R] when asked): row k-1 = agg_fwd of rs[:, :k].  Forward only."""
+        c = self.c
+        if not hasattr(c, "mlhot_agg_prefix_fwd"):
+            raise MlhotError(f"agg_prefix_fwd: {self.path} lacks mlhot_agg_prefix_fwd - rebuild with mlhot.build.build_product(force=True)")
+        if mode not in ("mean", "max", "baco"):
+            raise MlhotError(f"agg_prefix_fwd: mode must be 'mean', 'max' or 'baco', got {mode!r}")
+        if rs.dtype != torch.float32 or rs.dim() != 3 or min(rs.shape) < 1:
+            raise MlhotError(f"agg_prefix_fwd expects a non-empty fp32 [T, Nc, R] tensor, got {rs.dtype} {tuple(rs.shape)}")
+        if mode == "baco" and (lv is None or lv.dtype != torch.float32 or lv.shape != rs.shape or lv.device != rs.device):
+            raise MlhotError(f"agg_prefix_fwd: baco needs lv as fp32 {tuple(rs.shape)} on {rs.device}")
+        if mode != "baco":
+            lv = None
+        _chk(rs, lv)
+        T, Nc, R = rs.shape
+        r = torch.empty(Nc, T, R, device=rs.device)
+        sigma = torch.empty(Nc, T, R, device=rs.device) if (want_sigma and mode == "baco") else None
+        c.mlhot_agg_prefix_fwd.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._rc(c.mlhot_agg_prefix_fwd(AGG[mode], _ptr(rs), _ptr(lv), T, Nc, R, _ptr(r), _ptr(sigma), _stream(rs)), "mlhot_agg_prefix_fwd")
+        return r, sigma
+
     # ---- FAVOR+ --------------------------------------------------------------------------------
+    def favor_prefix_supported(self, T, H, Nq, Nc, d, m):
+        """Whether mlhot_favor_prefix_fwd serves this shape (else callers loop favor_fwd over the prefixes)."""
+        return self.favor_prefix_ws_bytes(T, H, Nq, Nc, d, m) > 0
+
+    def favor_prefix_ws_bytes(self, T, H, Nq, Nc, d, m):
+        """Workspace bytes of mlhot_favor_prefix_fwd; 0 for a shape it does not serve."""
+        c = self.c
+        if not hasattr(c, "mlhot_favor_prefix_fwd") or not hasattr(c, "mlhot_favor_prefix_ws_bytes"):
+            raise MlhotError(f"favor_prefix_fwd: {self.path} lacks mlhot_favor_prefix_fwd - rebuild with mlhot.build.build_product(force=True)")
+        c.mlhot_favor_prefix_ws_bytes.restype = C.c_size_t
+        c.mlhot_favor_prefix_ws_bytes.argtypes = [C.c_int] * 6
+        return c.mlhot_favor_prefix_ws_bytes(T, H, Nq, Nc, d, m)
+
+    def favor_prefix_fwd(self, q, k, v, proj):
+        """q [T,Nq,H,d], k/v [T,Nc,H,d], proj [m,d] -> out [Nc,T,Nq,d*H]: out[k-1] = favor_fwd on the first k keys / values.  Forward only."""
+        for name, t in (("q", q), ("k", k), ("v", v)):
+            if t.dtype != torch.float32 or t.dim() != 4:
+                raise MlhotError(f"favor_prefix_fwd: {name} must be fp32 [T, N, H, d], got {t.dtype} {tuple(t.shape)}")
+        T, Nq, H, d = q.shape
+        Nc = k.shape[1]
+        if tuple(k.shape) != (T, Nc, H, d) or v.shape != k.shape or proj.dtype != torch.float32 or proj.dim() != 2 or proj.shape[1] != d:
+            raise MlhotError(f"favor_prefix_fwd: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, proj {tuple(proj.shape)} do not fit together")
+        if any(t.device != q.device for t in (k, v, proj)):
+            raise MlhotError("favor_prefix_fwd: q, k, v and proj must lie on one device")
+        m = proj.shape[0]
+        wb = self.favor_prefix_ws_bytes(T, H, Nq, Nc, d, m)
+        if not wb:
+            raise MlhotError(f"favor_prefix_fwd serves Nq, Nc <= 32, d % 16 == 0, d <= 256, 16 <= m <= 1536 (got Nq={Nq} Nc={Nc} d={d} m={m}); "
+                             "mlhot.ops.favor_prefixes loops favor_fwd for other shapes")
+        _chk(q, k, v, proj)
+        out = torch.empty(Nc, T, Nq, d * H, device=q.device)
+        ws = self._bytes(wb, q)
+        P, i = C.c_void_p, C.c_int
+        self.c.mlhot_favor_prefix_fwd.argtypes = [P, P, P, P, i, i, i, i, i, i, P, P, C.c_size_t, P]
+        self._rc(self.c.mlhot_favor_prefix_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(proj), T, H, Nq, Nc, d, m, _ptr(out), _ptr(ws), ws.numel(),
+                                               _stream(q)), "mlhot_favor_prefix_fwd")
+        return out
+
     @staticmethod
     def _staged(call, exchange, direction):
         """Run `call(stage, xchg_ptr)` as the two staged halves around the caller's collective (include/mlhot.h, "strict sharded

@@ -459,6 +459,34 @@ class FavorFunction(torch.autograd.Function):
         return dq, dk, dv, None
 
 
+def _forward_only(what, *ts):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise MlhotError(f"{what} is forward-only (the evaluator's prefix sweep): call it under torch.no_grad() or on detached tensors")
+
+
+def agg_prefixes(mode, feats, lv=None):
+    """mean / max / baco over EVERY context prefix of feats [T, Nc, R] in one launch (csrc/prefix.h) -> r [Nc, T, R]:
+    r[k-1] is AggFunction's result for feats[:, :k].  Forward only."""
+    _forward_only("agg_prefixes", feats, lv)
+    _need_gpu(feats, lv)
+    r, _ = lib().agg_prefix_fwd(mode, _c(feats), _c(lv))
+    return r
+
+
+def favor_prefixes(qh, kh, vh, proj):
+    """FAVOR+ attention for EVERY context prefix: q [T, Nq, H, d], k / v [T, Nc, H, d] -> [Nc, T, Nq, d*H], element k-1 =
+    FavorFunction on kh[:, :k], vh[:, :k] (its batch-global key stabiliser over those k shots only).  Three launches
+    (csrc/prefix.h) in favor2.h's shape regime; other shapes loop mlhot_favor_fwd over the prefixes.  Forward only."""
+    _forward_only("favor_prefixes", qh, kh, vh, proj)
+    _need_gpu(qh, kh, vh, proj)
+    qh, kh, vh, proj = _c(qh), _c(kh), _c(vh), _c(proj)
+    T, Nq, H, d = qh.shape
+    Nc = kh.shape[1]
+    if lib().favor_prefix_supported(T, H, Nq, Nc, d, proj.shape[0]):
+        return lib().favor_prefix_fwd(qh, kh, vh, proj)
+    return torch.stack([lib().favor_fwd(qh, kh[:, :k].contiguous(), vh[:, :k].contiguous(), proj)[0] for k in range(1, Nc + 1)])
+
+
 class LossFunction(torch.autograd.Function):
     """LossFunc.calc_loss kinds: mlhot_loss_fwd / _bwd."""
 

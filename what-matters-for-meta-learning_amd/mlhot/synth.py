@@ -163,3 +163,56 @@ class SyntheticShapes(SyntheticShapesF32):
 
     def get_batch_u8(self, source, tasks_per_batch, shot):
         return self._draw_u8(source, tasks_per_batch, shot)
+
+
+class SyntheticViews:
+    """A loader with the EVAL-mode contract of the reference's ShapeNet3D / Distractor loaders (dataset/shapenet_3d.py:171-204,
+    shapenet_distractor.py:263-299): a fixed pool of objects x views, `val_rng` / `test_rng` of its own (the evaluator re-seeds them
+    before every sweep point), and draws that do not depend on `shot` - per task one object and one permutation of its views; the
+    context is the first `shot` views of the permutation, the targets are ALL views in that order.  So the batch at context size k
+    is a prefix of the batch at any larger size: the property the evaluator's prefix sweep rests on.
+    task "shapenet_3d": uint8 64 x 64 x 3 images, unit-quaternion labels; "distractor": 128 x 128 x 1, labels in [0, 1)^2.
+    mode "train" is the loaders' train-mode shape of the same pool - the targets are the `shot` views BEHIND the context, so nothing
+    but the context's first views is shared between context sizes (what the prefix sweep has to refuse)."""
+
+    def __init__(self, task="shapenet_3d", seed=42, objects=8, views=30, mode="eval"):
+        import numpy as np
+        if task not in ("shapenet_3d", "distractor"):
+            raise ValueError(task)
+        if mode not in ("eval", "train"):
+            raise ValueError(mode)
+        self.task, self.mode, self.views, self.test_counter = task, mode, views, 0
+        H, C = (64, 3) if task == "shapenet_3d" else (128, 1)
+        imgs = shape_images(objects * views * C, H, H, seed=seed).reshape(objects, views, C, H, H)
+        self.pool = np.ascontiguousarray(imgs.transpose(0, 1, 3, 4, 2))                       # [objects, views, H, W, C]
+        g = torch.Generator().manual_seed(seed)
+        if task == "shapenet_3d":
+            q = torch.nn.functional.normalize(torch.randn(objects, views, 4, generator=g), dim=-1)
+            self.labels = torch.where(q[..., 1:2] < 0, -q, q)
+        else:
+            self.labels = torch.rand(objects, views, 2, generator=g)
+        self.rng = np.random.RandomState(seed)
+        self.val_rng, self.test_rng = np.random.RandomState(seed + 1), np.random.RandomState(seed + 2)
+
+    def gen_bg(self, config, data="all"):
+        pass
+
+    def get_batch_u8(self, source, tasks_per_batch, shot):
+        """(ctx uint8 [T, shot, H, W, C], targets uint8 [T, Nq, H, W, C], ctx labels, target labels) as numpy / fp32 tensors."""
+        import numpy as np
+        rng = {"train": self.rng, "validation": self.val_rng, "test": self.test_rng}[source]
+        need = shot if self.mode == "eval" else 2 * shot
+        if not 1 <= need <= self.views:
+            raise ValueError(f"shot {shot} does not fit {self.views} views per object")
+        objs = rng.randint(0, self.pool.shape[0], tasks_per_batch)
+        perms = np.stack([rng.permutation(self.views) for _ in range(tasks_per_batch)])
+        tgt = perms if self.mode == "eval" else perms[:, shot:2 * shot]
+        ctx = perms[:, :shot]
+        o_np, o_t = objs[:, None], torch.from_numpy(objs)[:, None]
+        return (np.ascontiguousarray(self.pool[o_np, ctx]), np.ascontiguousarray(self.pool[o_np, tgt]),
+                self.labels[o_t, torch.from_numpy(np.ascontiguousarray(ctx))].contiguous(),
+                self.labels[o_t, torch.from_numpy(np.ascontiguousarray(tgt))].contiguous())
+
+    def get_batch(self, source, tasks_per_batch, shot):
+        xs, xq, ys, yq = self.get_batch_u8(source, tasks_per_batch, shot)
+        return host_convert(xs), host_convert(xq), ys, yq

@@ -80,6 +80,8 @@ class BBBEncoder(ModuleWrapper):
 
 class ANPMRShapeNet3D(ResNetNP):
     ATTENTION = True
+    PREFIX_SWEEP_REFUSAL = ("Bayes-by-backprop draws fresh weights in every forward (the reference does so per sweep point), so one "
+                            "encoder pass is not the K passes of the plain sweep")
 
     def __init__(self, config):
         nn.Module.__init__(self)

@@ -7,9 +7,11 @@ operators (run-time-shaped convolutions, linears, shot-axis aggregators, FAVOR+ 
 import torch
 from torch import nn
 
-from mlhot.ops import AggFunction, FavorFunction, HeadStacksFunction, LinearFunction, StackedLinearFunction
+from mlhot.ops import (AggFunction, FavorFunction, HeadStacksFunction, LinearFunction, StackedLinearFunction, agg_prefixes,
+                       favor_prefixes)
+from networks.ResNet import run_conv
 from networks.fast_attention import FastAttention
-from networks.models import AttnLinear, ImageEncoder, NPDecoder, _mlp3, run_trunks
+from networks.models import AttnLinear, ImageEncoder, NPDecoder, _aggregate_feature_map, _mlp3, run_trunks
 
 
 class HeadStack:
@@ -75,6 +77,7 @@ class ResNetNP(nn.Module):
     TRANSFORM_Y = False   # *Distractor classes: labels go through Linear(label_dim -> dim_w) first (CNPDistractor.py:43,89)
     CONTRASTIVE = False   # FCL* classes: forward takes the target labels too and returns a 4th value, the NT-Xent term
     N_HEADS = 8
+    PREFIX_SWEEP_REFUSAL = None   # set by subclasses whose forward is not a function of the batch alone: why forward_prefixes refuses
 
     def __init__(self, config):
         super().__init__()
@@ -225,7 +228,7 @@ class ResNetNP(nn.Module):
             st = stacks[id(mods)] = HeadStack(mods)
         return st
 
-    def _multihead_attention(self, k, v, q):
+    def _head_projections(self, k, v, q):
         if q.is_cuda and max(q.shape[0] * q.shape[1], k.shape[0] * k.shape[1]) <= 512 and q.shape[-1] % 4 == 0:
             # the three head stacks in ONE launch per direction (few rows: mlhot_linear_multi_*)
             sts = [self._stack(m) for m in (self._W_q, self._W_k, self._W_v)]
@@ -237,6 +240,10 @@ class ResNetNP(nn.Module):
             qh, kh, vh = HeadStacksFunction.apply(self.N_HEADS, 3, *args, *params)
         else:
             qh, kh, vh = self._heads(q, self._W_q), self._heads(k, self._W_k), self._heads(v, self._W_v)
+        return qh, kh, vh
+
+    def _multihead_attention(self, k, v, q):
+        qh, kh, vh = self._head_projections(k, v, q)
         merged = FavorFunction.apply(qh, kh, vh, self.attn.projection_matrix)
         return self._W(merged)
 
@@ -325,3 +332,65 @@ class ResNetNP(nn.Module):
         if self.CONTRASTIVE:
             return out, var, 0, contra
         return out, var, 0
+
+    def forward_prefixes(self, batch_train_images, label_train, batch_test_images, ks=None):
+        """The test-mode output for EVERY context prefix of one batch: (ctx images [T, Nc, ...], ctx labels, target images) ->
+        mu [K, T, Nq, out], element i equal to `self(ctx[:, :ks[i]], labels[:, :ks[i]], targets, test=True)[0]`; `ks` defaults to
+        1..Nc (a caller may chunk it: the results do not depend on the chunking, bit for bit).  Forward only, eval mode.
+
+        Nothing a ResNet trunk computes depends on the context size, so ONE run_trunks call does the context, target and decoder
+        passes of all prefixes; the task encoder and the head projections are per shot and run once too.  What sees k is the
+        shot-axis aggregation or the FAVOR+ attention - for all prefixes at once in mlhot.ops.agg_prefixes / favor_prefixes
+        (csrc/prefix.h) - and the Linears behind it: `_W` / `mu` and the decoder head.  Those run once per prefix over the plain
+        forward's T * Nq rows: the Linear entry picks its kernel by row count, so a launch over the rows of several prefixes would
+        take another kernel than the plain forward and than the same prefixes in a smaller chunk."""
+        if self.PREFIX_SWEEP_REFUSAL:
+            raise ValueError(f"{type(self).__name__}.forward_prefixes: {self.PREFIX_SWEEP_REFUSAL}")
+        if self.training:
+            raise ValueError("forward_prefixes is the evaluator's test-mode path: call model.eval() first")
+        Nc, Nq = batch_train_images.shape[1], batch_test_images.shape[1]
+        if Nc < 1:
+            raise ValueError("forward_prefixes needs at least one context shot")
+        ks = list(range(1, Nc + 1)) if ks is None else [int(k) for k in ks]
+        if not ks or min(ks) < 1 or max(ks) > Nc:
+            raise ValueError(f"forward_prefixes: ks must be context sizes in 1..{Nc}, got {ks}")
+        self._refresh_arena()
+        with torch.no_grad():
+            C, H, W = self.img_channels, self.img_size[0], self.img_size[1]
+            tgt_imgs = batch_test_images.reshape(-1, C, H, W)
+            ctx_imgs = batch_train_images.reshape(-1, C, H, W)
+            jobs, roles = [self.img_encoder.trunk_job(ctx_imgs)], ["ctx"]
+            if self.ATTENTION:
+                jobs.append(self.img_encoder.trunk_job(tgt_imgs)); roles.append("tgt")
+            jobs.append(self.decoder.trunk_job(tgt_imgs)); roles.append("dec")
+            maps = run_trunks(jobs)
+            if maps is None:            # no weight-stationary kernels for this image size: the per-operator route, still once per pass
+                dec_map = self.decoder.resnet.trunk(run_conv(self.decoder.conv1, tgt_imgs, relu=True), None)
+                x_ctx = self.img_encoder(ctx_imgs)
+                x_tgt = self.img_encoder(tgt_imgs) if self.ATTENTION else None
+            else:
+                fm = dict(zip(roles, maps))
+                dec_map = fm["dec"]
+                x_ctx = self.img_encoder.features(fm["ctx"])
+                x_tgt = self.img_encoder.features(fm["tgt"]) if self.ATTENTION else None
+            x_dec = _aggregate_feature_map(dec_map, self.decoder.aggregate).reshape(self.task_num, Nq, -1)
+            if self.TRANSFORM_Y:
+                label_train = LinearFunction.apply(label_train, self.transform_y.weight, self.transform_y.bias, "none")
+            feats = _mlp3(x_ctx, self.task_encoder, last_relu=True, side=label_train)
+            if self.ATTENTION:
+                qh, kh, vh = self._head_projections(x_ctx, feats, x_tgt)
+                merged = favor_prefixes(qh, kh, vh, self.attn.projection_matrix)             # [Nc, T, Nq, heads * 256]
+                samples, pre = (self._W(merged[k - 1]) for k in ks), self.mu
+            else:
+                if self.agg_mode in ("mean", "max"):
+                    r = agg_prefixes(self.agg_mode, feats)
+                elif self.agg_mode == "baco":
+                    mu_l = LinearFunction.apply(feats, self.latent_mu.weight, self.latent_mu.bias, "none")
+                    lv = LinearFunction.apply(feats, self.latent_var.weight, self.latent_var.bias, "none")
+                    r = agg_prefixes("baco", mu_l, lv)
+                else:
+                    raise TypeError("agg_mode is not applicable for CNP, choose from ['mean', 'max', 'baco']")
+                samples = (LinearFunction.apply(r[k - 1], self.mu.weight, self.mu.bias, "none")[:, None, :].expand(-1, Nq, -1) for k in ks)
+                pre = None
+            out = [_mlp3(sample, self.decoder.fc_mu, last_relu=False, side=x_dec, side_first=True, pre=pre) for sample in samples]
+            return torch.stack(out)

@@ -86,6 +86,11 @@ class VanillaNP(nn.Module):
         (mlhot_np_grads_flat_layout); mlhot.optim.FlatAdam lays the parameters out the same way."""
         return lib().np_grads_layout(self._dims(ctx_num, test_num))
 
+    def forward_prefixes(self, *args, **kwargs):
+        raise ValueError(f"{type(self).__name__}.forward_prefixes: the vanilla 128x128x1 family is outside the prefix sweep - its forward is "
+                         "one fused call, and its loaders draw shot + shot_max indices from numpy's global generator, so the "
+                         "reference's sweep has no prefix structure to reproduce")
+
     def forward(self, batch_train_images, label_train, batch_test_images, test=False):
         """ctx images [T,Nc,1,128,128], ctx labels [T,Nc,L], target images [T,Nq,1,128,128]
         -> (mu [T,Nq,y], None, 0)   (same contract as the reference forward)."""

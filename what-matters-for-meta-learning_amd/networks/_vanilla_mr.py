@@ -138,6 +138,10 @@ class VanillaMR(nn.Module):
         z = LinearFunction.apply(r, self.r_to_z.weight, self.r_to_z.bias, "none")
         return z[:, None, :].expand(-1, self.test_num, -1)
 
+    def forward_prefixes(self, *args, **kwargs):
+        raise ValueError(f"{type(self).__name__}.forward_prefixes: Bayes-by-backprop draws fresh weights in every forward (the reference "
+                         "does so per sweep point), so one encoder pass is not the K passes of the plain sweep")
+
     def forward(self, batch_train_images, label_train, batch_test_images, test=False):
         """-> (mu [T,Nq,y], None, kl of the TARGET pass's draws)  (ANPMR.py:173-216, CNPMR.py:128-172)."""
         self.test_num = batch_test_images.shape[1]
