@@ -44,7 +44,7 @@ const char* mlhot_last_error(void);
 /* Implementation switches for A/B tests (process-global, see Threading above): "conv2_tc" = 1 (default) runs the
  * weight-stationary conv2 kernels (csrc/conv_tc.h), 0 the generic implicit-GEMM problems; "tail_fused" = 1 (default) runs the
  * fused per-task tail kernels where they apply, "tail_spec" = bit mask of what the fused tails run specialised for the shipped
- * dimensions (csrc/tail_spec.h, cnp_spec.h; names in csrc/encoder.h enum TailSpec): 1 / 2 / 4 forward phases A / B / C, 8 / 16 / 32
+ * dimensions (csrc/tail_spec.h, cnp_spec.h; names in csrc/options.h enum TailSpec): 1 / 2 / 4 forward phases A / B / C, 8 / 16 / 32
  * backward phases C' / B' / A' (the CNP tail's one forward / backward kernel: 1 / 8), 64 phase A also folds the encoder Linear's
  * split-K partial results, 128 phase C' takes the loss's gradient itself when handed a loss descriptor, 512 phase B' as two
  * workgroups per (task, head), 1024 / 2048 phases C' / A' as two workgroups per task, 4096 four instead of two, 256 unassigned;

@@ -512,7 +512,7 @@ def test_model_edge_cases_vs_reference(gpulib, tail_impl, name):
     _run_case(gpulib, name)
 
 
-TAIL_SPEC_BITS = (1, 2, 4, 8, 16, 32, 64, 128, 512, 1024, 2048, 4096)       # csrc/encoder.h enum TailSpec (256 is unassigned)
+TAIL_SPEC_BITS = (1, 2, 4, 8, 16, 32, 64, 128, 512, 1024, 2048, 4096)       # csrc/options.h enum TailSpec (256 is unassigned)
 
 
 @pytest.mark.parametrize("bit", TAIL_SPEC_BITS)

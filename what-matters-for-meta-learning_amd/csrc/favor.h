@@ -201,8 +201,6 @@ struct SumRed {
   MLHOT_HD void finish(float s) const { out[0] = s; }
 };
 
-#define MLHOT_TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
-
 inline int favor_forward(const FavorDims& f, const float* q, const float* k, const float* v, const float* proj,
                          float* out, void* ws, size_t ws_bytes, hipStream_t s, const Stage& st = Stage{}) {
   FavorWs w = favor_carve(f, ws, ws_bytes);

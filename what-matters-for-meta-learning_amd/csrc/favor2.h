@@ -12,6 +12,7 @@
 #pragma once
 #include "common.h"
 #include "favor.h"
+#include "options.h"
 
 #ifndef MLHOT_HOSTSIM
 namespace mlhot {
@@ -701,10 +702,9 @@ inline int backward(const FavorDims& f, const float* q, const float* k, const fl
 
 namespace mlhot {
 // Which FAVOR+ implementation runs: the two-launch kernels above when the shot counts fit (and "favor2" is on), else favor.h's.
-extern int g_favor2;
 inline bool favor2_on(const FavorDims& f) {
 #ifndef MLHOT_HOSTSIM
-  return g_favor2 && fv::applies(f);
+  return g_opt.favor2 && fv::applies(f);
 #else
   (void)f; return false;
 #endif

@@ -2,9 +2,10 @@
 //   hipcc --offload-arch=gfx950 -O3 -shared -fPIC mlhot.hip -o libmlhot.so
 #include <thread>
 #include <stdarg.h>
-#include <mutex>
+#include <limits.h>
 
 #include "common.h"
+#include "options.h"
 #include "foreach.h"
 #include "igemm.h"
 #include "problems.h"
@@ -33,34 +34,9 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-Options g_opt = {1, 1, 0, 0, TAIL_SPEC_DEFAULT, 0, 1};
-int g_favor2 = 1;
-#ifndef MLHOT_HOSTSIM
-namespace rt { int g_trunk_fuse34 = 1, g_trunk_dual_dgrad = 1, g_trunk_wg_rows = 128; }
-#endif
-
+Options g_opt;      // defaults: options.h
 
 #ifndef MLHOT_HOSTSIM
-// ---- side lanes (common.h) ---------------------------------------------------------------------------
-int g_side_fold = 0;   // measured on c3: the folds beside the persistent one-workgroup-per-CU kernels cost +65 us per step (a fold workgroup and a conv workgroup do not fit one CU together, so the conv kernel waits for the fold), DESIGN.md section 4 round 4
-static std::mutex g_lane_mu;
-static SideLane g_lanes[8];
-static int g_nlanes = 0;
-SideLane* side_lane(hipStream_t main) {
-  if (!g_side_fold) return nullptr;
-  std::lock_guard<std::mutex> lk(g_lane_mu);
-  for (int i = 0; i < g_nlanes; ++i) if (g_lanes[i].main == main) return &g_lanes[i];
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(main, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return nullptr;   // no object creation inside a capture
-  if (g_nlanes == 8) return nullptr;
-  SideLane l{};
-  l.main = main;
-  if (hipStreamCreateWithFlags(&l.side, hipStreamNonBlocking) != hipSuccess) return nullptr;
-  if (hipEventCreateWithFlags(&l.ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&l.ev_join, hipEventDisableTiming) != hipSuccess) return nullptr;
-  g_lanes[g_nlanes] = l;
-  return &g_lanes[g_nlanes++];
-}
-
 // ---- per-launch event profiler -------------------------------------------------------------------
 bool g_prof_on = false;
 struct ProfRec { const char* what; hipEvent_t a, b; bool open; };
@@ -88,20 +64,27 @@ const char* mlhot_last_error(void) { return g_err; }
 
 // ---- run-time options -------------------------------------------------------------------------
 int mlhot_set_option(const char* name, int value) {
-  if (!strcmp(name, "conv2_tc")) { g_opt.conv2_tc = value; return MLHOT_OK; }
-  if (!strcmp(name, "conv2_split")) { g_opt.conv2_split = value; return MLHOT_OK; }
-  if (!strcmp(name, "tail_fused")) { g_opt.tail_fused = value; return MLHOT_OK; }
-  if (!strcmp(name, "tail_spec")) { g_opt.tail_spec = value; return MLHOT_OK; }     // bit mask, enum TailSpec (encoder.h); default TAIL_SPEC_DEFAULT = 7935 = all
-  if (!strcmp(name, "conv3_bwd_merged")) { g_opt.conv3_bwd_merged = value; return MLHOT_OK; }     // 0: two launches; 1: one launch, 128 + 128 workgroups; n > 1: n weight-gradient workgroups of 256
-  if (!strcmp(name, "materialize_a1")) { g_opt.materialize_a1 = value; return MLHOT_OK; }
-  if (!strcmp(name, "dbg")) { g_opt.dbg = value; return MLHOT_OK; }   // timing experiments only (results become wrong)
-  if (!strcmp(name, "favor2")) { g_favor2 = value; return MLHOT_OK; }
-#ifndef MLHOT_HOSTSIM
-  if (!strcmp(name, "trunk_dual_dgrad")) { rt::g_trunk_dual_dgrad = value; return MLHOT_OK; }   // 1 (default): a 3x3-skip block's two stride-2 data gradients in one 512-thread launch (resnet_ws.h dgrad2_dual_kernel)
-  if (!strcmp(name, "trunk_wg_rows")) { if (value < 16 || value > 128) { set_error("trunk_wg_rows: 16 .. 128"); return MLHOT_ERR_ARG; } rt::g_trunk_wg_rows = value; return MLHOT_OK; }   // slab rows (x 4 channel tiles = workgroups) a trunk weight-gradient launch is planned against
-  if (!strcmp(name, "trunk_fuse34")) { rt::g_trunk_fuse34 = value; return MLHOT_OK; }   // 1 (default): blocks 3-4 of a 64 x 64 trunk as one launch per direction (resnet_ws.h tail34_*)
-  if (!strcmp(name, "side_fold")) { g_side_fold = value; return MLHOT_OK; }   // 1 (default 0): slab folds of the encoder backward on the library's helper stream (common.h SideLane)
-#endif  // FAVOR+: the two-launch kernels (csrc/favor2.h, default) or favor.h's chain
+  static const struct { const char* name; int Options::*slot; int lo, hi; } table[] = {
+    {"conv2_tc", &Options::conv2_tc, INT_MIN, INT_MAX},
+    {"conv2_split", &Options::conv2_split, INT_MIN, INT_MAX},
+    {"tail_fused", &Options::tail_fused, INT_MIN, INT_MAX},
+    {"tail_spec", &Options::tail_spec, INT_MIN, INT_MAX},
+    {"conv3_bwd_merged", &Options::conv3_bwd_merged, INT_MIN, INT_MAX},
+    {"materialize_a1", &Options::materialize_a1, INT_MIN, INT_MAX},
+    {"dbg", &Options::dbg, INT_MIN, INT_MAX},
+    {"favor2", &Options::favor2, INT_MIN, INT_MAX},
+#ifndef MLHOT_HOSTSIM      // the host simulation has no trunk
+    {"trunk_dual_dgrad", &Options::trunk_dual_dgrad, INT_MIN, INT_MAX},
+    {"trunk_wg_rows", &Options::trunk_wg_rows, 16, 128},
+    {"trunk_fuse34", &Options::trunk_fuse34, INT_MIN, INT_MAX},
+#endif
+  };
+  for (const auto& o : table) {
+    if (strcmp(name, o.name)) continue;
+    if (value < o.lo || value > o.hi) { set_error("%s: %d .. %d", o.name, o.lo, o.hi); return MLHOT_ERR_ARG; }
+    g_opt.*o.slot = value;
+    return MLHOT_OK;
+  }
   set_error("mlhot_set_option: unknown option %s", name);
   return MLHOT_ERR_ARG;
 }
@@ -166,7 +149,7 @@ int mlhot_enc_vanilla_bwd(const float* img0, int n0, const float* img1, int n1, 
 // carry 80 % of the vanilla models' FLOPs; `saved` has the layout of mlhot_enc_vanilla_saved_bytes) -------------------------------
 size_t mlhot_conv12_scratch_bytes(int n_img) {
 #ifndef MLHOT_HOSTSIM
-  return ((size_t)conv12_grid(n_img < 1 ? 1 : n_img) * (C12_R2 + 320)) * sizeof(float) + 256;
+  return enc_bwd_slabs(nullptr, conv12_grid(n_img < 1 ? 1 : n_img), false).floats * sizeof(float) + 256;
 #else
   (void)n_img; return 256;
 #endif
@@ -177,7 +160,7 @@ int mlhot_conv12_fwd(const float* img, int n_img, const float* w1, const float* 
   if (n_img == 0) return MLHOT_OK;
 #ifndef MLHOT_HOSTSIM
   return conv12_forward(c2::ImgSrc{img, n_img, nullptr}, n_img, w1, b1, w2, b2, enc_saved_carve(n_img, saved, (size_t)-1 / 2),
-                        (hipStream_t)stream);
+                        enc_route(n_img, el::DW), (hipStream_t)stream);
 #else
   (void)img; (void)stream; set_error("conv12_fwd: GPU build only"); return MLHOT_ERR_ARG;
 #endif
@@ -189,19 +172,13 @@ int mlhot_conv12_bwd(const float* img, int n_img, const float* w1, const float* 
   if (scratch_bytes < mlhot_conv12_scratch_bytes(n_img)) { set_error("conv12_bwd: scratch too small"); return MLHOT_ERR_WORKSPACE; }
 #ifndef MLHOT_HOSTSIM
   hipStream_t s = (hipStream_t)stream;
-  const int grid = conv12_grid(n_img);
-  float* slab_w = reinterpret_cast<float*>(scratch);
-  float* slab_1 = slab_w + (size_t)grid * C12_R2;
+  const EncBwdSlabs sl = enc_bwd_slabs(reinterpret_cast<float*>(scratch), conv12_grid(n_img), false);
   MLHOT_TRY(conv12_backward(c2::ImgSrc{img, n_img, nullptr}, n_img, w1, b1, w2, dp2, enc_saved_carve(n_img, (void*)saved, (size_t)-1 / 2),
-                            slab_w, slab_w + C12_L2, slab_1, s, []() -> int { return MLHOT_OK; }));
-  c2::SumPartsMulti mp{};
-  mp.seg[0] = c2::SumParts{slab_w, dw2, grid, C12_L2, C12_R2, 1};
-  mp.seg[1] = c2::SumParts{slab_w + C12_L2, db2, grid, 48, C12_R2, 0};
-  mp.first[1] = c2::sum_parts_blocks(C12_L2);
-  mp.first[2] = mp.first[1] + c2::sum_parts_blocks(48);
-  mp.n = 2;
-  hipLaunchKernelGGL(c2::sum_parts_multi_kernel, dim3(mp.first[2]), dim3(256), 0, s, mp);
-  hipLaunchKernelGGL(c2::conv1_grads_kernel, dim3(16), dim3(320), 0, s, slab_1, grid, dw1, db1);
+                            sl, enc_route(n_img, el::DW), s));
+  SlabFolds folds;
+  MLHOT_TRY(conv12_pend_conv2(sl, n_img, dw2, db2, folds));
+  MLHOT_TRY(folds.flush(s, "slab_reduce"));
+  hipLaunchKernelGGL(c2::conv1_grads_kernel, dim3(16), dim3(320), 0, s, sl.c1, conv12_grid(n_img), dw1, db1);
   return check_launch("conv12_bwd");
 #else
   (void)img; (void)stream; set_error("conv12_bwd: GPU build only"); return MLHOT_ERR_ARG;

@@ -90,8 +90,8 @@ inline tf::CnpParams cnp_params(const mlhot_np_params& p) {
 #endif
 
 // ---- the route: what runs between the encoder and the loss for these dims and these options -----------------
-// np_route() is the ONE place that reads the dims' limits and the options tail_fused / tail_spec / conv2_tc; np_forward, np_backward,
-// np_scratch_carve and np_grads_flat_layout take its answer and pass it down.
+// np_route() is the ONE place that reads the dims' limits and the options tail_fused / tail_spec (the encoder's side of enc_fold comes
+// from enc_route(), encoder.h); np_forward, np_backward, np_scratch_carve and np_grads_flat_layout take its answer and pass it down.
 enum class Tail { Generic, Attention, Cnp };   // the operator chain below | tail_fused.h + tail_spec.h | tail_cnp.h + cnp_spec.h
 struct NpRoute {
   Tail family;
@@ -125,7 +125,7 @@ inline NpRoute np_route(const mlhot_np_dims& d) {
   }
   r.fwd_A = spec & TAIL_SPEC_FWD_A; r.fwd_B = spec & TAIL_SPEC_FWD_B; r.fwd_C = spec & TAIL_SPEC_FWD_C;
   r.bwd_C = spec & TAIL_SPEC_BWD_C; r.bwd_B = spec & TAIL_SPEC_BWD_B; r.bwd_A = spec & TAIL_SPEC_BWD_A;
-  r.enc_fold = r.fwd_A && (spec & TAIL_SPEC_ENC_FOLD) && g_opt.conv2_tc && d.dim_w == el::DW;
+  r.enc_fold = r.fwd_A && (spec & TAIL_SPEC_ENC_FOLD) && enc_route(d.T * (d.Nc + d.Nq), d.dim_w).own_linear;
   r.loss_in_kernel = r.bwd_C && (spec & TAIL_SPEC_LOSS);
   r.bwd_B_split = r.bwd_B && (spec & TAIL_SPEC_BWD_B_SPLIT);
   const int wg = (spec & TAIL_SPEC_WG4) ? 4 : 2;

@@ -11,7 +11,7 @@
 #pragma once
 #include "common.h"
 #include "foreach.h"
-#include "favor.h"          // MLHOT_TRY
+#include "options.h"
 #include "resnet_ws.h"
 #include "../../include/mlhot.h"
 
@@ -67,8 +67,8 @@ inline int conv_stride(int conv) { return (conv - 1) % 3 == 1 ? 1 : 2; }
 // slab-row target of a 3x3 / 1x1 weight-gradient job: every row is 147 KB written by the kernel and read again by the fold.  The
 // 4 x 4 / 2 x 2 output maps get 64 rows (256 workgroups): measured 128 / 64 / 32 rows at c5's shape - weight gradient of block 3's
 // conv1 19.2 / 17.9 / 22.9 us, conv2 13.0 / 13.0 / 15.4, fold 34.3 / 33.9 / 32.9
-extern int g_trunk_wg_rows;      // slab rows per weight-gradient launch of the larger maps (option "trunk_wg_rows", default 128)
-inline int wg_target(const Levels& lv, int conv) { return conv_hin(lv, conv) / conv_stride(conv) <= 4 ? 64 : g_trunk_wg_rows; }
+// slab rows per weight-gradient launch of the larger maps: option "trunk_wg_rows", default 128
+inline int wg_target(const Levels& lv, int conv) { return conv_hin(lv, conv) / conv_stride(conv) <= 4 ? 64 : g_opt.trunk_wg_rows; }
 
 // the band total a job's slab rows are planned against: the 1x1 skips of a step share a launch of their own (skip1_wgrad_kernel),
 // so they split ITS workgroups among themselves, not those of a launch that also serves the other passes
@@ -123,8 +123,7 @@ inline TrunkScratch trunk_carve(const mlhot_trunk_pass* ps, int n_pass, const ml
 }
 
 // Blocks 3 and 4 as one launch per direction (rw::tail34_*): 64 x 64 trunks (8 x 8 -> 4 x 4 -> 2 x 2 maps), "trunk_fuse34" option
-extern int g_trunk_fuse34, g_trunk_dual_dgrad;
-inline bool fuse34(const Levels& lv) { return g_trunk_fuse34 && lv.L[2] == 8; }
+inline bool fuse34(const Levels& lv) { return g_opt.trunk_fuse34 && lv.L[2] == 8; }
 
 inline int trunk_check(const mlhot_trunk_pass* ps, int n_pass, const mlhot_trunk_wset* ws, int n_wset, int C, int H) {
   if (!ps || !ws || n_pass < 1 || n_pass > MLHOT_TRUNK_MAX_PASS || n_wset < 1 || n_wset > MLHOT_TRUNK_MAX_WSET) { set_error("resnet trunk: bad pass / weight-set count"); return MLHOT_ERR_ARG; }
@@ -317,7 +316,7 @@ inline int trunk_backward(const mlhot_trunk_pass* ps, int n_pass, const mlhot_tr
       // launch 2: the 3x3-skip blocks' conv1 gradient, added onto launch 1's result and masked
       rw::DgJobs ja{}, jb2{}, jd{};
       bool any1 = false;
-      const bool dual = g_trunk_dual_dgrad && rw::dgrad2_dual_supported(lv.L[b]);
+      const bool dual = g_opt.trunk_dual_dgrad && rw::dgrad2_dual_supported(lv.L[b]);
       for (int p = 0; p < n_pass; ++p) {
         const int w = ps[p].wset;
         if (ws[w].skip_k == 1) { any1 = true; ja.j[ja.n++] = rw::DgJob{dm[p], sc.wimg[w][c1], sc.G[p][b - 1], xin[p], g[p], sc.wimg[w][sk], ps[p].n_img, 0, 0, 0}; }
