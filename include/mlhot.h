@@ -234,6 +234,22 @@ int mlhot_favor_prefix_fwd(const float* q, const float* k, const float* v, const
                            int T, int H, int Nq, int Nc, int d, int m, float* out,
                            void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the Linears and the loss behind the prefix operators, once for all prefixes (csrc/linear_rows.h) -----------------------
+ * mlhot_linear_rows_fwd: y[M,N] = act([src_0 | src_1][M, k_0 + k_1] w[N, k_0 + k_1]^T + b) with a ROW-INVARIANCE guarantee: the
+ * bits of output row i depend on the input rows that map to it, on w, b, k_0, k_1, N and act - not on M, on the row's index, on
+ * the grid or on the other rows of the launch (one kernel, one k order; mlhot_linear_fwd picks its kernel by M).  Output row i
+ * reads row (i / rep) % period of a source (period == 0: no wrap); `ld` is the source's row stride in floats.  b may be NULL.
+ * Served: k_0 > 0, k_0 % 4 == 0, k_1 % 4 == 0, 16-byte aligned source rows and w, act 0..2, any M, N >= 1 -
+ * mlhot_linear_rows_supported tells for a shape; other calls return MLHOT_ERR_UNSUPPORTED and write nothing.  GPU build only.
+ * mlhot_loss_prefix_fwd: loss[p] = what mlhot_loss_fwd(kind, mu + p * rows * y_dim, gt, rows, ..) writes, p < P, in one launch
+ * (the same reduction order per prefix); gt is shared by the prefixes.  Added within ABI 7: bindings look the symbols up. */
+typedef struct { const float* x; int ld; int k; int rep; int period; } mlhot_rows_src;
+int mlhot_linear_rows_supported(int k0, int k1, int N);
+int mlhot_linear_rows_fwd(const mlhot_rows_src* src, int n_src /* 1 | 2 */, const float* w, const float* b,
+                          float* y, int ldy, int M, int N, int act, void* stream);
+int mlhot_loss_prefix_fwd(int kind, const float* mu, const float* gt, int P, int rows, int y_dim, int gt_dim,
+                          float* loss /* [P] */, void* stream);
+
 /* ---- strict sharded parity of the key stabiliser -------------------------
  * fast_attention.py:96-97 takes torch.max over the keys of the WHOLE batch.  When a caller shards the meta-batch over
  * ranks, each rank's launch sequence can be run in two halves around the caller's own collectives on `xchg`

@@ -17,8 +17,7 @@ __global__ __launch_bounds__(256) void foreach_kernel(const F f, size_t n) {
 
 // 1024 threads, 4 independent strided accumulators per thread (4 loads in flight), then a fixed-order LDS tree
 template <class R>
-__global__ __launch_bounds__(1024) void reduce1_kernel(const R r, int n) {
-  __shared__ typename R::T sm[1024];
+__device__ __forceinline__ void reduce1_block(const R& r, int n, typename R::T* sm) {
   typename R::T a0 = r.identity(), a1 = r.identity(), a2 = r.identity(), a3 = r.identity();
   int i = threadIdx.x;
   for (; i + 3072 < n; i += 4096) {
@@ -33,6 +32,17 @@ __global__ __launch_bounds__(1024) void reduce1_kernel(const R r, int n) {
     __syncthreads();
   }
   if (threadIdx.x == 0) r.finish(sm[0]);
+}
+template <class R>
+__global__ __launch_bounds__(1024) void reduce1_kernel(const R r, int n) {
+  __shared__ typename R::T sm[1024];
+  reduce1_block(r, n, sm);
+}
+// P independent reductions of n items each, one workgroup per slice p = blockIdx.x: r.slice(p) reduced as reduce1_kernel reduces it
+template <class R>
+__global__ __launch_bounds__(1024) void reduce1_slices_kernel(const R r, int n) {
+  __shared__ typename R::T sm[1024];
+  reduce1_block(r.slice((int)blockIdx.x), n, sm);
 }
 #endif
 
@@ -99,6 +109,20 @@ int run_reduce1(const R& r, int n, hipStream_t stream, const char* what) {
 #else
   ProfScope ps(what, stream);
   hipLaunchKernelGGL((reduce1_kernel<R>), dim3(1), dim3(1024), 0, stream, r, n);
+  return check_launch(what);
+#endif
+}
+
+// run_reduce1 on each of r.slice(0 .. P-1) in ONE launch: the same per-slice order, so the same bits
+template <class R>
+int run_reduce1_slices(const R& r, int P, int n, hipStream_t stream, const char* what) {
+#ifdef MLHOT_HOSTSIM
+  for (int p = 0; p < P; ++p) MLHOT_TRY(run_reduce1(r.slice(p), n, stream, what));
+  return MLHOT_OK;
+#else
+  if (P <= 0) return MLHOT_OK;
+  ProfScope ps(what, stream);
+  hipLaunchKernelGGL((reduce1_slices_kernel<R>), dim3((unsigned)P), dim3(1024), 0, stream, r, n);
   return check_launch(what);
 #endif
 }

@@ -22,6 +22,7 @@
 #include "mt_normal.h"
 #include "nt_xent.h"
 #include "mlp_chain.h"
+#include "linear_rows.h"
 #include "resnet_trunk.h"
 #include "../../include/mlhot.h"
 
@@ -242,6 +243,13 @@ int mlhot_linear_multi_bwd(const mlhot_linear_job* jobs, int n_jobs, void* strea
 #endif
 }
 
+// ---- one Linear over the rows of many prefixes, bits independent of the row count (csrc/linear_rows.h) -------------
+int mlhot_linear_rows_supported(int k0, int k1, int N) { return linear_rows_shape_ok(k0, k1, N) ? 1 : 0; }
+int mlhot_linear_rows_fwd(const mlhot_rows_src* src, int n_src, const float* w, const float* b, float* y, int ldy, int M, int N, int act,
+                          void* stream) {
+  return linear_rows_forward(src, n_src, w, b, y, ldy, M, N, act, (hipStream_t)stream);
+}
+
 // ---- aggregators ------------------------------------------------------------------------------
 int mlhot_agg_fwd(int mode, const float* rs, const float* lv, int T, int Nc, int R, float* r, float* sigma_z,
                   int32_t* amax, void* stream) {
@@ -322,6 +330,11 @@ int mlhot_favor_bwd_staged(const float* q, const float* k, const float* v, const
 int mlhot_loss_fwd(int kind, const float* mu, const float* gt, int rows, int y_dim, int gt_dim, float* loss, void* stream) {
   if (kind < 0 || kind > 4 || rows <= 0 || y_dim <= 0 || y_dim > 8 || gt_dim < 1) { set_error("loss_fwd: bad argument"); return MLHOT_ERR_ARG; }
   return run_reduce1(LossRed{kind, y_dim, gt_dim, rows, mu, gt, loss}, rows, (hipStream_t)stream, "loss_fwd");
+}
+// loss[p] = mlhot_loss_fwd on prefix p of mu[P][rows][y_dim], gt shared: one launch, one workgroup per prefix
+int mlhot_loss_prefix_fwd(int kind, const float* mu, const float* gt, int P, int rows, int y_dim, int gt_dim, float* loss, void* stream) {
+  if (kind < 0 || kind > 4 || P <= 0 || rows <= 0 || y_dim <= 0 || y_dim > 8 || gt_dim < 1 || !mu || !gt || !loss) { set_error("loss_prefix_fwd: bad argument"); return MLHOT_ERR_ARG; }
+  return run_reduce1_slices(LossRed{kind, y_dim, gt_dim, rows, mu, gt, loss}, P, rows, (hipStream_t)stream, "loss_prefix_fwd");
 }
 int mlhot_loss_bwd(int kind, const float* mu, const float* gt, int rows, int y_dim, int gt_dim, const float* dloss,
                    float* dmu, void* stream) {

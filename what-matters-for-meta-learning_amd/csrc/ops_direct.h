@@ -352,6 +352,8 @@ struct LossRed {
     return sqrtf(s);
   }
   MLHOT_HD void finish(float s) const { out[0] = s / (float)(kind == 1 ? rows * y_dim : rows); }
+  // prefix p of mu[P][rows][y_dim] against the shared gt, into out[p] (mlhot_loss_prefix_fwd)
+  MLHOT_HD LossRed slice(int p) const { LossRed s = *this; s.mu += (size_t)p * rows * y_dim; s.out += p; return s; }
 };
 // loss + alpha * x[0] in the loss's own launch (trainer/model_trainer.py:77-78: `losses = loss + kl * beta`): the loss value as LossRed
 // leaves it, then the product and the sum rounded separately - the bits of mlhot_loss_fwd followed by mlhot_axpy.

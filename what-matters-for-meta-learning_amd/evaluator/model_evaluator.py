@@ -9,7 +9,9 @@ MI355X side: every batch runs the forward-only HIP path (one C call); the per-ba
 fetched once per sweep point (the reference syncs twice per point as well, but copies every batch synchronously);
 a data source with `get_batch_u8` is read through mlhot.ingest.BatchIngest with the next batch's uint8 copy in flight
 while the current forward runs.  `config.prefix_sweep` (off by default) evaluates every context size from ONE forward per
-batch at max_ctx_num (`_sweep_prefixes`; DESIGN.md "prefix sweep").  `refine()` (model_evaluator.py:33-93) feeds `None` contexts, which the CNP / ANP
+batch at max_ctx_num (`_sweep_prefixes`; DESIGN.md "prefix sweep"); `config.prefix_sweep_fold` on top of it runs the Linears
+behind the aggregation / attention and the losses once for all context sizes (`forward_prefixes(fold=True)`,
+`calc_loss_prefixes`).  `refine()` (model_evaluator.py:33-93) feeds `None` contexts, which the CNP / ANP
 plugins of the reference do not accept either (ANPShapeNet1D.py:127) - it belongs to the SingleTask baselines and is out
 of scope here.
 """
@@ -42,6 +44,11 @@ class ModelEvaluator(BaseEvaluator):
         """Context sizes 1..max_ctx_num, the sources interleaved per size in the reference's order (model_evaluator.py:103-110:
         its loaders may draw from numpy's global generator, so the order of the calls is part of the contract)."""
         mode = getattr(self.config, "prefix_sweep", False)
+        fold = getattr(self.config, "prefix_sweep_fold", False)
+        if fold is not True and fold is not False:
+            raise ValueError(f"config.prefix_sweep_fold must be False or True, got {fold!r}")
+        if fold and not mode:
+            raise ValueError("config.prefix_sweep_fold needs prefix_sweep: it folds the prefix sweep's Linears and losses into one launch each")
         if mode:
             return self._sweep_prefixes(sources, mode)
         res = {src: ([], []) for src in sources}
@@ -171,6 +178,7 @@ class ModelEvaluator(BaseEvaluator):
         self.model.eval()
         self._reset(source)
         n, K = self.config.val_iters, self.config.max_ctx_num
+        fold = getattr(self.config, "prefix_sweep_fold", False)
         rows = []
         with torch.no_grad():
             def stage():
@@ -181,8 +189,12 @@ class ModelEvaluator(BaseEvaluator):
                     ctx_x, qry_x, ctx_y, qry_y = self._host_batch(source, K)
                 else:
                     ctx_x, qry_x, ctx_y, qry_y = self.ingest.take(ticket)
-                mu = self.model.forward_prefixes(ctx_x, ctx_y, qry_x)
-                rows.append(torch.stack([self.loss.calc_loss(mu[k], None, qry_y, test=True).view(()) for k in range(K)]))
+                if fold:                                   # each Linear behind the aggregation once, ONE loss launch per batch
+                    mu = self.model.forward_prefixes(ctx_x, ctx_y, qry_x, fold=True)
+                    rows.append(self.loss.calc_loss_prefixes(mu, qry_y, test=True))
+                else:
+                    mu = self.model.forward_prefixes(ctx_x, ctx_y, qry_x)
+                    rows.append(torch.stack([self.loss.calc_loss(mu[k], None, qry_y, test=True).view(()) for k in range(K)]))
                 if self.ingest is not None and i + 1 < n:
                     ticket = stage()                       # next batch's copy overlaps with this forward
             vals = torch.stack(rows)                       # [val_iters, K]: column k-1 = the plain sweep's `vals` at context size k

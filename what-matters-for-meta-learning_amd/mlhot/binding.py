@@ -125,6 +125,10 @@ class ChainGrads(C.Structure):       # struct mlhot_chain_grads
                 ("dside_ld", C.c_int), ("dside_accumulate", C.c_int)]
 
 
+class RowsSrc(C.Structure):          # struct mlhot_rows_src
+    _fields_ = [("x", C.c_void_p), ("ld", C.c_int), ("k", C.c_int), ("rep", C.c_int), ("period", C.c_int)]
+
+
 class LinearJob(C.Structure):        # struct mlhot_linear_job
     _fields_ = [("x", C.c_void_p), ("ldx", C.c_int), ("w", C.c_void_p), ("b", C.c_void_p), ("y", C.c_void_p), ("ldy", C.c_int),
                 ("M", C.c_int), ("K", C.c_int), ("N", C.c_int), ("act", C.c_int), ("dy", C.c_void_p), ("lddy", C.c_int),
@@ -694,6 +698,65 @@ class MlhotLib:
         self._rc(self.c.mlhot_linear_fwd(_ptr(x), K, _ptr(w), _ptr(b), _ptr(y), N, M, K, N, ACT[act], _stream(x)), "mlhot_linear_fwd")
         return y
 
+    def _rows_symbols(self):
+        c = self.c
+        if not hasattr(c, "mlhot_linear_rows_fwd") or not hasattr(c, "mlhot_linear_rows_supported") or not hasattr(c, "mlhot_loss_prefix_fwd"):
+            raise MlhotError(f"linear_rows_fwd: {self.path} lacks mlhot_linear_rows_fwd / mlhot_loss_prefix_fwd - rebuild with mlhot.build.build_product(force=True)")
+        P, i = C.c_void_p, C.c_int
+        c.mlhot_linear_rows_supported.argtypes = [i, i, i]
+        c.mlhot_linear_rows_fwd.argtypes = [C.POINTER(RowsSrc), i, P, P, P, i, i, i, i, P]
+        c.mlhot_loss_prefix_fwd.argtypes = [i, P, P, i, i, i, i, P, P]
+        return c
+
+    def linear_rows_supported(self, k0, k1, N):
+        """Whether mlhot_linear_rows_fwd serves a layer with k ranges k0 | k1 and N outputs (pointers are checked per call)."""
+        return bool(self._rows_symbols().mlhot_linear_rows_supported(int(k0), int(k1), int(N)))
+
+    def linear_rows_fwd(self, sources, w, b, act="none", rows=None, out=None):
+        """y[M, N] = act([src_0 | src_1] w^T + b) with bits that do not depend on M (csrc/linear_rows.h).  sources: one or two
+        (x [R, k] with unit column stride, rep, period): output row i reads x[(i // rep) % period] (period 0: no wrap).  M = `rows`,
+        or R * rep of the sources without a period.  `out`: a [>= M, >= N] fp32 tensor with unit column stride to write into
+        (its first M rows x N columns are written, nothing else)."""
+        c = self._rows_symbols()
+        sources = [tuple(s) for s in sources]
+        if len(sources) not in (1, 2) or any(len(s) != 3 for s in sources):
+            raise MlhotError("linear_rows_fwd: sources must be one or two (tensor, rep, period) tuples")
+        if act not in ACT:
+            raise MlhotError(f"linear_rows_fwd: act must be one of {sorted(ACT)}, got {act!r}")
+        M = None if rows is None else int(rows)
+        for x, rep, period in sources:
+            if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2 or min(x.shape) < 1 or x.stride(1) != 1 or x.device != w.device:
+                raise MlhotError("linear_rows_fwd: a source must be a non-empty fp32 [rows, k] tensor with unit column stride on the weight's device")
+            if int(rep) < 1 or int(period) < 0:
+                raise MlhotError(f"linear_rows_fwd: rep >= 1 and period >= 0, got {rep}, {period}")
+            if rows is None and int(period) == 0:
+                if M is not None and M != x.shape[0] * int(rep):
+                    raise MlhotError(f"linear_rows_fwd: the sources disagree on the row count ({M} against {x.shape[0] * int(rep)})")
+                M = x.shape[0] * int(rep)
+        if M is None or M < 1:
+            raise MlhotError("linear_rows_fwd: every source wraps (period > 0): pass rows=")
+        for x, rep, period in sources:      # the last source row any output row reads must exist
+            last = (M - 1) // int(rep)
+            need = min(last + 1, int(period)) if int(period) else last + 1
+            if need > x.shape[0]:
+                raise MlhotError(f"linear_rows_fwd: {M} rows with rep {rep}, period {period} read {need} source rows, the source has {x.shape[0]}")
+        ktot = sum(s[0].shape[1] for s in sources)
+        if w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] != ktot or (b is not None and (b.dtype != torch.float32 or tuple(b.shape) != (w.shape[0],) or b.device != w.device)):
+            raise MlhotError(f"linear_rows_fwd: weight {tuple(w.shape)} / bias do not fit sources of {ktot} columns")
+        _chk(w, b)
+        N = w.shape[0]
+        if out is None:
+            out = torch.empty(M, N, device=w.device)
+        elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] < M or out.shape[1] < N or out.stride(1) != 1 or out.device != w.device:
+            raise MlhotError(f"linear_rows_fwd: out must be fp32 [>= {M}, >= {N}] with unit column stride on {w.device}")
+        arr = (RowsSrc * len(sources))()
+        for j, (x, rep, period) in enumerate(sources):
+            arr[j].x, arr[j].ld, arr[j].k = x.data_ptr(), (x.stride(0) if x.shape[0] > 1 else x.shape[1]), x.shape[1]
+            arr[j].rep, arr[j].period = int(rep), int(period)
+        ldy = out.stride(0) if out.shape[0] > 1 else out.shape[1]
+        self._rc(c.mlhot_linear_rows_fwd(arr, len(sources), _ptr(w), _ptr(b), _ptr(out), ldy, M, N, ACT[act], _stream(w)), "mlhot_linear_rows_fwd")
+        return out
+
     def linear_bwd(self, x, w, y, dy, act="none", need_dx=True, b=None):
         """`b`: the layer's bias tensor, only to find its gradient's slot in an installed arena."""
         _chk(x, w, y, dy)
@@ -928,6 +991,22 @@ class MlhotLib:
         rows = mu.numel() // mu.shape[-1]
         loss = torch.empty((), device=mu.device)
         self._rc(self.c.mlhot_loss_fwd(LOSS[kind], _ptr(mu), _ptr(gt), rows, mu.shape[-1], gt.shape[-1], _ptr(loss), _stream(mu)), "mlhot_loss_fwd")
+        return loss
+
+    def loss_prefix_fwd(self, kind, mu, gt):
+        """mu [P, ..., y_dim], gt [..., gt_dim] shared by the prefixes -> loss [P]: loss[p] = loss_fwd(kind, mu[p], gt), same bits, one launch."""
+        c = self._rows_symbols()
+        if kind not in LOSS:
+            raise MlhotError(f"loss_prefix_fwd: kind must be one of {sorted(LOSS)}, got {kind!r}")
+        if mu.dim() < 2 or mu.numel() == 0 or gt.numel() == 0:
+            raise MlhotError(f"loss_prefix_fwd expects mu [P, ..., y_dim], got {tuple(mu.shape)}")
+        _chk(mu, gt)
+        P, y_dim = mu.shape[0], mu.shape[-1]
+        rows = mu.numel() // (P * y_dim)
+        if gt.numel() // gt.shape[-1] != rows or mu.dtype != torch.float32 or gt.dtype != torch.float32:
+            raise MlhotError(f"loss_prefix_fwd: labels {tuple(gt.shape)} do not fit mu {tuple(mu.shape)} (fp32, one label row per row of a prefix)")
+        loss = torch.empty(P, device=mu.device)
+        self._rc(c.mlhot_loss_prefix_fwd(LOSS[kind], _ptr(mu), _ptr(gt), P, rows, y_dim, gt.shape[-1], _ptr(loss), _stream(mu)), "mlhot_loss_prefix_fwd")
         return loss
 
     def loss_bwd(self, kind, mu, gt, dloss):

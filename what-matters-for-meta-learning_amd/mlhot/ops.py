@@ -487,6 +487,25 @@ def favor_prefixes(qh, kh, vh, proj):
     return torch.stack([lib().favor_fwd(qh, kh[:, :k].contiguous(), vh[:, :k].contiguous(), proj)[0] for k in range(1, Nc + 1)])
 
 
+def linear_rows(sources, weight, bias, act="none", rows=None):
+    """y = act([src_0 | src_1] W^T + b) over the rows of MANY prefixes in one launch, with bits per row that do not depend on the
+    number of rows (csrc/linear_rows.h; LinearFunction picks its kernel by row count).  sources: one or two (tensor [R, k], rep,
+    period) - output row i reads source row (i // rep) % period, period 0 = no wrap.  Forward only."""
+    srcs = [tuple(s) for s in sources]
+    _forward_only("linear_rows", *[s[0] for s in srcs], weight, bias)
+    _need_gpu(*[s[0] for s in srcs], weight, bias)
+    srcs = [(x if x.stride(-1) == 1 else x.contiguous(), rep, period) for x, rep, period in srcs]
+    return lib().linear_rows_fwd(srcs, _c(weight.detach()), _c(bias.detach()) if bias is not None else None, act, rows=rows)
+
+
+def loss_prefixes(kind, mu, gt):
+    """LossFunction's value for each of mu[0 .. P-1] against the shared labels, [P], one launch (mlhot_loss_prefix_fwd): element p
+    has the bits of LossFunction.apply(kind, mu[p], gt).  Forward only."""
+    _forward_only("loss_prefixes", mu, gt)
+    _need_gpu(mu, gt)
+    return lib().loss_prefix_fwd(kind, _c(mu.float()), _c(gt.float()))
+
+
 class LossFunction(torch.autograd.Function):
     """LossFunc.calc_loss kinds: mlhot_loss_fwd / _bwd."""
 

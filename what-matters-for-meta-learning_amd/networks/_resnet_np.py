@@ -7,11 +7,42 @@ operators (run-time-shaped convolutions, linears, shot-axis aggregators, FAVOR+ 
 import torch
 from torch import nn
 
+import logging
+
+from mlhot import lib
 from mlhot.ops import (AggFunction, FavorFunction, HeadStacksFunction, LinearFunction, StackedLinearFunction, agg_prefixes,
-                       favor_prefixes)
+                       favor_prefixes, linear_rows)
 from networks.ResNet import run_conv
 from networks.fast_attention import FastAttention
 from networks.models import AttnLinear, ImageEncoder, NPDecoder, _aggregate_feature_map, _mlp3, run_trunks
+
+
+_fold_refusals = set()      # (k0, k1, N) of layers mlhot_linear_rows_fwd does not serve, each logged once
+
+
+def _take_prefixes(t, ks):
+    """t[[k - 1 for k in ks]]: a view for consecutive context sizes, else one index_select."""
+    if all(b == a + 1 for a, b in zip(ks, ks[1:])):
+        return t[ks[0] - 1:ks[0] - 1 + len(ks)]
+    return t.index_select(0, torch.tensor([k - 1 for k in ks], device=t.device))
+
+
+def _fold_linear(sources, lin, act, n_prefix):
+    """One Linear over the rows of `n_prefix` prefixes: mlhot.ops.linear_rows (bits per row independent of the row count).  A
+    layer the kernel does not serve runs per prefix through LinearFunction on the gathered rows - the rows of one prefix in one
+    call whatever the chunk, so still independent of the chunking."""
+    rows = next(x.shape[0] * rep for x, rep, period in sources if period == 0)
+    k0, k1 = sources[0][0].shape[1], sources[1][0].shape[1] if len(sources) > 1 else 0
+    if lib().linear_rows_supported(k0, k1, lin.weight.shape[0]):
+        return linear_rows(sources, lin.weight, lin.bias, act, rows=rows)
+    if (k0, k1, lin.weight.shape[0]) not in _fold_refusals:
+        _fold_refusals.add((k0, k1, lin.weight.shape[0]))
+        logging.getLogger(__name__).info("forward_prefixes(fold=True): no row-invariant kernel for a Linear [%d | %d] -> %d; it runs once per prefix",
+                                         k0, k1, lin.weight.shape[0])
+    idx = torch.arange(rows, device=lin.weight.device)
+    cols = [x[(idx // rep) % period if period else idx // rep] for x, rep, period in sources]
+    x = torch.cat(cols, dim=1) if len(cols) > 1 else cols[0]
+    return torch.cat([LinearFunction.apply(c, lin.weight, lin.bias, act) for c in x.chunk(n_prefix)])
 
 
 class HeadStack:
@@ -333,7 +364,16 @@ class ResNetNP(nn.Module):
             return out, var, 0, contra
         return out, var, 0
 
-    def forward_prefixes(self, batch_train_images, label_train, batch_test_images, ks=None):
+    def _fold_head(self, x_dec, sample, rep, n_prefix, Nq):
+        """The decoder head over the rows of all prefixes: fc_mu[0] on [x_dec | sample] - the plain forward's cat([x, sample]) - with
+        the decoder features wrapping every T * Nq rows and `sample` row i serving `rep` rows, then fc_mu[2], fc_mu[4]."""
+        x2 = x_dec.reshape(self.task_num * Nq, -1)
+        fc = self.decoder.fc_mu
+        h = _fold_linear([(x2, 1, x2.shape[0]), (sample, rep, 0)], fc[0], "relu", n_prefix)
+        h = _fold_linear([(h, 1, 0)], fc[2], "relu", n_prefix)
+        return _fold_linear([(h, 1, 0)], fc[4], "none", n_prefix).view(n_prefix, self.task_num, Nq, -1)
+
+    def forward_prefixes(self, batch_train_images, label_train, batch_test_images, ks=None, fold=False):
         """The test-mode output for EVERY context prefix of one batch: (ctx images [T, Nc, ...], ctx labels, target images) ->
         mu [K, T, Nq, out], element i equal to `self(ctx[:, :ks[i]], labels[:, :ks[i]], targets, test=True)[0]`; `ks` defaults to
         1..Nc (a caller may chunk it: the results do not depend on the chunking, bit for bit).  Forward only, eval mode.
@@ -343,7 +383,11 @@ class ResNetNP(nn.Module):
         shot-axis aggregation or the FAVOR+ attention - for all prefixes at once in mlhot.ops.agg_prefixes / favor_prefixes
         (csrc/prefix.h) - and the Linears behind it: `_W` / `mu` and the decoder head.  Those run once per prefix over the plain
         forward's T * Nq rows: the Linear entry picks its kernel by row count, so a launch over the rows of several prefixes would
-        take another kernel than the plain forward and than the same prefixes in a smaller chunk."""
+        take another kernel than the plain forward and than the same prefixes in a smaller chunk.
+
+        `fold=True` runs each of those Linears ONCE over the len(ks) * T * Nq rows of all prefixes through mlhot.ops.linear_rows,
+        whose bits per row do not depend on the row count (csrc/linear_rows.h): chunked == unchunked still holds bit for bit; against
+        fold=False and the plain forward the results agree to the Linear kernels' tolerance, not to the bit."""
         if self.PREFIX_SWEEP_REFUSAL:
             raise ValueError(f"{type(self).__name__}.forward_prefixes: {self.PREFIX_SWEEP_REFUSAL}")
         if self.training:
@@ -380,6 +424,11 @@ class ResNetNP(nn.Module):
             if self.ATTENTION:
                 qh, kh, vh = self._head_projections(x_ctx, feats, x_tgt)
                 merged = favor_prefixes(qh, kh, vh, self.attn.projection_matrix)             # [Nc, T, Nq, heads * 256]
+                if fold:
+                    rows = _take_prefixes(merged, ks).reshape(len(ks) * self.task_num * Nq, -1)
+                    sample = _fold_linear([(rows, 1, 0)], self._W.linear, "none", len(ks))
+                    sample = _fold_linear([(sample, 1, 0)], self.mu, "none", len(ks))
+                    return self._fold_head(x_dec, sample, 1, len(ks), Nq)
                 samples, pre = (self._W(merged[k - 1]) for k in ks), self.mu
             else:
                 if self.agg_mode in ("mean", "max"):
@@ -390,6 +439,9 @@ class ResNetNP(nn.Module):
                     r = agg_prefixes("baco", mu_l, lv)
                 else:
                     raise TypeError("agg_mode is not applicable for CNP, choose from ['mean', 'max', 'baco']")
+                if fold:
+                    z = _fold_linear([(_take_prefixes(r, ks).reshape(len(ks) * self.task_num, -1), 1, 0)], self.mu, "none", len(ks))
+                    return self._fold_head(x_dec, z, Nq, len(ks), Nq)
                 samples = (LinearFunction.apply(r[k - 1], self.mu.weight, self.mu.bias, "none")[:, None, :].expand(-1, Nq, -1) for k in ks)
                 pre = None
             out = [_mlp3(sample, self.decoder.fc_mu, last_relu=False, side=x_dec, side_first=True, pre=pre) for sample in samples]

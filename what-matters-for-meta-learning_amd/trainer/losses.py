@@ -11,7 +11,7 @@ outside the kernels' limits (N > 2048 rows or d > 256 / d % 16 != 0) raise - the
 import torch
 
 from mlhot.binding import MlhotError
-from mlhot.ops import LossFunction, NTXentFunction, add_scaled, loss_plus
+from mlhot.ops import LossFunction, NTXentFunction, add_scaled, loss_plus, loss_prefixes
 
 
 def nt_xent(z, div, mod, t=0.07):
@@ -42,6 +42,15 @@ class LossFunc:
         if self.task == "distractor":
             return LossFunction.apply("distractor", pr_mu, gt_y)
         return None
+
+    def calc_loss_prefixes(self, pr_mu, gt_y, test=False):
+        """`calc_loss(pr_mu[k], None, gt_y, test)` for every k of pr_mu [K, ...] (model.forward_prefixes' output) as ONE [K] device
+        tensor from one launch (mlhot.ops.loss_prefixes: the same bits per element); None where calc_loss returns None."""
+        kind = {"shapenet_3d": "quaternion", "shapenet_1d": "degree" if test else "azimuth", "pascal_1d": "mse",
+                "distractor": "distractor"}.get(self.task)
+        if self.loss_type != "mse" or kind is None:
+            return None
+        return loss_prefixes(kind, pr_mu, gt_y)
 
     def calc_objective(self, pr_mu, pr_var, gt_y, kl, beta):
         """`calc_loss(pr_mu, pr_var, gt_y) + kl * beta` (the reference's trainer/model_trainer.py:77-78) - the same value and gradients, bit
