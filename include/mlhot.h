@@ -416,6 +416,83 @@ size_t mlhot_augment_record_bytes(void);   /* sizeof(mlhot_aug_record): binding 
 int mlhot_augment_ingest_u8(const uint8_t* src, float* dst, long n_img, int H, int W, int C, float div,
                             const mlhot_aug_record* rec, const uint8_t* luts, int n_luts, void* stream);
 
+/* ---- device data augmentation of the IMAGE tasks (csrc/augment_img.h) ----
+ * The base Augmenter (utils/augment.py:22-63: shapenet_3d) and AugmenterDistractor (dataset/shapenet_distractor.py:54-81), one
+ * workgroup per image over planar LDS.  Scope: C in {1, 3}; H, W <= 64 for C = 3, <= 128 for C = 1; anything else is
+ * MLHOT_ERR_UNSUPPORTED.  src: channel-last bytes [n_img, H, W, C]; dst: fp32 [n_img, C, H, W].
+ *   pre_op  what the loader's `(images * 255).astype(uint8)` does to a byte b before the ops: 0 = b (shapenet_3d: float32(k) / 255
+ *           * 255 truncates back to k for every byte), 1 = (256 - b) mod 256 (distractor: uint8 * 255 wraps; a reproduced quirk).
+ *   output  (float)byte / div, then / div2: two IEEE fp32 divisions in that order.  shapenet_3d: div = 255, div2 = 1; distractor:
+ *           div = div2 = 255 (generate() divides, then shapenet_distractor.py:256 divides again; a reproduced quirk).
+ * CROP_PAD, GAMMA, BLUR, AFFINE: the op of mlhot_aug_record on every channel with the image's ONE parameter set - np.pad with
+ *   ((t, b), (l, r), (0, 0)): statistic modes per channel and line; linear_ramp's zero-step rule over all channels of a side.
+ * DROPOUT / COARSE_DROPOUT: drop_per_channel / coarse_per_channel = 0: one mask for all channels (items as in mlhot_aug_record);
+ *   != 0: item = c * H * W + pixel, or 2^30 + c * cells + cell.  C = 1: no effect.
+ * BRIGHTNESS  AddToBrightness((-30, 30)): bright_add in -30 .. 30, bright_space = MLHOT_CS_*.  C = 1: sat_u8(v + add).  C = 3: RGB ->
+ *   8-bit values of the space -> brightness channel b = sat_u8(b + add) -> RGB.  sat = clamp to 0 .. 255; `>>` floors.
+ *   YCRCB  Y = (4899 R + 9617 G + 1868 B + 2^13) >> 14; Cr = sat(((R - Y) * 11682 + 128 * 2^14 + 2^13) >> 14); Cb likewise with
+ *          (B - Y) * 9241.  Back: R = sat(Y + ((Cr - 128) * 22987 + 2^13 >> 14)), G = sat(Y + ((Cr - 128) * -11698 + (Cb - 128) * -5636
+ *          + 2^13 >> 14)), B = sat(Y + ((Cb - 128) * 29049 + 2^13 >> 14)).  Coefficients = round(c * 2^14) of 0.299 0.587 0.114 0.713
+ *          0.564 | 1.403 0.714 0.344 1.773.
+ *   YUV    the same Y; U = (B - Y) * 8061, V = (R - Y) * 14369; back R: (V - 128) * 18678, G: (U - 128) * -6472 + (V - 128) * -9519,
+ *          B: (U - 128) * 33292.  Real coefficients 0.492 0.877 | 1.140 0.395 0.581 2.032.
+ *   HSV    V = max, d = max - min; S = V ? (510 d + V) / (2 V) : 0; H (degrees / 2, 0 .. 179): d = 0: 0; else n = 30 (G - B) if
+ *          V = R, else 30 (B - R) + 60 d if V = G, else 30 (R - G) + 120 d; n < 0: n += 180 d; H = (2 n + d) / (2 d), 180 -> 0.
+ *          Back: i = H / 30, f = H - 30 i; p = (2 V (255 - S) + 255) / 510, q = (2 V (7650 - S f) + 7650) / 15300,
+ *          t = (2 V (7650 - S (30 - f)) + 7650) / 15300; (R, G, B) = (V,t,p) (q,V,p) (p,V,t) (p,q,V) (t,p,V) (V,p,q) for i = 0 .. 5.
+ *   HLS    L = (max + min + 1) >> 1; S = 0 if d = 0, else with m = max + min (m <= 255) or 510 - max - min: (510 d + m) / (2 m),
+ *          saturated; H as HSV.  Back (units of 1 / 65025): P2 = L (255 + S) if L <= 127 else 255 L + 255 S - L S; P1 = 510 L - P2;
+ *          channel at hue h (R: H + 60, G: H, B: H - 60, mod 180): N = 30 P1 + (P2 - P1) h if h < 30, 30 P2 if h < 90,
+ *          30 P1 + (P2 - P1)(120 - h) if h < 120, else 30 P1; value = sat((2 N + 7650) / 15300).
+ *   LAB, LUV  through the tables of mlhot_colour_tabs - built once on the host in float64 by mlhot.augment.colour_tables - linear light on the
+ *          integer grid 0 .. Q = 4080:
+ *            lin[256]   round(Q * (v / 255 <= 0.04045 ? (v / 255) / 12.92 : ((v / 255 + 0.055) / 1.055) ^ 2.4))
+ *            m[9]       sRGB -> XYZ (D65: 0.412453 0.357580 0.180423 / 0.212671 0.715160 0.072169 / 0.019334 0.119193 0.950227), each
+ *                       row divided by its sum (its white), times 2^12, rounded; the row's largest entry then takes the remainder
+ *                       so that the row sums to exactly 2^12 (grey stays grey); minv[9]: the inverse of the row-normalised real
+ *                       matrix, treated the same way
+ *            f[Q + 1]   round(2^15 * (t / Q > 216 / 24389 ? cbrt(t / Q) : (24389 / 27 * t / Q + 16) / 116))
+ *            s8[Q + 1]  round(255 * (u <= 0.0031308 ? 12.92 u : 1.055 u ^ (1 / 2.4) - 0.055)), u = t / Q
+ *            xn, zn     round(2^12 * 0.950456), round(2^12 * 1.088754); w = xn + 15 * 2^12 + 3 zn; un = (2 * 4 xn 2^16 + w) / (2 w),
+ *                       vn = (2 * 9 * 2^12 * 2^16 + w) / (2 w); wz = 12 * 2^16 - 3 un - 20 vn
+ *          x, y, z = (m row . lin[R G B] + 2^11) >> 12; F. = f[.]; Ln = 116 Fy - 16 * 2^15;
+ *          L8 = sat((2 * 255 Ln + 100 * 2^15) / (200 * 2^15)).
+ *          LAB: a8 = sat(128 + ((500 (Fx - Fy) + 2^14) >> 15)), b8 = sat(128 + ((200 (Fy - Fz) + 2^14) >> 15)).
+ *          LUV (neutral codes 97 and 136 are integers so that grey stays grey - own choice): d = xn x + 15 * 2^12 y + 3 zn z;
+ *            d = 0: u' = un, v' = vn; else u' = (2 * 4 xn x 2^16 + d) / (2 d), v' = (2 * 9 * 2^12 y 2^16 + d) / (2 d);
+ *            u8 = sat(97 + rdiv(255 * 13 Ln (u' - un), 354 * 2^31)), v8 = sat(136 + rdiv(255 * 13 Ln (v' - vn), 262 * 2^31)),
+ *            rdiv(a, b) = floor((2 a + b) / (2 b)).
+ *          Back, exact integer cubes: D = 1479000, Ny = 5000 L8 + 204000 (f = N / D);
+ *            lin(N) = 29 N > 6 D ? (N^3 + K / 2) / K, K = D^3 / Q : max(0, rdiv(Q * 108 (29 N - 4 D), 24389 D)), clamped to 0 .. 2 Q.
+ *          LAB: x = lin(Ny + 2958 (a8 - 128)), y = lin(Ny), z = lin(Ny - 7395 (b8 - 128)).
+ *          LUV: y = lin(Ny); L8 = 0: x = z = 0; else u' = un + rdiv(354 * 2^16 (u8 - 97), 1300 L8), v' = max(1, vn +
+ *            rdiv(262 * 2^16 (v8 - 136), 1300 L8)); x = rdiv(y max(0, u') vn, v' un), z = rdiv(y max(0, 12 * 2^16 - 3 u' - 20 v') vn,
+ *            v' wz), both clamped to 0 .. 2 Q.
+ *          R, G, B = s8[clamp((minv row . (x y z) + 2^11) >> 12, 0, Q)].                                                        */
+enum { MLHOT_AUG_BRIGHTNESS = 6 };
+enum { MLHOT_CS_YCRCB = 0, MLHOT_CS_HSV = 1, MLHOT_CS_HLS = 2, MLHOT_CS_LAB = 3, MLHOT_CS_LUV = 4, MLHOT_CS_YUV = 5 };
+#define MLHOT_CS_Q 4080
+typedef struct {
+  mlhot_aug_record base;          /* op[] may hold MLHOT_AUG_BRIGHTNESS; `on` bit 6 */
+  int32_t bright_add, bright_space;
+  int32_t drop_per_channel, coarse_per_channel;
+  int32_t reserved[4];
+} mlhot_aug_record_img;           /* 160 bytes */
+typedef struct {
+  int32_t m[9], minv[9];
+  int32_t xn, zn, un, vn, wz, reserved;
+  uint16_t lin[256];
+  uint16_t f[4096];               /* entries above Q repeat f[Q] */
+  uint8_t s8[4096];               /* likewise */
+} mlhot_colour_tabs;              /* 12896 bytes */
+size_t mlhot_augment_img_record_bytes(void);     /* sizeof(mlhot_aug_record_img): binding self-check */
+size_t mlhot_colour_tabs_bytes(void);
+/* rec: n_img records; luts as in mlhot_augment_ingest_u8; colour_tabs: one mlhot_colour_tabs struct, or NULL (when no record asks for
+ * LAB / LUV - such a step is then skipped).  All device pointers. */
+int mlhot_augment_ingest_u8_img(const uint8_t* src, float* dst, long n_img, int H, int W, int C, int pre_op, float div, float div2,
+                                const mlhot_aug_record_img* rec, const uint8_t* luts, int n_luts, const void* colour_tabs,
+                                void* stream);
+
 /* ---- optimizer: torch.optim.Adam (train.py:52-56) as ONE launch over flat buffers -------------------
  * param / grad / exp_avg / exp_avg_sq: n floats each, laid out alike (e.g. mlhot_np_grads_flat_layout).
  * step >= 1 is the 1-based update count (bias correction); grad_scale multiplies the gradient first

@@ -264,9 +264,10 @@ struct Dropout {
 
 struct CoarseDropout {       // a ch x cw keep-mask of Bernoulli(1 - p) cells, upscaled by nearest neighbour (src = dst * n_src / n_dst)
   uint8_t* p; uint32_t key, thresh; int W, H, ch, cw;
+  int cell0 = 0;             // first cell of this plane (augment_img.h: per_channel masks); 0 for one plane
   MLHOT_HD void operator()(int i) const {
     const int y = i / W, x = i - y * W;
-    const int cell = (y * ch / H) * cw + x * cw / W;
+    const int cell = cell0 + (y * ch / H) * cw + x * cw / W;
     if (pixel_hash(key, COARSE_CELL + (uint32_t)cell) < thresh) p[i] = 0;
   }
 };

@@ -18,6 +18,7 @@
 #include "conv_rt.h"
 #include "ingest.h"
 #include "augment.h"
+#include "augment_img.h"
 #include "bbb_multi.h"
 #include "mt_normal.h"
 #include "nt_xent.h"
@@ -620,6 +621,26 @@ int mlhot_augment_ingest_u8(const uint8_t* src, float* dst, long n_img, int H, i
     return MLHOT_ERR_UNSUPPORTED;
   }
   return aug::run(src, dst, n_img, H, W, div, rec, luts, n_luts, (hipStream_t)stream);
+}
+
+// ---- the same for the image tasks: three channels, AddToBrightness, per_channel dropouts (csrc/augment_img.h) -----------------
+size_t mlhot_augment_img_record_bytes(void) { return sizeof(mlhot_aug_record_img); }
+size_t mlhot_colour_tabs_bytes(void) { return sizeof(mlhot_colour_tabs); }
+int mlhot_augment_ingest_u8_img(const uint8_t* src, float* dst, long n_img, int H, int W, int C, int pre_op, float div, float div2,
+                                const mlhot_aug_record_img* rec, const uint8_t* luts, int n_luts, const void* colour_tabs,
+                                void* stream) {
+  if (n_img < 0 || H <= 0 || W <= 0 || C <= 0 || !(div > 0.f) || !(div2 > 0.f) || n_luts < 0 || pre_op < 0 || pre_op > 1 ||
+      (n_img > 0 && (!src || !dst || !rec)) || (n_luts > 0 && !luts)) {
+    set_error("augment_ingest_u8_img: bad argument");
+    return MLHOT_ERR_ARG;
+  }
+  if (!augimg::in_scope(H, W, C)) {
+    set_error("augment_ingest_u8_img: C = 3 with H, W <= %d or C = 1 with H, W <= %d only (got C=%d H=%d W=%d)", augimg::MAXD3, aug::MAXD,
+              C, H, W);
+    return MLHOT_ERR_UNSUPPORTED;
+  }
+  return augimg::run(src, dst, n_img, H, W, C, pre_op, div, div2, rec, luts, n_luts, (const mlhot_colour_tabs*)colour_tabs,
+                     (hipStream_t)stream);
 }
 
 // ---- fused Adam over a flat parameter / gradient buffer ------------------------------------------------

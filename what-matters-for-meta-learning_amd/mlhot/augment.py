@@ -44,7 +44,7 @@ class AugmentSpec:
         if task not in cls.SEQUENCES:
             raise NotImplementedError(
                 f"device augmentation covers the single-channel sequences {sorted(cls.SEQUENCES)}; task {task!r} uses the base "
-                "Augmenter (AddToBrightness, and segmentation maps for the distractor), which is not implemented on the device")
+                "Augmenter (AddToBrightness, per_channel dropouts): use config.device_augment_images (ImageAugmentSpec, ImageSampler)")
         return cls(task, cls.SEQUENCES[task])
 
 
@@ -144,6 +144,120 @@ class Sampler:
         rq, lq = self.side(n_qry, H, W, 1, lut_base=lc.shape[0])
         self.counter += 1
         return AugTable(np.concatenate([rc, rq]), np.concatenate([lc, lq]))
+
+
+# ---- the image tasks (shapenet_3d, distractor): DESIGN.md 6a-2, csrc/augment_img.h ---------------------------------------------------
+BRIGHTNESS = 6
+YCRCB, HSV, HLS, LAB, LUV, YUV = range(6)      # imgaug's six colour spaces of AddToBrightness (MLHOT_CS_*)
+IMG_RECORD_INTS = 40                           # mlhot_aug_record_img: the 32 ints of mlhot_aug_record, then
+F_BRIGHT_ADD, F_BRIGHT_SPACE, F_DROP_PER_CHANNEL, F_COARSE_PER_CHANNEL = 32, 33, 34, 35
+CS_Q = 4080                                    # MLHOT_CS_Q: the linear-light grid of the Lab / Luv tables
+
+
+class ImageAugmentSpec(AugmentSpec):
+    """The step list of an image task's Sequential, and what its loader does to the bytes around generate(): `pre_op` (what
+    `(images * 255).astype(uint8)` leaves of a byte), and the divisions behind it (`div`, then `div2`)."""
+
+    SEQUENCES = {
+        "shapenet_3d": (CROP_PAD, GAMMA, BRIGHTNESS, BLUR, AFFINE, ONEOF),       # utils/augment.py:22-63 Augmenter
+        "distractor": (AFFINE, ONEOF),                                           # dataset/shapenet_distractor.py:54-81
+    }
+    # shapenet_3d: float32(k) / 255 * 255 truncates back to k; one division (utils/augment.py:69,77).  distractor: uint8 * 255 wraps to
+    # (256 - k) mod 256, and shapenet_distractor.py:256 divides generate()'s output by 255 a second time - both reproduced.
+    BYTES = {"shapenet_3d": (0, 255.0, 1.0), "distractor": (1, 255.0, 255.0)}
+
+    def __init__(self, task, steps):
+        AugmentSpec.__init__(self, task, steps)
+        self.pre_op, self.div, self.div2 = self.BYTES[task]
+
+    @classmethod
+    def for_task(cls, task):
+        if task not in cls.SEQUENCES:
+            raise NotImplementedError(f"device augmentation of images covers {sorted(cls.SEQUENCES)}; task {task!r} is "
+                                      "config.device_augment's (AugmentSpec) or has no sequence")
+        return cls(task, cls.SEQUENCES[task])
+
+
+class ImageAugTable(AugTable):
+    """AugTable with records int32 [n_img, 40] (mlhot_aug_record_img) and the loader's byte handling of its spec."""
+
+    def __init__(self, records, luts, spec):
+        AugTable.__init__(self, records, luts)
+        self.pre_op, self.div, self.div2 = spec.pre_op, spec.div, spec.div2
+
+
+class ImageSampler(Sampler):
+    """Sampler for the image tasks: the same draws in the same order, then per image AddToBrightness's integer and colour space and
+    the two dropouts' per_channel flags (Dropout 0.5, CoarseDropout 0.2)."""
+
+    def __init__(self, spec, seed=0, rank=0):
+        if not isinstance(spec, ImageAugmentSpec):
+            spec = ImageAugmentSpec.for_task(spec)
+        Sampler.__init__(self, spec, seed=seed, rank=rank)
+
+    def side(self, n, H, W, side, lut_base=0):
+        base, luts = Sampler.side(self, n, H, W, side, lut_base=lut_base)
+        rng = self.rng
+        rec = np.zeros((n, IMG_RECORD_INTS), dtype=np.int32)
+        rec[:, :RECORD_INTS] = base
+        rec[:, F_BRIGHT_ADD] = rng.integers(-30, 31, n)
+        rec[:, F_BRIGHT_SPACE] = rng.integers(0, 6, n)
+        rec[:, F_DROP_PER_CHANNEL] = rng.random(n) < 0.5
+        rec[:, F_COARSE_PER_CHANNEL] = rng.random(n) < 0.2
+        return rec, luts
+
+    def batch(self, n_ctx, n_qry, H, W):
+        t = Sampler.batch(self, n_ctx, n_qry, H, W)
+        return ImageAugTable(t.records, t.luts, self.spec)
+
+
+def _rows_to_4096(m):
+    q = np.rint(m * 4096.0).astype(np.int64)
+    for row in q:
+        row[np.argmax(row)] += 4096 - row.sum()          # the row sums to exactly 2^12: grey stays grey
+    return q
+
+
+_COLOUR_TABLES = {}
+
+
+def colour_tables(device=None):
+    """The Lab / Luv tables of AddToBrightness (include/mlhot.h mlhot_colour_tabs), built once in float64: a uint8 array of
+    sizeof(mlhot_colour_tabs) bytes, or with `device` a tensor of it there (uploaded once per device).  They do not depend on the batch."""
+    if "host" not in _COLOUR_TABLES:
+        v = np.arange(256, dtype=np.float64) / 255.0
+        lin = np.rint(CS_Q * np.where(v <= 0.04045, v / 12.92, ((v + 0.055) / 1.055) ** 2.4))
+        u = np.minimum(np.arange(4096, dtype=np.float64), CS_Q) / CS_Q            # entries above Q repeat the last
+        f = np.rint(32768.0 * np.where(u > 216.0 / 24389.0, np.cbrt(u), (24389.0 / 27.0 * u + 16.0) / 116.0))
+        s8 = np.rint(255.0 * np.where(u <= 0.0031308, 12.92 * u, 1.055 * u ** (1.0 / 2.4) - 0.055))
+        m = np.array([[0.412453, 0.357580, 0.180423], [0.212671, 0.715160, 0.072169], [0.019334, 0.119193, 0.950227]])
+        m = m / m.sum(axis=1, keepdims=True)                                      # white-normalised rows
+        xn, zn = int(np.rint(4096 * 0.950456)), int(np.rint(4096 * 1.088754))
+        w = xn + 15 * 4096 + 3 * zn
+        un, vn = (2 * 4 * xn * 65536 + w) // (2 * w), (2 * 9 * 4096 * 65536 + w) // (2 * w)
+        head = np.concatenate([_rows_to_4096(m).ravel(), _rows_to_4096(np.linalg.inv(m)).ravel(),
+                               [xn, zn, un, vn, 12 * 65536 - 3 * un - 20 * vn, 0]]).astype(np.int32)
+        _COLOUR_TABLES["host"] = np.concatenate([head.view(np.uint8), lin.astype(np.uint16).view(np.uint8),
+                                                 f.astype(np.uint16).view(np.uint8), s8.astype(np.uint8)])
+    if device is None:
+        return _COLOUR_TABLES["host"]
+    import torch
+    key = str(torch.device(device))
+    if key not in _COLOUR_TABLES:
+        _COLOUR_TABLES[key] = torch.from_numpy(_COLOUR_TABLES["host"]).to(device)
+    return _COLOUR_TABLES[key]
+
+
+def check_trainer_config_images(config, data):
+    """The image tasks' switch (config.device_augment_images; absent = off): None when off, else the ImageSampler."""
+    if not getattr(config, "device_augment_images", False) or "data_aug" not in (getattr(config, "aug_list", None) or []):
+        return None
+    spec = ImageAugmentSpec.for_task(getattr(config, "task", None))
+    if getattr(data, "data_aug", False):
+        raise ValueError("config.device_augment_images: the loader still augments on the host (data.data_aug is True) - the batch would "
+                         "be augmented twice.  Build it with aug=[a for a in config.aug_list if a != 'data_aug'] (INTEGRATION.md)")
+    from .dist import rank as dist_rank
+    return ImageSampler(spec, seed=int(getattr(config, "seed", 0) or 0), rank=dist_rank())
 
 
 def check_trainer_config(config, data):

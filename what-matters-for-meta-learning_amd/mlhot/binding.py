@@ -25,6 +25,8 @@ _f = C.c_void_p  # every device pointer travels as void*
 ABI_VERSION = 7     # include/mlhot.h MLHOT_ABI_VERSION (2: + nt_xent, mt19937_normal, the *_staged entries, trunk / skinny flat gradients; 3: + conv12_fwd / _bwd; 4: + np_vanilla_bwd_loss; 5: + mt19937_advance; 6: + host_f32_to_u8_exact; 7: + loss_plus_fwd / _bwd)
 
 
+AUG_IMG_RECORD_BYTES = 160   # mlhot_aug_record_img (checked against mlhot_augment_img_record_bytes() before the first call)
+COLOUR_TABS_BYTES = 12896    # mlhot_colour_tabs
 AUG_RECORD_BYTES = 128   # include/mlhot.h mlhot_aug_record (checked against mlhot_augment_record_bytes() before the first augment call)
 
 
@@ -1091,6 +1093,51 @@ class MlhotLib:
                                               C.c_void_p, C.c_int, C.c_void_p]
         self._rc(c.mlhot_augment_ingest_u8(_ptr(src), _ptr(out), n_img, H, W, Cc, float(div), _ptr(records),
                                            _ptr(luts) if n_luts else None, n_luts, _stream(src)), "mlhot_augment_ingest_u8")
+        return out
+
+    def augment_ingest_u8_img(self, src, records, luts=None, colour_tabs=None, out=None, pre_op=0, div=255.0, div2=1.0):
+        """The image tasks' augmenting ingest (csrc/augment_img.h, include/mlhot.h mlhot_aug_record_img): src uint8 [..., H, W, C]
+        (C = 3 with H, W <= 64, or C = 1 with H, W <= 128) -> fp32 [..., C, H, W] = augmented byte / div / div2.  records: int32
+        [n_img, 40] (mlhot.augment.ImageSampler), luts: uint8 [n_luts, 256] or None, colour_tabs: uint8 [12896]
+        (mlhot.augment.colour_tables(device)) or None; all on src's device."""
+        if src.dtype != torch.uint8 or src.dim() < 3:
+            raise MlhotError(f"augment_ingest_u8_img expects a uint8 [..., H, W, C] tensor, got {src.dtype} {tuple(src.shape)}")
+        c = self.c
+        if not hasattr(c, "mlhot_augment_ingest_u8_img"):
+            raise MlhotError(f"augment_ingest_u8_img: {self.path} lacks mlhot_augment_ingest_u8_img - rebuild with mlhot.build.build_product(force=True)")
+        c.mlhot_augment_img_record_bytes.restype = C.c_size_t
+        c.mlhot_colour_tabs_bytes.restype = C.c_size_t
+        if c.mlhot_augment_img_record_bytes() != AUG_IMG_RECORD_BYTES or c.mlhot_colour_tabs_bytes() != COLOUR_TABS_BYTES:
+            raise MlhotError("mlhot: ABI struct size mismatch for mlhot_aug_record_img / mlhot_colour_tabs")
+        *lead, H, W, Cc = src.shape
+        n_img = 1
+        for v in lead:
+            n_img *= v
+        ints = AUG_IMG_RECORD_BYTES // 4
+        if records.dtype != torch.int32 or records.numel() != n_img * ints or records.device != src.device:
+            raise MlhotError(f"augment_ingest_u8_img: records must be int32 [{n_img}, {ints}] on {src.device}")
+        n_luts = 0
+        if luts is not None:
+            if luts.dtype != torch.uint8 or luts.dim() != 2 or luts.shape[1] != 256 or luts.device != src.device:
+                raise MlhotError("augment_ingest_u8_img: luts must be uint8 [n, 256] on the images' device")
+            n_luts = luts.shape[0]
+        if colour_tabs is not None and (colour_tabs.dtype != torch.uint8 or colour_tabs.numel() != COLOUR_TABS_BYTES
+                                        or colour_tabs.device != src.device):
+            raise MlhotError(f"augment_ingest_u8_img: colour_tabs must be uint8 [{COLOUR_TABS_BYTES}] on the images' device")
+        if pre_op not in (0, 1):
+            raise MlhotError(f"augment_ingest_u8_img: pre_op is 0 or 1, got {pre_op!r}")
+        _chk(src, out, records, luts, colour_tabs)
+        shape = (*lead, Cc, H, W)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=src.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != src.device:
+            raise MlhotError(f"augment_ingest_u8_img: out must be fp32 {shape} on {src.device}")
+        c.mlhot_augment_ingest_u8_img.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._rc(c.mlhot_augment_ingest_u8_img(_ptr(src), _ptr(out), n_img, H, W, Cc, int(pre_op), float(div), float(div2), _ptr(records),
+                                               _ptr(luts) if n_luts else None, n_luts,
+                                               _ptr(colour_tabs) if colour_tabs is not None else None, _stream(src)),
+                 "mlhot_augment_ingest_u8_img")
         return out
 
     # ---- fused Adam over flat buffers -------------------------------------------------------------

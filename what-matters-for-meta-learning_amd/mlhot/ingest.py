@@ -16,6 +16,8 @@ reading valid addresses.  There is no CPU fallback: the device must be a ROCm GP
 
 `stage(..., augment=table)` (mlhot.augment.Sampler.batch): the batch's augmentation records and gamma LUTs ride in the same pinned
 slot and the same H2D copy, and take() expands it with mlhot_augment_ingest_u8 (csrc/augment.h) instead of mlhot_ingest_u8_nhwc.
+An mlhot.augment.ImageAugTable (ImageSampler.batch: the image tasks, C = 3 or 1) travels the same way and is expanded with
+mlhot_augment_ingest_u8_img (csrc/augment_img.h) with the table's pre_op / div / div2.
 """
 import collections
 import threading
@@ -24,7 +26,7 @@ import numpy as np
 import torch
 
 from . import lib
-from .binding import AUG_RECORD_BYTES, MlhotError
+from .binding import AUG_IMG_RECORD_BYTES, AUG_RECORD_BYTES, MlhotError
 
 
 def _host(a, dtype):
@@ -43,11 +45,16 @@ def _layout(key):
 
 
 def _aug_layout(key, total):
-    """Behind the labels of an augmented slot: [records int32 [n, 32] | gamma LUTs uint8 [<= n, 256]], n = images of both sides."""
+    """Behind the labels of an augmented slot: [records int32 [n, 32] (image tasks: [n, 40]) | gamma LUTs uint8 [<= n, 256]], n = images
+    of both sides."""
     n = _n_images(key)
     rec_off = (total + 15) // 16 * 16
-    lut_off = rec_off + AUG_RECORD_BYTES * n
+    lut_off = rec_off + _record_bytes(key) * n
     return n, rec_off, lut_off, lut_off + 256 * n
+
+
+def _record_bytes(key):
+    return AUG_IMG_RECORD_BYTES if key[4] == "augimg" else AUG_RECORD_BYTES
 
 
 def _n_images(key):
@@ -56,7 +63,7 @@ def _n_images(key):
 
 class _Slot:
     """One staging slot: ONE pinned host buffer + its device twin holding a whole batch (images as bytes, labels as fp32, and for an
-    augmented batch - key + ("aug",) - its records and LUTs), so a batch is one H2D copy."""
+    augmented batch - key + ("aug",), or ("augimg",) for an ImageAugTable - its records and LUTs), so a batch is one H2D copy."""
 
     def __init__(self, key, device):
         n_img, n_lab, lab_off, total = _layout(key)
@@ -74,7 +81,8 @@ class _Slot:
         self.dev_lab = self.dev[lab_off:lab_end].view(torch.float32)
         self.n_bytes = None                    # bytes to copy: None = the whole buffer
         if self.augmented:
-            self.aug_rec_np = hn[rec_off:lut_off].view(np.int32).reshape(n_aug, AUG_RECORD_BYTES // 4)
+            self.aug_rec_np = hn[rec_off:lut_off].view(np.int32).reshape(n_aug, _record_bytes(key) // 4)
+            self.image_table = None            # an ImageAugTable's (pre_op, div, div2), set per batch
             self.aug_lut_np = hn[lut_off:total].reshape(n_aug, 256)
             self.dev_rec = self.dev[rec_off:lut_off].view(torch.int32)
             self.dev_lut = self.dev[lut_off:total].view(n_aug, 256)
@@ -145,11 +153,13 @@ class BatchIngest:
     def _slot_key(key, augment):
         if augment is None:
             return key
-        if key[0][-1] != 1 or key[1][-1] != 1:
+        from .augment import ImageAugTable
+        image = isinstance(augment, ImageAugTable)
+        if not image and (key[0][-1] != 1 or key[1][-1] != 1):
             raise MlhotError(f"BatchIngest: device augmentation needs single-channel images, got {key[0]} / {key[1]}")
         if augment.n_img != _n_images(key):
             raise MlhotError(f"BatchIngest: the augmentation table holds {augment.n_img} records for {_n_images(key)} images")
-        return key + ("aug",)
+        return key + ("augimg" if image else "aug",)
 
     @staticmethod
     def _put_augment(slot, augment):
@@ -158,6 +168,8 @@ class BatchIngest:
         if k:
             np.copyto(slot.aug_lut_np[:k], augment.luts)
         slot.n_luts = k
+        if slot.aug_rec_np.shape[1] * 4 == AUG_IMG_RECORD_BYTES:
+            slot.image_table = (augment.pre_op, augment.div, augment.div2)
         slot.n_bytes = slot.lut_off + 256 * k   # the copy stops behind the LUTs in use
 
     def stage_filled(self, key, fill, augment=None):
@@ -236,6 +248,18 @@ class BatchIngest:
 
     def _augment_into(self, L, key, slot, out):
         luts = slot.dev_lut[:slot.n_luts] if slot.n_luts else None
+        if slot.image_table is not None:
+            from .augment import colour_tables
+            pre_op, div, div2 = slot.image_table
+            kw = dict(colour_tabs=colour_tables(self.device), pre_op=pre_op, div=div, div2=div2)
+            if out.same_geometry:
+                _, _, H, W, Cc = key[0]
+                L.augment_ingest_u8_img(slot.dev_img.view(-1, H, W, Cc), slot.dev_rec, luts, out=out.img.view(-1, Cc, H, W), **kw)
+            else:
+                n0, r0 = out.n_img[0], int(np.prod(key[0][:-3])) * (AUG_IMG_RECORD_BYTES // 4)
+                L.augment_ingest_u8_img(slot.dev_img[:n0].view(key[0]), slot.dev_rec[:r0], luts, out=out.tensors[0], **kw)
+                L.augment_ingest_u8_img(slot.dev_img[n0:].view(key[1]), slot.dev_rec[r0:], luts, out=out.tensors[1], **kw)
+            return
         if out.same_geometry:
             _, _, H, W, Cc = key[0]
             L.augment_ingest_u8(slot.dev_img.view(-1, H, W, Cc), slot.dev_rec, luts, out=out.img.view(-1, Cc, H, W), div=self.div)
@@ -280,10 +304,19 @@ class ExactU8Feed:
         (T, Nc, C, H, W), (_, Nq, C2, H2, W2) = xs.shape, xq.shape
         key = ((T, Nc * C, H, W, 1), (T, Nq * C2, H2, W2, 1), tuple(ys.shape), tuple(yq.shape))
         L = lib()
+        from .augment import ImageAugTable
+        image = isinstance(augment, ImageAugTable)
+        if image:       # the image tasks' ops mix the channels of a pixel: the bytes are staged channel-last, as the kernel reads them
+            key = ((T, Nc, H, W, C), (T, Nq, H2, W2, C2), tuple(ys.shape), tuple(yq.shape))
 
         def fill(host_np):
             for src, dst in ((xs, host_np[0]), (xq, host_np[1])):
-                if L.host_f32_to_u8_exact(src.data_ptr(), dst.ctypes.data, src.numel(), self.div, threads=self.threads):
+                if image:
+                    planar = np.empty(tuple(src.shape), dtype=np.uint8)
+                    if L.host_f32_to_u8_exact(src.data_ptr(), planar.ctypes.data, src.numel(), self.div, threads=self.threads):
+                        return False
+                    np.copyto(dst, planar.transpose(0, 1, 3, 4, 2))
+                elif L.host_f32_to_u8_exact(src.data_ptr(), dst.ctypes.data, src.numel(), self.div, threads=self.threads):
                     return False
             np.copyto(host_np[2], ys.numpy())
             np.copyto(host_np[3], yq.numpy())

@@ -216,3 +216,30 @@ class SyntheticViews:
     def get_batch(self, source, tasks_per_batch, shot):
         xs, xq, ys, yq = self.get_batch_u8(source, tasks_per_batch, shot)
         return host_convert(xs), host_convert(xq), ys, yq
+
+
+def colour_images(n, H=64, W=64, seed=0):
+    """uint8 [n, H, W, 3] colour test images for the image tasks' augmentation: three independent `shape_images` planes (saturated and
+    mixed colours, flat regions and edges), every fourth image grey (R = G = B)."""
+    import numpy as np
+    img = np.ascontiguousarray(shape_images(3 * n, H, W, seed=seed).reshape(n, 3, H, W).transpose(0, 2, 3, 1))
+    img[::4] = img[::4, :, :, :1]
+    return img
+
+
+class SyntheticViewsF32:
+    """`SyntheticViews` in its train-mode shape WITHOUT `get_batch_u8`: fp32 [T, N, C, H, W] = bytes / 255 host batches, which take the
+    trainer's host-batch route (mlhot.ingest.ExactU8Feed).  Neither augments (`data_aug = False`): pair them with
+    config.device_augment_images."""
+
+    data_aug = False
+
+    def __init__(self, task="shapenet_3d", seed=42, objects=8, views=30):
+        self._views = SyntheticViews(task, seed=seed, objects=objects, views=views, mode="train")
+        self.task, self.test_counter = task, 0
+
+    def gen_bg(self, config, data="all"):
+        pass
+
+    def get_batch(self, source, tasks_per_batch, shot):
+        return self._views.get_batch(source, tasks_per_batch, shot)

@@ -101,14 +101,18 @@ class _HostPrefetch:
             return ("f32", dev, ev)
 
     def _stage_augmented(self, host_batch):
+        from mlhot.augment import ImageSampler
         xs, xq = host_batch[0], host_batch[1]
-        if xs.dim() != 5 or xq.dim() != 5 or xs.shape[2] != 1 or xq.shape[2] != 1:
+        if isinstance(self.augment, ImageSampler):      # config.device_augment_images: [T, N, C, H, W], C = 3 or 1 (the kernel checks)
+            if xs.dim() != 5 or xq.dim() != 5 or xs.shape[2:] != xq.shape[2:]:
+                raise ValueError(f"config.device_augment_images: [T, N, C, H, W] images of one geometry, got {tuple(xs.shape)} / {tuple(xq.shape)}")
+        elif xs.dim() != 5 or xq.dim() != 5 or xs.shape[2] != 1 or xq.shape[2] != 1:
             raise ValueError(f"config.device_augment: single-channel [T, N, 1, H, W] images only, got {tuple(xs.shape)} / {tuple(xq.shape)}")
         (T, Nc, _, H, W), Nq = xs.shape, xq.shape[1]
         table = self.augment.batch(T * Nc, T * Nq, H, W)
         ticket = self.u8.stage(host_batch, augment=table)
         if ticket is None:
-            raise ValueError("config.device_augment: a training batch is not exact bytes (every image element k / 255 for a byte k), so "
+            raise ValueError("config.device_augment / device_augment_images: a training batch is not exact bytes (every image element k / 255 for a byte k), so "
                              "it cannot take the byte route the augmentation runs on; the loader must hand out un-normalised byte images")
         return ticket
 
@@ -168,8 +172,9 @@ class _Feed:
         xs, xq, ys, yq = self._draw(source, u8=True)
         table = None
         if source == "train" and self.augment is not None:          # the reference augments training batches only (shapenet_1d.py:174)
+            from mlhot.augment import ImageSampler
             (T, Nc, H, W, Cc), Nq = xs.shape, xq.shape[1]
-            if Cc != 1 or xq.shape[-1] != 1:
+            if not isinstance(self.augment, ImageSampler) and (Cc != 1 or xq.shape[-1] != 1):
                 raise ValueError(f"config.device_augment: single-channel images only, got {tuple(xs.shape)}")
             table = self.augment.batch(T * Nc, T * Nq, H, W)
         return self.ingest.stage(xs, xq, ys, yq, augment=table)
@@ -276,6 +281,9 @@ class ModelTrainer(BaseTrainer):
         # refused before anything else is set up when the task has no device sequence or the loader still augments itself
         from mlhot.augment import check_trainer_config
         self._augment = check_trainer_config(config, data)
+        if self._augment is None:       # config.device_augment_images: the image tasks' switch (shapenet_3d, distractor), same rules
+            from mlhot.augment import check_trainer_config_images
+            self._augment = check_trainer_config_images(config, data)
         super().__init__(model=model, loss=loss, optimizer=optimizer, config=config)
         self.data = data
         # side stream: the RCCL kernels never sit in the compute queue; early bucket: models that know which gradients are complete
