@@ -149,7 +149,10 @@ int mlhot_conv12_bwd(const float* img, int n_img, const float* w1, const float* 
 size_t mlhot_linear_bwd_scratch_bytes(int M, int K, int N);
 int mlhot_linear_fwd(const float* x, int ldx, const float* w, const float* b, float* y, int ldy,
                      int M, int K, int N, int act, void* stream);
-/* dx (+)= (dy*act'(y)) w ; dw = (dy*act'(y))^T x ; db = column sums.  dx/dw/db may be NULL. */
+/* dx (+)= (dy*act'(y)) w ; dw = (dy*act'(y))^T x ; db = column sums.  dx/dw/db may be NULL.
+ * M == 0 is a valid call: y and dx are left untouched, dw and db are written as zeros (the gradient of an empty sum).
+ * Operands of these two entries need 4-byte alignment only and any ld >= their width: the float4 kernels are taken for
+ * 16-byte aligned rows, the generic ones otherwise (tests/test_linear_abi_gpu.py runs every such route). */
 int mlhot_linear_bwd(const float* x, int ldx, const float* w, const float* y, int ldy, const float* dy, int lddy,
                      int M, int K, int N, int act, float* dx, int lddx, int accumulate, float* dw, float* db,
                      void* scratch, size_t scratch_bytes, void* stream);

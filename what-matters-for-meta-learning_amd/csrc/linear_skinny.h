@@ -258,7 +258,8 @@ inline int run_wgrad(const float* dy, int lddy, const float* y, int ldy, int act
 
 inline int run_bwd(const float* dy, int lddy, const float* y, int ldy, int act, const float* w, const float* x, int ldx, float* dx, int lddx,
                    int accumulate, float* dw, float* db, int M, int K, int N, hipStream_t s, const char* what) {
-  if (M <= 0) return MLHOT_OK;
+  // no rows: dx has nothing to write, but dw / db are the gradient of an empty sum - the weight gradient's launch writes the zeros
+  if (M <= 0) return run_wgrad(dy, lddy, y, ldy, act, x, ldx, dw, db, M, K, N, s, what);
   BwdArgs a{dy, y, w, x, dx, dw, db, lddy, ldy, act, ldx, lddx, accumulate, M, K, N, (M + 31) / 32, 0, (N + 15) / 16};
   a.nd = a.gdx * ((K + 15) / 16);
   ProfScope ps(what, s);

@@ -63,8 +63,9 @@ struct Pool2Fwd {
   }
 };
 
-// residual join of a BasicBlock: y = relu(a + b)  (ResNet.py:69-72) and its backward g = dy * (y > 0)
-struct AddRelu { const float* a; const float* b; float* y; MLHOT_HD void operator()(size_t i) const { const float v = a[i] + b[i]; y[i] = v > 0.f ? v : 0.f; } };
+// residual join of a BasicBlock: y = relu(a + b)  (ResNet.py:69-72) and its backward g = dy * (y > 0).  A sum of -0.0 stays -0.0
+// as in torch.relu (max(v, 0) keeps the zero it was given): the output has torch's bits for every finite input.
+struct AddRelu { const float* a; const float* b; float* y; MLHOT_HD void operator()(size_t i) const { const float v = a[i] + b[i]; y[i] = v >= 0.f ? v : 0.f; } };
 // y = a + alpha * x  (a may be null: y = alpha * x), product and sum rounded separately like the two torch operators they replace
 // (trainer/model_trainer.py:77-78: loss + kl * beta)
 struct Axpy {
