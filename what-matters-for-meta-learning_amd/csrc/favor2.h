@@ -717,8 +717,16 @@ inline size_t favor_ws_need(const FavorDims& f) {
 #endif
   return a > b ? a : b;
 }
+// The contract of mlhot_favor_ws_bytes: a workspace smaller than the reported size is refused before anything is launched, whichever
+// implementation would run (the two carve differently, and each carve's own check leaves the 256-byte slack and the other's excess unseen).
+inline int favor_ws_check(const FavorDims& f, const void* ws, size_t ws_bytes, const char* what) {
+  const size_t need = favor_ws_need(f);
+  if (ws == nullptr || ws_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", what, ws_bytes, need); return MLHOT_ERR_WORKSPACE; }
+  return MLHOT_OK;
+}
 inline int favor_fwd_any(const FavorDims& f, const float* q, const float* k, const float* v, const float* proj, float* out, void* ws,
                          size_t ws_bytes, hipStream_t s, const Stage& st = Stage{}) {
+  MLHOT_TRY(favor_ws_check(f, ws, ws_bytes, "favor_fwd"));
 #ifndef MLHOT_HOSTSIM
   if (favor2_on(f)) return fv::forward(f, q, k, v, proj, out, ws, ws_bytes, s, st);
 #endif
@@ -727,6 +735,7 @@ inline int favor_fwd_any(const FavorDims& f, const float* q, const float* k, con
 inline int favor_bwd_any(const FavorDims& f, const float* q, const float* k, const float* v, const float* proj, const float* out,
                          const float* dout, float* dq, float* dk, float* dv, void* ws, size_t ws_bytes, hipStream_t s,
                          const Stage& st = Stage{}) {
+  MLHOT_TRY(favor_ws_check(f, ws, ws_bytes, "favor_bwd"));
 #ifndef MLHOT_HOSTSIM
   if (favor2_on(f)) return fv::backward(f, q, k, v, proj, out, dout, dq, dk, dv, ws, ws_bytes, s, st);
 #endif
