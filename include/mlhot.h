@@ -292,7 +292,10 @@ int mlhot_loss_plus_bwd(int kind, const float* mu, const float* gt, int rows, in
  * nn.Conv2d (cross-correlation, zero padding, NCHW, weight [Cout,Cin,k,k], optional fused ReLU) for
  * the 5x5 s2 p2 stem, the 3x3 s2 / s1 p1 block convs and the 1x1 s2 (3x3 in the BBB twin) skip of
  * ImageEncoder / NPDecoder (networks/models.py:63-192, networks/ResNet.py:25-74).  Backward: `y` is
- * the forward output (used for the ReLU mask when relu=1); dx / dw / db may be NULL.               */
+ * the forward output (used for the ReLU mask when relu=1); dx / dw / db may be NULL.  A shape with
+ * a non-positive extent or a kernel larger than the padded image (H + 2 pad < k or W + 2 pad < k) is
+ * MLHOT_ERR_ARG in fwd and bwd before anything is launched, and 0 scratch bytes.  db is computed as
+ * a column of the dw problem: db without dw is MLHOT_ERR_ARG; dw NULL needs no scratch.             */
 size_t mlhot_conv2d_bwd_scratch_bytes(int N, int Cin, int H, int W, int Cout, int k, int stride, int pad);
 int mlhot_conv2d_fwd(const float* x, const float* w, const float* b, float* y, int N, int Cin, int H, int W, int Cout, int k,
                      int stride, int pad, int relu, void* stream);

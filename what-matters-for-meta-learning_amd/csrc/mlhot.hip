@@ -361,19 +361,23 @@ int mlhot_loss_plus_bwd(int kind, const float* mu, const float* gt, int rows, in
 }
 
 // ---- E2 / D2 building blocks: run-time-shaped conv, residual join, 2x2 max-pool; B1: BBB sample -------
+// what the three conv2d entries refuse: a non-positive extent, or a kernel larger than the padded image (HO or WO <= 0)
+static bool conv2d_bad_shape(int N, int Cin, int H, int W, int Cout, int k, int stride, int pad) {
+  return N <= 0 || Cin <= 0 || Cout <= 0 || k <= 0 || stride <= 0 || pad < 0 || H + 2 * pad < k || W + 2 * pad < k;
+}
 size_t mlhot_conv2d_bwd_scratch_bytes(int N, int Cin, int H, int W, int Cout, int k, int stride, int pad) {
+  if (conv2d_bad_shape(N, Cin, H, W, Cout, k, stride, pad)) return 0;
   return conv_bwd_scratch_bytes(conv_shape(N, Cin, H, W, Cout, k, stride, pad));
 }
 int mlhot_conv2d_fwd(const float* x, const float* w, const float* b, float* y, int N, int Cin, int H, int W, int Cout, int k,
                      int stride, int pad, int relu, void* stream) {
-  if (N <= 0 || Cin <= 0 || Cout <= 0 || k <= 0 || stride <= 0 || pad < 0 || H + 2 * pad < k || W + 2 * pad < k) {
-    set_error("conv2d_fwd: bad argument"); return MLHOT_ERR_ARG;
-  }
+  if (conv2d_bad_shape(N, Cin, H, W, Cout, k, stride, pad)) { set_error("conv2d_fwd: bad argument"); return MLHOT_ERR_ARG; }
   return conv_rt_forward(conv_shape(N, Cin, H, W, Cout, k, stride, pad), x, w, b, y, relu, (hipStream_t)stream);
 }
 int mlhot_conv2d_bwd(const float* x, const float* w, const float* y, const float* dy, int N, int Cin, int H, int W, int Cout, int k,
                      int stride, int pad, int relu, float* dx, float* dw, float* db, void* scratch, size_t scratch_bytes, void* stream) {
-  if (N <= 0 || Cin <= 0 || Cout <= 0 || k <= 0 || stride <= 0 || pad < 0) { set_error("conv2d_bwd: bad argument"); return MLHOT_ERR_ARG; }
+  if (conv2d_bad_shape(N, Cin, H, W, Cout, k, stride, pad)) { set_error("conv2d_bwd: bad argument"); return MLHOT_ERR_ARG; }
+  if (db && !dw) { set_error("conv2d_bwd: db is a column of the dw problem, it needs dw"); return MLHOT_ERR_ARG; }   // else left unwritten
   return conv_rt_backward(conv_shape(N, Cin, H, W, Cout, k, stride, pad), x, w, relu ? y : nullptr, dy, dx, dw, db, scratch, scratch_bytes,
                           (hipStream_t)stream);
 }
