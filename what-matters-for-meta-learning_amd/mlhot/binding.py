@@ -3,11 +3,13 @@
 `MlhotLib(path)` wraps ONE shared object.  The product loads
 `csrc/libmlhot.so` through `mlhot.lib()`; the test-suite additionally wraps the
 host-simulation flavour (tests/hostsim) with the same class to check the index
-arithmetic without a GPU.  Every wrapper takes torch tensors, passes raw
-`data_ptr()`s and the current HIP stream, and raises `MlhotError` on a non-zero
-return code - nothing here computes anything.
+arithmetic without a GPU.  The signatures are declared once, in `SIGNATURES`,
+and applied when a library is loaded.  Every wrapper takes torch tensors, passes
+raw `data_ptr()`s and the current HIP stream, and raises `MlhotError` on a
+non-zero return code - nothing here computes anything.
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -21,21 +23,24 @@ LOSS = {"azimuth": 0, "mse": 1, "quaternion": 2, "degree": 3, "distractor": 4}
 
 _f = C.c_void_p  # every device pointer travels as void*
 
-
 ABI_VERSION = 7     # include/mlhot.h MLHOT_ABI_VERSION (2: + nt_xent, mt19937_normal, the *_staged entries, trunk / skinny flat gradients; 3: + conv12_fwd / _bwd; 4: + np_vanilla_bwd_loss; 5: + mt19937_advance; 6: + host_f32_to_u8_exact; 7: + loss_plus_fwd / _bwd)
 
 
-AUG_IMG_RECORD_BYTES = 160   # mlhot_aug_record_img (checked against mlhot_augment_img_record_bytes() before the first call)
+# sizeof of the records the augmenting ingests read (tensors built by mlhot/augment.py), checked against the library's *_bytes() at load
+AUG_RECORD_BYTES = 128       # mlhot_aug_record
+AUG_IMG_RECORD_BYTES = 160   # mlhot_aug_record_img
 COLOUR_TABS_BYTES = 12896    # mlhot_colour_tabs
-AUG_RECORD_BYTES = 128   # include/mlhot.h mlhot_aug_record (checked against mlhot_augment_record_bytes() before the first augment call)
 
 
 class MlhotError(RuntimeError):
     pass
 
 
-class EncParams(C.Structure):
+class EncParams(C.Structure):       # struct mlhot_enc_params
     _fields_ = [(n, _f) for n in ("w1", "b1", "w2", "b2", "w3", "b3", "wl", "bl")]
+
+
+EncGrads = EncParams                # struct mlhot_enc_grads: the same eight pointers, not const
 
 
 class NpDims(C.Structure):
@@ -179,6 +184,137 @@ def _chk(*ts):
             raise MlhotError(f"mlhot expects contiguous fp32 tensors, got {t.dtype} contiguous={t.is_contiguous()}")
 
 
+def _align256(x):
+    return (x + 255) // 256 * 256
+
+
+def _ingest_out(wrapper, src, out):
+    """The fp32 [..., C, H, W] destination of an ingest of src [..., H, W, C]: `out` when it fits, a new tensor when it is None."""
+    shape = (*src.shape[:-3], src.shape[-1], *src.shape[-3:-1])
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=src.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != src.device:
+        raise MlhotError(f"{wrapper}: out must be fp32 {shape} on {src.device}")
+    return out
+
+
+def _nhwc(wrapper, src):
+    """(n_img, H, W, C) of a uint8 [..., H, W, C] batch; n_img is the product of the leading dimensions."""
+    if src.dtype != torch.uint8 or src.dim() < 3:
+        raise MlhotError(f"{wrapper} expects a uint8 [..., H, W, C] tensor, got {src.dtype} {tuple(src.shape)}")
+    return (math.prod(src.shape[:-3]), *src.shape[-3:])
+
+
+# ---- the C ABI, once: name -> (restype, argtypes), one line per prototype of include/mlhot.h in the header's order
+# (tests/test_binding_abi.py holds this table to the header).  MlhotLib applies it when it loads a library.
+i, z, P, f32, i64, u64, L, s, _p = C.c_int, C.c_size_t, C.c_void_p, C.c_float, C.c_int64, C.c_uint64, C.c_long, C.c_char_p, C.POINTER
+_qkvp = [P, P, P, P, i, i, i, i, i, i]                # q, k, v, proj, T, H, Nq, Nc, d, m
+_model = [_p(NpDims), _p(NpParams), P, P, P]          # dims, params, ctx_x, ctx_y, qry_x
+_trunk = [_p(TrunkPass), i, _p(TrunkWset), i, i, i]   # passes, n_pass, wsets, n_wset, C, H
+SIGNATURES = {
+    "mlhot_version": (i, []),
+    "mlhot_last_error": (s, []),
+    "mlhot_set_option": (i, [s, i]),
+    # bench-only launch profiler
+    "mlhot_prof_begin": (i, [i]),
+    "mlhot_prof_end": (i, [_p(s), _p(f32), i]),
+    # NT-Xent
+    "mlhot_nt_xent_ws_floats": (z, [i]),
+    "mlhot_nt_xent_fwd": (i, [P, i, i, i, i, f32, P, P, P]),
+    "mlhot_nt_xent_bwd": (i, [P, i, i, i, i, f32, P, P, P, P]),
+    # torch's CPU normal_() stream; host-only helpers
+    "mlhot_mt19937_normal": (i, [P, P, P, P, i, i64, i64, P]),
+    "mlhot_mt19937_jump_ws_words": (z, [i]),
+    "mlhot_mt19937_normal_par": (i, [P, P, P, P, i, i64, i64, P, i, i, P, P]),
+    "mlhot_mt19937_advance": (i, [P, u64]),
+    "mlhot_host_f32_to_u8_exact": (i, [P, P, i64, f32, i, _p(i64)]),
+    # E1: vanilla image encoder, and its first block on its own
+    "mlhot_enc_vanilla_saved_bytes": (z, [i]),
+    "mlhot_enc_vanilla_scratch_bytes": (z, [i, i]),
+    "mlhot_enc_vanilla_fwd": (i, [P, i, P, i, _p(EncParams), i, P, i, P, i, P, P, z, P]),
+    "mlhot_enc_vanilla_bwd": (i, [P, i, P, i, _p(EncParams), i, P, i, P, i, P, _p(EncGrads), P, z, P]),
+    "mlhot_conv12_scratch_bytes": (z, [i]),
+    "mlhot_conv12_fwd": (i, [P, i, P, P, P, P, P, P]),
+    "mlhot_conv12_bwd": (i, [P, i, P, P, P, P, P, P, P, P, P, P, z, P]),
+    # nn.Linear; chains of few-row Linears; independent few-row Linears
+    "mlhot_linear_bwd_scratch_bytes": (z, [i, i, i]),
+    "mlhot_linear_fwd": (i, [P, i, P, P, P, i, i, i, i, i, P]),
+    "mlhot_linear_bwd": (i, [P, i, P, P, i, P, i, i, i, i, i, P, i, i, P, P, P, z, P]),
+    "mlhot_mlp_chain_fwd": (i, [P, i, i, _p(ChainLayer), i, P]),
+    "mlhot_mlp_chain_bwd": (i, [P, i, i, _p(ChainLayer), _p(ChainGrads), i, P, i, P, i, i, P]),
+    "mlhot_linear_multi_fwd": (i, [_p(LinearJob), i, P]),
+    "mlhot_linear_multi_bwd": (i, [_p(LinearJob), i, P]),
+    # G1: aggregation over the shot axis
+    "mlhot_agg_fwd": (i, [i, P, P, i, i, i, P, P, P, P]),
+    "mlhot_agg_bwd": (i, [i, P, P, P, P, P, P, i, i, i, P, P, P]),
+    # FAVOR+
+    "mlhot_favor_ws_bytes": (z, [i] * 6),
+    "mlhot_favor_fwd": (i, _qkvp + [P, P, z, P]),
+    "mlhot_favor_bwd": (i, _qkvp + [P, P, P, P, P, P, z, P]),
+    # every context prefix of one batch; the Linears and the loss behind the prefix operators
+    "mlhot_agg_prefix_fwd": (i, [i, P, P, i, i, i, P, P, P]),
+    "mlhot_favor_prefix_ws_bytes": (z, [i] * 6),
+    "mlhot_favor_prefix_fwd": (i, _qkvp + [P, P, z, P]),
+    "mlhot_linear_rows_supported": (i, [i, i, i]),
+    "mlhot_linear_rows_fwd": (i, [_p(RowsSrc), i, P, P, P, i, i, i, i, P]),
+    "mlhot_loss_prefix_fwd": (i, [i, P, P, i, i, i, i, P, P]),
+    # strict sharded parity of the key stabiliser
+    "mlhot_favor_fwd_staged": (i, _qkvp + [P, P, z, i, P, P]),
+    "mlhot_favor_bwd_staged": (i, _qkvp + [P, P, P, P, P, P, z, i, P, P]),
+    # L1: losses
+    "mlhot_loss_fwd": (i, [i, P, P, i, i, i, P, P]),
+    "mlhot_loss_bwd": (i, [i, P, P, i, i, i, P, P, P]),
+    "mlhot_loss_plus_fwd": (i, [i, P, P, i, i, i, P, f32, P, P, P]),
+    "mlhot_loss_plus_bwd": (i, [i, P, P, i, i, i, P, f32, P, P, P]),
+    # E2 / D2: ResNet building blocks
+    "mlhot_conv2d_bwd_scratch_bytes": (z, [i] * 8),
+    "mlhot_conv2d_fwd": (i, [P, P, P, P] + [i] * 9 + [P]),
+    "mlhot_conv2d_bwd": (i, [P, P, P, P] + [i] * 9 + [P, P, P, P, z, P]),
+    "mlhot_axpy": (i, [P, P, f32, P, z, P]),
+    "mlhot_add_relu_fwd": (i, [P, P, P, z, P]),
+    "mlhot_add_relu_bwd": (i, [P, P, P, z, P]),
+    "mlhot_pool2_fwd": (i, [P, P, P, i, i, i, P]),
+    "mlhot_pool2_bwd": (i, [P, P, P, i, i, i, P]),
+    # whole ResNet trunks
+    "mlhot_trunk_act_floats": (z, [i] * 4),
+    "mlhot_trunk_scratch_bytes": (z, _trunk + [i]),
+    "mlhot_trunk_fwd": (i, _trunk + [P, z, P]),
+    "mlhot_trunk_bwd": (i, _trunk + [P, z, P]),
+    # B1: Bayes-by-backprop weight sample + KL
+    "mlhot_bbb_sample_fwd": (i, [P, P, P, P, P, P, z, P]),
+    "mlhot_bbb_sample_bwd": (i, [P, P, P, P, P, P, P, z, P]),
+    "mlhot_bbb_sample_multi_scratch_floats": (z, [_p(BbbItem), i]),
+    "mlhot_bbb_sample_multi_fwd": (i, [_p(BbbItem), i, P, P, P]),
+    "mlhot_bbb_sample_multi_bwd": (i, [_p(BbbItem), i, P, P]),
+    # batch ingest, with and without device augmentation
+    "mlhot_ingest_u8_nhwc": (i, [P, P, L, i, i, i, f32, P]),
+    "mlhot_augment_record_bytes": (z, []),
+    "mlhot_augment_ingest_u8": (i, [P, P, L, i, i, i, f32, P, P, i, P]),
+    "mlhot_augment_img_record_bytes": (z, []),
+    "mlhot_colour_tabs_bytes": (z, []),
+    "mlhot_augment_ingest_u8_img": (i, [P, P, L, i, i, i, i, f32, f32, P, P, i, P, P]),
+    # optimizer
+    "mlhot_adam_step": (i, [P, P, P, P, z] + [f32] * 6 + [i, P]),
+    "mlhot_adam_step_counter": (i, [P, P, P, P, z] + [f32] * 6 + [P, P]),
+    # X1: ConvEmbeddingModel building blocks
+    "mlhot_bn_relu_fwd": (i, [P, P, P, P, P, f32, f32, i, i, i, P, P, P, P]),
+    "mlhot_bn_relu_bwd": (i, [P, P, P, P, P, P, f32, i, i, i, P, P, P, P]),
+    "mlhot_spatial_mean_fwd": (i, [P, P, i, i, P]),
+    "mlhot_spatial_mean_bwd": (i, [P, P, i, i, P]),
+    # whole vanilla CNP/ANP model
+    "mlhot_np_struct_bytes": (z, [i]),
+    "mlhot_np_saved_bytes": (z, [_p(NpDims)]),
+    "mlhot_np_scratch_bytes": (z, [_p(NpDims)]),
+    "mlhot_np_grads_flat_layout": (z, [_p(NpDims), _p(NpGrads)]),
+    "mlhot_np_vanilla_fwd": (i, _model + [P, P, P, z, P]),
+    "mlhot_np_vanilla_bwd": (i, _model + [P, P, _p(NpGrads), P, P, z, P]),
+    "mlhot_np_vanilla_bwd_loss": (i, _model + [P, P, _p(LossDesc), _p(NpGrads), P, P, z, P]),
+    "mlhot_np_vanilla_fwd_staged": (i, _model + [P, P, P, z, i, P, P]),
+    "mlhot_np_vanilla_bwd_staged": (i, _model + [P, P, _p(NpGrads), P, P, z, i, P, P]),
+}
+del i, z, P, f32, i64, u64, L, s
+
+
 class MlhotLib:
     _last = None      # the most recently loaded library (size queries of the static test helpers)
 
@@ -186,70 +322,32 @@ class MlhotLib:
         if not os.path.exists(path):
             raise MlhotError(f"mlhot: shared library not found: {path} (run __graft_entry__.build())")
         self.path = path
-        self.c = C.CDLL(path)
+        self.c = c = C.CDLL(path)
         MlhotLib._last = self
-        c = self.c
-        c.mlhot_version.restype = C.c_int
         if c.mlhot_version() != ABI_VERSION:       # before any other symbol is touched: an older prebuilt library lacks the newer ones
             raise MlhotError(f"mlhot: libmlhot.so has ABI version {c.mlhot_version()}, this binding needs {ABI_VERSION} "
                              f"(include/mlhot.h MLHOT_ABI_VERSION) - rebuild with mlhot.build.build_product(force=True)")
-        c.mlhot_last_error.restype = C.c_char_p
-        for fn in ("mlhot_enc_vanilla_saved_bytes", "mlhot_enc_vanilla_scratch_bytes", "mlhot_linear_bwd_scratch_bytes",
-                   "mlhot_favor_ws_bytes", "mlhot_np_struct_bytes", "mlhot_np_saved_bytes", "mlhot_np_scratch_bytes",
-                   "mlhot_np_grads_flat_layout", "mlhot_conv12_scratch_bytes"):
-            getattr(c, fn).restype = C.c_size_t
-        c.mlhot_conv12_scratch_bytes.argtypes = [C.c_int]
-        c.mlhot_enc_vanilla_saved_bytes.argtypes = [C.c_int]
-        c.mlhot_enc_vanilla_scratch_bytes.argtypes = [C.c_int, C.c_int]
-        c.mlhot_favor_ws_bytes.argtypes = [C.c_int] * 6
-        c.mlhot_np_struct_bytes.argtypes = [C.c_int]
-        c.mlhot_np_saved_bytes.argtypes = [C.POINTER(NpDims)]
-        c.mlhot_np_scratch_bytes.argtypes = [C.POINTER(NpDims)]
-        c.mlhot_np_grads_flat_layout.argtypes = [C.POINTER(NpDims), C.POINTER(NpGrads)]
-        i, z, P = C.c_int, C.c_size_t, C.c_void_p
-        c.mlhot_enc_vanilla_fwd.argtypes = [P, i, P, i, C.POINTER(EncParams), i, P, i, P, i, P, P, z, P]
-        c.mlhot_enc_vanilla_bwd.argtypes = [P, i, P, i, C.POINTER(EncParams), i, P, i, P, i, P, C.POINTER(EncParams), P, z, P]
-        c.mlhot_conv12_fwd.argtypes = [P, i, P, P, P, P, P, P]
-        c.mlhot_conv12_bwd.argtypes = [P, i, P, P, P, P, P, P, P, P, P, P, z, P]
-        c.mlhot_linear_fwd.argtypes = [P, i, P, P, P, i, i, i, i, i, P]
-        c.mlhot_linear_bwd.argtypes = [P, i, P, P, i, P, i, i, i, i, i, P, i, i, P, P, P, z, P]
-        c.mlhot_agg_fwd.argtypes = [i, P, P, i, i, i, P, P, P, P]
-        c.mlhot_agg_bwd.argtypes = [i, P, P, P, P, P, P, i, i, i, P, P, P]
-        c.mlhot_favor_fwd.argtypes = [P, P, P, P, i, i, i, i, i, i, P, P, z, P]
-        c.mlhot_favor_bwd.argtypes = [P, P, P, P, i, i, i, i, i, i, P, P, P, P, P, P, z, P]
-        c.mlhot_favor_fwd_staged.argtypes = [P, P, P, P, i, i, i, i, i, i, P, P, z, i, P, P]
-        c.mlhot_favor_bwd_staged.argtypes = [P, P, P, P, i, i, i, i, i, i, P, P, P, P, P, P, z, i, P, P]
-        c.mlhot_loss_fwd.argtypes = [i, P, P, i, i, i, P, P]
-        c.mlhot_loss_bwd.argtypes = [i, P, P, i, i, i, P, P, P]
-        c.mlhot_loss_plus_fwd.argtypes = [i, P, P, i, i, i, P, C.c_float, P, P, P]
-        c.mlhot_loss_plus_bwd.argtypes = [i, P, P, i, i, i, P, C.c_float, P, P, P]
-        c.mlhot_conv2d_bwd_scratch_bytes.restype = C.c_size_t
-        c.mlhot_conv2d_bwd_scratch_bytes.argtypes = [i] * 8
-        c.mlhot_conv2d_fwd.argtypes = [P, P, P, P] + [i] * 9 + [P]
-        c.mlhot_conv2d_bwd.argtypes = [P, P, P, P] + [i] * 9 + [P, P, P, P, z, P]
-        c.mlhot_add_relu_fwd.argtypes = [P, P, P, z, P]
-        c.mlhot_add_relu_bwd.argtypes = [P, P, P, z, P]
-        c.mlhot_pool2_fwd.argtypes = [P, P, P, i, i, i, P]
-        c.mlhot_pool2_bwd.argtypes = [P, P, P, i, i, i, P]
-        c.mlhot_bbb_sample_fwd.argtypes = [P, P, P, P, P, P, z, P]
-        c.mlhot_bbb_sample_bwd.argtypes = [P, P, P, P, P, P, P, z, P]
-        f32 = C.c_float
-        c.mlhot_bn_relu_fwd.argtypes = [P, P, P, P, P, f32, f32, i, i, i, P, P, P, P]
-        c.mlhot_bn_relu_bwd.argtypes = [P, P, P, P, P, P, f32, i, i, i, P, P, P, P]
-        c.mlhot_spatial_mean_fwd.argtypes = [P, P, i, i, P]
-        c.mlhot_spatial_mean_bwd.argtypes = [P, P, i, i, P]
-        c.mlhot_np_vanilla_fwd.argtypes = [C.POINTER(NpDims), C.POINTER(NpParams), P, P, P, P, P, P, z, P]
-        c.mlhot_np_vanilla_bwd.argtypes = [C.POINTER(NpDims), C.POINTER(NpParams), P, P, P, P, P, C.POINTER(NpGrads), P, P, z, P]
-        c.mlhot_np_vanilla_fwd_staged.argtypes = [C.POINTER(NpDims), C.POINTER(NpParams), P, P, P, P, P, P, z, i, P, P]
-        c.mlhot_np_vanilla_bwd_loss.argtypes = [C.POINTER(NpDims), C.POINTER(NpParams), P, P, P, P, P, C.POINTER(LossDesc), C.POINTER(NpGrads), P, P, z, P]
-        c.mlhot_np_vanilla_bwd_staged.argtypes = [C.POINTER(NpDims), C.POINTER(NpParams), P, P, P, P, P, C.POINTER(NpGrads), P, P, z, i, P, P]
-        c.mlhot_mlp_chain_fwd.argtypes = [P, i, i, C.POINTER(ChainLayer), i, P]
-        c.mlhot_mlp_chain_bwd.argtypes = [P, i, i, C.POINTER(ChainLayer), C.POINTER(ChainGrads), i, P, i, P, i, i, P]
-        c.mlhot_linear_multi_fwd.argtypes = [C.POINTER(LinearJob), i, P]
-        c.mlhot_linear_multi_bwd.argtypes = [C.POINTER(LinearJob), i, P]
-        for which, st in ((0, NpDims), (1, NpParams), (2, NpGrads), (3, ChainLayer), (4, ChainGrads), (5, LinearJob)):
-            if c.mlhot_np_struct_bytes(which) != C.sizeof(st):
-                raise MlhotError(f"mlhot: ABI struct size mismatch for {st.__name__}")
+        # a prebuilt library of the right ABI version may still predate an entry added within that version: it loads, and the
+        # wrappers of what it lacks say so when they are called (_fn)
+        self.missing = {name for name in SIGNATURES if not hasattr(c, name)}
+        for name, (restype, argtypes) in SIGNATURES.items():
+            if name not in self.missing:
+                fn = getattr(c, name)
+                fn.restype = restype
+                fn.argtypes = argtypes
+        sizes = [("mlhot_np_struct_bytes", (w,), C.sizeof(st), st.__name__)
+                 for w, st in enumerate((NpDims, NpParams, NpGrads, ChainLayer, ChainGrads, LinearJob))]
+        sizes += [("mlhot_augment_record_bytes", (), AUG_RECORD_BYTES, "mlhot_aug_record"), ("mlhot_colour_tabs_bytes", (), COLOUR_TABS_BYTES, "mlhot_colour_tabs"),
+                  ("mlhot_augment_img_record_bytes", (), AUG_IMG_RECORD_BYTES, "mlhot_aug_record_img")]
+        for symbol, args, want, what in sizes:
+            if symbol not in self.missing and getattr(c, symbol)(*args) != want:
+                raise MlhotError(f"mlhot: ABI struct size mismatch for {what}")
+
+    def _fn(self, wrapper, symbol):
+        """The entry `symbol` of the loaded library, for the wrappers of entries added within an ABI version."""
+        if symbol in self.missing:
+            raise MlhotError(f"{wrapper}: {self.path} lacks {symbol} - rebuild with mlhot.build.build_product(force=True)")
+        return getattr(self.c, symbol)
 
     # ------------------------------------------------------------------------------------------
     def _rc(self, rc, what):
@@ -261,20 +359,17 @@ class MlhotLib:
         return torch.empty(max(int(n), 256), dtype=torch.uint8, device=like.device)
 
     def set_option(self, name, value):
-        self.c.mlhot_set_option.argtypes = [C.c_char_p, C.c_int]
         self._rc(self.c.mlhot_set_option(name.encode(), int(value)), "mlhot_set_option")
 
     # ---- bench-only launch profiler -----------------------------------------------------------
     def prof_begin(self, max_records=4096):
         self._prof_cap = max_records
-        self.c.mlhot_prof_begin.argtypes = [C.c_int]
         self._rc(self.c.mlhot_prof_begin(max_records), "mlhot_prof_begin")
 
     def prof_end(self):
         """-> list of (label, ms) per kernel launch since prof_begin()"""
         cap = self._prof_cap
         labels, ms = (C.c_char_p * cap)(), (C.c_float * cap)()
-        self.c.mlhot_prof_end.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
         n = self.c.mlhot_prof_end(labels, ms, cap)
         return [(labels[i].decode(), float(ms[i])) for i in range(n)]
 
@@ -331,15 +426,13 @@ class MlhotLib:
     def enc_saved_views(saved, n):
         """Test / diagnostic helper: the activations the encoder forward kept for its backward
         (csrc/encoder.h EncSaved: 256-byte aligned a1 | p2 | am2 | a3) as tensor views."""
-        def al(x):
-            return (x + 255) // 256 * 256
         o = 0
         a1 = saved[o:o + n * 32 * 4096 * 4].view(torch.float32).view(n, 32, 64, 64)
-        o = al(o + n * 32 * 4096 * 4)
+        o = _align256(o + n * 32 * 4096 * 4)
         p2 = saved[o:o + n * 48 * 256 * 4].view(torch.float32).view(n, 48, 16, 16)
-        o = al(o + n * 48 * 256 * 4)
+        o = _align256(o + n * 48 * 256 * 4)
         am2 = saved[o:o + n * 48 * 256].view(n, 48, 16, 16)
-        o = al(o + n * 48 * 256)
+        o = _align256(o + n * 48 * 256)
         a3 = saved[o:o + n * 4096 * 4].view(torch.float32).view(n, 64, 8, 8)
         return a1, p2, am2, a3
 
@@ -348,13 +441,11 @@ class MlhotLib:
         """Test / diagnostic helper: the piecewise-linear routing decisions the fused encoder forward took, in the form
         oracle.ref_cpu.vanilla_encoder_routed takes them: (conv1 ReLU mask [n,32,64,64] unpacked from the forward's sign-bit
         words, pool arg-max [n,48,16,16], pooled-conv2 ReLU mask, conv3 ReLU mask) as CPU tensors."""
-        def al(x):
-            return (x + 255) // 256 * 256
         _, p2, am2, a3 = MlhotLib.enc_saved_views(saved, n)
-        o = al(n * 32 * 4096 * 4)
-        o = al(o + n * 48 * 256 * 4)
-        o = al(o + n * 48 * 256)
-        o = al(o + n * 4096 * 4)
+        o = _align256(n * 32 * 4096 * 4)
+        o = _align256(o + n * 48 * 256 * 4)
+        o = _align256(o + n * 48 * 256)
+        o = _align256(o + n * 4096 * 4)
         # records [img][row][column group cg][dword 4r + 2h + g], bit 16e + c = channel 16h + c of column 16cg + 4(2g + e) + r
         # (csrc/conv_tc.h m1_record)
         words = saved[o:o + n * 4096 * 4].view(torch.int32).view(n, 64, 4, 4, 2, 2, 1, 1).cpu()      # n, y, cg, r, h, g
@@ -367,17 +458,15 @@ class MlhotLib:
     def np_saved_views(saved, dims):
         """Test / diagnostic helper: activations mlhot_np_vanilla_fwd kept (csrc/np_vanilla.h np_saved_carve) as tensor views:
         the encoder blob (first; see enc_routes) and the task-side layers' post-ReLU outputs."""
-        def al(x):
-            return (x + 255) // 256 * 256
         Rc, Rq = dims.T * dims.Nc, dims.T * dims.Nq
         n, dw = Rc + Rq, dims.dim_w
         lib = MlhotLib._last
-        o = al(lib.c.mlhot_enc_vanilla_saved_bytes(n))
+        o = _align256(lib.c.mlhot_enc_vanilla_saved_bytes(n))
 
         def take(rows, cols, dtype=torch.float32):
             nonlocal o
             v = saved[o:o + rows * cols * 4].view(dtype).view(rows, cols)
-            o = al(o + rows * cols * 4)
+            o = _align256(o + rows * cols * 4)
             return v
         out = {"enc": saved, "n": n}
         out["dec_in"] = take(Rq, dw + dims.dim_z)
@@ -496,7 +585,6 @@ class MlhotLib:
         ws2 = [torch.empty_like(m) for m in mus] if epss2 is not None else None
         kl = torch.empty((), device=mus[0].device)
         items = self._bbb_items(mus, rhos, epss, ws=ws, epss2=epss2, ws2=ws2)
-        self.c.mlhot_bbb_sample_multi_scratch_floats.restype = C.c_size_t
         partial = torch.empty(self.c.mlhot_bbb_sample_multi_scratch_floats(items, len(mus)), device=mus[0].device)
         self._rc(self.c.mlhot_bbb_sample_multi_fwd(items, len(mus), _ptr(partial), _ptr(kl), _stream(mus[0])), "mlhot_bbb_sample_multi_fwd")
         return (ws, kl) if epss2 is None else (ws, ws2, kl)
@@ -515,11 +603,8 @@ class MlhotLib:
         if not z.is_cuda:
             raise MlhotError("mlhot_nt_xent_fwd: device tensors only")
         N, d = z.shape
-        self.c.mlhot_nt_xent_ws_floats.restype = C.c_size_t
-        self.c.mlhot_nt_xent_ws_floats.argtypes = [C.c_int]
         ws = torch.empty(self.c.mlhot_nt_xent_ws_floats(N), device=z.device)
         loss = torch.empty((), device=z.device)
-        self.c.mlhot_nt_xent_fwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         self._rc(self.c.mlhot_nt_xent_fwd(_ptr(z), N, d, div, mod, t, _ptr(ws), _ptr(loss), _stream(z)), "mlhot_nt_xent_fwd")
         return loss, ws
 
@@ -527,8 +612,6 @@ class MlhotLib:
         _chk(z, ws, dloss)
         N, d = z.shape
         dz = torch.empty_like(z)
-        self.c.mlhot_nt_xent_bwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p]
         self._rc(self.c.mlhot_nt_xent_bwd(_ptr(z), N, d, div, mod, t, _ptr(ws), _ptr(dloss), _ptr(dz), _stream(z)), "mlhot_nt_xent_bwd")
         return dz
 
@@ -539,7 +622,6 @@ class MlhotLib:
             raise MlhotError("mlhot_mt19937_normal: device tensors only")
         if engine.dtype != torch.int32 or engine.numel() != 626 or segs.dtype != torch.int64 or out.dtype != torch.float32:
             raise MlhotError("mlhot_mt19937_normal: engine int32[626], segs int64[nseg, 4], out float32")
-        self.c.mlhot_mt19937_normal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
         self._rc(self.c.mlhot_mt19937_normal(_ptr(engine), _ptr(uniform_ws), _ptr(out), _ptr(segs), nseg, total_outputs, total_groups,
                                              _stream(out)), "mlhot_mt19937_normal")
 
@@ -550,24 +632,17 @@ class MlhotLib:
         if engine.dtype != torch.int32 or engine.numel() != 626 or segs.dtype != torch.int64 or out.dtype != torch.float32 or \
                 polys.dtype != torch.int32 or tuple(polys.shape) != (n_sub - 1, 624) or jump_ws.dtype != torch.int32:
             raise MlhotError("mlhot_mt19937_normal_par: engine int32[626], segs int64[nseg, 4], out float32, polys int32[n_sub - 1, 624]")
-        self.c.mlhot_mt19937_jump_ws_words.restype = C.c_size_t
-        self.c.mlhot_mt19937_jump_ws_words.argtypes = [C.c_int]
         if jump_ws.numel() < self.c.mlhot_mt19937_jump_ws_words(n_sub):
             raise MlhotError("mlhot_mt19937_normal_par: jump workspace too small")
-        self.c.mlhot_mt19937_normal_par.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
-                                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         self._rc(self.c.mlhot_mt19937_normal_par(_ptr(engine), _ptr(uniform_ws), _ptr(out), _ptr(segs), nseg, total_outputs, total_groups,
                                                  _ptr(polys), n_sub, stride_blocks, _ptr(jump_ws), _stream(out)), "mlhot_mt19937_normal_par")
 
     def mt19937_jump_ws_words(self, n_sub):
-        self.c.mlhot_mt19937_jump_ws_words.restype = C.c_size_t
-        self.c.mlhot_mt19937_jump_ws_words.argtypes = [C.c_int]
         return int(self.c.mlhot_mt19937_jump_ws_words(n_sub))
 
     def host_f32_to_u8_exact(self, src_ptr, dst_ptr, n, div=255.0, threads=1):
         """Raw host pointers (ints), n elements: bytes into dst, returns the number of elements that do NOT round-trip through
         (float)byte / div bit for bit.  Host only; `threads` native threads inside the call (the GIL is released for its duration)."""
-        self.c.mlhot_host_f32_to_u8_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int, C.POINTER(C.c_int64)]
         bad = C.c_int64(0)
         self._rc(self.c.mlhot_host_f32_to_u8_exact(C.c_void_p(src_ptr), C.c_void_p(dst_ptr), int(n), float(div), int(threads), C.byref(bad)),
                  "mlhot_host_f32_to_u8_exact")
@@ -578,7 +653,6 @@ class MlhotLib:
         import numpy as np
         if not (isinstance(engine, np.ndarray) and engine.dtype == np.uint32 and engine.size == 626 and engine.flags.c_contiguous and engine.flags.writeable):
             raise MlhotError("mt19937_advance: engine must be a writeable contiguous numpy uint32[626]")
-        self.c.mlhot_mt19937_advance.argtypes = [C.c_void_p, C.c_uint64]
         self._rc(self.c.mlhot_mt19937_advance(C.c_void_p(engine.ctypes.data), int(n_outputs)), "mlhot_mt19937_advance")
         return engine
 
@@ -609,8 +683,6 @@ class MlhotLib:
     def trunk_acts(self, img):
         """The nine saved-activation tensors of one pass (a0, then (mid_i, y_i) of the four blocks) as views of one buffer."""
         n, C_, H, _ = img.shape
-        self.c.mlhot_trunk_act_floats.restype = C.c_size_t
-        self.c.mlhot_trunk_act_floats.argtypes = [C.c_int] * 4
         sizes = [self.c.mlhot_trunk_act_floats(C_, H, n, k) for k in range(9)]
         offs, tot = [], 0
         for sz in sizes:
@@ -624,8 +696,6 @@ class MlhotLib:
         return out
 
     def _trunk_scratch(self, pa, n_pass, wa, n_wset, C_, H, backward, like):
-        self.c.mlhot_trunk_scratch_bytes.restype = C.c_size_t
-        self.c.mlhot_trunk_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         sb = self.c.mlhot_trunk_scratch_bytes(pa, n_pass, wa, n_wset, C_, H, backward)
         if sb == 0:
             raise MlhotError(f"mlhot_trunk: {self.c.mlhot_last_error().decode()}")
@@ -640,7 +710,6 @@ class MlhotLib:
         full = [(img, w, self.trunk_acts(img)) for img, w in passes]
         pa, wa = self._trunk_structs(full, wsets)
         sb, scratch = self._trunk_scratch(pa, len(full), wa, len(wsets), C_, H, 0, imgs[0])
-        self.c.mlhot_trunk_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         self._rc(self.c.mlhot_trunk_fwd(pa, len(full), wa, len(wsets), C_, H, _ptr(scratch), sb, _stream(imgs[0])), "mlhot_trunk_fwd")
         return [acts for _, _, acts in full]
 
@@ -652,7 +721,6 @@ class MlhotLib:
         grads = [[_grad_like(t) for t in ts] for ts, _ in wsets]
         pa, wa = self._trunk_structs(passes, wsets, grads=grads, dfeats=dfeats)
         sb, scratch = self._trunk_scratch(pa, len(passes), wa, len(wsets), C_, H, 1, imgs[0])
-        self.c.mlhot_trunk_bwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         self._rc(self.c.mlhot_trunk_bwd(pa, len(passes), wa, len(wsets), C_, H, _ptr(scratch), sb, _stream(imgs[0])), "mlhot_trunk_bwd")
         return grads
 
@@ -700,26 +768,16 @@ class MlhotLib:
         self._rc(self.c.mlhot_linear_fwd(_ptr(x), K, _ptr(w), _ptr(b), _ptr(y), N, M, K, N, ACT[act], _stream(x)), "mlhot_linear_fwd")
         return y
 
-    def _rows_symbols(self):
-        c = self.c
-        if not hasattr(c, "mlhot_linear_rows_fwd") or not hasattr(c, "mlhot_linear_rows_supported") or not hasattr(c, "mlhot_loss_prefix_fwd"):
-            raise MlhotError(f"linear_rows_fwd: {self.path} lacks mlhot_linear_rows_fwd / mlhot_loss_prefix_fwd - rebuild with mlhot.build.build_product(force=True)")
-        P, i = C.c_void_p, C.c_int
-        c.mlhot_linear_rows_supported.argtypes = [i, i, i]
-        c.mlhot_linear_rows_fwd.argtypes = [C.POINTER(RowsSrc), i, P, P, P, i, i, i, i, P]
-        c.mlhot_loss_prefix_fwd.argtypes = [i, P, P, i, i, i, i, P, P]
-        return c
-
     def linear_rows_supported(self, k0, k1, N):
         """Whether mlhot_linear_rows_fwd serves a layer with k ranges k0 | k1 and N outputs (pointers are checked per call)."""
-        return bool(self._rows_symbols().mlhot_linear_rows_supported(int(k0), int(k1), int(N)))
+        return bool(self._fn("linear_rows_supported", "mlhot_linear_rows_supported")(int(k0), int(k1), int(N)))
 
     def linear_rows_fwd(self, sources, w, b, act="none", rows=None, out=None):
         """y[M, N] = act([src_0 | src_1] w^T + b) with bits that do not depend on M (csrc/linear_rows.h).  sources: one or two
         (x [R, k] with unit column stride, rep, period): output row i reads x[(i // rep) % period] (period 0: no wrap).  M = `rows`,
         or R * rep of the sources without a period.  `out`: a [>= M, >= N] fp32 tensor with unit column stride to write into
         (its first M rows x N columns are written, nothing else)."""
-        c = self._rows_symbols()
+        fn = self._fn("linear_rows_fwd", "mlhot_linear_rows_fwd")
         sources = [tuple(s) for s in sources]
         if len(sources) not in (1, 2) or any(len(s) != 3 for s in sources):
             raise MlhotError("linear_rows_fwd: sources must be one or two (tensor, rep, period) tuples")
@@ -756,7 +814,7 @@ class MlhotLib:
             arr[j].x, arr[j].ld, arr[j].k = x.data_ptr(), (x.stride(0) if x.shape[0] > 1 else x.shape[1]), x.shape[1]
             arr[j].rep, arr[j].period = int(rep), int(period)
         ldy = out.stride(0) if out.shape[0] > 1 else out.shape[1]
-        self._rc(c.mlhot_linear_rows_fwd(arr, len(sources), _ptr(w), _ptr(b), _ptr(out), ldy, M, N, ACT[act], _stream(w)), "mlhot_linear_rows_fwd")
+        self._rc(fn(arr, len(sources), _ptr(w), _ptr(b), _ptr(out), ldy, M, N, ACT[act], _stream(w)), "mlhot_linear_rows_fwd")
         return out
 
     def linear_bwd(self, x, w, y, dy, act="none", need_dx=True, b=None):
@@ -863,7 +921,6 @@ class MlhotLib:
         """a + alpha * x (a None: alpha * x), elementwise, one launch."""
         _chk(a, x)
         y = torch.empty_like(x)
-        self.c.mlhot_axpy.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]
         self._rc(self.c.mlhot_axpy(_ptr(a), _ptr(x), float(alpha), _ptr(y), x.numel(), _stream(x)), "mlhot_axpy")
         return y
 
@@ -888,9 +945,7 @@ class MlhotLib:
 
     def agg_prefix_fwd(self, mode, rs, lv=None, want_sigma=False):
         """rs [T,Nc,R] (baco: + lv) -> r [Nc,T,R] (and sigma_z [Nc,T,R] when asked): row k-1 = agg_fwd of rs[:, :k].  Forward only."""
-        c = self.c
-        if not hasattr(c, "mlhot_agg_prefix_fwd"):
-            raise MlhotError(f"agg_prefix_fwd: {self.path} lacks mlhot_agg_prefix_fwd - rebuild with mlhot.build.build_product(force=True)")
+        fn = self._fn("agg_prefix_fwd", "mlhot_agg_prefix_fwd")
         if mode not in ("mean", "max", "baco"):
             raise MlhotError(f"agg_prefix_fwd: mode must be 'mean', 'max' or 'baco', got {mode!r}")
         if rs.dtype != torch.float32 or rs.dim() != 3 or min(rs.shape) < 1:
@@ -903,8 +958,7 @@ class MlhotLib:
         T, Nc, R = rs.shape
         r = torch.empty(Nc, T, R, device=rs.device)
         sigma = torch.empty(Nc, T, R, device=rs.device) if (want_sigma and mode == "baco") else None
-        c.mlhot_agg_prefix_fwd.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        self._rc(c.mlhot_agg_prefix_fwd(AGG[mode], _ptr(rs), _ptr(lv), T, Nc, R, _ptr(r), _ptr(sigma), _stream(rs)), "mlhot_agg_prefix_fwd")
+        self._rc(fn(AGG[mode], _ptr(rs), _ptr(lv), T, Nc, R, _ptr(r), _ptr(sigma), _stream(rs)), "mlhot_agg_prefix_fwd")
         return r, sigma
 
     # ---- FAVOR+ --------------------------------------------------------------------------------
@@ -914,12 +968,7 @@ class MlhotLib:
 
     def favor_prefix_ws_bytes(self, T, H, Nq, Nc, d, m):
         """Workspace bytes of mlhot_favor_prefix_fwd; 0 for a shape it does not serve."""
-        c = self.c
-        if not hasattr(c, "mlhot_favor_prefix_fwd") or not hasattr(c, "mlhot_favor_prefix_ws_bytes"):
-            raise MlhotError(f"favor_prefix_fwd: {self.path} lacks mlhot_favor_prefix_fwd - rebuild with mlhot.build.build_product(force=True)")
-        c.mlhot_favor_prefix_ws_bytes.restype = C.c_size_t
-        c.mlhot_favor_prefix_ws_bytes.argtypes = [C.c_int] * 6
-        return c.mlhot_favor_prefix_ws_bytes(T, H, Nq, Nc, d, m)
+        return self._fn("favor_prefix_fwd", "mlhot_favor_prefix_ws_bytes")(T, H, Nq, Nc, d, m)
 
     def favor_prefix_fwd(self, q, k, v, proj):
         """q [T,Nq,H,d], k/v [T,Nc,H,d], proj [m,d] -> out [Nc,T,Nq,d*H]: out[k-1] = favor_fwd on the first k keys / values.  Forward only."""
@@ -940,10 +989,8 @@ class MlhotLib:
         _chk(q, k, v, proj)
         out = torch.empty(Nc, T, Nq, d * H, device=q.device)
         ws = self._bytes(wb, q)
-        P, i = C.c_void_p, C.c_int
-        self.c.mlhot_favor_prefix_fwd.argtypes = [P, P, P, P, i, i, i, i, i, i, P, P, C.c_size_t, P]
-        self._rc(self.c.mlhot_favor_prefix_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(proj), T, H, Nq, Nc, d, m, _ptr(out), _ptr(ws), ws.numel(),
-                                               _stream(q)), "mlhot_favor_prefix_fwd")
+        fn = self._fn("favor_prefix_fwd", "mlhot_favor_prefix_fwd")
+        self._rc(fn(_ptr(q), _ptr(k), _ptr(v), _ptr(proj), T, H, Nq, Nc, d, m, _ptr(out), _ptr(ws), ws.numel(), _stream(q)), "mlhot_favor_prefix_fwd")
         return out
 
     @staticmethod
@@ -997,7 +1044,7 @@ class MlhotLib:
 
     def loss_prefix_fwd(self, kind, mu, gt):
         """mu [P, ..., y_dim], gt [..., gt_dim] shared by the prefixes -> loss [P]: loss[p] = loss_fwd(kind, mu[p], gt), same bits, one launch."""
-        c = self._rows_symbols()
+        fn = self._fn("loss_prefix_fwd", "mlhot_loss_prefix_fwd")
         if kind not in LOSS:
             raise MlhotError(f"loss_prefix_fwd: kind must be one of {sorted(LOSS)}, got {kind!r}")
         if mu.dim() < 2 or mu.numel() == 0 or gt.numel() == 0:
@@ -1008,7 +1055,7 @@ class MlhotLib:
         if gt.numel() // gt.shape[-1] != rows or mu.dtype != torch.float32 or gt.dtype != torch.float32:
             raise MlhotError(f"loss_prefix_fwd: labels {tuple(gt.shape)} do not fit mu {tuple(mu.shape)} (fp32, one label row per row of a prefix)")
         loss = torch.empty(P, device=mu.device)
-        self._rc(c.mlhot_loss_prefix_fwd(LOSS[kind], _ptr(mu), _ptr(gt), P, rows, y_dim, gt.shape[-1], _ptr(loss), _stream(mu)), "mlhot_loss_prefix_fwd")
+        self._rc(fn(LOSS[kind], _ptr(mu), _ptr(gt), P, rows, y_dim, gt.shape[-1], _ptr(loss), _stream(mu)), "mlhot_loss_prefix_fwd")
         return loss
 
     def loss_bwd(self, kind, mu, gt, dloss):
@@ -1044,19 +1091,9 @@ class MlhotLib:
     def ingest_u8_nhwc(self, src, out=None, div=255.0):
         """src: uint8 [..., H, W, C] on the device (channel-last, as the data loaders hold images) ->
         fp32 [..., C, H, W] = src / div (dataset/shapenet_1d.py:189-190 + utils/utils.py:26-30)."""
-        if src.dtype != torch.uint8 or src.dim() < 3:
-            raise MlhotError(f"ingest_u8_nhwc expects a uint8 [..., H, W, C] tensor, got {src.dtype} {tuple(src.shape)}")
+        n_img, H, W, Cc = _nhwc("ingest_u8_nhwc", src)
         _chk(src, out)
-        *lead, H, W, Cc = src.shape
-        shape = (*lead, Cc, H, W)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=src.device)
-        elif out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != src.device:
-            raise MlhotError(f"ingest_u8_nhwc: out must be fp32 {shape} on {src.device}")
-        n_img = 1
-        for v in lead:
-            n_img *= v
-        self.c.mlhot_ingest_u8_nhwc.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]
+        out = _ingest_out("ingest_u8_nhwc", src, out)
         self._rc(self.c.mlhot_ingest_u8_nhwc(_ptr(src), _ptr(out), n_img, H, W, Cc, float(div), _stream(src)), "mlhot_ingest_u8_nhwc")
         return out
 
@@ -1064,18 +1101,8 @@ class MlhotLib:
         """ingest_u8_nhwc with the 1D loaders' data augmentation in front (csrc/augment.h, include/mlhot.h mlhot_aug_record):
         src uint8 [..., H, W, 1] -> fp32 [..., 1, H, W].  records: int32 [n_img, 32] (mlhot.augment.Sampler), luts: uint8
         [n_luts, 256] or None; both on src's device."""
-        if src.dtype != torch.uint8 or src.dim() < 3:
-            raise MlhotError(f"augment_ingest_u8 expects a uint8 [..., H, W, C] tensor, got {src.dtype} {tuple(src.shape)}")
-        c = self.c
-        if not hasattr(c, "mlhot_augment_ingest_u8"):
-            raise MlhotError(f"augment_ingest_u8: {self.path} lacks mlhot_augment_ingest_u8 - rebuild with mlhot.build.build_product(force=True)")
-        c.mlhot_augment_record_bytes.restype = C.c_size_t
-        if c.mlhot_augment_record_bytes() != AUG_RECORD_BYTES:
-            raise MlhotError("mlhot: ABI struct size mismatch for mlhot_aug_record")
-        *lead, H, W, Cc = src.shape
-        n_img = 1
-        for v in lead:
-            n_img *= v
+        n_img, H, W, Cc = _nhwc("augment_ingest_u8", src)
+        fn = self._fn("augment_ingest_u8", "mlhot_augment_ingest_u8")
         if records.dtype != torch.int32 or records.numel() != n_img * (AUG_RECORD_BYTES // 4) or records.device != src.device:
             raise MlhotError(f"augment_ingest_u8: records must be int32 [{n_img}, {AUG_RECORD_BYTES // 4}] on {src.device}")
         n_luts = 0
@@ -1084,15 +1111,9 @@ class MlhotLib:
                 raise MlhotError("augment_ingest_u8: luts must be uint8 [n, 256] on the images' device")
             n_luts = luts.shape[0]
         _chk(src, out, records, luts)
-        shape = (*lead, Cc, H, W)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=src.device)
-        elif out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != src.device:
-            raise MlhotError(f"augment_ingest_u8: out must be fp32 {shape} on {src.device}")
-        c.mlhot_augment_ingest_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
-                                              C.c_void_p, C.c_int, C.c_void_p]
-        self._rc(c.mlhot_augment_ingest_u8(_ptr(src), _ptr(out), n_img, H, W, Cc, float(div), _ptr(records),
-                                           _ptr(luts) if n_luts else None, n_luts, _stream(src)), "mlhot_augment_ingest_u8")
+        out = _ingest_out("augment_ingest_u8", src, out)
+        self._rc(fn(_ptr(src), _ptr(out), n_img, H, W, Cc, float(div), _ptr(records), _ptr(luts) if n_luts else None, n_luts, _stream(src)),
+                 "mlhot_augment_ingest_u8")
         return out
 
     def augment_ingest_u8_img(self, src, records, luts=None, colour_tabs=None, out=None, pre_op=0, div=255.0, div2=1.0):
@@ -1100,19 +1121,8 @@ class MlhotLib:
         (C = 3 with H, W <= 64, or C = 1 with H, W <= 128) -> fp32 [..., C, H, W] = augmented byte / div / div2.  records: int32
         [n_img, 40] (mlhot.augment.ImageSampler), luts: uint8 [n_luts, 256] or None, colour_tabs: uint8 [12896]
         (mlhot.augment.colour_tables(device)) or None; all on src's device."""
-        if src.dtype != torch.uint8 or src.dim() < 3:
-            raise MlhotError(f"augment_ingest_u8_img expects a uint8 [..., H, W, C] tensor, got {src.dtype} {tuple(src.shape)}")
-        c = self.c
-        if not hasattr(c, "mlhot_augment_ingest_u8_img"):
-            raise MlhotError(f"augment_ingest_u8_img: {self.path} lacks mlhot_augment_ingest_u8_img - rebuild with mlhot.build.build_product(force=True)")
-        c.mlhot_augment_img_record_bytes.restype = C.c_size_t
-        c.mlhot_colour_tabs_bytes.restype = C.c_size_t
-        if c.mlhot_augment_img_record_bytes() != AUG_IMG_RECORD_BYTES or c.mlhot_colour_tabs_bytes() != COLOUR_TABS_BYTES:
-            raise MlhotError("mlhot: ABI struct size mismatch for mlhot_aug_record_img / mlhot_colour_tabs")
-        *lead, H, W, Cc = src.shape
-        n_img = 1
-        for v in lead:
-            n_img *= v
+        n_img, H, W, Cc = _nhwc("augment_ingest_u8_img", src)
+        fn = self._fn("augment_ingest_u8_img", "mlhot_augment_ingest_u8_img")
         ints = AUG_IMG_RECORD_BYTES // 4
         if records.dtype != torch.int32 or records.numel() != n_img * ints or records.device != src.device:
             raise MlhotError(f"augment_ingest_u8_img: records must be int32 [{n_img}, {ints}] on {src.device}")
@@ -1127,17 +1137,9 @@ class MlhotLib:
         if pre_op not in (0, 1):
             raise MlhotError(f"augment_ingest_u8_img: pre_op is 0 or 1, got {pre_op!r}")
         _chk(src, out, records, luts, colour_tabs)
-        shape = (*lead, Cc, H, W)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=src.device)
-        elif out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != src.device:
-            raise MlhotError(f"augment_ingest_u8_img: out must be fp32 {shape} on {src.device}")
-        c.mlhot_augment_ingest_u8_img.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
-                                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        self._rc(c.mlhot_augment_ingest_u8_img(_ptr(src), _ptr(out), n_img, H, W, Cc, int(pre_op), float(div), float(div2), _ptr(records),
-                                               _ptr(luts) if n_luts else None, n_luts,
-                                               _ptr(colour_tabs) if colour_tabs is not None else None, _stream(src)),
-                 "mlhot_augment_ingest_u8_img")
+        out = _ingest_out("augment_ingest_u8_img", src, out)
+        self._rc(fn(_ptr(src), _ptr(out), n_img, H, W, Cc, int(pre_op), float(div), float(div2), _ptr(records), _ptr(luts) if n_luts else None,
+                    n_luts, _ptr(colour_tabs), _stream(src)), "mlhot_augment_ingest_u8_img")
         return out
 
     # ---- fused Adam over flat buffers -------------------------------------------------------------
@@ -1146,8 +1148,6 @@ class MlhotLib:
         n = param.numel()
         if not (grad.numel() == exp_avg.numel() == exp_avg_sq.numel() == n):
             raise MlhotError("adam_step: buffers differ in size")
-        f = C.c_float
-        self.c.mlhot_adam_step.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [f] * 6 + [C.c_int, C.c_void_p]
         self._rc(self.c.mlhot_adam_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), n, lr, beta1, beta2, eps,
                                         weight_decay, grad_scale, int(step), _stream(param)), "mlhot_adam_step")
 
@@ -1157,8 +1157,6 @@ class MlhotLib:
         n = param.numel()
         if not (grad.numel() == exp_avg.numel() == exp_avg_sq.numel() == n) or step_counter.dtype != torch.int32:
             raise MlhotError("adam_step_counter: buffers differ in size, or the counter is not int32")
-        f = C.c_float
-        self.c.mlhot_adam_step_counter.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [f] * 6 + [C.c_void_p, C.c_void_p]
         self._rc(self.c.mlhot_adam_step_counter(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), n, lr, beta1, beta2, eps,
                                                 weight_decay, grad_scale, _ptr(step_counter), _stream(param)), "mlhot_adam_step_counter")
 
