@@ -281,14 +281,22 @@ struct AggBwd {
       const float* lsrc = lv + t * Nc * R + j;
       float* ldst = dlv + t * Nc * R + j;
       const float sz = sigma[i], mz = r[i];
+      // mu_n - mu_z cancels where ONE shot's variance sits at the 1e-5 floor: that shot carries mu_z, mu_n - mu_z is ~ 1e-5 |mu_z|,
+      // and the half ulp the STORED mu_z is off by is 1e-3 of it (its d lv was that far off float64).  What the stored value lacks,
+      // from the sums centred on it: mu_z = s2 / s1  =>  mu_z - mz = sigma_z (sum_m (mu_m - mz) / var_m - mz)   (the prior's term: -mz)
+      // The sum is only known after the shot loop, so that loop leaves each shot's factor in dlv and a second one, of two loads and
+      // one store per shot and no transcendental, multiplies the corrected difference in.
+      float cs = 0.f;
       for (int n = 0; n < Nc; ++n) {
         const float l = lsrc[(size_t)n * R];
         const float var = 1e-5f + softplus_f(l);
-        const float mu = src[(size_t)n * R];
+        cs += (src[(size_t)n * R] - mz) / var;
         dst[(size_t)n * R] = g * sz / var;
         // d mu_z / d var_n = -(mu_n - mu_z) * sigma_z / var_n^2 ; d var / d lv = sigmoid(lv)
-        ldst[(size_t)n * R] = -g * (mu - mz) * sz / (var * var) * (l > 20.f ? 1.f : sigmoid_f(l));
+        ldst[(size_t)n * R] = -g * sz / (var * var) * (l > 20.f ? 1.f : sigmoid_f(l));
       }
+      const float dz = sz * (cs - mz);
+      for (int n = 0; n < Nc; ++n) ldst[(size_t)n * R] *= (src[(size_t)n * R] - mz) - dz;
     }
   }
 };
