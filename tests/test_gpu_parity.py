@@ -1184,33 +1184,51 @@ def _trunk_dict(ws):
     return d
 
 
-@pytest.mark.parametrize("C,H,skip_k,ns,share", [(3, 64, 3, (5,), False), (3, 64, 1, (7, 3), True), (3, 64, 3, (33, 2, 9), False),
-                                                 (1, 128, 1, (3,), False), (1, 128, 1, (2, 5), True), (3, 64, 1, (120,), False),
-                                                 # production-sized image counts for the 1 x 128 x 128 (Distractor) geometries: thousands
-                                                 # of bands per launch, so the band loops (band += workgroups), the multi-band
-                                                 # weight-gradient slab rows and the stem / 1x1-skip row splitting all run
-                                                 (1, 128, 1, (96, 40), True), (1, 128, 3, (70,), False)])
-def test_resnet_trunk_fwd_bwd_vs_torch(gpulib, C, H, skip_k, ns, share):
+# (C, H, skip_k, images per pass, one shared weight set?) under the names these cases have always had
+_TRUNK_CASES = [(3, 64, 3, (5,), False), (3, 64, 1, (7, 3), True), (3, 64, 3, (33, 2, 9), False),
+                (1, 128, 1, (3,), False), (1, 128, 1, (2, 5), True), (3, 64, 1, (120,), False),
+                # production-sized image counts for the 1 x 128 x 128 (Distractor) geometries: thousands
+                # of bands per launch, so the band loops (band += workgroups), the multi-band
+                # weight-gradient slab rows and the stem / 1x1-skip row splitting all run
+                (1, 128, 1, (96, 40), True), (1, 128, 3, (70,), False)]
+
+
+def _trunk_params():
+    """The eight cases above (one skip kernel for every weight set, default options), then the route's cases of
+    tests/test_trunk_route_gpu.py (a skip kernel per weight set, options away from their defaults)."""
+    from tests.test_trunk_route_gpu import CASES
+    out = [pytest.param(C, H, (k,) * (1 if share else len(ns)), ns, share, {}, id=f"{C}-{H}-{k}-ns{i}-{share}")
+           for i, (C, H, k, ns, share) in enumerate(_TRUNK_CASES)]
+    return out + [pytest.param(*case, id=name) for name, case in CASES.items()]
+
+
+@pytest.mark.parametrize("C,H,skips,ns,share,opts", _trunk_params())
+def test_resnet_trunk_fwd_bwd_vs_torch(gpulib, C, H, skips, ns, share, opts):
     """mlhot_trunk_fwd / _bwd: several passes in one call (ragged image counts that end in partial bands; passes that share a
-    weight set; the 1x1 and the 3x3 skip convolution; both supported image geometries) against torch's conv2d + autograd on the CPU.
+    weight set; the 1x1 and the 3x3 skip convolution, also side by side in one call; both supported image geometries; the trunk's
+    options away from their defaults) against torch's conv2d + autograd on the CPU.
     Every saved activation at 1e-5; gradients at 1e-4 with the reference evaluated under the kernels' ReLU routing (each
     differing decision proven a tie)."""
+    from tests.test_trunk_route_gpu import _with_options
     g = torch.Generator().manual_seed(C * 1000 + H + sum(ns))
     imgs = [torch.rand(n, C, H, H, generator=g) for n in ns]
-    wsets = [_trunk_weights(C, skip_k, 1)] if share else [_trunk_weights(C, skip_k, 1 + i) for i in range(len(ns))]
+    wsets = [_trunk_weights(C, k, 1 + i) for i, k in enumerate(skips)]
     passes = [(i, 0 if share else i) for i in range(len(ns))]
     imgs_d = [t.to(DEV) for t in imgs]
-    wsets_d = [([t.to(DEV) for t in ws], skip_k) for ws in wsets]
-    acts = gpulib.trunk_fwd([(imgs_d[i], w) for i, w in passes], wsets_d)
+    wsets_d = [([t.to(DEV) for t in ws], k) for ws, k in zip(wsets, skips)]
     dfeats = [torch.randn(n, 64, H // 32, H // 32, generator=g) for n in ns]
-    grads = gpulib.trunk_bwd([(imgs_d[i], w, acts[pi]) for pi, (i, w) in enumerate(passes)], wsets_d, [d.to(DEV) for d in dfeats])
+
+    def run():
+        acts = gpulib.trunk_fwd([(imgs_d[i], w) for i, w in passes], wsets_d)
+        return acts, gpulib.trunk_bwd([(imgs_d[i], w, acts[pi]) for pi, (i, w) in enumerate(passes)], wsets_d, [d.to(DEV) for d in dfeats])
+    acts, grads = _with_options(gpulib, opts, run)
     # reference under the kernels' routing
     ref_w = [[t.clone().requires_grad_() for t in ws] for ws in wsets]
     flips = 0
     for pi, (i, w) in enumerate(passes):
         route = [(a.cpu() > 0).float() for a in acts[pi]]
         pre = []
-        out = O.resnet_features(imgs[i], _trunk_dict(ref_w[w]), "t.", "reshape", skip_pad=1 if skip_k == 3 else 0, route=route, pre=pre)
+        out = O.resnet_features(imgs[i], _trunk_dict(ref_w[w]), "t.", "reshape", skip_pad=1 if skips[w] == 3 else 0, route=route, pre=pre)
         assert U.rel_err(acts[pi][8].reshape(ns[pi], -1), out) <= 1e-5, pi
         flips += sum(U.relu_flips(m, v, f"pass {pi}") for m, v in zip(route, pre))
         (out * dfeats[pi].reshape(ns[pi], -1)).sum().backward()

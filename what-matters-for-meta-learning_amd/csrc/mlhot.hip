@@ -579,7 +579,7 @@ size_t mlhot_trunk_act_floats(int C, int H, int n_img, int k) {
 size_t mlhot_trunk_scratch_bytes(const mlhot_trunk_pass* passes, int n_pass, const mlhot_trunk_wset* wsets, int n_wset, int C, int H, int backward) {
 #ifndef MLHOT_HOSTSIM
   if (rt::trunk_check(passes, n_pass, wsets, n_wset, C, H)) return 0;
-  return rt::trunk_carve(passes, n_pass, wsets, n_wset, rt::trunk_levels(C, H), backward != 0, nullptr, 0).bytes;
+  return rt::trunk_call(passes, n_pass, wsets, n_wset, C, H, backward != 0, nullptr, 0, nullptr).sc.bytes;
 #else
   (void)passes; (void)n_pass; (void)wsets; (void)n_wset; (void)C; (void)H; (void)backward; return 0;
 #endif

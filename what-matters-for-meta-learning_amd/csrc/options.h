@@ -1,7 +1,7 @@
 // Run-time switches (mlhot_set_option): which implementation of a hot-path row runs.  The generic igemm problems are always
 // available as the A/B reference of the specialised kernels.  Every switch lives here, with its default; mlhot_set_option's table
 // (mlhot.hip) is the only writer.  Readers: enc_route() (encoder.h) for the encoder's, np_route() (np_vanilla.h) for the tail's,
-// favor2.h and resnet_trunk.h for their own.
+// trunk_route() (resnet_trunk.h) for the three trunk_* ones, favor2.h for its own.
 #pragma once
 
 namespace mlhot {
