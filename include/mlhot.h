@@ -499,6 +499,22 @@ int mlhot_augment_ingest_u8_img(const uint8_t* src, float* dst, long n_img, int 
                                 const mlhot_aug_record_img* rec, const uint8_t* luts, int n_luts, const void* colour_tabs,
                                 void* stream);
 
+/* ---- resident image pool: a batch described by image ids, gathered and composed on the device (csrc/pool_ingest.h) ----
+ * pool: uint8 [n_pool, H, W, 4], channel-last RGBA; bank: uint8 [n_bank, H, W, 3] backgrounds (NULL when n_bank is 0).  Per output
+ * image i: ids[i] in [0, n_pool) and bg[i] = -1 (no composition) or in [0, n_bank).  Per pixel p and channel c < 3
+ *     byte = (bg[i] >= 0 && pool[ids[i]][p][3] == 255) ? bank[bg[i]][p][c] : pool[ids[i]][p][c]
+ * (dataset/shapenet_3d.py:235-239: rgb * mask + bg * (1 - mask) with mask = alpha < 1.0 on k / 255 floats - a 0/1 mask makes that a
+ * select), dst: fp32 [n_img, 3, H, W] = (float)byte / div, the divide of mlhot_ingest_u8_nhwc.  Any H, W.  The entries check n_bank
+ * against NULL and nothing else about the indices: the caller range-checks ids and bg on the host before it ships them
+ * (mlhot.ingest.BatchIngest.stage_ids).  Added within ABI 7 (a pure addition).  All device pointers. */
+int mlhot_pool_ingest_u8(const uint8_t* pool, long n_pool, const int* ids, const uint8_t* bank, long n_bank, const int* bg, float* dst,
+                         long n_img, int H, int W, float div, void* stream);
+/* The composed bytes as the input of mlhot_augment_ingest_u8_img's op sequence with C = 3, pre_op = 0, div2 = 1: same records, LUTs and
+ * colour tables.  H, W <= 64, MLHOT_ERR_UNSUPPORTED otherwise. */
+int mlhot_pool_augment_ingest_u8_img(const uint8_t* pool, long n_pool, const int* ids, const uint8_t* bank, long n_bank, const int* bg,
+                                     float* dst, long n_img, int H, int W, float div, const mlhot_aug_record_img* rec,
+                                     const uint8_t* luts, int n_luts, const void* colour_tabs, void* stream);
+
 /* ---- optimizer: torch.optim.Adam (train.py:52-56) as ONE launch over flat buffers -------------------
  * param / grad / exp_avg / exp_avg_sq: n floats each, laid out alike (e.g. mlhot_np_grads_flat_layout).
  * step >= 1 is the 1-based update count (bias correction); grad_scale multiplies the gradient first

@@ -7,8 +7,12 @@
 // New against augment.h: three channels through every op, AddToBrightness with its six colour spaces (integer / fixed point; Lab and
 // Luv through host-built tables, mlhot_colour_tabs), per_channel dropouts, the loaders' byte handling (pre_op, div2).  The spec is
 // DESIGN.md 6a-2 and include/mlhot.h; tests/augment_img_ref.py restates it in numpy and this file matches that bit for bit.
+//
+// The de-interleave stage reads through a source functor: NhwcSrc, the packed channel-last bytes (mlhot_augment_ingest_u8_img), or
+// PoolSrc, image ids[i] of the resident RGBA pool composed over the background bank (mlhot_pool_augment_ingest_u8_img).
 #pragma once
 #include "augment.h"
+#include "pool_ingest.h"
 
 namespace mlhot {
 namespace augimg {
@@ -254,12 +258,70 @@ MLHOT_DEV void augment_image_planes(const Exec& ex, const mlhot_aug_record_img& 
 
 MLHOT_HD uint8_t pre_byte(uint8_t b, int pre_op) { return pre_op ? (uint8_t)(256 - b) : b; }
 
+// ---- where the kernel's de-interleave stage reads an image's bytes from: a functor that fills the planar set [C][H][W] ------------------
+struct NhwcSrc {             // packed channel-last images of C channels (mlhot_augment_ingest_u8_img)
+  const uint8_t* src; int C, pre_op;
 #ifndef MLHOT_HOSTSIM
-__global__ __launch_bounds__(NT) void augment_img_ingest_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, int H, int W, int C,
-                                                                int pre_op, float div, float div2,
+  __device__ __forceinline__ void fill_block(uint8_t* planes, long img, int HW, int vec) const {
+    const int CHW = C * HW;
+    const uint8_t* s = src + img * CHW;
+    if (vec) {                                                          // CHW % 4 == 0, src 4-byte aligned: one dword per lane step
+      for (int q = threadIdx.x; q < CHW / 4; q += NT) {
+        const uint32_t w = reinterpret_cast<const uint32_t*>(s)[q];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int e = 4 * q + j, p = e / C, c = e - p * C;
+          planes[c * HW + p] = pre_byte((uint8_t)(w >> (8 * j)), pre_op);
+        }
+      }
+    } else {
+      for (int e = threadIdx.x; e < CHW; e += NT) { const int p = e / C, c = e - p * C; planes[c * HW + p] = pre_byte(s[e], pre_op); }
+    }
+  }
+#endif
+  void fill_loop(uint8_t* planes, long img, int HW) const {
+    const int CHW = C * HW;
+    const uint8_t* sp = src + img * CHW;
+    for (int e = 0; e < CHW; ++e) { const int p = e / C, c = e - p * C; planes[c * HW + p] = pre_byte(sp[e], pre_op); }
+  }
+};
+
+struct PoolSrc {             // image ids[img] of the resident RGBA pool, composed over the bank (pool_ingest.h): C = 3
+  const uint8_t* pool; const int* ids; const uint8_t* bank; const int* bg;
+#ifndef MLHOT_HOSTSIM
+  __device__ __forceinline__ void fill_block(uint8_t* planes, long img, int HW, int vec) const {
+    const int b = bg[img];
+    const uint8_t* px = pool + (long)ids[img] * HW * 4;
+    const uint8_t* bk = b >= 0 ? bank + (long)b * HW * 3 : px;
+    for (int p = threadIdx.x; p < HW; p += NT) {
+      if (vec) {                                                        // pool 4-byte aligned: a pixel is one dword
+        const uint32_t w = reinterpret_cast<const uint32_t*>(px)[p];
+        const bool sel = b >= 0 && (w >> 24) == 255u;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) planes[c * HW + p] = sel ? bk[3 * p + c] : (uint8_t)(w >> (8 * c));
+      } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) planes[c * HW + p] = pool::composed_byte(px + 4 * p, bk + 3 * p, b, c);
+      }
+    }
+  }
+#endif
+  void fill_loop(uint8_t* planes, long img, int HW) const {
+    const int b = bg[img];
+    const uint8_t* px = pool + (long)ids[img] * HW * 4;
+    const uint8_t* bk = b >= 0 ? bank + (long)b * HW * 3 : px;
+    for (int p = 0; p < HW; ++p)
+      for (int c = 0; c < 3; ++c) planes[c * HW + p] = pool::composed_byte(px + 4 * p, bk + 3 * p, b, c);
+  }
+};
+
+#ifndef MLHOT_HOSTSIM
+template <class Src>
+__global__ __launch_bounds__(NT) void augment_img_ingest_kernel(const Src src, float* __restrict__ dst, int H, int W, int C,
+                                                                float div, float div2,
                                                                 const mlhot_aug_record_img* __restrict__ rec,
                                                                 const uint8_t* __restrict__ luts, int n_luts,
-                                                                const mlhot_colour_tabs* __restrict__ ct, int vec) {
+                                                                const mlhot_colour_tabs* __restrict__ ct, int vec_in, int vec_out) {
   // 16384 + 16384 + 19600 + 1680 + 32 + 5120 = 59200 bytes of the 64 KB static limit
   __shared__ __attribute__((aligned(16))) uint8_t s_a[SET_BYTES];
   __shared__ __attribute__((aligned(16))) uint8_t s_b[SET_BYTES];
@@ -267,24 +329,12 @@ __global__ __launch_bounds__(NT) void augment_img_ingest_kernel(const uint8_t* _
   __shared__ int s_stat[MAXC * MAXP], s_flag[2 + 2 * MAXC], s_coef[5 * 2 * MAXD];
   const long img = blockIdx.x;
   const int HW = H * W, CHW = C * HW;
-  const uint8_t* s = src + img * CHW;
-  if (vec) {                                                          // CHW % 4 == 0, src 4-byte aligned: one dword per lane step
-    for (int q = threadIdx.x; q < CHW / 4; q += NT) {
-      const uint32_t w = reinterpret_cast<const uint32_t*>(s)[q];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int e = 4 * q + j, p = e / C, c = e - p * C;
-        s_a[c * HW + p] = pre_byte((uint8_t)(w >> (8 * j)), pre_op);
-      }
-    }
-  } else {
-    for (int e = threadIdx.x; e < CHW; e += NT) { const int p = e / C, c = e - p * C; s_a[c * HW + p] = pre_byte(s[e], pre_op); }
-  }
+  src.fill_block(s_a, img, HW, vec_in);
   __syncthreads();
   PlaneSets pl{s_a, s_b, s_pad, s_stat, s_flag, s_coef};
   augment_image_planes(BlockExec{}, rec[img], luts, n_luts, ct, H, W, C, pl);
   float* o = dst + img * CHW;
-  if (vec) {                                                          // dst 16-byte aligned: float4 stores
+  if (vec_out) {                                                      // CHW % 4 == 0, dst 16-byte aligned: float4 stores
     for (int q = threadIdx.x; q < CHW / 4; q += NT) {
       const uint32_t w = reinterpret_cast<const uint32_t*>(pl.cur)[q];
       float4 v;
@@ -304,29 +354,44 @@ inline bool in_scope(int H, int W, int C) {
   return H >= 1 && W >= 1 && ((C == 1 && H <= MAXD && W <= MAXD) || (C == 3 && H <= MAXD3 && W <= MAXD3));
 }
 
-inline int run(const uint8_t* src, float* dst, long n_img, int H, int W, int C, int pre_op, float div, float div2,
-               const mlhot_aug_record_img* rec, const uint8_t* luts, int n_luts, const mlhot_colour_tabs* ct, hipStream_t s) {
+// vec_in: may the source read dwords?  vec_out: C * H * W % 4 == 0 and dst 16-byte aligned (float4 stores)
+template <class Src>
+inline int run_src(const Src& src, int vec_in, int vec_out, float* dst, long n_img, int H, int W, int C, float div, float div2,
+                   const mlhot_aug_record_img* rec, const uint8_t* luts, int n_luts, const mlhot_colour_tabs* ct, hipStream_t s,
+                   const char* what) {
   if (n_img == 0) return MLHOT_OK;
   const int HW = H * W, CHW = C * HW;
 #ifndef MLHOT_HOSTSIM
-  const int vec = (CHW & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
-  ProfScope ps("augment.ingest.u8.img", s);
-  hipLaunchKernelGGL(augment_img_ingest_kernel, dim3((unsigned)n_img), dim3(NT), 0, s, src, dst, H, W, C, pre_op, div, div2, rec, luts,
-                     n_luts, ct, vec);
-  return check_launch("augment.ingest.u8.img");
+  ProfScope ps(what, s);
+  hipLaunchKernelGGL(augment_img_ingest_kernel<Src>, dim3((unsigned)n_img), dim3(NT), 0, s, src, dst, H, W, C, div, div2, rec, luts,
+                     n_luts, ct, vec_in, vec_out);
+  return check_launch(what);
 #else
-  (void)s;
+  (void)s; (void)vec_in; (void)vec_out; (void)what;
   static thread_local uint8_t a[SET_BYTES], b[SET_BYTES], pad[PAD_BYTES];
   static thread_local int stat[MAXC * MAXP], flag[2 + 2 * MAXC], coef[5 * 2 * MAXD];
   for (long img = 0; img < n_img; ++img) {
-    const uint8_t* sp = src + img * CHW;
-    for (int e = 0; e < CHW; ++e) { const int p = e / C, c = e - p * C; a[c * HW + p] = pre_byte(sp[e], pre_op); }
+    src.fill_loop(a, img, HW);
     PlaneSets pl{a, b, pad, stat, flag, coef};
     augment_image_planes(LoopExec{}, rec[img], luts, n_luts, ct, H, W, C, pl);
     for (int i = 0; i < CHW; ++i) dst[img * CHW + i] = (float)pl.cur[i] / div / div2;
   }
   return MLHOT_OK;
 #endif
+}
+
+inline int run(const uint8_t* src, float* dst, long n_img, int H, int W, int C, int pre_op, float div, float div2,
+               const mlhot_aug_record_img* rec, const uint8_t* luts, int n_luts, const mlhot_colour_tabs* ct, hipStream_t s) {
+  const int vec = ((C * H * W) & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+  return run_src(NhwcSrc{src, C, pre_op}, vec, vec, dst, n_img, H, W, C, div, div2, rec, luts, n_luts, ct, s, "augment.ingest.u8.img");
+}
+
+inline int run_pool(const uint8_t* pool, const int* ids, const uint8_t* bank, const int* bg, float* dst, long n_img, int H, int W,
+                    float div, const mlhot_aug_record_img* rec, const uint8_t* luts, int n_luts, const mlhot_colour_tabs* ct,
+                    hipStream_t s) {
+  const int vec_in = (reinterpret_cast<uintptr_t>(pool) & 3) == 0;
+  const int vec_out = ((3 * H * W) & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+  return run_src(PoolSrc{pool, ids, bank, bg}, vec_in, vec_out, dst, n_img, H, W, 3, div, 1.0f, rec, luts, n_luts, ct, s, "pool.augment.ingest.u8.img");
 }
 
 }  // namespace augimg

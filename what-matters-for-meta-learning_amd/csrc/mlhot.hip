@@ -17,6 +17,7 @@
 #include "np_vanilla.h"
 #include "conv_rt.h"
 #include "ingest.h"
+#include "pool_ingest.h"
 #include "augment.h"
 #include "augment_img.h"
 #include "bbb_multi.h"
@@ -645,6 +646,34 @@ int mlhot_augment_ingest_u8_img(const uint8_t* src, float* dst, long n_img, int 
   }
   return augimg::run(src, dst, n_img, H, W, C, pre_op, div, div2, rec, luts, n_luts, (const mlhot_colour_tabs*)colour_tabs,
                      (hipStream_t)stream);
+}
+
+// ---- resident image pool: gather by id, compose the epoch's backgrounds, ingest (csrc/pool_ingest.h) ---------------------------
+static int pool_args(const char* what, const uint8_t* pool, long n_pool, const int* ids, const uint8_t* bank, long n_bank, const int* bg,
+                     float* dst, long n_img, int H, int W, float div) {
+  if (n_img < 0 || n_pool < 0 || n_bank < 0 || H <= 0 || W <= 0 || !(div > 0.f) || (n_bank > 0 && !bank) ||
+      (n_img > 0 && (!pool || n_pool == 0 || !ids || !bg || !dst))) {
+    set_error("%s: bad argument", what);
+    return MLHOT_ERR_ARG;
+  }
+  return MLHOT_OK;
+}
+int mlhot_pool_ingest_u8(const uint8_t* pool, long n_pool, const int* ids, const uint8_t* bank, long n_bank, const int* bg, float* dst,
+                         long n_img, int H, int W, float div, void* stream) {
+  MLHOT_TRY(pool_args("pool_ingest_u8", pool, n_pool, ids, bank, n_bank, bg, dst, n_img, H, W, div));
+  return pool::run(pool, ids, bank, bg, dst, n_img, H, W, div, (hipStream_t)stream);
+}
+int mlhot_pool_augment_ingest_u8_img(const uint8_t* pool, long n_pool, const int* ids, const uint8_t* bank, long n_bank, const int* bg,
+                                     float* dst, long n_img, int H, int W, float div, const mlhot_aug_record_img* rec,
+                                     const uint8_t* luts, int n_luts, const void* colour_tabs, void* stream) {
+  MLHOT_TRY(pool_args("pool_augment_ingest_u8_img", pool, n_pool, ids, bank, n_bank, bg, dst, n_img, H, W, div));
+  if (n_luts < 0 || (n_img > 0 && !rec) || (n_luts > 0 && !luts)) { set_error("pool_augment_ingest_u8_img: bad argument"); return MLHOT_ERR_ARG; }
+  if (!augimg::in_scope(H, W, 3)) {
+    set_error("pool_augment_ingest_u8_img: H, W <= %d only (got H=%d W=%d)", augimg::MAXD3, H, W);
+    return MLHOT_ERR_UNSUPPORTED;
+  }
+  return augimg::run_pool(pool, ids, bank, bg, dst, n_img, H, W, div, rec, luts, n_luts, (const mlhot_colour_tabs*)colour_tabs,
+                          (hipStream_t)stream);
 }
 
 // ---- fused Adam over a flat parameter / gradient buffer ------------------------------------------------

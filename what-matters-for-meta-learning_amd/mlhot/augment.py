@@ -248,6 +248,64 @@ def colour_tables(device=None):
     return _COLOUR_TABLES[key]
 
 
+# ---- the resident pool's backgrounds (csrc/pool_ingest.h) --------------------------------------------------------------
+BG_TAG = 0x62673364            # "bg3d": keeps this hash chain apart from the dropouts' (csrc/augment.h image_key)
+
+
+def fmix32(h):
+    """murmur3's 32-bit finaliser over uint64 arrays holding 32-bit values (csrc/augment.h fmix32)."""
+    h = np.asarray(h, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    h = h ^ (h >> np.uint64(16))
+    h = (h * np.uint64(0x85EBCA6B)) & np.uint64(0xFFFFFFFF)
+    h = h ^ (h >> np.uint64(13))
+    h = (h * np.uint64(0xC2B2AE35)) & np.uint64(0xFFFFFFFF)
+    return h ^ (h >> np.uint64(16))
+
+
+class BackgroundSampler:
+    """Which background of the bank stands behind a training image: bg = mulhi32(hash(seed, epoch, id), B) with the finaliser chain
+    of the dropouts over (seed, BG_TAG, epoch, id), epoch = it // bg_gen_freq (0 when config.gen_bg is off).  -1 (no composition) at
+    epoch 0 - the training images show the file's backgrounds until the first regeneration - and for every other source, whose
+    backgrounds the reference's trainer never regenerates.  A pure function of (seed, epoch, id): no rank, no batch position, no
+    generator - an image keeps its background for exactly one epoch, as the reference's in-place regeneration gives."""
+
+    def __init__(self, n_bank, seed=0, bg_gen_freq=1, gen_bg=True):
+        self.n_bank, self.seed = int(n_bank), int(seed) & 0xFFFFFFFF
+        self.bg_gen_freq, self.gen_bg = max(1, int(bg_gen_freq)), bool(gen_bg)
+
+    def epoch(self, it):
+        return int(it) // self.bg_gen_freq if self.gen_bg else 0
+
+    def batch(self, ids, epoch, source="train"):
+        """int32 bg indices shaped like `ids` (any integer array of pool ids)."""
+        ids = np.asarray(ids)
+        if source != "train" or epoch <= 0 or self.n_bank <= 0:
+            return np.full(ids.shape, -1, dtype=np.int32)
+        k = fmix32(np.uint64((self.seed + 0x9E3779B9) & 0xFFFFFFFF))
+        k = fmix32(k ^ np.uint64(BG_TAG))
+        k = fmix32(k ^ np.uint64(int(epoch) & 0xFFFFFFFF))
+        h = fmix32(k ^ (ids.astype(np.int64).astype(np.uint64) & np.uint64(0xFFFFFFFF)))
+        return ((h * np.uint64(self.n_bank)) >> np.uint64(32)).astype(np.int32)
+
+
+def check_trainer_config_pool(config, data):
+    """The resident pool's switch (config.resident_pool; absent = off): is it on?  Refuses - ValueError, with the reason - what the
+    route cannot do: another task, a loader without the protocol, a loader that still augments itself."""
+    if not getattr(config, "resident_pool", False):
+        return False
+    if getattr(config, "task", None) != "shapenet_3d":
+        raise ValueError(f"config.resident_pool: the resident RGBA pool serves task 'shapenet_3d' only (its loader composes backgrounds by "
+                         f"alpha); task {getattr(config, 'task', None)!r} has no alpha channel - leave the switch off")
+    if not (hasattr(data, "rgba_pool") and hasattr(data, "get_batch_ids")):
+        raise ValueError("config.resident_pool: the loader lacks the protocol - rgba_pool('train') -> (uint8 [N, H, W, 4], bank) and "
+                         "get_batch_ids(source, tasks_per_batch, shot) -> (ctx_ids, qry_ids, ys, yq) (INTEGRATION.md)")
+    if getattr(data, "data_aug", False):
+        raise ValueError("config.resident_pool: the loader still augments on the host (data.data_aug is True), and batches described by "
+                         "ids never pass through it.  Build it with aug=[a for a in config.aug_list if a != 'data_aug'] and set "
+                         "config.device_augment_images (INTEGRATION.md)")
+    return True
+
+
 def check_trainer_config_images(config, data):
     """The image tasks' switch (config.device_augment_images; absent = off): None when off, else the ImageSampler."""
     if not getattr(config, "device_augment_images", False) or "data_aug" not in (getattr(config, "aug_list", None) or []):

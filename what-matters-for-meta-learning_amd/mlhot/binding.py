@@ -293,6 +293,8 @@ SIGNATURES = {
     "mlhot_augment_img_record_bytes": (z, []),
     "mlhot_colour_tabs_bytes": (z, []),
     "mlhot_augment_ingest_u8_img": (i, [P, P, L, i, i, i, i, f32, f32, P, P, i, P, P]),
+    "mlhot_pool_ingest_u8": (i, [P, L, P, P, L, P, P, L, i, i, f32, P]),
+    "mlhot_pool_augment_ingest_u8_img": (i, [P, L, P, P, L, P, P, L, i, i, f32, P, P, i, P, P]),
     # optimizer
     "mlhot_adam_step": (i, [P, P, P, P, z] + [f32] * 6 + [i, P]),
     "mlhot_adam_step_counter": (i, [P, P, P, P, z] + [f32] * 6 + [P, P]),
@@ -1140,6 +1142,66 @@ class MlhotLib:
         out = _ingest_out("augment_ingest_u8_img", src, out)
         self._rc(fn(_ptr(src), _ptr(out), n_img, H, W, Cc, int(pre_op), float(div), float(div2), _ptr(records), _ptr(luts) if n_luts else None,
                     n_luts, _ptr(colour_tabs), _stream(src)), "mlhot_augment_ingest_u8_img")
+        return out
+
+    # ---- resident image pool (csrc/pool_ingest.h) ----------------------------------------------------
+    @staticmethod
+    def _pool_args(wrapper, pool, ids, bank, bg, out):
+        """Shapes, dtypes and devices of a pool call; -> (n_pool, n_bank, n_img, H, W, bg, out).  Indices that live on the host (the
+        host build) are range-checked here; device indices are trusted - BatchIngest.stage_ids checks them before it ships them."""
+        if pool.dtype != torch.uint8 or pool.dim() != 4 or pool.shape[-1] != 4:
+            raise MlhotError(f"{wrapper}: the pool must be uint8 [N, H, W, 4] (RGBA, channel-last), got {pool.dtype} {tuple(pool.shape)}")
+        n_pool, H, W, _ = pool.shape
+        if bank is not None and (bank.dtype != torch.uint8 or bank.dim() != 4 or tuple(bank.shape[1:]) != (H, W, 3) or bank.device != pool.device):
+            raise MlhotError(f"{wrapper}: the bank must be uint8 [B, {H}, {W}, 3] on {pool.device}, got {bank.dtype} {tuple(bank.shape)}")
+        n_bank = 0 if bank is None else bank.shape[0]
+        if ids.dtype != torch.int32 or ids.device != pool.device:
+            raise MlhotError(f"{wrapper}: ids must be int32 on {pool.device}")
+        n_img = ids.numel()
+        if bg is None:
+            bg = torch.full((n_img,), -1, dtype=torch.int32, device=pool.device)
+        if bg.dtype != torch.int32 or bg.numel() != n_img or bg.device != pool.device:
+            raise MlhotError(f"{wrapper}: bg must be int32 [{n_img}] on {pool.device}")
+        if not ids.is_cuda:
+            from .ingest import check_pool_indices
+            check_pool_indices(ids.numpy(), bg.numpy(), n_pool, n_bank)
+        shape = (*ids.shape, 3, H, W)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=pool.device)
+        elif out.dtype != torch.float32 or out.numel() != math.prod(shape) or out.device != pool.device:
+            raise MlhotError(f"{wrapper}: out must be fp32 {shape} on {pool.device}")
+        _chk(pool, ids, bank, bg, out)
+        return n_pool, n_bank, n_img, H, W, bg, out
+
+    def pool_ingest_u8(self, pool, ids, bank=None, bg=None, out=None, div=255.0):
+        """Images `ids` (int32 [...]) of the resident pool (uint8 [N, H, W, 4]) with bank[bg] (uint8 [B, H, W, 3]; bg int32, -1 = none)
+        behind every pixel whose alpha is 255 -> fp32 [..., 3, H, W] = byte / div (include/mlhot.h mlhot_pool_ingest_u8)."""
+        fn = self._fn("pool_ingest_u8", "mlhot_pool_ingest_u8")
+        n_pool, n_bank, n_img, H, W, bg, out = self._pool_args("pool_ingest_u8", pool, ids, bank, bg, out)
+        self._rc(fn(_ptr(pool), n_pool, _ptr(ids), _ptr(bank) if n_bank else None, n_bank, _ptr(bg), _ptr(out), n_img, H, W, float(div),
+                    _stream(pool)), "mlhot_pool_ingest_u8")
+        return out
+
+    def pool_augment_ingest_u8_img(self, pool, ids, records, bank=None, bg=None, luts=None, colour_tabs=None, out=None, div=255.0):
+        """pool_ingest_u8 with the shapenet_3d image augmentation behind the composition (augment_ingest_u8_img's records int32
+        [n_img, 40], luts and colour tables; C = 3, pre_op = 0); H, W <= 64."""
+        fn = self._fn("pool_augment_ingest_u8_img", "mlhot_pool_augment_ingest_u8_img")
+        n_pool, n_bank, n_img, H, W, bg, out = self._pool_args("pool_augment_ingest_u8_img", pool, ids, bank, bg, out)
+        ints = AUG_IMG_RECORD_BYTES // 4
+        if records.dtype != torch.int32 or records.numel() != n_img * ints or records.device != pool.device:
+            raise MlhotError(f"pool_augment_ingest_u8_img: records must be int32 [{n_img}, {ints}] on {pool.device}")
+        n_luts = 0
+        if luts is not None:
+            if luts.dtype != torch.uint8 or luts.dim() != 2 or luts.shape[1] != 256 or luts.device != pool.device:
+                raise MlhotError("pool_augment_ingest_u8_img: luts must be uint8 [n, 256] on the pool's device")
+            n_luts = luts.shape[0]
+        if colour_tabs is not None and (colour_tabs.dtype != torch.uint8 or colour_tabs.numel() != COLOUR_TABS_BYTES
+                                        or colour_tabs.device != pool.device):
+            raise MlhotError(f"pool_augment_ingest_u8_img: colour_tabs must be uint8 [{COLOUR_TABS_BYTES}] on the pool's device")
+        _chk(records, luts, colour_tabs)
+        self._rc(fn(_ptr(pool), n_pool, _ptr(ids), _ptr(bank) if n_bank else None, n_bank, _ptr(bg), _ptr(out), n_img, H, W, float(div),
+                    _ptr(records), _ptr(luts) if n_luts else None, n_luts, _ptr(colour_tabs), _stream(pool)),
+                 "mlhot_pool_augment_ingest_u8_img")
         return out
 
     # ---- fused Adam over flat buffers -------------------------------------------------------------

@@ -18,6 +18,10 @@ reading valid addresses.  There is no CPU fallback: the device must be a ROCm GP
 slot and the same H2D copy, and take() expands it with mlhot_augment_ingest_u8 (csrc/augment.h) instead of mlhot_ingest_u8_nhwc.
 An mlhot.augment.ImageAugTable (ImageSampler.batch: the image tasks, C = 3 or 1) travels the same way and is expanded with
 mlhot_augment_ingest_u8_img (csrc/augment_img.h) with the table's pre_op / div / div2.
+
+`BatchIngest(device, pool=ResidentPool(images_rgba, bank, device))` + `stage_ids(ctx_ids, qry_ids, ys, yq, bg=..., augment=...)`: the
+loader's RGBA pool and background bank live on the device, a batch is its image ids (+ one bank index per image), and take() gathers,
+composes and converts with mlhot_pool_ingest_u8 / mlhot_pool_augment_ingest_u8_img (csrc/pool_ingest.h).
 """
 import collections
 import threading
@@ -92,6 +96,94 @@ class _Slot:
         self.busy = False
 
 
+def check_pool_indices(ids, bg, n_pool, n_bank):
+    """The range check of a batch described by ids, on the HOST arrays, before anything is shipped: the kernels trust them."""
+    ids, bg = np.asarray(ids), np.asarray(bg)
+    if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= n_pool):
+        raise MlhotError(f"resident pool: image id out of range [0, {n_pool}): min {int(ids.min())}, max {int(ids.max())}")
+    if bg.shape != ids.shape:
+        raise MlhotError(f"resident pool: {bg.shape} bg indices for {ids.shape} ids")
+    if bg.size and (int(bg.min()) < -1 or int(bg.max()) >= n_bank):
+        raise MlhotError(f"resident pool: bg index out of range [-1, {n_bank}): min {int(bg.min())}, max {int(bg.max())}")
+
+
+def pool_bytes(a, channels, what, L=None, div=255.0):
+    """A loader's image pool as contiguous uint8 [n, H, W, channels]: uint8 as it is; fp32 (the reference holds k / 255 floats) through
+    mlhot_host_f32_to_u8_exact, refused unless EVERY element is exactly k / div."""
+    t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a.contiguous()
+    if t.dim() != 4 or t.shape[-1] != channels or t.device.type != "cpu":
+        raise MlhotError(f"ResidentPool: {what} must be a host array [n, H, W, {channels}] (channel-last), got {tuple(t.shape)}")
+    if t.dtype == torch.uint8:
+        return t
+    if t.dtype != torch.float32:
+        raise MlhotError(f"ResidentPool: {what} must be uint8 or float32, got {t.dtype}")
+    out = torch.empty(t.shape, dtype=torch.uint8)
+    bad = (L or lib()).host_f32_to_u8_exact(t.data_ptr(), out.data_ptr(), t.numel(), div, threads=default_feed_threads())
+    if bad:
+        raise MlhotError(f"ResidentPool: {bad} of {t.numel()} elements of {what} are not exactly k / {div:g} for a byte k - the pool "
+                         "cannot be held as bytes")
+    return out
+
+
+class ResidentPool:
+    """A loader's RGBA image pool (uint8 [N, H, W, 4]) and its background bank (uint8 [B, H, W, 3], or None), uploaded ONCE: batches
+    are then described by image ids (BatchIngest.stage_ids) and gathered, composed and converted on the device (csrc/pool_ingest.h)."""
+
+    def __init__(self, images_u8, bank_u8=None, device="cuda:0", div=255.0):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise MlhotError("ResidentPool: the pool lives on a ROCm device; there is no CPU fallback")
+        pool = pool_bytes(images_u8, 4, "the image pool", div=div)
+        bank = None if bank_u8 is None or len(bank_u8) == 0 else pool_bytes(bank_u8, 3, "the background bank", div=div)
+        if bank is not None and tuple(bank.shape[1:3]) != tuple(pool.shape[1:3]):
+            raise MlhotError(f"ResidentPool: backgrounds of {tuple(bank.shape[1:3])} behind images of {tuple(pool.shape[1:3])}")
+        try:
+            self.pool = pool.to(self.device)
+            self.bank = None if bank is None else bank.to(self.device)
+        except RuntimeError as e:              # torch.OutOfMemoryError is one
+            need = pool.numel() + (0 if bank is None else bank.numel())
+            raise MlhotError(f"ResidentPool: cannot hold {need / 2 ** 20:.0f} MiB of images on {self.device} ({e}); leave "
+                             "config.resident_pool off - batches then cross PCIe as bytes") from e
+        self.n_pool, self.H, self.W = pool.shape[0], pool.shape[1], pool.shape[2]
+        self.n_bank = 0 if bank is None else bank.shape[0]
+
+
+class _IdSlot:
+    """A staging slot of a batch described by ids: [ids int32 (ctx, qry) | bg int32 | pad to 16 | ctx labels | qry labels] and, when the
+    batch is augmented, [records int32 [n, 40] | gamma LUTs] behind them - no image bytes.  key = (ctx ids shape, qry ids shape, ctx
+    labels shape, qry labels shape, "pool" | "poolaug")."""
+
+    def __init__(self, key, device):
+        n = int(np.prod(key[0])) + int(np.prod(key[1]))
+        n_lab = [int(np.prod(key[2])), int(np.prod(key[3]))]
+        lab_off = (8 * n + 15) // 16 * 16
+        lab_end = total = lab_off + 4 * (n_lab[0] + n_lab[1])
+        self.augmented = key[4] == "poolaug"
+        if self.augmented:
+            rec_off = (total + 15) // 16 * 16
+            lut_off = rec_off + AUG_IMG_RECORD_BYTES * n
+            total = lut_off + 256 * n
+        self.host = torch.empty(max(total, 16), dtype=torch.uint8).pin_memory()
+        self.dev = torch.empty(max(total, 16), dtype=torch.uint8, device=device)
+        hn = self.host.numpy()
+        self.n_img = n
+        self.ids_np, self.bg_np = hn[:4 * n].view(np.int32), hn[4 * n:8 * n].view(np.int32)
+        self.lab_np = [hn[lab_off:lab_off + 4 * n_lab[0]].view(np.float32).reshape(key[2]),
+                       hn[lab_off + 4 * n_lab[0]:lab_end].view(np.float32).reshape(key[3])]
+        self.dev_ids, self.dev_bg = self.dev[:4 * n].view(torch.int32), self.dev[4 * n:8 * n].view(torch.int32)
+        self.dev_lab = self.dev[lab_off:lab_end].view(torch.float32)
+        self.n_bytes = lab_end                 # bytes to copy: ids + bg + labels (+ records + the LUTs in use)
+        if self.augmented:
+            self.aug_rec_np = hn[rec_off:lut_off].view(np.int32).reshape(n, AUG_IMG_RECORD_BYTES // 4)
+            self.aug_lut_np = hn[lut_off:total].reshape(n, 256)
+            self.dev_rec = self.dev[rec_off:lut_off].view(torch.int32)
+            self.dev_lut = self.dev[lut_off:total].view(n, 256)
+            self.lut_off, self.n_luts, self.image_table = lut_off, 0, None
+        self.copied = torch.cuda.Event()
+        self.consumed = torch.cuda.Event()
+        self.busy = False
+
+
 class _Out:
     """The fixed fp32 tensors batches of one shape are delivered in: images of both sets in one flat buffer (one ingest
     launch when the image geometry is shared), labels in another (one device copy)."""
@@ -108,11 +200,14 @@ class _Out:
 
 
 class BatchIngest:
-    def __init__(self, device, slots=2, div=255.0):
+    def __init__(self, device, slots=2, div=255.0, pool=None):
         device = torch.device(device)
         if device.type != "cuda":
             raise MlhotError("BatchIngest: the ingest path needs a ROCm device; there is no CPU fallback")
         self.device, self.n_slots, self.div = device, slots, div
+        if pool is not None and pool.device != device:
+            raise MlhotError(f"BatchIngest: the resident pool lives on {pool.device}, the ingest on {device}")
+        self.pool = pool                        # a ResidentPool: stage_ids() describes batches by image ids
         self.copy_stream = torch.cuda.Stream(device)
         self._slots = {}                        # shapes -> [slot, ...]
         self._out = {}                          # shapes -> _Out (fixed fp32 outputs)
@@ -121,14 +216,14 @@ class BatchIngest:
         # slot choice and the queue are guarded; the fill and the copy of a reserved slot are not (they touch only that slot).
         self._lock = threading.Lock()
 
-    def _free_slot(self, key):
+    def _free_slot(self, key, make=_Slot):
         with self._lock:
             ring = self._slots.setdefault(key, [])
             slot = next((sl for sl in ring if not sl.busy), None)
             if slot is None:
                 if len(ring) >= self.n_slots:
                     raise MlhotError("BatchIngest: more batches staged than slots; call take() first")
-                slot = _Slot(key, self.device)
+                slot = make(key, self.device)
                 ring.append(slot)
             slot.busy = True                    # reserved from here on (given back by take(), or by a fill that refuses the batch)
         slot.copied.synchronize()               # the previous H2D out of this pinned buffer is done (no-op when fresh)
@@ -148,6 +243,43 @@ class BatchIngest:
         if augment is not None:
             self._put_augment(slot, augment)
         return self._ship(key, slot)
+
+    def stage_ids(self, ctx_ids, qry_ids, ys, yq, bg=None, augment=None):
+        """Queue one batch of the resident pool: image ids [T, Nc] / [T, Nq] (any integer type), labels fp32 [T, N, L]; `bg`: one bank
+        index (or -1) per id, context ids first then targets - (ctx [T, Nc], qry [T, Nq]) or one flat array - None = no composition;
+        `augment`: an mlhot.augment.ImageAugTable of the shapenet_3d sequence, or None.  Ids and bg indices are range-checked here, on
+        the host; ids, bg, labels and records ride in one pinned slot and one H2D copy - no image bytes.  Returns a ticket."""
+        pool = self.pool
+        if pool is None:
+            raise MlhotError("BatchIngest.stage_ids: no resident pool (BatchIngest(device, pool=ResidentPool(...)))")
+        ci, qi = np.asarray(ctx_ids), np.asarray(qry_ids)
+        if ci.ndim != 2 or qi.ndim != 2 or ci.shape[0] != qi.shape[0] or ci.dtype.kind not in "iu" or qi.dtype.kind not in "iu":
+            raise MlhotError(f"BatchIngest.stage_ids: integer ids [T, Nc] and [T, Nq], got {ci.shape} {ci.dtype} / {qi.shape} {qi.dtype}")
+        ids = np.concatenate([ci.reshape(-1), qi.reshape(-1)]).astype(np.int64)
+        if bg is None:
+            bgs = np.full(ids.shape, -1, dtype=np.int64)
+        else:
+            parts = bg if isinstance(bg, (tuple, list)) else (bg,)
+            bgs = np.concatenate([np.asarray(b).reshape(-1) for b in parts]).astype(np.int64)
+        check_pool_indices(ids, bgs, pool.n_pool, pool.n_bank)
+        lab = [_host(ys, torch.float32), _host(yq, torch.float32)]
+        if augment is not None:
+            from .augment import ImageAugTable
+            if not isinstance(augment, ImageAugTable) or (augment.pre_op, augment.div2) != (0, 1.0):
+                raise MlhotError("BatchIngest.stage_ids: augment must be an ImageAugTable of the shapenet_3d sequence (pre_op 0, one division)")
+            if augment.n_img != ids.size:
+                raise MlhotError(f"BatchIngest.stage_ids: the augmentation table holds {augment.n_img} records for {ids.size} images")
+        T, H, W = ci.shape[0], pool.H, pool.W
+        slot = self._free_slot((tuple(ci.shape), tuple(qi.shape), tuple(lab[0].shape), tuple(lab[1].shape), "pool" if augment is None else "poolaug"),
+                               make=_IdSlot)
+        np.copyto(slot.ids_np, ids, casting="unsafe")
+        np.copyto(slot.bg_np, bgs, casting="unsafe")
+        for h, t in zip(slot.lab_np, lab):
+            np.copyto(h, t.numpy())
+        if augment is not None:
+            self._put_augment(slot, augment)
+        # delivered in the tensors a byte batch of the same shape is delivered in
+        return self._ship(((T, ci.shape[1], H, W, 3), (T, qi.shape[1], H, W, 3), tuple(lab[0].shape), tuple(lab[1].shape)), slot)
 
     @staticmethod
     def _slot_key(key, augment):
@@ -232,7 +364,9 @@ class BatchIngest:
             out = self._out[key] = _Out(key, self.device)
         L = lib()
         with torch.cuda.device(self.device):
-            if slot.augmented:
+            if isinstance(slot, _IdSlot):
+                self._pool_into(L, slot, out)
+            elif slot.augmented:
                 self._augment_into(L, key, slot, out)
             elif out.same_geometry:             # both image sets are one packed run of (H, W, C) images
                 _, _, H, W, Cc = key[0]
@@ -245,6 +379,16 @@ class BatchIngest:
         slot.consumed.record(cur)
         slot.busy = False
         return out.tensors
+
+    def _pool_into(self, L, slot, out):
+        pool = self.pool
+        dst = out.img.view(slot.n_img, 3, pool.H, pool.W)
+        if not slot.augmented:
+            L.pool_ingest_u8(pool.pool, slot.dev_ids, pool.bank, slot.dev_bg, out=dst, div=self.div)
+            return
+        from .augment import colour_tables
+        L.pool_augment_ingest_u8_img(pool.pool, slot.dev_ids, slot.dev_rec, pool.bank, slot.dev_bg, slot.dev_lut[:slot.n_luts] if slot.n_luts else None,
+                                     colour_tables(self.device), out=dst, div=slot.image_table[1])
 
     def _augment_into(self, L, key, slot, out):
         luts = slot.dev_lut[:slot.n_luts] if slot.n_luts else None

@@ -243,3 +243,81 @@ class SyntheticViewsF32:
 
     def get_batch(self, source, tasks_per_batch, shot):
         return self._views.get_batch(source, tasks_per_batch, shot)
+
+
+class SyntheticViewsRGBA:
+    """The ShapeNet3D loader's TRAIN-mode shape over a pool that still has its alpha channel (dataset/shapenet_3d.py:113, 231-254):
+    objects x views RGBA images uint8 [N, 64, 64, 4] - alpha 255 inside the shapes except a sprinkling of 254 right next to it, small
+    values elsewhere - and a small background bank uint8 [B, 64, 64, 3].  It speaks the resident pool's protocol (`rgba_pool`,
+    `get_batch_ids`: mlhot.ingest.ResidentPool, config.resident_pool) and, for the sources that keep their routes, `get_batch_u8`
+    (the file's RGB, no composition).  Draws as SyntheticViews(mode="train"): per task one object, context = the first `shot` views of
+    a permutation, targets = the `shot` behind them.  It neither augments nor regenerates (`data_aug = False`, `gen_bg` a no-op)."""
+
+    data_aug = False
+
+    def __init__(self, seed=42, objects=8, views=30, bank=5, H=64, W=64):
+        import numpy as np
+        self.task, self.views, self.test_counter = "shapenet_3d", views, 0
+        n = objects * views
+        rgb = colour_images(n, H, W, seed=seed)
+        grey = shape_images(n, H, W, seed=seed + 7)                               # shapes at 90 .. 255 over a gradient below 81
+        y, x = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+        alpha = np.where(grey >= 90, np.where((x + 2 * y)[None] % 7 == 0, 254, 255), grey).astype(np.uint8)
+        self.pool = np.ascontiguousarray(np.concatenate([rgb, alpha[..., None]], axis=-1))       # [N, H, W, 4]
+        self.bank = colour_images(bank, H, W, seed=seed + 13)                     # [B, H, W, 3]
+        g = torch.Generator().manual_seed(seed)
+        q = torch.nn.functional.normalize(torch.randn(n, 4, generator=g), dim=-1)
+        self.labels = torch.where(q[..., 1:2] < 0, -q, q)
+        self.rng = np.random.RandomState(seed)
+        self.val_rng, self.test_rng = np.random.RandomState(seed + 1), np.random.RandomState(seed + 2)
+
+    def gen_bg(self, config, data="all"):
+        pass
+
+    def rgba_pool(self, source="train"):
+        return self.pool, self.bank
+
+    def get_batch_ids(self, source, tasks_per_batch, shot):
+        """(ctx ids int32 [T, shot], target ids int32 [T, shot], ctx labels, target labels): ids index rgba_pool()'s images."""
+        import numpy as np
+        rng = {"train": self.rng, "validation": self.val_rng, "test": self.test_rng}[source]
+        if not 1 <= 2 * shot <= self.views:
+            raise ValueError(f"shot {shot} does not fit {self.views} views per object")
+        objs = rng.randint(0, self.pool.shape[0] // self.views, tasks_per_batch)
+        perms = np.stack([rng.permutation(self.views) for _ in range(tasks_per_batch)])
+        ids = (objs[:, None] * self.views + perms[:, :2 * shot]).astype(np.int32)
+        ci, qi = np.ascontiguousarray(ids[:, :shot]), np.ascontiguousarray(ids[:, shot:])
+        return ci, qi, self.labels[torch.from_numpy(ci).long()].contiguous(), self.labels[torch.from_numpy(qi).long()].contiguous()
+
+    def get_batch_u8(self, source, tasks_per_batch, shot):
+        ci, qi, ys, yq = self.get_batch_ids(source, tasks_per_batch, shot)
+        import numpy as np
+        return np.ascontiguousarray(self.pool[ci][..., :3]), np.ascontiguousarray(self.pool[qi][..., :3]), ys, yq
+
+
+class SyntheticViewsRGBAHost:
+    """`SyntheticViewsRGBA`'s twin for today's route: the same draws, but the backgrounds are composed on the HOST - the select of
+    dataset/shapenet_3d.py:235-239 with the mlhot.augment.BackgroundSampler handed in, at an epoch that every `gen_bg` call advances
+    (the trainer calls it every bg_gen_freq iterations) - and the batches are fp32 [T, N, 3, H, W] = bytes / 255 host tensors
+    (the trainer's host-batch route).  No `get_batch_u8`, no pool protocol."""
+
+    data_aug = False
+
+    def __init__(self, sampler, **kw):
+        self._rgba, self.sampler, self.epoch = SyntheticViewsRGBA(**kw), sampler, 0
+        self.task, self.test_counter = "shapenet_3d", 0
+        self.val_rng, self.test_rng = self._rgba.val_rng, self._rgba.test_rng
+
+    def gen_bg(self, config, data="all"):
+        self.epoch += 1                  # the reference regenerates in place: every training image gets this epoch's background
+
+    def compose(self, ids, source):
+        import numpy as np
+        px = self._rgba.pool[ids]
+        bg = self.sampler.batch(ids, self.epoch, source)
+        take = (bg >= 0)[..., None, None] & (px[..., 3] == 255)
+        return np.where(take[..., None], self._rgba.bank[np.maximum(bg, 0)], px[..., :3])
+
+    def get_batch(self, source, tasks_per_batch, shot):
+        ci, qi, ys, yq = self._rgba.get_batch_ids(source, tasks_per_batch, shot)
+        return host_convert(self.compose(ci, source)), host_convert(self.compose(qi, source)), ys, yq

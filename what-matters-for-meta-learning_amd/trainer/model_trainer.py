@@ -140,11 +140,22 @@ class _Feed:
     batches through `_HostPrefetch` (`host`), or the reference's plain `.to(device)` (neither).  Owns the tickets of the training
     batches that were drawn ahead; the draw order against the data source is the reference's (see ModelTrainer.train)."""
 
-    def __init__(self, config, data, augment):
+    def __init__(self, config, data, augment, resident=False):
         self.config, self.data, self.augment = config, data, augment
         self.ingest = self.host = None
+        self.backgrounds = None                 # config.resident_pool: the mlhot.augment.BackgroundSampler of the training batches
+        self.train_it = 1                       # ... and the iteration the NEXT training batch drawn belongs to (start())
         cuda = torch.device(config.device).type == "cuda"
-        if hasattr(data, "get_batch_u8") and cuda and getattr(config, "ingest_u8", True):
+        if resident:
+            if not cuda:
+                raise ValueError("config.resident_pool keeps the image pool on the device: it needs a ROCm device")
+            from mlhot.augment import BackgroundSampler
+            from mlhot.ingest import BatchIngest, ResidentPool
+            pool = ResidentPool(*data.rgba_pool("train"), device=config.device)       # ONE upload; batches are ids from here on
+            self.ingest = BatchIngest(config.device, pool=pool)
+            self.backgrounds = BackgroundSampler(pool.n_bank, seed=int(getattr(config, "seed", 0) or 0),
+                                                 bg_gen_freq=getattr(config, "bg_gen_freq", 1), gen_bg=getattr(config, "gen_bg", True))
+        elif hasattr(data, "get_batch_u8") and cuda and getattr(config, "ingest_u8", True):
             from mlhot.ingest import BatchIngest
             self.ingest = BatchIngest(config.device)
         elif cuda and getattr(config, "host_prefetch", True):
@@ -165,8 +176,26 @@ class _Feed:
         get = self.data.get_batch_u8 if u8 else self.data.get_batch
         return get(source=source, tasks_per_batch=self.config.tasks_per_batch, shot=self.config.max_ctx_num)
 
+    def start(self, it):
+        """train() begins at iteration `it`: the next training batch drawn is that iteration's (the resident pool's epochs)."""
+        self.train_it = it
+
+    def _stage_ids(self):
+        """config.resident_pool: one training batch as image ids.  The epoch is the one of the iteration the batch is FOR - a batch
+        drawn ahead carries its own - so nothing waits for a regeneration and the loader's gen_bg is never called."""
+        ci, qi, ys, yq = self.data.get_batch_ids(source="train", tasks_per_batch=self.config.tasks_per_batch, shot=self.config.max_ctx_num)
+        epoch = self.backgrounds.epoch(self.train_it)
+        self.train_it += 1
+        table = None
+        if self.augment is not None:
+            pool = self.ingest.pool
+            table = self.augment.batch(ci.size, qi.size, pool.H, pool.W)
+        return self.ingest.stage_ids(ci, qi, ys, yq, bg=(self.backgrounds.batch(ci, epoch), self.backgrounds.batch(qi, epoch)), augment=table)
+
     def _stage(self, source):
         """Draw one batch of `source` and put it on its way to the device; returns the ticket the route's take() wants."""
+        if self.backgrounds is not None and source == "train":
+            return self._stage_ids()
         if self.ingest is None:
             return self.host.stage(self._draw(source), augment=source == "train")
         xs, xq, ys, yq = self._draw(source, u8=True)
@@ -185,8 +214,8 @@ class _Feed:
         overlaps with the step the caller is about to run; the host route's (host-blocking) copies go out BEHIND that step's
         launch: stage_ahead()."""
         route = self.host if self.ingest is None else self.ingest
-        if route is None:
-            return tuple(t.to(self.config.device) for t in self._draw(source))
+        if route is None or (self.backgrounds is not None and source != "train" and not hasattr(self.data, "get_batch_u8")):
+            return tuple(t.to(self.config.device) for t in self._draw(source))      # (resident pool: the other sources keep their routes)
         if source != "train":
             return route.take(self._stage(source))
         batch = route.take(self.ahead.popleft() if self.ahead else self._stage("train"))
@@ -279,7 +308,10 @@ class ModelTrainer(BaseTrainer):
     def __init__(self, model, loss, optimizer, config, data):
         # config.device_augment + "data_aug" in config.aug_list: the loader's image augmentation on the device (mlhot/augment.py);
         # refused before anything else is set up when the task has no device sequence or the loader still augments itself
-        from mlhot.augment import check_trainer_config
+        from mlhot.augment import check_trainer_config, check_trainer_config_pool
+        # config.resident_pool: training batches as ids into the loader's RGBA pool held on the device, backgrounds composed there
+        # (mlhot/ingest.py ResidentPool, csrc/pool_ingest.h); absent = off.  Refused first, with the reason, where it cannot serve
+        self._resident = check_trainer_config_pool(config, data)
         self._augment = check_trainer_config(config, data)
         if self._augment is None:       # config.device_augment_images: the image tasks' switch (shapenet_3d, distractor), same rules
             from mlhot.augment import check_trainer_config_images
@@ -327,7 +359,7 @@ class ModelTrainer(BaseTrainer):
         self._one = None                # the backward's seed (see _step_body)
         self._late = _LateLoss(config.device)
         self._eps = None                # graph_steps of a Bayes-by-backprop model: its eps draws staged per step (networks/bbb/eps.py)
-        self._feed = _Feed(config, data, self._augment)
+        self._feed = _Feed(config, data, self._augment, resident=self._resident)
         self.ingest, self._host_prefetch = self._feed.ingest, self._feed.host      # which route the batches take (at most one is set)
 
     def _announce(self):
@@ -342,6 +374,10 @@ class ModelTrainer(BaseTrainer):
             self._log("mlhot: host batches are copied on a copy stream behind the step" +
                       (" - as bytes when every image element is exactly k / 255 (checked per batch), as fp32 otherwise" if self._host_prefetch.u8 is not None else "")
                       + f"; up to {_depth(self.config)} batches are drawn ahead where no validation round / background regeneration lies between")
+        if self._resident:
+            pool = self.ingest.pool
+            self._log(f"mlhot: config.resident_pool - {pool.n_pool} RGBA images and {pool.n_bank} backgrounds are held on the device; training batches cross "
+                      "PCIe as image ids and the epoch's backgrounds are composed there (data.gen_bg is not called; the choice is a hash of seed, epoch, id)")
         if self._graph_default and self._lagged():
             self._log("mlhot: every iteration's loss is logged and checked one iteration late (read behind the NEXT iteration's launch; flushed before "
                       "validation rounds, checkpoints and the end of training).  config.lagged_loss_log = False reads it right behind the step.")
@@ -371,8 +407,9 @@ class ModelTrainer(BaseTrainer):
         self._log("\n================== Start training ===================")
         self._announce()
         it = self.start_iter
+        self._feed.start(it)
         for it in range(self.start_iter, self.iterations + 1):
-            if it % self.config.bg_gen_freq == 0 and self.config.gen_bg:
+            if it % self.config.bg_gen_freq == 0 and self.config.gen_bg and not self._resident:      # resident pool: composed per batch on the device
                 self.data.gen_bg(self.config, data="train")
             # The reference draws train_k, [validation / test batches of k], [gen_bg(k+1)], train_k+1 - and its loaders may share
             # one global generator.  Batch k+1 is therefore prefetched (drawn while step k computes) only when nothing else
@@ -402,7 +439,8 @@ class ModelTrainer(BaseTrainer):
         model_trainer.py:59-70)."""
         n = 0
         for i in range(it, it + _depth(self.config)):
-            if i < self.iterations and i % self.config.val_freq != 0 and not ((i + 1) % self.config.bg_gen_freq == 0 and self.config.gen_bg):
+            regen = (i + 1) % self.config.bg_gen_freq == 0 and self.config.gen_bg and not getattr(self, "_resident", False)
+            if i < self.iterations and i % self.config.val_freq != 0 and not regen:
                 n += 1
             else:
                 break
