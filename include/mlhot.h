@@ -515,6 +515,22 @@ int mlhot_pool_augment_ingest_u8_img(const uint8_t* pool, long n_pool, const int
                                      float* dst, long n_img, int H, int W, float div, const mlhot_aug_record_img* rec,
                                      const uint8_t* luts, int n_luts, const void* colour_tabs, void* stream);
 
+/* ---- resident grey pool: the single-channel tasks (shapenet_1d, pascal_1d, distractor) by image ids ----
+ * pool: uint8 [n_pool, H, W, 1] - the bytes the loader's byte batch carries (Distractor: 255 - images, inverted once by the loader);
+ * ids[i] in [0, n_pool).  Each entry gives, bit for bit, what its byte twin gives on the gathered images pool[ids] with the same
+ * remaining arguments: no alpha, no bank, no new semantics.  dst: fp32 [n_img, 1, H, W].  As above the entries check nothing about the
+ * indices - the caller range-checks them on the host - and the image's byte offset ids[i] * H * W is taken in 64 bits (a pool may
+ * exceed 2 GiB).  Added within ABI 7 (pure additions).  All device pointers. */
+/* = mlhot_ingest_u8_nhwc(pool[ids], C = 1, div).  Any H, W. */
+int mlhot_pool1_ingest_u8(const uint8_t* pool, long n_pool, const int* ids, float* dst, long n_img, int H, int W, float div, void* stream);
+/* = mlhot_augment_ingest_u8(pool[ids], C = 1, div, rec, luts).  H, W <= 128, MLHOT_ERR_UNSUPPORTED otherwise. */
+int mlhot_pool1_augment_ingest_u8(const uint8_t* pool, long n_pool, const int* ids, float* dst, long n_img, int H, int W, float div,
+                                  const mlhot_aug_record* rec, const uint8_t* luts, int n_luts, void* stream);
+/* = mlhot_augment_ingest_u8_img(pool[ids], C = 1, pre_op, div, div2, rec, luts, colour_tabs).  H, W <= 128, MLHOT_ERR_UNSUPPORTED otherwise. */
+int mlhot_pool1_augment_ingest_u8_img(const uint8_t* pool, long n_pool, const int* ids, float* dst, long n_img, int H, int W, int pre_op,
+                                      float div, float div2, const mlhot_aug_record_img* rec, const uint8_t* luts, int n_luts,
+                                      const void* colour_tabs, void* stream);
+
 /* ---- optimizer: torch.optim.Adam (train.py:52-56) as ONE launch over flat buffers -------------------
  * param / grad / exp_avg / exp_avg_sq: n floats each, laid out alike (e.g. mlhot_np_grads_flat_layout).
  * step >= 1 is the 1-based update count (bias correction); grad_scale multiplies the gradient first

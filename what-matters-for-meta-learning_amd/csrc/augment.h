@@ -314,6 +314,17 @@ MLHOT_DEV void augment_image(const Exec& ex, const mlhot_aug_record& r, const ui
   }
 }
 
+// ---- where the load stage finds image `img`'s H * W bytes: packed one behind the other (mlhot_augment_ingest_u8), or image ids[img] of
+// the resident grey pool (mlhot_pool1_augment_ingest_u8; the byte offset in 64 bits - a pool can exceed 2 GiB) ---------
+struct PackedSrc {
+  const uint8_t* src;
+  MLHOT_HD const uint8_t* image(long img, int HW) const { return src + img * HW; }
+};
+struct GreyPoolSrc {
+  const uint8_t* pool; const int* ids;
+  MLHOT_HD const uint8_t* image(long img, int HW) const { return pool + (long)ids[img] * HW; }
+};
+
 #ifndef MLHOT_HOSTSIM
 struct BlockExec {
   template <class F>
@@ -323,14 +334,15 @@ struct BlockExec {
   }
 };
 
-__global__ __launch_bounds__(NT) void augment_ingest_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, int H, int W,
+template <class Src>
+__global__ __launch_bounds__(NT) void augment_ingest_kernel(const Src src, float* __restrict__ dst, int H, int W,
                                                             float div, const mlhot_aug_record* __restrict__ rec,
                                                             const uint8_t* __restrict__ luts, int n_luts, int vec) {
   __shared__ uint8_t s_a[MAXD * MAXD], s_b[MAXD * MAXD], s_pad[MAXP * MAXP];
   __shared__ int s_stat[MAXP], s_flag[2], s_coef[5 * 2 * MAXD];
   const long img = blockIdx.x;
   const int HW = H * W;
-  const uint8_t* s = src + img * HW;
+  const uint8_t* __restrict__ s = src.image(img, HW);
   if (vec) {                                                          // HW % 4 == 0, 4-byte aligned: one dword per lane step
     for (int q = threadIdx.x; q < HW / 4; q += NT) reinterpret_cast<uint32_t*>(s_a)[q] = reinterpret_cast<const uint32_t*>(s)[q];
   } else {
@@ -361,28 +373,40 @@ struct LoopExec {
 };
 #endif
 
-inline int run(const uint8_t* src, float* dst, long n_img, int H, int W, float div, const mlhot_aug_record* rec, const uint8_t* luts,
-               int n_luts, hipStream_t s) {
+// base: the pointer the images are read from (its alignment decides the dword loads)
+template <class Src>
+inline int run_src(const Src& src, const uint8_t* base, float* dst, long n_img, int H, int W, float div, const mlhot_aug_record* rec,
+                   const uint8_t* luts, int n_luts, hipStream_t s, const char* what) {
   if (n_img == 0) return MLHOT_OK;
 #ifndef MLHOT_HOSTSIM
   const int HW = H * W;
-  const int vec = (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
-  ProfScope ps("augment.ingest.u8", s);
-  hipLaunchKernelGGL(augment_ingest_kernel, dim3((unsigned)n_img), dim3(NT), 0, s, src, dst, H, W, div, rec, luts, n_luts, vec);
-  return check_launch("augment.ingest.u8");
+  const int vec = (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(base) & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+  ProfScope ps(what, s);
+  hipLaunchKernelGGL(augment_ingest_kernel<Src>, dim3((unsigned)n_img), dim3(NT), 0, s, src, dst, H, W, div, rec, luts, n_luts, vec);
+  return check_launch(what);
 #else
-  (void)s;
+  (void)s; (void)base; (void)what;
   static thread_local uint8_t a[MAXD * MAXD], b[MAXD * MAXD], pad[MAXP * MAXP];
   static thread_local int stat[MAXP], flag[2], coef[5 * 2 * MAXD];
   const int HW = H * W;
   for (long img = 0; img < n_img; ++img) {
-    memcpy(a, src + img * HW, (size_t)HW);
+    memcpy(a, src.image(img, HW), (size_t)HW);
     Planes pl{a, b, pad, stat, flag, coef};
     augment_image(LoopExec{}, rec[img], luts, n_luts, H, W, pl);
     for (int i = 0; i < HW; ++i) dst[img * HW + i] = (float)pl.cur[i] / div;
   }
   return MLHOT_OK;
 #endif
+}
+
+inline int run(const uint8_t* src, float* dst, long n_img, int H, int W, float div, const mlhot_aug_record* rec, const uint8_t* luts,
+               int n_luts, hipStream_t s) {
+  return run_src(PackedSrc{src}, src, dst, n_img, H, W, div, rec, luts, n_luts, s, "augment.ingest.u8");
+}
+
+inline int run_pool1(const uint8_t* pool, const int* ids, float* dst, long n_img, int H, int W, float div, const mlhot_aug_record* rec,
+                     const uint8_t* luts, int n_luts, hipStream_t s) {
+  return run_src(GreyPoolSrc{pool, ids}, pool, dst, n_img, H, W, div, rec, luts, n_luts, s, "pool1.augment.ingest.u8");
 }
 
 }  // namespace aug

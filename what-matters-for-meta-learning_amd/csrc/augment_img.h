@@ -8,8 +8,9 @@
 // Luv through host-built tables, mlhot_colour_tabs), per_channel dropouts, the loaders' byte handling (pre_op, div2).  The spec is
 // DESIGN.md 6a-2 and include/mlhot.h; tests/augment_img_ref.py restates it in numpy and this file matches that bit for bit.
 //
-// The de-interleave stage reads through a source functor: NhwcSrc, the packed channel-last bytes (mlhot_augment_ingest_u8_img), or
-// PoolSrc, image ids[i] of the resident RGBA pool composed over the background bank (mlhot_pool_augment_ingest_u8_img).
+// The de-interleave stage reads through a source functor: NhwcSrc, the packed channel-last bytes (mlhot_augment_ingest_u8_img),
+// PoolSrc, image ids[i] of the resident RGBA pool composed over the background bank (mlhot_pool_augment_ingest_u8_img), or
+// GreyPoolImgSrc, image ids[i] of the resident single-channel pool (mlhot_pool1_augment_ingest_u8_img).
 #pragma once
 #include "augment.h"
 #include "pool_ingest.h"
@@ -315,6 +316,28 @@ struct PoolSrc {             // image ids[img] of the resident RGBA pool, compos
   }
 };
 
+struct GreyPoolImgSrc {      // image ids[img] of the resident grey pool: C = 1, pre_byte as NhwcSrc applies it
+  const uint8_t* pool; const int* ids; int pre_op;
+#ifndef MLHOT_HOSTSIM
+  __device__ __forceinline__ void fill_block(uint8_t* planes, long img, int HW, int vec) const {
+    const uint8_t* s = pool + (long)ids[img] * HW;
+    if (vec) {                                                          // HW % 4 == 0, pool 4-byte aligned: one dword per lane step
+      for (int q = threadIdx.x; q < HW / 4; q += NT) {
+        const uint32_t w = reinterpret_cast<const uint32_t*>(s)[q];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) planes[4 * q + j] = pre_byte((uint8_t)(w >> (8 * j)), pre_op);
+      }
+    } else {
+      for (int p = threadIdx.x; p < HW; p += NT) planes[p] = pre_byte(s[p], pre_op);
+    }
+  }
+#endif
+  void fill_loop(uint8_t* planes, long img, int HW) const {
+    const uint8_t* sp = pool + (long)ids[img] * HW;
+    for (int p = 0; p < HW; ++p) planes[p] = pre_byte(sp[p], pre_op);
+  }
+};
+
 #ifndef MLHOT_HOSTSIM
 template <class Src>
 __global__ __launch_bounds__(NT) void augment_img_ingest_kernel(const Src src, float* __restrict__ dst, int H, int W, int C,
@@ -392,6 +415,14 @@ inline int run_pool(const uint8_t* pool, const int* ids, const uint8_t* bank, co
   const int vec_in = (reinterpret_cast<uintptr_t>(pool) & 3) == 0;
   const int vec_out = ((3 * H * W) & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
   return run_src(PoolSrc{pool, ids, bank, bg}, vec_in, vec_out, dst, n_img, H, W, 3, div, 1.0f, rec, luts, n_luts, ct, s, "pool.augment.ingest.u8.img");
+}
+
+inline int run_pool1(const uint8_t* pool, const int* ids, float* dst, long n_img, int H, int W, int pre_op, float div, float div2,
+                     const mlhot_aug_record_img* rec, const uint8_t* luts, int n_luts, const mlhot_colour_tabs* ct, hipStream_t s) {
+  const int vec_in = ((H * W) & 3) == 0 && (reinterpret_cast<uintptr_t>(pool) & 3) == 0;
+  const int vec_out = ((H * W) & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+  return run_src(GreyPoolImgSrc{pool, ids, pre_op}, vec_in, vec_out, dst, n_img, H, W, 1, div, div2, rec, luts, n_luts, ct, s,
+                 "pool1.augment.ingest.u8.img");
 }
 
 }  // namespace augimg

@@ -676,6 +676,44 @@ int mlhot_pool_augment_ingest_u8_img(const uint8_t* pool, long n_pool, const int
                           (hipStream_t)stream);
 }
 
+// ---- resident grey pool (uint8 [n_pool, H, W, 1]: the 1D tasks, Distractor): gather by id + the three byte entries' work -----------
+static int pool1_args(const char* what, const uint8_t* pool, long n_pool, const int* ids, float* dst, long n_img, int H, int W, float div) {
+  if (n_img < 0 || n_pool < 0 || H <= 0 || W <= 0 || !(div > 0.f) || (n_img > 0 && (!pool || n_pool == 0 || !ids || !dst))) {
+    set_error("%s: bad argument", what);
+    return MLHOT_ERR_ARG;
+  }
+  return MLHOT_OK;
+}
+int mlhot_pool1_ingest_u8(const uint8_t* pool, long n_pool, const int* ids, float* dst, long n_img, int H, int W, float div, void* stream) {
+  MLHOT_TRY(pool1_args("pool1_ingest_u8", pool, n_pool, ids, dst, n_img, H, W, div));
+  return pool::pool1::run(pool, ids, dst, n_img, H, W, div, (hipStream_t)stream);
+}
+int mlhot_pool1_augment_ingest_u8(const uint8_t* pool, long n_pool, const int* ids, float* dst, long n_img, int H, int W, float div,
+                                  const mlhot_aug_record* rec, const uint8_t* luts, int n_luts, void* stream) {
+  MLHOT_TRY(pool1_args("pool1_augment_ingest_u8", pool, n_pool, ids, dst, n_img, H, W, div));
+  if (n_luts < 0 || (n_img > 0 && !rec) || (n_luts > 0 && !luts)) { set_error("pool1_augment_ingest_u8: bad argument"); return MLHOT_ERR_ARG; }
+  if (H > aug::MAXD || W > aug::MAXD) {
+    set_error("pool1_augment_ingest_u8: H, W <= %d only (got H=%d W=%d)", aug::MAXD, H, W);
+    return MLHOT_ERR_UNSUPPORTED;
+  }
+  return aug::run_pool1(pool, ids, dst, n_img, H, W, div, rec, luts, n_luts, (hipStream_t)stream);
+}
+int mlhot_pool1_augment_ingest_u8_img(const uint8_t* pool, long n_pool, const int* ids, float* dst, long n_img, int H, int W, int pre_op,
+                                      float div, float div2, const mlhot_aug_record_img* rec, const uint8_t* luts, int n_luts,
+                                      const void* colour_tabs, void* stream) {
+  MLHOT_TRY(pool1_args("pool1_augment_ingest_u8_img", pool, n_pool, ids, dst, n_img, H, W, div));
+  if (!(div2 > 0.f) || pre_op < 0 || pre_op > 1 || n_luts < 0 || (n_img > 0 && !rec) || (n_luts > 0 && !luts)) {
+    set_error("pool1_augment_ingest_u8_img: bad argument");
+    return MLHOT_ERR_ARG;
+  }
+  if (!augimg::in_scope(H, W, 1)) {
+    set_error("pool1_augment_ingest_u8_img: H, W <= %d only (got H=%d W=%d)", aug::MAXD, H, W);
+    return MLHOT_ERR_UNSUPPORTED;
+  }
+  return augimg::run_pool1(pool, ids, dst, n_img, H, W, pre_op, div, div2, rec, luts, n_luts, (const mlhot_colour_tabs*)colour_tabs,
+                           (hipStream_t)stream);
+}
+
 // ---- fused Adam over a flat parameter / gradient buffer ------------------------------------------------
 int mlhot_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
                     float eps, float weight_decay, float grad_scale, int step, void* stream) {

@@ -12,6 +12,8 @@
 // three float4 stores; QPT quads in flight per lane.  Image and quad come from the flat quad index, so the grid fills the chip at any
 // batch size; id and bg are per-lane loads (wave-uniform only when an image has >= 64 quads).  Ids and bg indices are range-checked
 // on the host before they are shipped (mlhot/ingest.py); the kernels trust them.
+//
+// Below it, namespace pool1: the single-channel ("grey") pools of the 1D tasks and Distractor - a plain gather + divide.
 #pragma once
 #include "ingest.h"
 
@@ -113,6 +115,74 @@ inline int run(const uint8_t* pool, const int* ids, const uint8_t* bank, const i
 #endif
   return run_foreach(PoolAny{pool, ids, bank, bg, dst, HW, div}, (size_t)n_img * 3 * HW, s, "pool.ingest.u8.any");
 }
+
+// ---- single-channel ("grey") pool: the 1D tasks and Distractor ----------------------------------------------------------
+// pool: uint8 [N, H, W, 1] - the bytes the loaders' byte batches carry; no alpha, no bank.  Gather + the divide of ingest.h, so the bits
+// of mlhot_ingest_u8_nhwc(pool[ids], C = 1).  ingest.h's C = 1 kernel with a gathered source: a lane owns a quad of 4 consecutive
+// pixels of ONE image = one dword load and one float4 store, so a wave's store instruction writes 1 KiB in one piece; QPT quads in
+// flight per lane; image and quad from the flat quad index, ids loaded per lane; the image's byte offset ids[img] * HW in 64 bits - a
+// ShapeNet1D pool can exceed 2 GiB.  (A lane owning 16 bytes - one 16-byte load, four float4 stores - was measured first: 1.46 x the
+// plain ingest, because each of its store instructions scatters 64 pieces of 16 bytes at a 64-byte stride)
+namespace pool1 {
+
+#ifndef MLHOT_HOSTSIM
+
+__global__ __launch_bounds__(NT) void pool1_gather_kernel(const uint8_t* __restrict__ pool, const int* __restrict__ ids,
+                                                          float* __restrict__ dst, long n_quads, int quads_per_img, int HW, float div) {
+  const long stride = (long)gridDim.x * NT;
+  const long q0 = (long)blockIdx.x * NT + threadIdx.x;
+  uint32_t px[QPT];              // 4 grey pixels each
+#pragma unroll
+  for (int u = 0; u < QPT; ++u) {
+    const long q = q0 + u * stride;
+    px[u] = 0u;
+    if (q < n_quads) {
+      const long img = q / quads_per_img;
+      const int qi = (int)(q - img * quads_per_img);
+      px[u] = *reinterpret_cast<const uint32_t*>(pool + (long)ids[img] * HW + 4 * qi);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < QPT; ++u) {
+    const long q = q0 + u * stride;
+    if (q >= n_quads) continue;
+    const uint32_t w = px[u];
+    float4 v;
+    v.x = (float)(uint8_t)(w) / div;
+    v.y = (float)(uint8_t)(w >> 8) / div;
+    v.z = (float)(uint8_t)(w >> 16) / div;
+    v.w = (float)(uint8_t)(w >> 24) / div;
+    reinterpret_cast<float4*>(dst)[q] = v;       // HW % 4 == 0: quad q of the batch is floats [4 q, 4 q + 4) of the destination
+  }
+}
+
+#endif  // !MLHOT_HOSTSIM
+
+// any H * W and any alignment: one index per destination float
+struct Pool1Any {
+  const uint8_t* pool; const int* ids; float* dst; int HW; float div;
+  MLHOT_HD void operator()(size_t i) const {
+    const size_t img = i / (size_t)HW;
+    dst[i] = (float)pool[(size_t)ids[img] * HW + (i - img * (size_t)HW)] / div;
+  }
+};
+
+inline int run(const uint8_t* pool, const int* ids, float* dst, long n_img, int H, int W, float div, hipStream_t s) {
+  const int HW = H * W;
+  if (n_img == 0) return MLHOT_OK;
+#ifndef MLHOT_HOSTSIM
+  if ((HW & 3) == 0 && (reinterpret_cast<uintptr_t>(pool) & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+    const long n_quads = n_img * (long)(HW / 4);
+    const int grid = (int)((n_quads + (long)NT * QPT - 1) / ((long)NT * QPT));
+    ProfScope ps("pool1.ingest.u8", s);
+    hipLaunchKernelGGL(pool1_gather_kernel, dim3(grid), dim3(NT), 0, s, pool, ids, dst, n_quads, HW / 4, HW, div);
+    return check_launch("pool1.ingest.u8");
+  }
+#endif
+  return run_foreach(Pool1Any{pool, ids, dst, HW, div}, (size_t)n_img * HW, s, "pool1.ingest.u8.any");
+}
+
+}  // namespace pool1
 
 }  // namespace pool
 }  // namespace mlhot

@@ -288,21 +288,32 @@ class BackgroundSampler:
         return ((h * np.uint64(self.n_bank)) >> np.uint64(32)).astype(np.int32)
 
 
+GREY_POOL_TASKS = ("shapenet_1d", "pascal_1d", "distractor")        # single-channel loaders: ResidentPool's grey kind
+
+
 def check_trainer_config_pool(config, data):
     """The resident pool's switch (config.resident_pool; absent = off): is it on?  Refuses - ValueError, with the reason - what the
-    route cannot do: another task, a loader without the protocol, a loader that still augments itself."""
+    route cannot do: another task, a loader without the task's protocol (rgba_pool for shapenet_3d, grey_pool for the
+    single-channel tasks), a loader that still augments itself."""
     if not getattr(config, "resident_pool", False):
         return False
-    if getattr(config, "task", None) != "shapenet_3d":
-        raise ValueError(f"config.resident_pool: the resident RGBA pool serves task 'shapenet_3d' only (its loader composes backgrounds by "
-                         f"alpha); task {getattr(config, 'task', None)!r} has no alpha channel - leave the switch off")
-    if not (hasattr(data, "rgba_pool") and hasattr(data, "get_batch_ids")):
+    task = getattr(config, "task", None)
+    if task in GREY_POOL_TASKS:
+        if not (hasattr(data, "grey_pool") and hasattr(data, "get_batch_ids")):
+            raise ValueError(f"config.resident_pool: the resident RGBA pool (rgba_pool) serves task 'shapenet_3d' only (its loader composes "
+                             f"backgrounds by alpha); task {task!r} has no alpha channel and needs grey_pool('train') -> uint8 [N, H, W, 1] "
+                             "(the bytes of get_batch_u8) and get_batch_ids(source, tasks_per_batch, shot) -> (ctx_ids, qry_ids, ys, yq) "
+                             "(INTEGRATION.md) - or leave the switch off")
+    elif task != "shapenet_3d":
+        raise ValueError(f"config.resident_pool serves tasks 'shapenet_3d' (rgba_pool) and {', '.join(GREY_POOL_TASKS)} (grey_pool); task "
+                         f"{task!r} has no resident route - leave the switch off")
+    elif not (hasattr(data, "rgba_pool") and hasattr(data, "get_batch_ids")):
         raise ValueError("config.resident_pool: the loader lacks the protocol - rgba_pool('train') -> (uint8 [N, H, W, 4], bank) and "
                          "get_batch_ids(source, tasks_per_batch, shot) -> (ctx_ids, qry_ids, ys, yq) (INTEGRATION.md)")
     if getattr(data, "data_aug", False):
         raise ValueError("config.resident_pool: the loader still augments on the host (data.data_aug is True), and batches described by "
                          "ids never pass through it.  Build it with aug=[a for a in config.aug_list if a != 'data_aug'] and set "
-                         "config.device_augment_images (INTEGRATION.md)")
+                         + ("config.device_augment_images" if task in ("shapenet_3d", "distractor") else "config.device_augment") + " (INTEGRATION.md)")
     return True
 
 

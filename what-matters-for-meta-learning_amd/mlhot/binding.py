@@ -295,6 +295,9 @@ SIGNATURES = {
     "mlhot_augment_ingest_u8_img": (i, [P, P, L, i, i, i, i, f32, f32, P, P, i, P, P]),
     "mlhot_pool_ingest_u8": (i, [P, L, P, P, L, P, P, L, i, i, f32, P]),
     "mlhot_pool_augment_ingest_u8_img": (i, [P, L, P, P, L, P, P, L, i, i, f32, P, P, i, P, P]),
+    "mlhot_pool1_ingest_u8": (i, [P, L, P, P, L, i, i, f32, P]),
+    "mlhot_pool1_augment_ingest_u8": (i, [P, L, P, P, L, i, i, f32, P, P, i, P]),
+    "mlhot_pool1_augment_ingest_u8_img": (i, [P, L, P, P, L, i, i, i, f32, f32, P, P, i, P, P]),
     # optimizer
     "mlhot_adam_step": (i, [P, P, P, P, z] + [f32] * 6 + [i, P]),
     "mlhot_adam_step_counter": (i, [P, P, P, P, z] + [f32] * 6 + [P, P]),
@@ -1202,6 +1205,73 @@ class MlhotLib:
         self._rc(fn(_ptr(pool), n_pool, _ptr(ids), _ptr(bank) if n_bank else None, n_bank, _ptr(bg), _ptr(out), n_img, H, W, float(div),
                     _ptr(records), _ptr(luts) if n_luts else None, n_luts, _ptr(colour_tabs), _stream(pool)),
                  "mlhot_pool_augment_ingest_u8_img")
+        return out
+
+    # ---- resident grey pool: uint8 [N, H, W, 1] (csrc/pool_ingest.h pool1, augment.h / augment_img.h source functors) ------------
+    @staticmethod
+    def _pool1_args(wrapper, pool, ids, out):
+        """Shapes, dtypes and devices of a grey-pool call; -> (n_pool, n_img, H, W, out).  Host ids (the host build) are range-checked
+        here; device ids are trusted - BatchIngest.stage_ids checks them before it ships them."""
+        if pool.dtype != torch.uint8 or pool.dim() != 4 or pool.shape[-1] != 1:
+            raise MlhotError(f"{wrapper}: the pool must be uint8 [N, H, W, 1] (single-channel), got {pool.dtype} {tuple(pool.shape)}")
+        n_pool, H, W, _ = pool.shape
+        if ids.dtype != torch.int32 or ids.device != pool.device:
+            raise MlhotError(f"{wrapper}: ids must be int32 on {pool.device}")
+        n_img = ids.numel()
+        if not ids.is_cuda:
+            from .ingest import check_pool_indices
+            check_pool_indices(ids.numpy(), torch.full(tuple(ids.shape), -1).numpy(), n_pool, 0)
+        shape = (*ids.shape, 1, H, W)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=pool.device)
+        elif out.dtype != torch.float32 or out.numel() != math.prod(shape) or out.device != pool.device:
+            raise MlhotError(f"{wrapper}: out must be fp32 {shape} on {pool.device}")
+        _chk(pool, ids, out)
+        return n_pool, n_img, H, W, out
+
+    @staticmethod
+    def _pool1_table(wrapper, pool, n_img, records, ints, luts):
+        if records.dtype != torch.int32 or records.numel() != n_img * ints or records.device != pool.device:
+            raise MlhotError(f"{wrapper}: records must be int32 [{n_img}, {ints}] on {pool.device}")
+        n_luts = 0
+        if luts is not None:
+            if luts.dtype != torch.uint8 or luts.dim() != 2 or luts.shape[1] != 256 or luts.device != pool.device:
+                raise MlhotError(f"{wrapper}: luts must be uint8 [n, 256] on the pool's device")
+            n_luts = luts.shape[0]
+        _chk(records, luts)
+        return n_luts
+
+    def pool1_ingest_u8(self, pool, ids, out=None, div=255.0):
+        """Images `ids` (int32 [...]) of the resident grey pool (uint8 [N, H, W, 1]) -> fp32 [..., 1, H, W] = byte / div: the bits of
+        ingest_u8_nhwc(pool[ids]) (include/mlhot.h mlhot_pool1_ingest_u8)."""
+        fn = self._fn("pool1_ingest_u8", "mlhot_pool1_ingest_u8")
+        n_pool, n_img, H, W, out = self._pool1_args("pool1_ingest_u8", pool, ids, out)
+        self._rc(fn(_ptr(pool), n_pool, _ptr(ids), _ptr(out), n_img, H, W, float(div), _stream(pool)), "mlhot_pool1_ingest_u8")
+        return out
+
+    def pool1_augment_ingest_u8(self, pool, ids, records, luts=None, out=None, div=255.0):
+        """augment_ingest_u8 (the 1D sequences; records int32 [n_img, 32]) on images `ids` of the grey pool; H, W <= 128."""
+        fn = self._fn("pool1_augment_ingest_u8", "mlhot_pool1_augment_ingest_u8")
+        n_pool, n_img, H, W, out = self._pool1_args("pool1_augment_ingest_u8", pool, ids, out)
+        n_luts = self._pool1_table("pool1_augment_ingest_u8", pool, n_img, records, AUG_RECORD_BYTES // 4, luts)
+        self._rc(fn(_ptr(pool), n_pool, _ptr(ids), _ptr(out), n_img, H, W, float(div), _ptr(records), _ptr(luts) if n_luts else None, n_luts,
+                    _stream(pool)), "mlhot_pool1_augment_ingest_u8")
+        return out
+
+    def pool1_augment_ingest_u8_img(self, pool, ids, records, luts=None, colour_tabs=None, out=None, pre_op=0, div=255.0, div2=1.0):
+        """augment_ingest_u8_img with C = 1 (Distractor's sequence; records int32 [n_img, 40], pre_op, div, div2 as there) on images
+        `ids` of the grey pool; H, W <= 128."""
+        fn = self._fn("pool1_augment_ingest_u8_img", "mlhot_pool1_augment_ingest_u8_img")
+        n_pool, n_img, H, W, out = self._pool1_args("pool1_augment_ingest_u8_img", pool, ids, out)
+        n_luts = self._pool1_table("pool1_augment_ingest_u8_img", pool, n_img, records, AUG_IMG_RECORD_BYTES // 4, luts)
+        if colour_tabs is not None and (colour_tabs.dtype != torch.uint8 or colour_tabs.numel() != COLOUR_TABS_BYTES
+                                        or colour_tabs.device != pool.device):
+            raise MlhotError(f"pool1_augment_ingest_u8_img: colour_tabs must be uint8 [{COLOUR_TABS_BYTES}] on the pool's device")
+        if pre_op not in (0, 1):
+            raise MlhotError(f"pool1_augment_ingest_u8_img: pre_op is 0 or 1, got {pre_op!r}")
+        _chk(colour_tabs)
+        self._rc(fn(_ptr(pool), n_pool, _ptr(ids), _ptr(out), n_img, H, W, int(pre_op), float(div), float(div2), _ptr(records),
+                    _ptr(luts) if n_luts else None, n_luts, _ptr(colour_tabs), _stream(pool)), "mlhot_pool1_augment_ingest_u8_img")
         return out
 
     # ---- fused Adam over flat buffers -------------------------------------------------------------

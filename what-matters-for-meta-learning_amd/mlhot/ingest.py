@@ -22,6 +22,11 @@ mlhot_augment_ingest_u8_img (csrc/augment_img.h) with the table's pre_op / div /
 `BatchIngest(device, pool=ResidentPool(images_rgba, bank, device))` + `stage_ids(ctx_ids, qry_ids, ys, yq, bg=..., augment=...)`: the
 loader's RGBA pool and background bank live on the device, a batch is its image ids (+ one bank index per image), and take() gathers,
 composes and converts with mlhot_pool_ingest_u8 / mlhot_pool_augment_ingest_u8_img (csrc/pool_ingest.h).
+
+`ResidentPool(images_grey, device=...)` with a single-channel pool uint8 [N, H, W, 1] (shapenet_1d, pascal_1d, distractor: the bytes the
+loader's `get_batch_u8` would carry) serves the same `stage_ids` - no bank, no bg; `augment` an AugTable (the 1D sequences) or an
+ImageAugTable (Distractor's) - through mlhot_pool1_ingest_u8 / mlhot_pool1_augment_ingest_u8 / mlhot_pool1_augment_ingest_u8_img
+(DESIGN.md 6a-4): what take() delivers is, bit for bit, what stage() delivers for the byte batch pool[ids].
 """
 import collections
 import threading
@@ -125,16 +130,42 @@ def pool_bytes(a, channels, what, L=None, div=255.0):
     return out
 
 
+def check_grey_batch(n_img, bg, augment):
+    """What a batch of a GREY pool may carry, checked before a slot is taken: no bg (there is no bank on this route), and as `augment`
+    None, an AugTable (the 1D sequences: 128-byte records) or an ImageAugTable (Distractor's sequence with its pre_op / div / div2:
+    160-byte records) of one record per image.  -> the slot kind."""
+    from .augment import AugTable, ImageAugTable
+    if bg is not None:
+        raise MlhotError("BatchIngest.stage_ids: a grey pool has no background bank - bg must be None")
+    if augment is None:
+        return "pool1"
+    if not isinstance(augment, AugTable):
+        raise MlhotError(f"BatchIngest.stage_ids: on a grey pool augment is None, an AugTable (shapenet_1d / pascal_1d) or an ImageAugTable "
+                         f"(distractor), got {type(augment).__name__}")
+    image = isinstance(augment, ImageAugTable)
+    ints = (AUG_IMG_RECORD_BYTES if image else AUG_RECORD_BYTES) // 4
+    if augment.records.ndim != 2 or augment.records.shape[1] != ints:
+        raise MlhotError(f"BatchIngest.stage_ids: {type(augment).__name__} records must be int32 [n, {ints}], got {augment.records.shape}")
+    if augment.n_img != n_img:
+        raise MlhotError(f"BatchIngest.stage_ids: the augmentation table holds {augment.n_img} records for {n_img} images")
+    return "pool1augimg" if image else "pool1aug"
+
+
 class ResidentPool:
-    """A loader's RGBA image pool (uint8 [N, H, W, 4]) and its background bank (uint8 [B, H, W, 3], or None), uploaded ONCE: batches
-    are then described by image ids (BatchIngest.stage_ids) and gathered, composed and converted on the device (csrc/pool_ingest.h)."""
+    """A loader's image pool, uploaded ONCE: batches are then described by image ids (BatchIngest.stage_ids) and gathered and converted
+    on the device (csrc/pool_ingest.h).  The kind is read from the last dimension: uint8 [N, H, W, 4] is an RGBA pool with its
+    background bank (uint8 [B, H, W, 3], or None), uint8 [N, H, W, 1] a grey pool, which has no bank (`grey`; 6a-4)."""
 
     def __init__(self, images_u8, bank_u8=None, device="cuda:0", div=255.0):
         self.device = torch.device(device)
+        shape = tuple(images_u8.shape)
+        self.grey = len(shape) == 4 and shape[-1] == 1
+        if self.grey and bank_u8 is not None and len(bank_u8) > 0:
+            raise MlhotError("ResidentPool: a grey pool [N, H, W, 1] has no alpha to compose behind - it takes no background bank")
         if self.device.type != "cuda":
             raise MlhotError("ResidentPool: the pool lives on a ROCm device; there is no CPU fallback")
-        pool = pool_bytes(images_u8, 4, "the image pool", div=div)
-        bank = None if bank_u8 is None or len(bank_u8) == 0 else pool_bytes(bank_u8, 3, "the background bank", div=div)
+        pool = pool_bytes(images_u8, 1 if self.grey else 4, "the image pool", div=div)
+        bank = None if self.grey or bank_u8 is None or len(bank_u8) == 0 else pool_bytes(bank_u8, 3, "the background bank", div=div)
         if bank is not None and tuple(bank.shape[1:3]) != tuple(pool.shape[1:3]):
             raise MlhotError(f"ResidentPool: backgrounds of {tuple(bank.shape[1:3])} behind images of {tuple(pool.shape[1:3])}")
         try:
@@ -151,34 +182,38 @@ class ResidentPool:
 class _IdSlot:
     """A staging slot of a batch described by ids: [ids int32 (ctx, qry) | bg int32 | pad to 16 | ctx labels | qry labels] and, when the
     batch is augmented, [records int32 [n, 40] | gamma LUTs] behind them - no image bytes.  key = (ctx ids shape, qry ids shape, ctx
-    labels shape, qry labels shape, "pool" | "poolaug")."""
+    labels shape, qry labels shape, kind): "pool" | "poolaug" for an RGBA pool; "pool1" | "pool1aug" | "pool1augimg" for a grey pool,
+    which has no bg array and whose record area follows the table kind - [n, 32] (AugTable) or [n, 40] (ImageAugTable)."""
 
     def __init__(self, key, device):
         n = int(np.prod(key[0])) + int(np.prod(key[1]))
         n_lab = [int(np.prod(key[2])), int(np.prod(key[3]))]
-        lab_off = (8 * n + 15) // 16 * 16
+        grey = key[4].startswith("pool1")
+        lab_off = ((4 if grey else 8) * n + 15) // 16 * 16
         lab_end = total = lab_off + 4 * (n_lab[0] + n_lab[1])
-        self.augmented = key[4] == "poolaug"
+        self.augmented = key[4] in ("poolaug", "pool1aug", "pool1augimg")
+        rec_bytes = AUG_RECORD_BYTES if key[4] == "pool1aug" else AUG_IMG_RECORD_BYTES
         if self.augmented:
             rec_off = (total + 15) // 16 * 16
-            lut_off = rec_off + AUG_IMG_RECORD_BYTES * n
+            lut_off = rec_off + rec_bytes * n
             total = lut_off + 256 * n
         self.host = torch.empty(max(total, 16), dtype=torch.uint8).pin_memory()
         self.dev = torch.empty(max(total, 16), dtype=torch.uint8, device=device)
         hn = self.host.numpy()
         self.n_img = n
-        self.ids_np, self.bg_np = hn[:4 * n].view(np.int32), hn[4 * n:8 * n].view(np.int32)
+        self.ids_np, self.bg_np = hn[:4 * n].view(np.int32), None if grey else hn[4 * n:8 * n].view(np.int32)
         self.lab_np = [hn[lab_off:lab_off + 4 * n_lab[0]].view(np.float32).reshape(key[2]),
                        hn[lab_off + 4 * n_lab[0]:lab_end].view(np.float32).reshape(key[3])]
-        self.dev_ids, self.dev_bg = self.dev[:4 * n].view(torch.int32), self.dev[4 * n:8 * n].view(torch.int32)
+        self.dev_ids, self.dev_bg = self.dev[:4 * n].view(torch.int32), None if grey else self.dev[4 * n:8 * n].view(torch.int32)
         self.dev_lab = self.dev[lab_off:lab_end].view(torch.float32)
-        self.n_bytes = lab_end                 # bytes to copy: ids + bg + labels (+ records + the LUTs in use)
+        self.n_bytes = lab_end                 # bytes to copy: ids (+ bg) + labels (+ records + the LUTs in use)
+        self.image_table = None                # an ImageAugTable's (pre_op, div, div2), set per batch
         if self.augmented:
-            self.aug_rec_np = hn[rec_off:lut_off].view(np.int32).reshape(n, AUG_IMG_RECORD_BYTES // 4)
+            self.aug_rec_np = hn[rec_off:lut_off].view(np.int32).reshape(n, rec_bytes // 4)
             self.aug_lut_np = hn[lut_off:total].reshape(n, 256)
             self.dev_rec = self.dev[rec_off:lut_off].view(torch.int32)
             self.dev_lut = self.dev[lut_off:total].view(n, 256)
-            self.lut_off, self.n_luts, self.image_table = lut_off, 0, None
+            self.lut_off, self.n_luts = lut_off, 0
         self.copied = torch.cuda.Event()
         self.consumed = torch.cuda.Event()
         self.busy = False
@@ -248,7 +283,9 @@ class BatchIngest:
         """Queue one batch of the resident pool: image ids [T, Nc] / [T, Nq] (any integer type), labels fp32 [T, N, L]; `bg`: one bank
         index (or -1) per id, context ids first then targets - (ctx [T, Nc], qry [T, Nq]) or one flat array - None = no composition;
         `augment`: an mlhot.augment.ImageAugTable of the shapenet_3d sequence, or None.  Ids and bg indices are range-checked here, on
-        the host; ids, bg, labels and records ride in one pinned slot and one H2D copy - no image bytes.  Returns a ticket."""
+        the host; ids, bg, labels and records ride in one pinned slot and one H2D copy - no image bytes.  Returns a ticket.
+        On a grey pool (ResidentPool.grey): `bg` must be None; `augment` is None, an AugTable (the 1D sequences) or an ImageAugTable
+        carrying Distractor's (pre_op, div, div2) - check_grey_batch."""
         pool = self.pool
         if pool is None:
             raise MlhotError("BatchIngest.stage_ids: no resident pool (BatchIngest(device, pool=ResidentPool(...)))")
@@ -256,6 +293,7 @@ class BatchIngest:
         if ci.ndim != 2 or qi.ndim != 2 or ci.shape[0] != qi.shape[0] or ci.dtype.kind not in "iu" or qi.dtype.kind not in "iu":
             raise MlhotError(f"BatchIngest.stage_ids: integer ids [T, Nc] and [T, Nq], got {ci.shape} {ci.dtype} / {qi.shape} {qi.dtype}")
         ids = np.concatenate([ci.reshape(-1), qi.reshape(-1)]).astype(np.int64)
+        kind = check_grey_batch(ids.size, bg, augment) if pool.grey else None
         if bg is None:
             bgs = np.full(ids.shape, -1, dtype=np.int64)
         else:
@@ -263,23 +301,26 @@ class BatchIngest:
             bgs = np.concatenate([np.asarray(b).reshape(-1) for b in parts]).astype(np.int64)
         check_pool_indices(ids, bgs, pool.n_pool, pool.n_bank)
         lab = [_host(ys, torch.float32), _host(yq, torch.float32)]
-        if augment is not None:
+        if augment is not None and not pool.grey:
             from .augment import ImageAugTable
             if not isinstance(augment, ImageAugTable) or (augment.pre_op, augment.div2) != (0, 1.0):
                 raise MlhotError("BatchIngest.stage_ids: augment must be an ImageAugTable of the shapenet_3d sequence (pre_op 0, one division)")
             if augment.n_img != ids.size:
                 raise MlhotError(f"BatchIngest.stage_ids: the augmentation table holds {augment.n_img} records for {ids.size} images")
         T, H, W = ci.shape[0], pool.H, pool.W
-        slot = self._free_slot((tuple(ci.shape), tuple(qi.shape), tuple(lab[0].shape), tuple(lab[1].shape), "pool" if augment is None else "poolaug"),
-                               make=_IdSlot)
+        if kind is None:
+            kind = "pool" if augment is None else "poolaug"
+        slot = self._free_slot((tuple(ci.shape), tuple(qi.shape), tuple(lab[0].shape), tuple(lab[1].shape), kind), make=_IdSlot)
         np.copyto(slot.ids_np, ids, casting="unsafe")
-        np.copyto(slot.bg_np, bgs, casting="unsafe")
+        if slot.bg_np is not None:
+            np.copyto(slot.bg_np, bgs, casting="unsafe")
         for h, t in zip(slot.lab_np, lab):
             np.copyto(h, t.numpy())
         if augment is not None:
             self._put_augment(slot, augment)
         # delivered in the tensors a byte batch of the same shape is delivered in
-        return self._ship(((T, ci.shape[1], H, W, 3), (T, qi.shape[1], H, W, 3), tuple(lab[0].shape), tuple(lab[1].shape)), slot)
+        Cc = 1 if pool.grey else 3
+        return self._ship(((T, ci.shape[1], H, W, Cc), (T, qi.shape[1], H, W, Cc), tuple(lab[0].shape), tuple(lab[1].shape)), slot)
 
     @staticmethod
     def _slot_key(key, augment):
@@ -382,6 +423,19 @@ class BatchIngest:
 
     def _pool_into(self, L, slot, out):
         pool = self.pool
+        if pool.grey:
+            dst = out.img.view(slot.n_img, 1, pool.H, pool.W)
+            luts = slot.dev_lut[:slot.n_luts] if slot.augmented and slot.n_luts else None
+            if not slot.augmented:
+                L.pool1_ingest_u8(pool.pool, slot.dev_ids, out=dst, div=self.div)
+            elif slot.image_table is None:      # an AugTable: the 1D sequences, the byte route's division
+                L.pool1_augment_ingest_u8(pool.pool, slot.dev_ids, slot.dev_rec, luts, out=dst, div=self.div)
+            else:
+                from .augment import colour_tables
+                pre_op, div, div2 = slot.image_table
+                L.pool1_augment_ingest_u8_img(pool.pool, slot.dev_ids, slot.dev_rec, luts, colour_tables(self.device), out=dst,
+                                              pre_op=pre_op, div=div, div2=div2)
+            return
         dst = out.img.view(slot.n_img, 3, pool.H, pool.W)
         if not slot.augmented:
             L.pool_ingest_u8(pool.pool, slot.dev_ids, pool.bank, slot.dev_bg, out=dst, div=self.div)

@@ -321,3 +321,56 @@ class SyntheticViewsRGBAHost:
     def get_batch(self, source, tasks_per_batch, shot):
         ci, qi, ys, yq = self._rgba.get_batch_ids(source, tasks_per_batch, shot)
         return host_convert(self.compose(ci, source)), host_convert(self.compose(qi, source)), ys, yq
+
+
+class SyntheticGreyPool:
+    """A single-channel loader (task "shapenet_1d", "pascal_1d" or "distractor") over a fixed pool of structured images uint8
+    [N, H, W, 1] that speaks BOTH routes of the trainer: the resident grey pool's protocol (`grey_pool`, `get_batch_ids`:
+    mlhot.ingest.ResidentPool, config.resident_pool) and the byte route (`get_batch_u8`).  The two are twins: from the same generator
+    state `get_batch_u8` returns grey_pool()[ids] for the ids - and the labels - `get_batch_ids` returns.  Draws as the 1D loaders: a
+    training batch has a random context size in [3, shot], every image of a task is drawn from the whole pool; the labels belong to the
+    images (shapenet_1d: [cos a, sin a, a]; pascal_1d: one value in [0, 1); distractor: two).  For "distractor" the pool is handed over
+    already inverted - 255 - images, the bytes dataset/shapenet_distractor.py:233 ships - and `get_batch_u8` ships the same bytes.
+    It does not augment (`data_aug = False`): pair it with config.device_augment (1D) or config.device_augment_images (distractor)."""
+
+    data_aug = False
+
+    def __init__(self, task="shapenet_1d", seed=42, pool=96, H=128, W=128):
+        import numpy as np
+        if task not in ("shapenet_1d", "pascal_1d", "distractor"):
+            raise ValueError(task)
+        self.task, self.test_counter = task, 0
+        images = shape_images(pool, H, W, seed=seed)[..., None]
+        self.pool = np.ascontiguousarray(255 - images if task == "distractor" else images)      # [N, H, W, 1]: what crosses PCIe today
+        g = torch.Generator().manual_seed(seed)
+        if task == "shapenet_1d":
+            a = torch.rand(pool, 1, generator=g) * 2 * math.pi
+            self.labels = torch.cat([torch.cos(a), torch.sin(a), a], dim=-1)
+        else:
+            self.labels = torch.rand(pool, 1 if task == "pascal_1d" else 2, generator=g)
+        self.rng = np.random.RandomState(seed)
+        self.val_rng, self.test_rng = np.random.RandomState(seed + 1), np.random.RandomState(seed + 2)
+
+    def gen_bg(self, config, data="all"):
+        pass
+
+    def grey_pool(self, source="train"):
+        return self.pool
+
+    def get_batch_ids(self, source, tasks_per_batch, shot):
+        """(ctx ids int32 [T, Nc], target ids int32 [T, shot], ctx labels, target labels): ids index grey_pool()'s images."""
+        import numpy as np
+        rng = {"train": self.rng, "validation": self.val_rng, "test": self.test_rng}[source]
+        n_ctx = int(rng.randint(3, shot + 1)) if source == "train" else shot
+        ids = rng.randint(0, self.pool.shape[0], (tasks_per_batch, n_ctx + shot)).astype(np.int32)
+        ci, qi = np.ascontiguousarray(ids[:, :n_ctx]), np.ascontiguousarray(ids[:, n_ctx:])
+        return ci, qi, self.labels[torch.from_numpy(ci).long()].contiguous(), self.labels[torch.from_numpy(qi).long()].contiguous()
+
+    def get_batch_u8(self, source, tasks_per_batch, shot):
+        import numpy as np
+        ci, qi, ys, yq = self.get_batch_ids(source, tasks_per_batch, shot)
+        return np.ascontiguousarray(self.pool[ci]), np.ascontiguousarray(self.pool[qi]), ys, yq
+
+    def get_batch(self, source, tasks_per_batch, shot):
+        xs, xq, ys, yq = self.get_batch_u8(source, tasks_per_batch, shot)
+        return host_convert(xs), host_convert(xq), ys, yq

@@ -151,7 +151,12 @@ class _Feed:
                 raise ValueError("config.resident_pool keeps the image pool on the device: it needs a ROCm device")
             from mlhot.augment import BackgroundSampler
             from mlhot.ingest import BatchIngest, ResidentPool
-            pool = ResidentPool(*data.rgba_pool("train"), device=config.device)       # ONE upload; batches are ids from here on
+            # ONE upload; batches are ids from here on.  shapenet_3d: the RGBA pool + bank; the single-channel tasks: the grey pool
+            from mlhot.augment import GREY_POOL_TASKS
+            if getattr(config, "task", None) in GREY_POOL_TASKS:
+                pool = ResidentPool(data.grey_pool("train"), device=config.device)
+            else:
+                pool = ResidentPool(*data.rgba_pool("train"), device=config.device)
             self.ingest = BatchIngest(config.device, pool=pool)
             self.backgrounds = BackgroundSampler(pool.n_bank, seed=int(getattr(config, "seed", 0) or 0),
                                                  bg_gen_freq=getattr(config, "bg_gen_freq", 1), gen_bg=getattr(config, "gen_bg", True))
@@ -190,6 +195,8 @@ class _Feed:
         if self.augment is not None:
             pool = self.ingest.pool
             table = self.augment.batch(ci.size, qi.size, pool.H, pool.W)
+        if self.ingest.pool.grey:               # no bank, no epochs: ids, labels and the table drawn from the byte route's sampler
+            return self.ingest.stage_ids(ci, qi, ys, yq, augment=table)
         return self.ingest.stage_ids(ci, qi, ys, yq, bg=(self.backgrounds.batch(ci, epoch), self.backgrounds.batch(qi, epoch)), augment=table)
 
     def _stage(self, source):
@@ -374,7 +381,14 @@ class ModelTrainer(BaseTrainer):
             self._log("mlhot: host batches are copied on a copy stream behind the step" +
                       (" - as bytes when every image element is exactly k / 255 (checked per batch), as fp32 otherwise" if self._host_prefetch.u8 is not None else "")
                       + f"; up to {_depth(self.config)} batches are drawn ahead where no validation round / background regeneration lies between")
-        if self._resident:
+        if self._resident and self.ingest.pool.grey:
+            pool, n = self.ingest.pool, 2 * int(self.config.tasks_per_batch) * int(self.config.max_ctx_num)
+            record = 0 if self._augment is None else (160 if hasattr(self._augment.spec, "pre_op") else 128)      # ImageAugTable / AugTable
+            self._log(f"mlhot: config.resident_pool - {pool.n_pool} single-channel images of {pool.H} x {pool.W} ({pool.n_pool * pool.H * pool.W / 2 ** 20:.1f} "
+                      f"MiB) are held on the device; a training batch of up to {n} images crosses PCIe as its ids, labels and augmentation records - "
+                      f"{n * (4 + record)} bytes + labels" + (" + 256 per gamma table in use" if record == 128 else "")
+                      + f" - instead of {n * pool.H * pool.W} image bytes")
+        elif self._resident:
             pool = self.ingest.pool
             self._log(f"mlhot: config.resident_pool - {pool.n_pool} RGBA images and {pool.n_bank} backgrounds are held on the device; training batches cross "
                       "PCIe as image ids and the epoch's backgrounds are composed there (data.gen_bg is not called; the choice is a hash of seed, epoch, id)")
