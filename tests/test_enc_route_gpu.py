@@ -14,33 +14,8 @@ from tests import util as U
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
-DEFAULTS = {"conv2_tc": 1, "conv2_split": 0, "conv3_bwd_merged": 1, "materialize_a1": 0, "tail_spec": 7935}
-
-
-def _enc_params(dim_w, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    shapes = [("0.weight", (32, 1, 3, 3), 0.3), ("0.bias", (32,), 0.1), ("2.weight", (48, 32, 3, 3), 0.06), ("2.bias", (48,), 0.1),
-              ("5.weight", (64, 48, 3, 3), 0.05), ("5.bias", (64,), 0.1), ("8.weight", (dim_w, 4096), 0.02), ("8.bias", (dim_w,), 0.1)]
-    return {"encoder_w0." + k: torch.randn(*s, generator=g) * a for k, s, a in shapes}
-
-
-def _with_options(gpulib, opts, fn):
-    try:
-        for k, v in opts.items():
-            gpulib.set_option(k, v)
-        return fn()
-    finally:
-        for k, v in DEFAULTS.items():
-            gpulib.set_option(k, v)
-
-
-def _labels(gpulib, fn):
-    gpulib.prof_begin(256)
-    try:
-        out = fn()
-    finally:
-        labels = [label for label, _ in gpulib.prof_end()]
-    return labels, out
+DEFAULTS = U.ENC_OPTION_DEFAULTS
+_enc_params, _with_options, _labels = U.enc_params, U.with_options, U.launch_labels     # shared with tests/enc_cases.py
 
 
 def encoder_labels(gpulib, n, dim_w, opts):
@@ -98,10 +73,7 @@ ENC_CASES = {
 MODEL_CASES = {"default": {}, "tail_spec_0": {"tail_spec": 0}}
 
 # Recorded on the parent commit by encoder_labels / model_labels above (see the module's docstring).
-FWD_WS = ["enc.conv12", "enc.conv3", "enc.linear", "slab_reduce"]
-BWD_WS_TAIL = ["enc.bwd.conv12.wgrad", "enc.bwd.conv12.dgrad", "slab_reduce", "slab_reduce"]      # conv1's gradients (tensors of their own), the deferred folds
-BWD_WS = ["enc.bwd.linear", "enc.bwd.conv3.wgrad", "enc.bwd.conv3.dgrad"] + BWD_WS_TAIL
-BWD_WS_MERGED = ["enc.bwd.linear", "enc.bwd.conv3"] + BWD_WS_TAIL
+FWD_WS, BWD_WS_TAIL, BWD_WS, BWD_WS_MERGED = U.ENC_FWD_WS, U.ENC_BWD_WS_TAIL, U.ENC_BWD_WS, U.ENC_BWD_WS_MERGED
 ENC_EXPECTED = {
     "n3": (FWD_WS, BWD_WS),
     "n33": (FWD_WS, BWD_WS),

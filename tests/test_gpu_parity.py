@@ -417,7 +417,7 @@ def _vanilla_flips(routes, pres, tie=None):
     return flips
 
 
-FLIP_RATE = 1e-6        # bound on the share of routing decisions that may sit on a tie and fall the other way
+FLIP_RATE = U.FLIP_RATE
 
 
 def _count_decisions(obj):

@@ -294,3 +294,44 @@ def self_routes_vanilla(x, p, prefix="encoder_w0."):
     n, c, h, w = a2.shape
     win = a2.reshape(n, c, h // 2, 2, w // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(n, c, h // 2, w // 2, 4)
     return (taps["a1"] > 0).float(), win.argmax(dim=4).to(torch.uint8), (taps["p2"] > 0).float(), (taps["a3"] > 0).float()
+
+
+# ---- vanilla encoder: parameters, options, launch labels (tests/enc_cases.py, tests/test_enc_route_gpu.py, tests/test_gpu_parity.py) ----
+FLIP_RATE = 1e-6        # bound on the share of routing decisions that may sit on a tie and fall the other way
+
+ENC_OPTION_DEFAULTS = {"conv2_tc": 1, "conv2_split": 0, "conv3_bwd_merged": 1, "materialize_a1": 0, "tail_spec": 7935}
+
+
+def enc_params(dim_w, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    shapes = [("0.weight", (32, 1, 3, 3), 0.3), ("0.bias", (32,), 0.1), ("2.weight", (48, 32, 3, 3), 0.06), ("2.bias", (48,), 0.1),
+              ("5.weight", (64, 48, 3, 3), 0.05), ("5.bias", (64,), 0.1), ("8.weight", (dim_w, 4096), 0.02), ("8.bias", (dim_w,), 0.1)]
+    return {"encoder_w0." + k: torch.randn(*s, generator=g) * a for k, s, a in shapes}
+
+
+def with_options(gpulib, opts, fn):
+    """fn() under the options `opts`; every option of ENC_OPTION_DEFAULTS is back at its default afterwards."""
+    try:
+        for k, v in opts.items():
+            gpulib.set_option(k, v)
+        return fn()
+    finally:
+        for k, v in ENC_OPTION_DEFAULTS.items():
+            gpulib.set_option(k, v)
+
+
+def launch_labels(gpulib, fn):
+    """-> (the labels of the launches fn() made, counted through mlhot_prof_begin / _end, fn's result)"""
+    gpulib.prof_begin(256)
+    try:
+        out = fn()
+    finally:
+        labels = [label for label, _ in gpulib.prof_end()]
+    return labels, out
+
+
+# the weight-stationary encoder's launches, recorded by tests/test_enc_route_gpu.py (see its docstring)
+ENC_FWD_WS = ["enc.conv12", "enc.conv3", "enc.linear", "slab_reduce"]
+ENC_BWD_WS_TAIL = ["enc.bwd.conv12.wgrad", "enc.bwd.conv12.dgrad", "slab_reduce", "slab_reduce"]      # conv1's gradients (tensors of their own), the deferred folds
+ENC_BWD_WS = ["enc.bwd.linear", "enc.bwd.conv3.wgrad", "enc.bwd.conv3.dgrad"] + ENC_BWD_WS_TAIL
+ENC_BWD_WS_MERGED = ["enc.bwd.linear", "enc.bwd.conv3"] + ENC_BWD_WS_TAIL

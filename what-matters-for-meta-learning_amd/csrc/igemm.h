@@ -263,20 +263,28 @@ inline size_t igemm_slab_bytes(int M, int N, int nsplit) { return nsplit > 1 ? (
 template <class P, int BM, int BN, int BK, int WM, int WN>
 int run_igemm(const P& p, int nsplit, float* slab, hipStream_t stream, const char* what) {
   if (p.M <= 0 || p.N <= 0) return MLHOT_OK;
-#ifdef MLHOT_HOSTSIM
-  (void)nsplit; (void)slab; (void)stream; (void)what;
-  for (int m = 0; m < p.M; ++m)
-    for (int n = 0; n < p.N; ++n) {
-      float s = 0.f;
-      for (int k = 0; k < p.K; ++k) s = fmaf(p.A(m, k), p.B(k, n), s);
-      p.store(m, n, s);
-    }
-  return MLHOT_OK;
-#else
+  // split-K: the requested number of chunks, each a whole number of k tiles; the launch (and the host loop) runs the chunks this leaves
   if (nsplit < 1) nsplit = 1;
   int k_chunk = (p.K + nsplit - 1) / nsplit;
   k_chunk = (k_chunk + BK - 1) / BK * BK;
   if (k_chunk < BK) k_chunk = BK;
+#ifdef MLHOT_HOSTSIM
+  // as the device sums: one fma chain per k chunk, the chunks' partial results added in order (one chain over a whole split-K
+  // reduction drifts with its length)
+  (void)slab; (void)stream; (void)what;
+  for (int m = 0; m < p.M; ++m)
+    for (int n = 0; n < p.N; ++n) {
+      float t = 0.f;
+      for (int k0 = 0; k0 < p.K; k0 += k_chunk) {
+        const int k1 = k0 + k_chunk < p.K ? k0 + k_chunk : p.K;
+        float s = 0.f;
+        for (int k = k0; k < k1; ++k) s = fmaf(p.A(m, k), p.B(k, n), s);
+        t = k0 == 0 ? s : t + s;
+      }
+      p.store(m, n, t);
+    }
+  return MLHOT_OK;
+#else
   nsplit = (p.K + k_chunk - 1) / k_chunk;
   if (nsplit < 1) nsplit = 1;
   dim3 grid((p.M + BM - 1) / BM, (p.N + BN - 1) / BN, nsplit);
