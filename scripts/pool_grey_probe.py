@@ -86,7 +86,7 @@ def trainer_run(resident, iters, warm):
                 t0 = time.perf_counter()
                 ticket = tr._feed._stage("train")
                 stage.append(time.perf_counter() - t0)
-                nbytes.append(ticket.host.numel() if ticket.n_bytes is None else ticket.n_bytes)
+                nbytes.append(ticket.n_bytes)
                 tr._feed.ingest.take(ticket)
             torch.cuda.synchronize()
         finally:

@@ -83,6 +83,46 @@ def test_batch_ingest_ships_the_table_with_the_batch(gpulib):
         assert not torch.equal(plain[0], cx) and not torch.equal(plain[1], qx)
 
 
+def split_geometry_case(sampler, C, direct, as_table=None):
+    """Context images [2, 3, 8, 8, C] and targets [2, 2, 12, 8, C] through BatchIngest.stage() + take(): one launch per side.  The table
+    is drawn as Sampler.batch draws it - one side() call per side, the targets' LUT rows behind the context's - and each side must equal,
+    bit for bit, `direct(side's bytes, its rows of the records, the WHOLE LUT table)` - the library entry called directly."""
+    from mlhot.ingest import BatchIngest
+    rng = np.random.default_rng(5)
+    ing = BatchIngest(DEV)
+    for _ in range(2):                                    # the second batch reuses the first one's slot
+        xs, xq = rng.integers(0, 256, (2, 3, 8, 8, C), dtype=np.uint8), rng.integers(0, 256, (2, 2, 12, 8, C), dtype=np.uint8)
+        ys, yq = torch.from_numpy(rng.random((2, 3, 3), dtype=np.float32)), torch.from_numpy(rng.random((2, 2, 3), dtype=np.float32))
+        t = luts = None
+        rows = [None, None]
+        if sampler is not None:
+            rc, lc = sampler.side(6, 8, 8, 0)
+            rq, lq = sampler.side(4, 12, 8, 1, lut_base=lc.shape[0])
+            sampler.counter += 1
+            t = A.AugTable(np.concatenate([rc, rq]), np.concatenate([lc, lq]))
+            t = t if as_table is None else as_table(t)
+            rows = [torch.from_numpy(t.records[:6]).to(DEV), torch.from_numpy(t.records[6:]).to(DEV)]
+            luts = torch.from_numpy(t.luts).to(DEV) if len(t.luts) else None
+        cx, qx, cy, qy = ing.take(ing.stage(xs, xq, ys, yq, augment=t))
+        assert cx.shape == (2, 3, C, 8, 8) and qx.shape == (2, 2, C, 12, 8)
+        for got, x, rec in ((cx, xs, rows[0]), (qx, xq, rows[1])):
+            want = direct(torch.from_numpy(x).to(DEV), rec, luts, t)
+            assert want.shape == got.shape and torch.equal(got.view(torch.int32), want.view(torch.int32))
+        assert torch.equal(cy.cpu(), ys) and torch.equal(qy.cpu(), yq)
+    return t
+
+
+@pytest.mark.gpu
+def test_batch_ingest_split_geometry_plain(gpulib):
+    split_geometry_case(None, 1, lambda src, rec, luts, t: gpulib.ingest_u8_nhwc(src))
+
+
+@pytest.mark.gpu
+def test_batch_ingest_split_geometry_with_a_table(gpulib):
+    t = split_geometry_case(A.Sampler("pascal_1d", seed=6), 1, lambda src, rec, luts, t: gpulib.augment_ingest_u8(src, rec, luts))
+    assert (t.records[:6, A.F_LUT] >= 0).any() and (t.records[6:, A.F_LUT] >= 0).any()        # both sides index the one LUT table
+
+
 # ---- trainer ---------------------------------------------------------------------------------------------------------------------
 def _train(tmp_path, tag, data, **over):
     from networks.ANPShapeNet1D import ANPShapeNet1D

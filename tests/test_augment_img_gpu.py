@@ -81,6 +81,16 @@ def test_batch_ingest_ships_the_image_table_with_the_batch(gpulib, task):
         assert not torch.equal(ing.take(ing.stage(xs, xq, ys, yq))[0], cx)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("task,C", [("shapenet_3d", 3), ("distractor", 1)])
+def test_batch_ingest_split_geometry_with_an_image_table(gpulib, task, C):
+    from tests.test_augment_gpu import split_geometry_case
+    sampler = A.ImageSampler(task, seed=6)
+    split_geometry_case(sampler, C, lambda src, rec, luts, t: gpulib.augment_ingest_u8_img(src, rec, luts, A.colour_tables(DEV), pre_op=t.pre_op,
+                                                                                           div=t.div, div2=t.div2),
+                        as_table=lambda t: A.ImageAugTable(t.records, t.luts, sampler.spec))
+
+
 # ---- trainer ---------------------------------------------------------------------------------------------------------------------
 _UNSET = object()
 

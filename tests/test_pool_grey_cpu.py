@@ -150,7 +150,7 @@ def test_grey_pool_and_batch_refusals():
     with pytest.raises(MlhotError, match="no background bank"):
         ResidentPool(pool, np.zeros((2, 8, 8, 3), dtype=np.uint8), device="cpu")   # a bank with a grey pool (refused before the device is)
     t1, _, ti = tables(8, 8)
-    assert check_grey_batch(5, None, None) == "pool1" and check_grey_batch(5, None, t1) == "pool1aug" and check_grey_batch(5, None, ti) == "pool1augimg"
+    assert check_grey_batch(5, None, None).name == "pool1" and check_grey_batch(5, None, t1).name == "pool1aug" and check_grey_batch(5, None, ti).name == "pool1augimg"
     with pytest.raises(MlhotError, match="bg must be None"):
         check_grey_batch(5, np.full(5, -1), None)                                  # bg given
     with pytest.raises(MlhotError, match="AugTable"):

@@ -1102,20 +1102,30 @@ class MlhotLib:
         self._rc(self.c.mlhot_ingest_u8_nhwc(_ptr(src), _ptr(out), n_img, H, W, Cc, float(div), _stream(src)), "mlhot_ingest_u8_nhwc")
         return out
 
+    @staticmethod
+    def _table_args(wrapper, device, n_img, records, ints, luts, colour_tabs=None, pre_op=0):
+        """The table of an augmenting ingest of n_img images on `device`: records int32 [n_img, ints], luts uint8 [n, 256] or None, and
+        for the image entries colour_tabs uint8 [COLOUR_TABS_BYTES] or None and pre_op; -> n_luts."""
+        if records.dtype != torch.int32 or records.numel() != n_img * ints or records.device != device:
+            raise MlhotError(f"{wrapper}: records must be int32 [{n_img}, {ints}] on {device}")
+        if luts is not None and (luts.dtype != torch.uint8 or luts.dim() != 2 or luts.shape[1] != 256 or luts.device != device):
+            raise MlhotError(f"{wrapper}: luts must be uint8 [n, 256] on {device}")
+        if colour_tabs is not None and (colour_tabs.dtype != torch.uint8 or colour_tabs.numel() != COLOUR_TABS_BYTES
+                                        or colour_tabs.device != device):
+            raise MlhotError(f"{wrapper}: colour_tabs must be uint8 [{COLOUR_TABS_BYTES}] on {device}")
+        if pre_op not in (0, 1):
+            raise MlhotError(f"{wrapper}: pre_op is 0 or 1, got {pre_op!r}")
+        _chk(records, luts, colour_tabs)
+        return 0 if luts is None else luts.shape[0]
+
     def augment_ingest_u8(self, src, records, luts=None, out=None, div=255.0):
         """ingest_u8_nhwc with the 1D loaders' data augmentation in front (csrc/augment.h, include/mlhot.h mlhot_aug_record):
         src uint8 [..., H, W, 1] -> fp32 [..., 1, H, W].  records: int32 [n_img, 32] (mlhot.augment.Sampler), luts: uint8
         [n_luts, 256] or None; both on src's device."""
         n_img, H, W, Cc = _nhwc("augment_ingest_u8", src)
         fn = self._fn("augment_ingest_u8", "mlhot_augment_ingest_u8")
-        if records.dtype != torch.int32 or records.numel() != n_img * (AUG_RECORD_BYTES // 4) or records.device != src.device:
-            raise MlhotError(f"augment_ingest_u8: records must be int32 [{n_img}, {AUG_RECORD_BYTES // 4}] on {src.device}")
-        n_luts = 0
-        if luts is not None:
-            if luts.dtype != torch.uint8 or luts.dim() != 2 or luts.shape[1] != 256 or luts.device != src.device:
-                raise MlhotError("augment_ingest_u8: luts must be uint8 [n, 256] on the images' device")
-            n_luts = luts.shape[0]
-        _chk(src, out, records, luts)
+        n_luts = self._table_args("augment_ingest_u8", src.device, n_img, records, AUG_RECORD_BYTES // 4, luts)
+        _chk(src, out)
         out = _ingest_out("augment_ingest_u8", src, out)
         self._rc(fn(_ptr(src), _ptr(out), n_img, H, W, Cc, float(div), _ptr(records), _ptr(luts) if n_luts else None, n_luts, _stream(src)),
                  "mlhot_augment_ingest_u8")
@@ -1128,32 +1138,23 @@ class MlhotLib:
         (mlhot.augment.colour_tables(device)) or None; all on src's device."""
         n_img, H, W, Cc = _nhwc("augment_ingest_u8_img", src)
         fn = self._fn("augment_ingest_u8_img", "mlhot_augment_ingest_u8_img")
-        ints = AUG_IMG_RECORD_BYTES // 4
-        if records.dtype != torch.int32 or records.numel() != n_img * ints or records.device != src.device:
-            raise MlhotError(f"augment_ingest_u8_img: records must be int32 [{n_img}, {ints}] on {src.device}")
-        n_luts = 0
-        if luts is not None:
-            if luts.dtype != torch.uint8 or luts.dim() != 2 or luts.shape[1] != 256 or luts.device != src.device:
-                raise MlhotError("augment_ingest_u8_img: luts must be uint8 [n, 256] on the images' device")
-            n_luts = luts.shape[0]
-        if colour_tabs is not None and (colour_tabs.dtype != torch.uint8 or colour_tabs.numel() != COLOUR_TABS_BYTES
-                                        or colour_tabs.device != src.device):
-            raise MlhotError(f"augment_ingest_u8_img: colour_tabs must be uint8 [{COLOUR_TABS_BYTES}] on the images' device")
-        if pre_op not in (0, 1):
-            raise MlhotError(f"augment_ingest_u8_img: pre_op is 0 or 1, got {pre_op!r}")
-        _chk(src, out, records, luts, colour_tabs)
+        n_luts = self._table_args("augment_ingest_u8_img", src.device, n_img, records, AUG_IMG_RECORD_BYTES // 4, luts, colour_tabs, pre_op)
+        _chk(src, out)
         out = _ingest_out("augment_ingest_u8_img", src, out)
         self._rc(fn(_ptr(src), _ptr(out), n_img, H, W, Cc, int(pre_op), float(div), float(div2), _ptr(records), _ptr(luts) if n_luts else None,
                     n_luts, _ptr(colour_tabs), _stream(src)), "mlhot_augment_ingest_u8_img")
         return out
 
-    # ---- resident image pool (csrc/pool_ingest.h) ----------------------------------------------------
+    # ---- resident image pools (csrc/pool_ingest.h): RGBA uint8 [N, H, W, 4] with a bank, or grey uint8 [N, H, W, 1] (pool1) --------
     @staticmethod
-    def _pool_args(wrapper, pool, ids, bank, bg, out):
-        """Shapes, dtypes and devices of a pool call; -> (n_pool, n_bank, n_img, H, W, bg, out).  Indices that live on the host (the
-        host build) are range-checked here; device indices are trusted - BatchIngest.stage_ids checks them before it ships them."""
-        if pool.dtype != torch.uint8 or pool.dim() != 4 or pool.shape[-1] != 4:
-            raise MlhotError(f"{wrapper}: the pool must be uint8 [N, H, W, 4] (RGBA, channel-last), got {pool.dtype} {tuple(pool.shape)}")
+    def _pool_args(wrapper, pool, channels, ids, out, bank=None, bg=None):
+        """Shapes, dtypes and devices of a call on a pool of `channels` (4: RGBA, delivered as 3; 1: grey, which has neither bank nor bg);
+        -> (n_pool, n_bank, n_img, H, W, bg, out).  Indices that live on the host (the host build) are range-checked here; device
+        indices are trusted - BatchIngest.stage_ids checks them before it ships them."""
+        rgba = channels == 4
+        if pool.dtype != torch.uint8 or pool.dim() != 4 or pool.shape[-1] != channels:
+            raise MlhotError(f"{wrapper}: the pool must be uint8 [N, H, W, {channels}] ({'RGBA, channel-last' if rgba else 'single-channel'}), "
+                             f"got {pool.dtype} {tuple(pool.shape)}")
         n_pool, H, W, _ = pool.shape
         if bank is not None and (bank.dtype != torch.uint8 or bank.dim() != 4 or tuple(bank.shape[1:]) != (H, W, 3) or bank.device != pool.device):
             raise MlhotError(f"{wrapper}: the bank must be uint8 [B, {H}, {W}, 3] on {pool.device}, got {bank.dtype} {tuple(bank.shape)}")
@@ -1161,14 +1162,14 @@ class MlhotLib:
         if ids.dtype != torch.int32 or ids.device != pool.device:
             raise MlhotError(f"{wrapper}: ids must be int32 on {pool.device}")
         n_img = ids.numel()
-        if bg is None:
+        if bg is None and rgba:
             bg = torch.full((n_img,), -1, dtype=torch.int32, device=pool.device)
-        if bg.dtype != torch.int32 or bg.numel() != n_img or bg.device != pool.device:
+        if bg is not None and (bg.dtype != torch.int32 or bg.numel() != n_img or bg.device != pool.device):
             raise MlhotError(f"{wrapper}: bg must be int32 [{n_img}] on {pool.device}")
         if not ids.is_cuda:
             from .ingest import check_pool_indices
-            check_pool_indices(ids.numpy(), bg.numpy(), n_pool, n_bank)
-        shape = (*ids.shape, 3, H, W)
+            check_pool_indices(ids.numpy(), (torch.full(tuple(ids.shape), -1) if bg is None else bg).numpy(), n_pool, n_bank)
+        shape = (*ids.shape, 3 if rgba else 1, H, W)
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=pool.device)
         elif out.dtype != torch.float32 or out.numel() != math.prod(shape) or out.device != pool.device:
@@ -1180,7 +1181,7 @@ class MlhotLib:
         """Images `ids` (int32 [...]) of the resident pool (uint8 [N, H, W, 4]) with bank[bg] (uint8 [B, H, W, 3]; bg int32, -1 = none)
         behind every pixel whose alpha is 255 -> fp32 [..., 3, H, W] = byte / div (include/mlhot.h mlhot_pool_ingest_u8)."""
         fn = self._fn("pool_ingest_u8", "mlhot_pool_ingest_u8")
-        n_pool, n_bank, n_img, H, W, bg, out = self._pool_args("pool_ingest_u8", pool, ids, bank, bg, out)
+        n_pool, n_bank, n_img, H, W, bg, out = self._pool_args("pool_ingest_u8", pool, 4, ids, out, bank, bg)
         self._rc(fn(_ptr(pool), n_pool, _ptr(ids), _ptr(bank) if n_bank else None, n_bank, _ptr(bg), _ptr(out), n_img, H, W, float(div),
                     _stream(pool)), "mlhot_pool_ingest_u8")
         return out
@@ -1189,71 +1190,26 @@ class MlhotLib:
         """pool_ingest_u8 with the shapenet_3d image augmentation behind the composition (augment_ingest_u8_img's records int32
         [n_img, 40], luts and colour tables; C = 3, pre_op = 0); H, W <= 64."""
         fn = self._fn("pool_augment_ingest_u8_img", "mlhot_pool_augment_ingest_u8_img")
-        n_pool, n_bank, n_img, H, W, bg, out = self._pool_args("pool_augment_ingest_u8_img", pool, ids, bank, bg, out)
-        ints = AUG_IMG_RECORD_BYTES // 4
-        if records.dtype != torch.int32 or records.numel() != n_img * ints or records.device != pool.device:
-            raise MlhotError(f"pool_augment_ingest_u8_img: records must be int32 [{n_img}, {ints}] on {pool.device}")
-        n_luts = 0
-        if luts is not None:
-            if luts.dtype != torch.uint8 or luts.dim() != 2 or luts.shape[1] != 256 or luts.device != pool.device:
-                raise MlhotError("pool_augment_ingest_u8_img: luts must be uint8 [n, 256] on the pool's device")
-            n_luts = luts.shape[0]
-        if colour_tabs is not None and (colour_tabs.dtype != torch.uint8 or colour_tabs.numel() != COLOUR_TABS_BYTES
-                                        or colour_tabs.device != pool.device):
-            raise MlhotError(f"pool_augment_ingest_u8_img: colour_tabs must be uint8 [{COLOUR_TABS_BYTES}] on the pool's device")
-        _chk(records, luts, colour_tabs)
+        n_pool, n_bank, n_img, H, W, bg, out = self._pool_args("pool_augment_ingest_u8_img", pool, 4, ids, out, bank, bg)
+        n_luts = self._table_args("pool_augment_ingest_u8_img", pool.device, n_img, records, AUG_IMG_RECORD_BYTES // 4, luts, colour_tabs)
         self._rc(fn(_ptr(pool), n_pool, _ptr(ids), _ptr(bank) if n_bank else None, n_bank, _ptr(bg), _ptr(out), n_img, H, W, float(div),
                     _ptr(records), _ptr(luts) if n_luts else None, n_luts, _ptr(colour_tabs), _stream(pool)),
                  "mlhot_pool_augment_ingest_u8_img")
         return out
 
-    # ---- resident grey pool: uint8 [N, H, W, 1] (csrc/pool_ingest.h pool1, augment.h / augment_img.h source functors) ------------
-    @staticmethod
-    def _pool1_args(wrapper, pool, ids, out):
-        """Shapes, dtypes and devices of a grey-pool call; -> (n_pool, n_img, H, W, out).  Host ids (the host build) are range-checked
-        here; device ids are trusted - BatchIngest.stage_ids checks them before it ships them."""
-        if pool.dtype != torch.uint8 or pool.dim() != 4 or pool.shape[-1] != 1:
-            raise MlhotError(f"{wrapper}: the pool must be uint8 [N, H, W, 1] (single-channel), got {pool.dtype} {tuple(pool.shape)}")
-        n_pool, H, W, _ = pool.shape
-        if ids.dtype != torch.int32 or ids.device != pool.device:
-            raise MlhotError(f"{wrapper}: ids must be int32 on {pool.device}")
-        n_img = ids.numel()
-        if not ids.is_cuda:
-            from .ingest import check_pool_indices
-            check_pool_indices(ids.numpy(), torch.full(tuple(ids.shape), -1).numpy(), n_pool, 0)
-        shape = (*ids.shape, 1, H, W)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=pool.device)
-        elif out.dtype != torch.float32 or out.numel() != math.prod(shape) or out.device != pool.device:
-            raise MlhotError(f"{wrapper}: out must be fp32 {shape} on {pool.device}")
-        _chk(pool, ids, out)
-        return n_pool, n_img, H, W, out
-
-    @staticmethod
-    def _pool1_table(wrapper, pool, n_img, records, ints, luts):
-        if records.dtype != torch.int32 or records.numel() != n_img * ints or records.device != pool.device:
-            raise MlhotError(f"{wrapper}: records must be int32 [{n_img}, {ints}] on {pool.device}")
-        n_luts = 0
-        if luts is not None:
-            if luts.dtype != torch.uint8 or luts.dim() != 2 or luts.shape[1] != 256 or luts.device != pool.device:
-                raise MlhotError(f"{wrapper}: luts must be uint8 [n, 256] on the pool's device")
-            n_luts = luts.shape[0]
-        _chk(records, luts)
-        return n_luts
-
     def pool1_ingest_u8(self, pool, ids, out=None, div=255.0):
         """Images `ids` (int32 [...]) of the resident grey pool (uint8 [N, H, W, 1]) -> fp32 [..., 1, H, W] = byte / div: the bits of
         ingest_u8_nhwc(pool[ids]) (include/mlhot.h mlhot_pool1_ingest_u8)."""
         fn = self._fn("pool1_ingest_u8", "mlhot_pool1_ingest_u8")
-        n_pool, n_img, H, W, out = self._pool1_args("pool1_ingest_u8", pool, ids, out)
+        n_pool, _, n_img, H, W, _, out = self._pool_args("pool1_ingest_u8", pool, 1, ids, out)
         self._rc(fn(_ptr(pool), n_pool, _ptr(ids), _ptr(out), n_img, H, W, float(div), _stream(pool)), "mlhot_pool1_ingest_u8")
         return out
 
     def pool1_augment_ingest_u8(self, pool, ids, records, luts=None, out=None, div=255.0):
         """augment_ingest_u8 (the 1D sequences; records int32 [n_img, 32]) on images `ids` of the grey pool; H, W <= 128."""
         fn = self._fn("pool1_augment_ingest_u8", "mlhot_pool1_augment_ingest_u8")
-        n_pool, n_img, H, W, out = self._pool1_args("pool1_augment_ingest_u8", pool, ids, out)
-        n_luts = self._pool1_table("pool1_augment_ingest_u8", pool, n_img, records, AUG_RECORD_BYTES // 4, luts)
+        n_pool, _, n_img, H, W, _, out = self._pool_args("pool1_augment_ingest_u8", pool, 1, ids, out)
+        n_luts = self._table_args("pool1_augment_ingest_u8", pool.device, n_img, records, AUG_RECORD_BYTES // 4, luts)
         self._rc(fn(_ptr(pool), n_pool, _ptr(ids), _ptr(out), n_img, H, W, float(div), _ptr(records), _ptr(luts) if n_luts else None, n_luts,
                     _stream(pool)), "mlhot_pool1_augment_ingest_u8")
         return out
@@ -1262,14 +1218,8 @@ class MlhotLib:
         """augment_ingest_u8_img with C = 1 (Distractor's sequence; records int32 [n_img, 40], pre_op, div, div2 as there) on images
         `ids` of the grey pool; H, W <= 128."""
         fn = self._fn("pool1_augment_ingest_u8_img", "mlhot_pool1_augment_ingest_u8_img")
-        n_pool, n_img, H, W, out = self._pool1_args("pool1_augment_ingest_u8_img", pool, ids, out)
-        n_luts = self._pool1_table("pool1_augment_ingest_u8_img", pool, n_img, records, AUG_IMG_RECORD_BYTES // 4, luts)
-        if colour_tabs is not None and (colour_tabs.dtype != torch.uint8 or colour_tabs.numel() != COLOUR_TABS_BYTES
-                                        or colour_tabs.device != pool.device):
-            raise MlhotError(f"pool1_augment_ingest_u8_img: colour_tabs must be uint8 [{COLOUR_TABS_BYTES}] on the pool's device")
-        if pre_op not in (0, 1):
-            raise MlhotError(f"pool1_augment_ingest_u8_img: pre_op is 0 or 1, got {pre_op!r}")
-        _chk(colour_tabs)
+        n_pool, _, n_img, H, W, _, out = self._pool_args("pool1_augment_ingest_u8_img", pool, 1, ids, out)
+        n_luts = self._table_args("pool1_augment_ingest_u8_img", pool.device, n_img, records, AUG_IMG_RECORD_BYTES // 4, luts, colour_tabs, pre_op)
         self._rc(fn(_ptr(pool), n_pool, _ptr(ids), _ptr(out), n_img, H, W, int(pre_op), float(div), float(div2), _ptr(records),
                     _ptr(luts) if n_luts else None, n_luts, _ptr(colour_tabs), _stream(pool)), "mlhot_pool1_augment_ingest_u8_img")
         return out

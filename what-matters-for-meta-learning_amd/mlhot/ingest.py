@@ -14,27 +14,31 @@ and `mlhot_ingest_u8_nhwc` does the divide + permute on the device (bit-identica
 `take()` writes into the same device tensors for every batch of the same shape, so a captured hipGraph of the step keeps
 reading valid addresses.  There is no CPU fallback: the device must be a ROCm GPU.
 
-`stage(..., augment=table)` (mlhot.augment.Sampler.batch): the batch's augmentation records and gamma LUTs ride in the same pinned
-slot and the same H2D copy, and take() expands it with mlhot_augment_ingest_u8 (csrc/augment.h) instead of mlhot_ingest_u8_nhwc.
-An mlhot.augment.ImageAugTable (ImageSampler.batch: the image tasks, C = 3 or 1) travels the same way and is expanded with
-mlhot_augment_ingest_u8_img (csrc/augment_img.h) with the table's pre_op / div / div2.
+A batch takes one of the eight routes of `ROUTES`, decided once, when it is staged, from where its images come from
+and the table that rides with it:
 
-`BatchIngest(device, pool=ResidentPool(images_rgba, bank, device))` + `stage_ids(ctx_ids, qry_ids, ys, yq, bg=..., augment=...)`: the
-loader's RGBA pool and background bank live on the device, a batch is its image ids (+ one bank index per image), and take() gathers,
-composes and converts with mlhot_pool_ingest_u8 / mlhot_pool_augment_ingest_u8_img (csrc/pool_ingest.h).
+    source \\ augment=     None                an AugTable (1D sequences)     an ImageAugTable (image tasks)
+    BYTES  stage()         ingest_u8_nhwc      augment_ingest_u8 (C = 1)      augment_ingest_u8_img
+    RGBA   stage_ids()     pool_ingest_u8      -                              pool_augment_ingest_u8_img
+    GREY   stage_ids()     pool1_ingest_u8     pool1_augment_ingest_u8        pool1_augment_ingest_u8_img
 
-`ResidentPool(images_grey, device=...)` with a single-channel pool uint8 [N, H, W, 1] (shapenet_1d, pascal_1d, distractor: the bytes the
-loader's `get_batch_u8` would carry) serves the same `stage_ids` - no bank, no bg; `augment` an AugTable (the 1D sequences) or an
-ImageAugTable (Distractor's) - through mlhot_pool1_ingest_u8 / mlhot_pool1_augment_ingest_u8 / mlhot_pool1_augment_ingest_u8_img
-(DESIGN.md 6a-4): what take() delivers is, bit for bit, what stage() delivers for the byte batch pool[ids].
+BYTES: the images themselves are staged.  RGBA / GREY: `BatchIngest(device, pool=ResidentPool(...))` holds the loader's pool on the
+device (uint8 [N, H, W, 4] with its background bank, or uint8 [N, H, W, 1]) and a batch is its image ids, for the RGBA pool with one
+bank index per image (csrc/pool_ingest.h); what take() delivers is, bit for bit, what the BYTES route
+delivers for the byte batch pool[ids].  Whatever the route, the batch - payload, labels, and the table's records and gamma LUTs
+(mlhot.augment.Sampler.batch / ImageSampler.batch) - is ONE pinned slot (`slot_layout`) and one H2D copy, and take() expands it with
+the route's one library entry (`BatchIngest._expand`).
 """
 import collections
+import math
 import threading
+import typing
 
 import numpy as np
 import torch
 
 from . import lib
+from .augment import AugTable, ImageAugTable, colour_tables
 from .binding import AUG_IMG_RECORD_BYTES, AUG_RECORD_BYTES, MlhotError
 
 
@@ -45,57 +49,134 @@ def _host(a, dtype):
     return t
 
 
-def _layout(key):
-    """Byte layout of one packed staging buffer: [ctx images | qry images | pad to 16 | ctx labels | qry labels]."""
-    n_img = [int(np.prod(key[0])), int(np.prod(key[1]))]
-    n_lab = [int(np.prod(key[2])), int(np.prod(key[3]))]
-    lab_off = (n_img[0] + n_img[1] + 15) // 16 * 16
-    return n_img, n_lab, lab_off, lab_off + 4 * (n_lab[0] + n_lab[1])
+# ---- routes ----------------------------------------------------------------------------------------------------------------------------
+BYTES, RGBA, GREY = "packed bytes", "the RGBA pool", "a grey pool"       # where a batch's images come from
 
 
-def _aug_layout(key, total):
-    """Behind the labels of an augmented slot: [records int32 [n, 32] (image tasks: [n, 40]) | gamma LUTs uint8 [<= n, 256]], n = images
-    of both sides."""
-    n = _n_images(key)
-    rec_off = (total + 15) // 16 * 16
-    lut_off = rec_off + _record_bytes(key) * n
-    return n, rec_off, lut_off, lut_off + 256 * n
+class Route(typing.NamedTuple):
+    name: str           # the last element of the slot key
+    source: str         # BYTES | RGBA | GREY
+    table: type         # what rides with the batch: None, AugTable or ImageAugTable
+    record_ints: int    # int32s per record of that table: 0, 32 (mlhot_aug_record) or 40 (mlhot_aug_record_img)
+    ids: bool           # the payload: int32 image ids (stage_ids) instead of the images' bytes (stage)
+    bg: bool            # ... followed by one int32 bank index per id
+    channels: int       # channels delivered by an id route (a byte route delivers its images' own)
+    entry: str          # the MlhotLib method that expands the slot
 
 
-def _record_bytes(key):
-    return AUG_IMG_RECORD_BYTES if key[4] == "augimg" else AUG_RECORD_BYTES
+_INTS, _IMG_INTS = AUG_RECORD_BYTES // 4, AUG_IMG_RECORD_BYTES // 4
+ROUTES = {(r.source, r.table): r for r in (
+    Route("u8", BYTES, None, 0, False, False, 0, "ingest_u8_nhwc"),
+    Route("aug", BYTES, AugTable, _INTS, False, False, 0, "augment_ingest_u8"),
+    Route("augimg", BYTES, ImageAugTable, _IMG_INTS, False, False, 0, "augment_ingest_u8_img"),
+    Route("pool", RGBA, None, 0, True, True, 3, "pool_ingest_u8"),
+    Route("poolaug", RGBA, ImageAugTable, _IMG_INTS, True, True, 3, "pool_augment_ingest_u8_img"),
+    Route("pool1", GREY, None, 0, True, False, 1, "pool1_ingest_u8"),
+    Route("pool1aug", GREY, AugTable, _INTS, True, False, 1, "pool1_augment_ingest_u8"),
+    Route("pool1augimg", GREY, ImageAugTable, _IMG_INTS, True, False, 1, "pool1_augment_ingest_u8_img"),
+)}
+_TABLES_OF = {BYTES: "None, an AugTable (single-channel images) or an ImageAugTable",
+              RGBA: "None or an ImageAugTable of the shapenet_3d sequence (pre_op 0, one division)",
+              GREY: "None, an AugTable (shapenet_1d / pascal_1d) or an ImageAugTable (distractor)"}
 
 
-def _n_images(key):
-    return int(np.prod(key[0][:-3])) + int(np.prod(key[1][:-3]))
+def check_table(source, augment, n_img, bg=None, channels=(1, 1)):
+    """May `augment` ride on a batch of `n_img` images from `source`?  -> the batch's Route, or MlhotError - before a slot is taken.
+    `bg`: what the caller passed as bank indices (only the RGBA pool has a bank); `channels`: of the context and target images of a
+    BYTES batch."""
+    who = "BatchIngest.stage" if source == BYTES else "BatchIngest.stage_ids"
+    if bg is not None and source == GREY:
+        raise MlhotError(f"{who}: a grey pool has no background bank - bg must be None")
+    table = None if augment is None else next((t for t in (ImageAugTable, AugTable) if isinstance(augment, t)), type(augment))
+    route = ROUTES.get((source, table))
+    if route is None:
+        raise MlhotError(f"{who}: on {source} augment is {_TABLES_OF[source]}, got {type(augment).__name__}")
+    if table is None:
+        return route
+    if source == RGBA and (augment.pre_op, augment.div2) != (0, 1.0):      # its entry composes, augments and divides once
+        raise MlhotError(f"{who}: on {source} augment is {_TABLES_OF[source]}, got (pre_op, div2) = {(augment.pre_op, augment.div2)}")
+    if augment.records.ndim != 2 or augment.records.shape[1] != route.record_ints:
+        raise MlhotError(f"{who}: {table.__name__} records must be int32 [n, {route.record_ints}], got {augment.records.shape}")
+    if augment.n_img != n_img:
+        raise MlhotError(f"{who}: the augmentation table holds {augment.n_img} records for {n_img} images")
+    if source == BYTES and table is AugTable and tuple(channels) != (1, 1):
+        raise MlhotError(f"{who}: an AugTable (config.device_augment: the 1D sequences) needs single-channel images, got {channels[0]} / "
+                         f"{channels[1]} channels; the image tasks draw an ImageAugTable (config.device_augment_images)")
+    return route
+
+
+def check_grey_batch(n_img, bg, augment):
+    """What a batch of a GREY pool may carry (check_table): no bg, and as `augment` None, an AugTable (128-byte records) or an
+    ImageAugTable (Distractor's sequence with its pre_op / div / div2: 160-byte records) of one record per image.  -> its Route."""
+    return check_table(GREY, augment, n_img, bg=bg)
+
+
+# ---- one slot ----------------------------------------------------------------------------------------------------------------------------
+class Layout(typing.NamedTuple):
+    """Byte offsets of one staging buffer: [payload | pad to 16 | ctx labels | qry labels] and, behind a route with a table,
+    [pad to 16 | records int32 [n_img, ints] | gamma LUTs uint8 [<= n_img, 256]]."""
+    parts: tuple        # where the payload's parts end: (0, ctx images, qry images), or (0, ids int32[, bg int32])
+    lab_off: int
+    lab_mid: int        # ctx labels | qry labels
+    lab_end: int
+    rec_off: int
+    lut_off: int
+    total: int          # the buffer: at least 16 bytes
+    n_img: int          # images of both sides = records = LUT rows
+
+
+def _pad16(n):
+    return (n + 15) // 16 * 16
+
+
+def slot_layout(route, key):
+    """The Layout of `route`'s slot for key = (ctx, qry, ctx labels, qry labels) shapes; ctx / qry are the image shapes [T, N, H, W, C]
+    of a byte route and the id shapes [T, N] of an id route.  Integers only: no torch, no device."""
+    lead = [s if route.ids else s[:-3] for s in key[:2]]
+    n_img = math.prod(lead[0]) + math.prod(lead[1])
+    if route.ids:
+        parts = (0, 4 * n_img, 8 * n_img) if route.bg else (0, 4 * n_img)
+    else:
+        parts = (0, math.prod(key[0]), math.prod(key[0]) + math.prod(key[1]))
+    lab_off = _pad16(parts[-1])
+    lab_mid = lab_off + 4 * math.prod(key[2])
+    lab_end = lab_mid + 4 * math.prod(key[3])
+    rec_off = _pad16(lab_end)
+    lut_off = rec_off + 4 * route.record_ints * n_img
+    end = lut_off + 256 * n_img if route.record_ints else lab_end
+    return Layout(parts, lab_off, lab_mid, lab_end, rec_off, lut_off, max(end, 16), n_img)
 
 
 class _Slot:
-    """One staging slot: ONE pinned host buffer + its device twin holding a whole batch (images as bytes, labels as fp32, and for an
-    augmented batch - key + ("aug",), or ("augimg",) for an ImageAugTable - its records and LUTs), so a batch is one H2D copy."""
+    """One staging slot: ONE pinned host buffer + its device twin holding a whole batch of `route` (slot_layout), so a batch is one
+    H2D copy.  The ingest's ring key is key + (route.name,)."""
 
-    def __init__(self, key, device):
-        n_img, n_lab, lab_off, total = _layout(key)
-        lab_end = total
-        self.augmented = len(key) > 4
-        if self.augmented:
-            n_aug, rec_off, lut_off, total = _aug_layout(key, total)
-        self.host = torch.empty(max(total, 16), dtype=torch.uint8).pin_memory()
-        self.dev = torch.empty(max(total, 16), dtype=torch.uint8, device=device)
-        hn = self.host.numpy()
-        self.host_np = [hn[:n_img[0]].reshape(key[0]), hn[n_img[0]:n_img[0] + n_img[1]].reshape(key[1]),
-                        hn[lab_off:lab_off + 4 * n_lab[0]].view(np.float32).reshape(key[2]),
-                        hn[lab_off + 4 * n_lab[0]:lab_end].view(np.float32).reshape(key[3])]
-        self.dev_img = self.dev[:n_img[0] + n_img[1]]
-        self.dev_lab = self.dev[lab_off:lab_end].view(torch.float32)
-        self.n_bytes = None                    # bytes to copy: None = the whole buffer
-        if self.augmented:
-            self.aug_rec_np = hn[rec_off:lut_off].view(np.int32).reshape(n_aug, _record_bytes(key) // 4)
-            self.image_table = None            # an ImageAugTable's (pre_op, div, div2), set per batch
-            self.aug_lut_np = hn[lut_off:total].reshape(n_aug, 256)
-            self.dev_rec = self.dev[rec_off:lut_off].view(torch.int32)
-            self.dev_lut = self.dev[lut_off:total].view(n_aug, 256)
-            self.lut_off, self.n_luts = lut_off, 0
+    def __init__(self, route, key, device):
+        lay = slot_layout(route, key)
+        self.route, self.layout = route, lay
+        self.host = torch.empty(lay.total, dtype=torch.uint8).pin_memory()
+        self.dev = torch.empty(lay.total, dtype=torch.uint8, device=device)
+        hn, p = self.host.numpy(), lay.parts
+        # the four views a byte batch is written through (stage_filled's `fill`), or ids[, bg] and the labels
+        if route.ids:
+            self.host_np = [hn[a:b].view(np.int32) for a, b in zip(p, p[1:])]
+            self.dev_ids = self.dev[p[0]:p[1]].view(torch.int32)
+            self.dev_bg = self.dev[p[1]:p[2]].view(torch.int32) if route.bg else None
+        else:
+            self.host_np = [hn[p[0]:p[1]].reshape(key[0]), hn[p[1]:p[2]].reshape(key[1])]
+            self.dev_img = self.dev[:p[2]]
+        self.host_np += [hn[lay.lab_off:lay.lab_mid].view(np.float32).reshape(key[2]),
+                         hn[lay.lab_mid:lay.lab_end].view(np.float32).reshape(key[3])]
+        self.dev_lab = self.dev[lay.lab_off:lay.lab_end].view(torch.float32)
+        self.n_bytes = lay.lab_end             # bytes to copy: up to the end of the last section in use (_put_augment)
+        if route.record_ints:
+            self.rec_np = hn[lay.rec_off:lay.lut_off].view(np.int32).reshape(lay.n_img, route.record_ints)
+            lut_end = lay.lut_off + 256 * lay.n_img
+            self.lut_np = hn[lay.lut_off:lut_end].reshape(lay.n_img, 256)
+            self.dev_rec = self.dev[lay.rec_off:lay.lut_off].view(torch.int32).view(lay.n_img, route.record_ints)
+            self.dev_lut = self.dev[lay.lut_off:lut_end].view(lay.n_img, 256)
+        self.n_luts = 0                        # LUT rows of the staged batch ...
+        self.image_table = None                # ... and its ImageAugTable's (pre_op, div, div2)
         self.copied = torch.cuda.Event()       # H2D of this slot finished (host buffer reusable, device buffer readable)
         self.consumed = torch.cuda.Event()     # the kernels that read this slot's device buffer finished
         self.busy = False
@@ -130,27 +211,6 @@ def pool_bytes(a, channels, what, L=None, div=255.0):
     return out
 
 
-def check_grey_batch(n_img, bg, augment):
-    """What a batch of a GREY pool may carry, checked before a slot is taken: no bg (there is no bank on this route), and as `augment`
-    None, an AugTable (the 1D sequences: 128-byte records) or an ImageAugTable (Distractor's sequence with its pre_op / div / div2:
-    160-byte records) of one record per image.  -> the slot kind."""
-    from .augment import AugTable, ImageAugTable
-    if bg is not None:
-        raise MlhotError("BatchIngest.stage_ids: a grey pool has no background bank - bg must be None")
-    if augment is None:
-        return "pool1"
-    if not isinstance(augment, AugTable):
-        raise MlhotError(f"BatchIngest.stage_ids: on a grey pool augment is None, an AugTable (shapenet_1d / pascal_1d) or an ImageAugTable "
-                         f"(distractor), got {type(augment).__name__}")
-    image = isinstance(augment, ImageAugTable)
-    ints = (AUG_IMG_RECORD_BYTES if image else AUG_RECORD_BYTES) // 4
-    if augment.records.ndim != 2 or augment.records.shape[1] != ints:
-        raise MlhotError(f"BatchIngest.stage_ids: {type(augment).__name__} records must be int32 [n, {ints}], got {augment.records.shape}")
-    if augment.n_img != n_img:
-        raise MlhotError(f"BatchIngest.stage_ids: the augmentation table holds {augment.n_img} records for {n_img} images")
-    return "pool1augimg" if image else "pool1aug"
-
-
 class ResidentPool:
     """A loader's image pool, uploaded ONCE: batches are then described by image ids (BatchIngest.stage_ids) and gathered and converted
     on the device (csrc/pool_ingest.h).  The kind is read from the last dimension: uint8 [N, H, W, 4] is an RGBA pool with its
@@ -179,57 +239,17 @@ class ResidentPool:
         self.n_bank = 0 if bank is None else bank.shape[0]
 
 
-class _IdSlot:
-    """A staging slot of a batch described by ids: [ids int32 (ctx, qry) | bg int32 | pad to 16 | ctx labels | qry labels] and, when the
-    batch is augmented, [records int32 [n, 40] | gamma LUTs] behind them - no image bytes.  key = (ctx ids shape, qry ids shape, ctx
-    labels shape, qry labels shape, kind): "pool" | "poolaug" for an RGBA pool; "pool1" | "pool1aug" | "pool1augimg" for a grey pool,
-    which has no bg array and whose record area follows the table kind - [n, 32] (AugTable) or [n, 40] (ImageAugTable)."""
-
-    def __init__(self, key, device):
-        n = int(np.prod(key[0])) + int(np.prod(key[1]))
-        n_lab = [int(np.prod(key[2])), int(np.prod(key[3]))]
-        grey = key[4].startswith("pool1")
-        lab_off = ((4 if grey else 8) * n + 15) // 16 * 16
-        lab_end = total = lab_off + 4 * (n_lab[0] + n_lab[1])
-        self.augmented = key[4] in ("poolaug", "pool1aug", "pool1augimg")
-        rec_bytes = AUG_RECORD_BYTES if key[4] == "pool1aug" else AUG_IMG_RECORD_BYTES
-        if self.augmented:
-            rec_off = (total + 15) // 16 * 16
-            lut_off = rec_off + rec_bytes * n
-            total = lut_off + 256 * n
-        self.host = torch.empty(max(total, 16), dtype=torch.uint8).pin_memory()
-        self.dev = torch.empty(max(total, 16), dtype=torch.uint8, device=device)
-        hn = self.host.numpy()
-        self.n_img = n
-        self.ids_np, self.bg_np = hn[:4 * n].view(np.int32), None if grey else hn[4 * n:8 * n].view(np.int32)
-        self.lab_np = [hn[lab_off:lab_off + 4 * n_lab[0]].view(np.float32).reshape(key[2]),
-                       hn[lab_off + 4 * n_lab[0]:lab_end].view(np.float32).reshape(key[3])]
-        self.dev_ids, self.dev_bg = self.dev[:4 * n].view(torch.int32), None if grey else self.dev[4 * n:8 * n].view(torch.int32)
-        self.dev_lab = self.dev[lab_off:lab_end].view(torch.float32)
-        self.n_bytes = lab_end                 # bytes to copy: ids (+ bg) + labels (+ records + the LUTs in use)
-        self.image_table = None                # an ImageAugTable's (pre_op, div, div2), set per batch
-        if self.augmented:
-            self.aug_rec_np = hn[rec_off:lut_off].view(np.int32).reshape(n, rec_bytes // 4)
-            self.aug_lut_np = hn[lut_off:total].reshape(n, 256)
-            self.dev_rec = self.dev[rec_off:lut_off].view(torch.int32)
-            self.dev_lut = self.dev[lut_off:total].view(n, 256)
-            self.lut_off, self.n_luts = lut_off, 0
-        self.copied = torch.cuda.Event()
-        self.consumed = torch.cuda.Event()
-        self.busy = False
-
-
 class _Out:
     """The fixed fp32 tensors batches of one shape are delivered in: images of both sets in one flat buffer (one ingest
     launch when the image geometry is shared), labels in another (one device copy)."""
 
     def __init__(self, key, device):
         (T, Nc, H, W, Cc), (_, Nq, H2, W2, C2) = key[0], key[1]
-        n_img, n_lab, _, _ = _layout(key)
+        n_img, n_lab = [math.prod(key[0]), math.prod(key[1])], [math.prod(key[2]), math.prod(key[3])]
         self.same_geometry = (H, W, Cc) == (H2, W2, C2)
         self.img = torch.empty(n_img[0] + n_img[1], device=device)
         self.lab = torch.empty(n_lab[0] + n_lab[1], device=device)
-        self.n_img = n_img
+        self.key, self.n_img = key, n_img
         self.tensors = (self.img[:n_img[0]].view(T, Nc, Cc, H, W), self.img[n_img[0]:].view(T, Nq, C2, H2, W2),
                         self.lab[:n_lab[0]].view(key[2]), self.lab[n_lab[0]:].view(key[3]))
 
@@ -244,21 +264,21 @@ class BatchIngest:
             raise MlhotError(f"BatchIngest: the resident pool lives on {pool.device}, the ingest on {device}")
         self.pool = pool                        # a ResidentPool: stage_ids() describes batches by image ids
         self.copy_stream = torch.cuda.Stream(device)
-        self._slots = {}                        # shapes -> [slot, ...]
+        self._slots = {}                        # shapes + (route name,) -> [slot, ...]
         self._out = {}                          # shapes -> _Out (fixed fp32 outputs)
         self._queue = collections.deque()
         # stage*() may run on a worker thread while the owner take()s an earlier batch (trainer._HostPrefetch, two batches drawn ahead):
         # slot choice and the queue are guarded; the fill and the copy of a reserved slot are not (they touch only that slot).
         self._lock = threading.Lock()
 
-    def _free_slot(self, key, make=_Slot):
+    def _free_slot(self, route, key):
         with self._lock:
-            ring = self._slots.setdefault(key, [])
+            ring = self._slots.setdefault(key + (route.name,), [])
             slot = next((sl for sl in ring if not sl.busy), None)
             if slot is None:
                 if len(ring) >= self.n_slots:
                     raise MlhotError("BatchIngest: more batches staged than slots; call take() first")
-                slot = make(key, self.device)
+                slot = _Slot(route, key, self.device)
                 ring.append(slot)
             slot.busy = True                    # reserved from here on (given back by take(), or by a fill that refuses the batch)
         slot.copied.synchronize()               # the previous H2D out of this pinned buffer is done (no-op when fresh)
@@ -266,26 +286,32 @@ class BatchIngest:
 
     def stage(self, xs_u8, xq_u8, ys, yq, augment=None):
         """Queue one host batch: images uint8 [T,N,H,W,C] (channel-last), labels fp32 [T,N,L].  Returns a ticket.  `augment`: an
-        mlhot.augment.AugTable for the context images then the targets (C = 1), or None."""
+        mlhot.augment.AugTable (C = 1) or ImageAugTable for the context images then the targets, or None."""
         src = [_host(xs_u8, torch.uint8), _host(xq_u8, torch.uint8), _host(ys, torch.float32), _host(yq, torch.float32)]
         if src[0].dim() != 5 or src[1].dim() != 5:
             raise MlhotError("BatchIngest: images must be [T, N, H, W, C]")
-        key = tuple(tuple(t.shape) for t in src)
-        slot = self._free_slot(self._slot_key(key, augment))
-        for h, t in zip(slot.host_np, src):
-            np.copyto(h, t.numpy())             # one thread on purpose: torch's copy_ wakes the whole OpenMP pool, whose
-                                                # spinning workers then starve the HIP runtime's helper threads
-        if augment is not None:
-            self._put_augment(slot, augment)
-        return self._ship(key, slot)
+
+        def fill(host_np):
+            for h, t in zip(host_np, src):
+                np.copyto(h, t.numpy())         # one thread on purpose: torch's copy_ wakes the whole OpenMP pool, whose
+            return True                         # spinning workers then starve the HIP runtime's helper threads
+        return self.stage_filled(tuple(tuple(t.shape) for t in src), fill, augment=augment)
+
+    def stage_filled(self, key, fill, augment=None):
+        """Queue a batch whose bytes the CALLER writes into the pinned staging buffers: `fill(host_np)` gets the slot's four numpy views
+        ([ctx images u8 | qry images u8 | ctx labels f32 | qry labels f32], shaped like `key`) and returns True to ship the batch or
+        False to give the slot back (nothing is queued; returns None).  `augment` as in stage()."""
+        n_img = math.prod(key[0][:-3]) + math.prod(key[1][:-3])
+        slot = self._free_slot(check_table(BYTES, augment, n_img, channels=(key[0][-1], key[1][-1])), key)
+        return self._fill_and_ship(key, slot, fill, augment)
 
     def stage_ids(self, ctx_ids, qry_ids, ys, yq, bg=None, augment=None):
         """Queue one batch of the resident pool: image ids [T, Nc] / [T, Nq] (any integer type), labels fp32 [T, N, L]; `bg`: one bank
         index (or -1) per id, context ids first then targets - (ctx [T, Nc], qry [T, Nq]) or one flat array - None = no composition;
-        `augment`: an mlhot.augment.ImageAugTable of the shapenet_3d sequence, or None.  Ids and bg indices are range-checked here, on
-        the host; ids, bg, labels and records ride in one pinned slot and one H2D copy - no image bytes.  Returns a ticket.
-        On a grey pool (ResidentPool.grey): `bg` must be None; `augment` is None, an AugTable (the 1D sequences) or an ImageAugTable
-        carrying Distractor's (pre_op, div, div2) - check_grey_batch."""
+        `augment`: what check_table allows on the pool - on an RGBA pool an mlhot.augment.ImageAugTable of the shapenet_3d sequence;
+        on a grey pool (ResidentPool.grey, where `bg` must be None) an AugTable (the 1D sequences) or an ImageAugTable carrying
+        Distractor's (pre_op, div, div2) - or None.  Ids and bg indices are range-checked here, on the host; ids, bg, labels and
+        records ride in one pinned slot and one H2D copy - no image bytes.  Returns a ticket."""
         pool = self.pool
         if pool is None:
             raise MlhotError("BatchIngest.stage_ids: no resident pool (BatchIngest(device, pool=ResidentPool(...)))")
@@ -293,7 +319,7 @@ class BatchIngest:
         if ci.ndim != 2 or qi.ndim != 2 or ci.shape[0] != qi.shape[0] or ci.dtype.kind not in "iu" or qi.dtype.kind not in "iu":
             raise MlhotError(f"BatchIngest.stage_ids: integer ids [T, Nc] and [T, Nq], got {ci.shape} {ci.dtype} / {qi.shape} {qi.dtype}")
         ids = np.concatenate([ci.reshape(-1), qi.reshape(-1)]).astype(np.int64)
-        kind = check_grey_batch(ids.size, bg, augment) if pool.grey else None
+        route = check_table(GREY if pool.grey else RGBA, augment, ids.size, bg=bg)
         if bg is None:
             bgs = np.full(ids.shape, -1, dtype=np.int64)
         else:
@@ -301,58 +327,22 @@ class BatchIngest:
             bgs = np.concatenate([np.asarray(b).reshape(-1) for b in parts]).astype(np.int64)
         check_pool_indices(ids, bgs, pool.n_pool, pool.n_bank)
         lab = [_host(ys, torch.float32), _host(yq, torch.float32)]
-        if augment is not None and not pool.grey:
-            from .augment import ImageAugTable
-            if not isinstance(augment, ImageAugTable) or (augment.pre_op, augment.div2) != (0, 1.0):
-                raise MlhotError("BatchIngest.stage_ids: augment must be an ImageAugTable of the shapenet_3d sequence (pre_op 0, one division)")
-            if augment.n_img != ids.size:
-                raise MlhotError(f"BatchIngest.stage_ids: the augmentation table holds {augment.n_img} records for {ids.size} images")
-        T, H, W = ci.shape[0], pool.H, pool.W
-        if kind is None:
-            kind = "pool" if augment is None else "poolaug"
-        slot = self._free_slot((tuple(ci.shape), tuple(qi.shape), tuple(lab[0].shape), tuple(lab[1].shape), kind), make=_IdSlot)
-        np.copyto(slot.ids_np, ids, casting="unsafe")
-        if slot.bg_np is not None:
-            np.copyto(slot.bg_np, bgs, casting="unsafe")
-        for h, t in zip(slot.lab_np, lab):
-            np.copyto(h, t.numpy())
-        if augment is not None:
-            self._put_augment(slot, augment)
+        key = (tuple(ci.shape), tuple(qi.shape), tuple(lab[0].shape), tuple(lab[1].shape))
+
+        def fill(host_np):
+            for h, a in zip(host_np, ([ids, bgs] if route.bg else [ids]) + [t.numpy() for t in lab]):
+                np.copyto(h, a, casting="unsafe")
+            return True
         # delivered in the tensors a byte batch of the same shape is delivered in
-        Cc = 1 if pool.grey else 3
-        return self._ship(((T, ci.shape[1], H, W, Cc), (T, qi.shape[1], H, W, Cc), tuple(lab[0].shape), tuple(lab[1].shape)), slot)
+        (T, Nc), Nq, geom = ci.shape, qi.shape[1], (pool.H, pool.W, route.channels)
+        return self._fill_and_ship(((T, Nc) + geom, (T, Nq) + geom) + key[2:], self._free_slot(route, key), fill, augment)
 
-    @staticmethod
-    def _slot_key(key, augment):
-        if augment is None:
-            return key
-        from .augment import ImageAugTable
-        image = isinstance(augment, ImageAugTable)
-        if not image and (key[0][-1] != 1 or key[1][-1] != 1):
-            raise MlhotError(f"BatchIngest: device augmentation needs single-channel images, got {key[0]} / {key[1]}")
-        if augment.n_img != _n_images(key):
-            raise MlhotError(f"BatchIngest: the augmentation table holds {augment.n_img} records for {_n_images(key)} images")
-        return key + ("augimg" if image else "aug",)
-
-    @staticmethod
-    def _put_augment(slot, augment):
-        np.copyto(slot.aug_rec_np, augment.records)
-        k = augment.luts.shape[0]
-        if k:
-            np.copyto(slot.aug_lut_np[:k], augment.luts)
-        slot.n_luts = k
-        if slot.aug_rec_np.shape[1] * 4 == AUG_IMG_RECORD_BYTES:
-            slot.image_table = (augment.pre_op, augment.div, augment.div2)
-        slot.n_bytes = slot.lut_off + 256 * k   # the copy stops behind the LUTs in use
-
-    def stage_filled(self, key, fill, augment=None):
-        """Queue a batch whose bytes the CALLER writes into the pinned staging buffers: `fill(host_np)` gets the slot's four numpy views
-        ([ctx images u8 | qry images u8 | ctx labels f32 | qry labels f32], shaped like `key`) and returns True to ship the batch or
-        False to give the slot back (nothing is queued; returns None).  `augment` as in stage()."""
-        slot = self._free_slot(self._slot_key(key, augment))
+    def _fill_and_ship(self, out_key, slot, fill, augment):
+        """Write a reserved slot - `fill(slot.host_np)`, then the table behind the labels - and start its H2D copy; a fill that
+        returns False or raises gives the slot back."""
         try:
             ok = fill(slot.host_np)
-            if ok and augment is not None:
+            if ok:
                 self._put_augment(slot, augment)
         except BaseException:
             slot.busy = False
@@ -360,19 +350,26 @@ class BatchIngest:
         if not ok:
             slot.busy = False
             return None
-        return self._ship(key, slot)
-
-    def _ship(self, key, slot):
         with torch.cuda.stream(self.copy_stream):
             self.copy_stream.wait_event(slot.consumed)      # do not overwrite bytes an ingest kernel still reads
-            if slot.n_bytes is None:
-                slot.dev.copy_(slot.host, non_blocking=True)
-            else:
-                slot.dev[:slot.n_bytes].copy_(slot.host[:slot.n_bytes], non_blocking=True)
+            slot.dev[:slot.n_bytes].copy_(slot.host[:slot.n_bytes], non_blocking=True)
             slot.copied.record(self.copy_stream)
         with self._lock:
-            self._queue.append((key, slot))
+            self._queue.append((out_key, slot))
         return slot
+
+    @staticmethod
+    def _put_augment(slot, augment):
+        if augment is None:
+            return
+        np.copyto(slot.rec_np, augment.records)
+        k = augment.luts.shape[0]
+        if k:
+            np.copyto(slot.lut_np[:k], augment.luts)
+        slot.n_luts = k
+        if slot.route.table is ImageAugTable:
+            slot.image_table = (augment.pre_op, augment.div, augment.div2)
+        slot.n_bytes = slot.layout.lut_off + 256 * k        # the copy stops behind the LUTs in use
 
     def device_views(self, ticket=None):
         """(uint8 [n, H, W, C] staged images on the device, fp32 [n, C, H, W] destination) of a staged batch whose two
@@ -403,68 +400,39 @@ class BatchIngest:
         out = self._out.get(key)
         if out is None:
             out = self._out[key] = _Out(key, self.device)
-        L = lib()
         with torch.cuda.device(self.device):
-            if isinstance(slot, _IdSlot):
-                self._pool_into(L, slot, out)
-            elif slot.augmented:
-                self._augment_into(L, key, slot, out)
-            elif out.same_geometry:             # both image sets are one packed run of (H, W, C) images
-                _, _, H, W, Cc = key[0]
-                L.ingest_u8_nhwc(slot.dev_img.view(-1, H, W, Cc), out=out.img.view(-1, Cc, H, W), div=self.div)
-            else:
-                n0 = out.n_img[0]
-                L.ingest_u8_nhwc(slot.dev_img[:n0].view(key[0]), out=out.tensors[0], div=self.div)
-                L.ingest_u8_nhwc(slot.dev_img[n0:].view(key[1]), out=out.tensors[1], div=self.div)
+            self._expand(slot, out)
             out.lab.copy_(slot.dev_lab)
         slot.consumed.record(cur)
         slot.busy = False
         return out.tensors
 
-    def _pool_into(self, L, slot, out):
-        pool = self.pool
-        if pool.grey:
-            dst = out.img.view(slot.n_img, 1, pool.H, pool.W)
-            luts = slot.dev_lut[:slot.n_luts] if slot.augmented and slot.n_luts else None
-            if not slot.augmented:
-                L.pool1_ingest_u8(pool.pool, slot.dev_ids, out=dst, div=self.div)
-            elif slot.image_table is None:      # an AugTable: the 1D sequences, the byte route's division
-                L.pool1_augment_ingest_u8(pool.pool, slot.dev_ids, slot.dev_rec, luts, out=dst, div=self.div)
-            else:
-                from .augment import colour_tables
-                pre_op, div, div2 = slot.image_table
-                L.pool1_augment_ingest_u8_img(pool.pool, slot.dev_ids, slot.dev_rec, luts, colour_tables(self.device), out=dst,
-                                              pre_op=pre_op, div=div, div2=div2)
-            return
-        dst = out.img.view(slot.n_img, 3, pool.H, pool.W)
-        if not slot.augmented:
-            L.pool_ingest_u8(pool.pool, slot.dev_ids, pool.bank, slot.dev_bg, out=dst, div=self.div)
-            return
-        from .augment import colour_tables
-        L.pool_augment_ingest_u8_img(pool.pool, slot.dev_ids, slot.dev_rec, pool.bank, slot.dev_bg, slot.dev_lut[:slot.n_luts] if slot.n_luts else None,
-                                     colour_tables(self.device), out=dst, div=slot.image_table[1])
-
-    def _augment_into(self, L, key, slot, out):
-        luts = slot.dev_lut[:slot.n_luts] if slot.n_luts else None
-        if slot.image_table is not None:
-            from .augment import colour_tables
+    def _expand(self, slot, out):
+        """The one call into the library: slot -> out.img through the route's entry, its arguments built from the route and the slot."""
+        route = slot.route
+        entry, kw = getattr(lib(), route.entry), {"div": self.div}
+        if route.record_ints:
+            kw.update(records=slot.dev_rec, luts=slot.dev_lut[:slot.n_luts] if slot.n_luts else None)
+        if route.table is ImageAugTable:
             pre_op, div, div2 = slot.image_table
-            kw = dict(colour_tabs=colour_tables(self.device), pre_op=pre_op, div=div, div2=div2)
-            if out.same_geometry:
-                _, _, H, W, Cc = key[0]
-                L.augment_ingest_u8_img(slot.dev_img.view(-1, H, W, Cc), slot.dev_rec, luts, out=out.img.view(-1, Cc, H, W), **kw)
-            else:
-                n0, r0 = out.n_img[0], int(np.prod(key[0][:-3])) * (AUG_IMG_RECORD_BYTES // 4)
-                L.augment_ingest_u8_img(slot.dev_img[:n0].view(key[0]), slot.dev_rec[:r0], luts, out=out.tensors[0], **kw)
-                L.augment_ingest_u8_img(slot.dev_img[n0:].view(key[1]), slot.dev_rec[r0:], luts, out=out.tensors[1], **kw)
-            return
-        if out.same_geometry:
-            _, _, H, W, Cc = key[0]
-            L.augment_ingest_u8(slot.dev_img.view(-1, H, W, Cc), slot.dev_rec, luts, out=out.img.view(-1, Cc, H, W), div=self.div)
-        else:
-            n0, r0 = out.n_img[0], int(np.prod(key[0][:-3]))
-            L.augment_ingest_u8(slot.dev_img[:n0].view(key[0]), slot.dev_rec[:r0 * 32], luts, out=out.tensors[0], div=self.div)
-            L.augment_ingest_u8(slot.dev_img[n0:].view(key[1]), slot.dev_rec[r0 * 32:], luts, out=out.tensors[1], div=self.div)
+            kw.update(colour_tabs=colour_tables(self.device), div=div)
+            if route.source != RGBA:            # the RGBA pool's entry has neither: check_table admits only (0, 1.0) there
+                kw.update(pre_op=pre_op, div2=div2)
+        key, n = out.key, slot.layout.n_img
+        _, _, H, W, Cc = key[0]
+        if route.ids:
+            if route.bg:
+                kw.update(bank=self.pool.bank, bg=slot.dev_bg)
+            entry(self.pool.pool, slot.dev_ids, out=out.img.view(n, Cc, H, W), **kw)
+        elif out.same_geometry:                 # both image sets are one packed run of (H, W, C) images
+            entry(slot.dev_img.view(n, H, W, Cc), out=out.img.view(n, Cc, H, W), **kw)
+        else:                                   # one launch per side, each with its rows of the records and the whole LUT table
+            n0, r0 = out.n_img[0], math.prod(key[0][:-3])
+            for img, dst, rows in ((slot.dev_img[:n0].view(key[0]), out.tensors[0], slice(0, r0)),
+                                   (slot.dev_img[n0:].view(key[1]), out.tensors[1], slice(r0, n))):
+                if route.record_ints:
+                    kw["records"] = slot.dev_rec[rows]
+                entry(img, out=dst, **kw)
 
 
 class ExactU8Feed:
@@ -502,7 +470,6 @@ class ExactU8Feed:
         (T, Nc, C, H, W), (_, Nq, C2, H2, W2) = xs.shape, xq.shape
         key = ((T, Nc * C, H, W, 1), (T, Nq * C2, H2, W2, 1), tuple(ys.shape), tuple(yq.shape))
         L = lib()
-        from .augment import ImageAugTable
         image = isinstance(augment, ImageAugTable)
         if image:       # the image tasks' ops mix the channels of a pixel: the bytes are staged channel-last, as the kernel reads them
             key = ((T, Nc, H, W, C), (T, Nq, H2, W2, C2), tuple(ys.shape), tuple(yq.shape))

@@ -208,11 +208,8 @@ class _Feed:
         xs, xq, ys, yq = self._draw(source, u8=True)
         table = None
         if source == "train" and self.augment is not None:          # the reference augments training batches only (shapenet_1d.py:174)
-            from mlhot.augment import ImageSampler
-            (T, Nc, H, W, Cc), Nq = xs.shape, xq.shape[1]
-            if not isinstance(self.augment, ImageSampler) and (Cc != 1 or xq.shape[-1] != 1):
-                raise ValueError(f"config.device_augment: single-channel images only, got {tuple(xs.shape)}")
-            table = self.augment.batch(T * Nc, T * Nq, H, W)
+            (T, Nc, H, W, _), Nq = xs.shape, xq.shape[1]
+            table = self.augment.batch(T * Nc, T * Nq, H, W)        # (stage() refuses an AugTable on multi-channel images)
         return self.ingest.stage(xs, xq, ys, yq, augment=table)
 
     def batch(self, source, ahead=0):
