@@ -253,6 +253,25 @@ int mlhot_linear_rows_fwd(const mlhot_rows_src* src, int n_src /* 1 | 2 */, cons
 int mlhot_loss_prefix_fwd(int kind, const float* mu, const float* gt, int P, int rows, int y_dim, int gt_dim,
                           float* loss /* [P] */, void* stream);
 
+/* ---- cached context: the key side of FAVOR+ once, the query side for any number of rows (csrc/favor_cached.h) -------------------
+ * mlhot_favor_keys_fwd: k[T,Nc,H,d] (what the head projections write), proj[m,d] -> state, mlhot_favor_keys_bytes(..) bytes:
+ *   floats [0, T H Nc mp): the finished key features F_k[T,H,Nc,mp] = ratio (exp(dd_k - diag_k - M) + 1e-4), mp = m rounded up to 16,
+ *   features >= m zeros; float T H Nc mp: M, the key stabiliser = the maximum of dd_k over ALL T tasks of this call
+ *   (fast_attention.py:96-97); the rest is the call's scratch.  A state serves queries of the same T tasks only.
+ * mlhot_favor_query_fwd: q[T,Nq,H,d], state, v[T,Nc,H,d], proj -> out[T,Nq,d*H] in mlhot_favor_fwd's merged order, for ANY Nq >= 1
+ *   in one launch, with a ROW-INVARIANCE guarantee: the bits of out[t,n,:] depend on q[t,n], state, v, proj and the dimensions -
+ *   not on Nq, on n, on the grid or on the other query rows (so a caller may chunk, pad or reorder the rows freely).
+ * Shapes: Nc <= 32, d % 16 == 0, d <= 256, 16 <= m <= 1536 (favor2.h's, on the context side), 16-byte aligned pointers; for others
+ * the _bytes functions return 0 and the calls MLHOT_ERR_UNSUPPORTED, writing nothing (callers keep k and run mlhot_favor_fwd).
+ * Forward only; GPU build only.  Added within ABI 7: bindings look the symbols up. */
+size_t mlhot_favor_keys_bytes(int T, int H, int Nc, int d, int m);
+int mlhot_favor_keys_fwd(const float* k, const float* proj, int T, int H, int Nc, int d, int m,
+                         void* state, size_t state_bytes, void* stream);
+size_t mlhot_favor_query_ws_bytes(int T, int H, int Nq, int Nc, int d, int m);
+int mlhot_favor_query_fwd(const float* q, const void* state, const float* v, const float* proj,
+                          int T, int H, int Nq, int Nc, int d, int m, float* out,
+                          void* ws, size_t ws_bytes, void* stream);
+
 /* ---- strict sharded parity of the key stabiliser -------------------------
  * fast_attention.py:96-97 takes torch.max over the keys of the WHOLE batch.  When a caller shards the meta-batch over
  * ranks, each rank's launch sequence can be run in two halves around the caller's own collectives on `xchg`

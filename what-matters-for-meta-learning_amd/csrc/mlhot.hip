@@ -25,6 +25,7 @@
 #include "nt_xent.h"
 #include "mlp_chain.h"
 #include "linear_rows.h"
+#include "favor_cached.h"
 #include "resnet_trunk.h"
 #include "../../include/mlhot.h"
 
@@ -302,6 +303,16 @@ int mlhot_favor_prefix_fwd(const float* q, const float* k, const float* v, const
 #else
   (void)ws; (void)ws_bytes; (void)stream; set_error("favor_prefix_fwd: GPU build only"); return MLHOT_ERR_UNSUPPORTED;
 #endif
+}
+// the context side once, the query side for any number of rows (csrc/favor_cached.h)
+size_t mlhot_favor_keys_bytes(int T, int H, int Nc, int d, int m) { return favor_keys_need(T, H, Nc, d, m); }
+int mlhot_favor_keys_fwd(const float* k, const float* proj, int T, int H, int Nc, int d, int m, void* state, size_t state_bytes, void* stream) {
+  return favor_keys_forward(k, proj, T, H, Nc, d, m, state, state_bytes, (hipStream_t)stream);
+}
+size_t mlhot_favor_query_ws_bytes(int T, int H, int Nq, int Nc, int d, int m) { return favor_query_ws_need(T, H, Nq, Nc, d, m); }
+int mlhot_favor_query_fwd(const float* q, const void* state, const float* v, const float* proj, int T, int H, int Nq, int Nc,
+                          int d, int m, float* out, void* ws, size_t ws_bytes, void* stream) {
+  return favor_query_forward(q, state, v, proj, T, H, Nq, Nc, d, m, out, ws, ws_bytes, (hipStream_t)stream);
 }
 // Staged passes (strict sharded parity of the key stabiliser, csrc/stab_xchg.h): stage 0 runs up to the rank-local scalar and
 // publishes it in xchg, stage 1 takes the batch-wide scalar from xchg and runs the rest.

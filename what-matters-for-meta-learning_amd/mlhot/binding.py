@@ -258,6 +258,11 @@ SIGNATURES = {
     "mlhot_linear_rows_supported": (i, [i, i, i]),
     "mlhot_linear_rows_fwd": (i, [_p(RowsSrc), i, P, P, P, i, i, i, i, P]),
     "mlhot_loss_prefix_fwd": (i, [i, P, P, i, i, i, i, P, P]),
+    # cached context: the key side once, the query side for any number of rows
+    "mlhot_favor_keys_bytes": (z, [i] * 5),
+    "mlhot_favor_keys_fwd": (i, [P, P, i, i, i, i, i, P, z, P]),
+    "mlhot_favor_query_ws_bytes": (z, [i] * 6),
+    "mlhot_favor_query_fwd": (i, _qkvp + [P, P, z, P]),
     # strict sharded parity of the key stabiliser
     "mlhot_favor_fwd_staged": (i, _qkvp + [P, P, z, i, P, P]),
     "mlhot_favor_bwd_staged": (i, _qkvp + [P, P, P, P, P, P, z, i, P, P]),
@@ -996,6 +1001,59 @@ class MlhotLib:
         ws = self._bytes(wb, q)
         fn = self._fn("favor_prefix_fwd", "mlhot_favor_prefix_fwd")
         self._rc(fn(_ptr(q), _ptr(k), _ptr(v), _ptr(proj), T, H, Nq, Nc, d, m, _ptr(out), _ptr(ws), ws.numel(), _stream(q)), "mlhot_favor_prefix_fwd")
+        return out
+
+    def favor_keys_bytes(self, T, H, Nc, d, m):
+        """State bytes of mlhot_favor_keys_fwd; 0 for a shape the cached-context kernels do not serve."""
+        return self._fn("favor_keys_fwd", "mlhot_favor_keys_bytes")(T, H, Nc, d, m)
+
+    def favor_keys_fwd(self, k, proj):
+        """k [T,Nc,H,d], proj [m,d] -> state (uint8): the finished key features F_k [T,H,Nc,mp] and the batch-global stabiliser M
+        (include/mlhot.h; favor_state_views shows them).  Forward only."""
+        if k.dtype != torch.float32 or k.dim() != 4 or proj.dtype != torch.float32 or proj.dim() != 2 or proj.shape[1] != k.shape[3] or proj.device != k.device:
+            raise MlhotError(f"favor_keys_fwd: k must be fp32 [T, Nc, H, d] and proj fp32 [m, d] on one device, got {tuple(k.shape)}, {tuple(proj.shape)}")
+        T, Nc, H, d = k.shape
+        m = proj.shape[0]
+        nb = self.favor_keys_bytes(T, H, Nc, d, m)
+        if not nb:
+            raise MlhotError(f"favor_keys_fwd serves Nc <= 32, d % 16 == 0, d <= 256, 16 <= m <= 1536 (got Nc={Nc} d={d} m={m}); "
+                             "mlhot.ops.favor_keys keeps the keys for other shapes")
+        _chk(k, proj)
+        state = self._bytes(nb, k)
+        fn = self._fn("favor_keys_fwd", "mlhot_favor_keys_fwd")
+        self._rc(fn(_ptr(k), _ptr(proj), T, H, Nc, d, m, _ptr(state), state.numel(), _stream(k)), "mlhot_favor_keys_fwd")
+        return state
+
+    @staticmethod
+    def favor_state_views(state, T, H, Nc, m):
+        """(F_k [T,H,Nc,mp], M [1]) as fp32 views of a mlhot_favor_keys_fwd state."""
+        mp = (m + 15) // 16 * 16
+        f = state.view(torch.float32)
+        n = T * H * Nc * mp
+        return f[:n].view(T, H, Nc, mp), f[n:n + 1]
+
+    def favor_query_fwd(self, q, state, v, proj):
+        """q [T,Nq,H,d], a mlhot_favor_keys_fwd state, v [T,Nc,H,d], proj [m,d] -> out [T,Nq,d*H] (merged order), any Nq >= 1, bits
+        per row independent of the other rows (csrc/favor_cached.h).  Forward only."""
+        for name, t in (("q", q), ("v", v)):
+            if t.dtype != torch.float32 or t.dim() != 4:
+                raise MlhotError(f"favor_query_fwd: {name} must be fp32 [T, N, H, d], got {t.dtype} {tuple(t.shape)}")
+        T, Nq, H, d = q.shape
+        Nc = v.shape[1]
+        if tuple(v.shape) != (T, Nc, H, d) or proj.dtype != torch.float32 or proj.dim() != 2 or proj.shape[1] != d or Nq < 1:
+            raise MlhotError(f"favor_query_fwd: q {tuple(q.shape)}, v {tuple(v.shape)}, proj {tuple(proj.shape)} do not fit together")
+        if any(t.device != q.device for t in (state, v, proj)):
+            raise MlhotError("favor_query_fwd: q, state, v and proj must lie on one device")
+        m = proj.shape[0]
+        nb = self.favor_keys_bytes(T, H, Nc, d, m)
+        if not nb or state.dtype != torch.uint8 or state.numel() < nb:
+            raise MlhotError(f"favor_query_fwd: the state is not mlhot_favor_keys_fwd's for T={T} H={H} Nc={Nc} d={d} m={m} "
+                             f"({state.numel()} bytes, {nb} needed; 0 = shape not served)")
+        _chk(q, v, proj, state)
+        out = torch.empty(T, Nq, d * H, device=q.device)
+        ws = self._bytes(self._fn("favor_query_fwd", "mlhot_favor_query_ws_bytes")(T, H, Nq, Nc, d, m), q)
+        fn = self._fn("favor_query_fwd", "mlhot_favor_query_fwd")
+        self._rc(fn(_ptr(q), _ptr(state), _ptr(v), _ptr(proj), T, H, Nq, Nc, d, m, _ptr(out), _ptr(ws), ws.numel(), _stream(q)), "mlhot_favor_query_fwd")
         return out
 
     @staticmethod

@@ -487,6 +487,53 @@ def favor_prefixes(qh, kh, vh, proj):
     return torch.stack([lib().favor_fwd(qh, kh[:, :k].contiguous(), vh[:, :k].contiguous(), proj)[0] for k in range(1, Nc + 1)])
 
 
+class FavorKeyState:
+    """What favor_keys leaves for favor_query.  `route` says what it holds: "cached" - `buf` is mlhot_favor_keys_fwd's state (the
+    finished key features F_k and the batch-global stabiliser M; features() shows them) and favor_query is row-invariant;
+    "plain" - a shape outside the cached kernels' envelope: `kh` itself, favor_query runs mlhot_favor_fwd, no invariance."""
+
+    def __init__(self, route, dims, buf=None, kh=None):
+        self.route, self.dims, self.buf, self.kh = route, dims, buf, kh      # dims = (T, Nc, H, d, m)
+
+    def features(self):
+        """(F_k [T, H, Nc, mp], M [1]) of a "cached" state, as views."""
+        if self.route != "cached":
+            raise MlhotError("FavorKeyState.features: this state holds the keys themselves (route 'plain')")
+        T, Nc, H, d, m = self.dims
+        return lib().favor_state_views(self.buf, T, H, Nc, m)
+
+
+def favor_keys(kh, proj):
+    """The context side of FAVOR+ once: k [T, Nc, H, d] (the head projections' layout), proj [m, d] -> FavorKeyState for any
+    number of favor_query calls on the SAME T tasks (the key stabiliser is the maximum over the whole batch of kh).  Two launches
+    (csrc/favor_cached.h) for Nc <= 32, d % 16 == 0, d <= 256, 16 <= m <= 1536; other shapes keep kh.  Forward only."""
+    _forward_only("favor_keys", kh, proj)
+    _need_gpu(kh, proj)
+    kh, proj = _c(kh.detach()), _c(proj.detach())
+    T, Nc, H, d = kh.shape
+    dims = (T, Nc, H, d, proj.shape[0])
+    if lib().favor_keys_bytes(T, H, Nc, d, proj.shape[0]):
+        return FavorKeyState("cached", dims, buf=lib().favor_keys_fwd(kh, proj))
+    return FavorKeyState("plain", dims, kh=kh)
+
+
+def favor_query(qh, state, vh, proj):
+    """FAVOR+ attention of q [T, Nq, H, d] against a favor_keys state and v [T, Nc, H, d] -> merged [T, Nq, d*H], any Nq >= 1 in
+    one launch.  On the "cached" route the bits of a row do not depend on the other rows of the call (csrc/favor_cached.h); the
+    "plain" route is mlhot_favor_fwd on the kept keys.  Forward only."""
+    _forward_only("favor_query", qh, vh, proj)
+    _need_gpu(qh, vh, proj)
+    if not isinstance(state, FavorKeyState):
+        raise MlhotError("favor_query: state must come from favor_keys")
+    qh, vh, proj = _c(qh.detach()), _c(vh.detach()), _c(proj.detach())
+    T, Nc, H, d, m = state.dims
+    if tuple(vh.shape) != (T, Nc, H, d) or qh.dim() != 4 or (qh.shape[0], qh.shape[2], qh.shape[3]) != (T, H, d) or tuple(proj.shape) != (m, d):
+        raise MlhotError(f"favor_query: the state was built for T={T} Nc={Nc} H={H} d={d} m={m}; got q {tuple(qh.shape)}, v {tuple(vh.shape)}, proj {tuple(proj.shape)}")
+    if state.route == "cached":
+        return lib().favor_query_fwd(qh, state.buf, vh, proj)
+    return lib().favor_fwd(qh, state.kh, vh, proj)[0]
+
+
 def linear_rows(sources, weight, bias, act="none", rows=None):
     """y = act([src_0 | src_1] W^T + b) over the rows of MANY prefixes in one launch, with bits per row that do not depend on the
     number of rows (csrc/linear_rows.h; LinearFunction picks its kernel by row count).  sources: one or two (tensor [R, k], rep,

@@ -11,7 +11,7 @@ import logging
 
 from mlhot import lib
 from mlhot.ops import (AggFunction, FavorFunction, HeadStacksFunction, LinearFunction, StackedLinearFunction, agg_prefixes,
-                       favor_prefixes, linear_rows)
+                       favor_keys, favor_prefixes, favor_query, linear_rows)
 from networks.ResNet import run_conv
 from networks.fast_attention import FastAttention
 from networks.models import AttnLinear, ImageEncoder, NPDecoder, _aggregate_feature_map, _mlp3, run_trunks
@@ -43,6 +43,23 @@ def _fold_linear(sources, lin, act, n_prefix):
     cols = [x[(idx // rep) % period if period else idx // rep] for x, rep, period in sources]
     x = torch.cat(cols, dim=1) if len(cols) > 1 else cols[0]
     return torch.cat([LinearFunction.apply(c, lin.weight, lin.bias, act) for c in x.chunk(n_prefix)])
+
+
+class ContextState:
+    """What ResNetNP.condition leaves for ResNetNP.predict.  `kind`: "attention" - `keys` (mlhot.ops.FavorKeyState) and the value
+    heads `vh` [T, Nc, H, 256]; "latent" - the task embedding `z` [T, 256]; "empty" - no context shot.  `owner` is the model,
+    `fingerprint` its parameters' versions when the state was made: predict refuses a state whose model has moved on."""
+
+    def __init__(self, owner, T, Nc, fingerprint, kind, keys=None, vh=None, z=None):
+        self.owner, self.T, self.Nc, self.fingerprint, self.kind = owner, T, Nc, fingerprint, kind
+        self.keys, self.vh, self.z = keys, vh, z
+
+
+class _Stacked:
+    """A head stack's [N*h, k] weight and [N*h] bias with nn.Linear's attribute names (for _fold_linear)."""
+
+    def __init__(self, weight, bias):
+        self.weight, self.bias = weight, bias
 
 
 class HeadStack:
@@ -446,3 +463,94 @@ class ResNetNP(nn.Module):
                 pre = None
             out = [_mlp3(sample, self.decoder.fc_mu, last_relu=False, side=x_dec, side_first=True, pre=pre) for sample in samples]
             return torch.stack(out)
+
+    # ---- cached context: condition once, predict for any targets --------------------------------------------------
+    def _fingerprint(self):
+        return tuple(p._version for p in self.parameters()) + tuple(b._version for b in self.buffers())
+
+    def _cached_refusals(self, what):
+        if self.PREFIX_SWEEP_REFUSAL:
+            raise ValueError(f"{type(self).__name__}.{what}: Bayes-by-backprop draws fresh weights in every forward, so a cached "
+                             f"context is not the reference's forward ({self.PREFIX_SWEEP_REFUSAL})")
+        if self.training:
+            raise ValueError(f"{what} is a test-mode path: call model.eval() first")
+
+    def condition(self, batch_train_images, label_train):
+        """(ctx images [T, Nc, ...], ctx labels) -> ContextState: everything of `forward(..., test=True)` that does not depend on
+        the targets, once - the context trunk pass, the task encoder and, for the attention models, the key / value head
+        projections and the FAVOR+ key features (mlhot.ops.favor_keys); for the others the aggregation and `mu`.  The key
+        stabiliser is the maximum over all T tasks of THIS batch, so predict reproduces forward on the same T tasks.  Eval mode."""
+        self._cached_refusals("condition")
+        T, Nc = batch_train_images.shape[0], batch_train_images.shape[1]
+        if T != self.task_num:
+            raise ValueError(f"condition: {T} tasks, the model was built for tasks_per_batch = {self.task_num}")
+        self._refresh_arena()
+        with torch.no_grad():
+            if self.ATTENTION:
+                for mods in (self._W_q, self._W_k, self._W_v):       # stack the heads now: re-pointing a parameter must not look like an update later
+                    self._stack(mods).tensors()
+            if Nc == 0:
+                return ContextState(self, T, 0, self._fingerprint(), "empty")
+            C, H, W = self.img_channels, self.img_size[0], self.img_size[1]
+            ctx_imgs = batch_train_images.reshape(-1, C, H, W)
+            maps = run_trunks([self.img_encoder.trunk_job(ctx_imgs)])
+            x_ctx = self.img_encoder.features(maps[0]) if maps is not None else self.img_encoder(ctx_imgs)
+            if self.TRANSFORM_Y:
+                label_train = LinearFunction.apply(label_train, self.transform_y.weight, self.transform_y.bias, "none")
+            feats = _mlp3(x_ctx, self.task_encoder, last_relu=True, side=label_train)
+            if self.ATTENTION:
+                kh, vh = self._heads(x_ctx, self._W_k), self._heads(feats, self._W_v)
+                keys = favor_keys(kh, self.attn.projection_matrix)
+                return ContextState(self, T, Nc, self._fingerprint(), "attention", keys=keys, vh=vh.contiguous())
+            return ContextState(self, T, Nc, self._fingerprint(), "latent", z=self._aggregate(feats))
+
+    def predict(self, state, batch_test_images, chunk=None):
+        """(ContextState, target images [T, Nq, ...]) -> mu [T, Nq, out] = `forward(ctx, labels, targets, test=True)[0]` for the
+        context the state was made from, any Nq >= 1.  One run_trunks call does the target (attention models) and decoder passes;
+        the query head projection, `_W`, `mu` and the decoder head go through mlhot.ops.linear_rows and the attention through
+        mlhot.ops.favor_query, so nothing behind the trunks depends on how many targets share the call.  `chunk` bounds the
+        targets per launch sequence.  Against forward the result agrees to the kernels' tolerance, not to the bit."""
+        self._cached_refusals("predict")
+        if not isinstance(state, ContextState) or state.owner is not self:
+            raise ValueError("predict: the state was not made by this model's condition()")
+        if batch_test_images.shape[0] != state.T or state.T != self.task_num:
+            raise ValueError(f"predict: the state holds {state.T} tasks, the targets {batch_test_images.shape[0]} (the key stabiliser "
+                             "is the maximum over the conditioned batch: predict serves the same tasks)")
+        if state.fingerprint != self._fingerprint():
+            raise ValueError("predict: the state is stale - a parameter of the model changed since condition()")
+        Nq = batch_test_images.shape[1]
+        if Nq < 1:
+            raise ValueError("predict needs at least one target")
+        if chunk is not None and int(chunk) < 1:
+            raise ValueError(f"predict: chunk must be a positive number of targets, got {chunk}")
+        if chunk is None or int(chunk) >= Nq:
+            return self._predict_targets(state, batch_test_images)
+        chunk = int(chunk)
+        return torch.cat([self._predict_targets(state, batch_test_images[:, i:i + chunk].contiguous()) for i in range(0, Nq, chunk)], dim=1)
+
+    def _predict_targets(self, state, batch_test_images):
+        self._refresh_arena()
+        with torch.no_grad():
+            T, Nq = self.task_num, batch_test_images.shape[1]
+            C, H, W = self.img_channels, self.img_size[0], self.img_size[1]
+            tgt_imgs = batch_test_images.reshape(-1, C, H, W)
+            attend = state.kind == "attention"
+            jobs = ([self.img_encoder.trunk_job(tgt_imgs)] if attend else []) + [self.decoder.trunk_job(tgt_imgs)]
+            maps = run_trunks(jobs)
+            if maps is None:            # no weight-stationary kernels for this image size: the per-operator route
+                dec_map = self.decoder.resnet.trunk(run_conv(self.decoder.conv1, tgt_imgs, relu=True), None)
+                x_tgt = self.img_encoder(tgt_imgs) if attend else None
+            else:
+                dec_map = maps[-1]
+                x_tgt = self.img_encoder.features(maps[0]) if attend else None
+            x_dec = _aggregate_feature_map(dec_map, self.decoder.aggregate).reshape(T, Nq, -1)
+            if attend:
+                w, b = self._stack(self._W_q).tensors()
+                qh = _fold_linear([(x_tgt.reshape(T * Nq, -1), 1, 0)], _Stacked(w, b), "none", 1).view(T, Nq, self.N_HEADS, -1)
+                merged = favor_query(qh, state.keys, state.vh, self.attn.projection_matrix)
+                sample = _fold_linear([(merged.reshape(T * Nq, -1), 1, 0)], self._W.linear, "none", 1)
+                sample = _fold_linear([(sample, 1, 0)], self.mu, "none", 1)
+                return self._fold_head(x_dec, sample, 1, 1, Nq)[0]
+            if state.kind == "latent":
+                return self._fold_head(x_dec, state.z, Nq, 1, Nq)[0]
+            return self._fold_head(x_dec, torch.zeros(T * Nq, 256, device=batch_test_images.device), 1, 1, Nq)[0]
