@@ -272,6 +272,24 @@ int mlhot_favor_query_fwd(const float* q, const void* state, const float* v, con
                           int T, int H, int Nq, int Nc, int d, int m, float* out,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* ---- cached context of the vanilla family: everything behind the encoder that sees the targets, ONE launch (csrc/np_query.h) ------
+ * mlhot_np_query_fwd: x_qry[T*Nq,dim_w] (the encoder's target rows) -> mu[T*Nq,y_dim] against a conditioned context, any Nq >= 1:
+ *   attention models with d->Nc > 0: key_state = mlhot_favor_keys_fwd's state for (T, 8 heads, Nc, dim_w, m_feat) and vh[T,Nc,8,dim_w]
+ *     (z NULL): per head the query projection, the query features, S V / D into the merged tile, then _W, r_to_z and decoder0;
+ *   every other case: z[T,dim_z] (the aggregated context through r_to_z, or zeros without a context shot; key_state, vh NULL):
+ *     decoder0([x | z[t]]).
+ * Grid task x 16-row target tile, no workspace, with the ROW-INVARIANCE guarantee of mlhot_favor_query_fwd: the bits of mu[t,n,:]
+ * depend on x_qry[t,n], the state, the parameters and the dimensions only.  d->Nq is ignored; of p the query-side fields are read
+ * (wq_*, wo_*, r2z_*, dec_*, proj).  Served (mlhot_np_query_supported): dim_w % 16 == 0, dim_w <= 64, dim_z % 4 == 0, dim_z <= 64,
+ * dec_hidden % 4 == 0, dec_hidden <= 128, y_dim <= 16 and, for the attention, dim_r == dim_w, Nc <= 32, 16 <= m_feat <= 272; 16-byte
+ * aligned pointers.  Otherwise MLHOT_ERR_UNSUPPORTED, nothing written.  Forward only; GPU build only.  Added within ABI 7: bindings
+ * look the symbols up.  (mlhot_np_dims / mlhot_np_params: "whole vanilla CNP/ANP model" below.) */
+struct mlhot_np_dims;
+struct mlhot_np_params;
+int mlhot_np_query_supported(const struct mlhot_np_dims* d);
+int mlhot_np_query_fwd(const struct mlhot_np_dims* d, const struct mlhot_np_params* p, const float* x_qry, int Nq,
+                       const void* key_state, const float* vh, const float* z, float* mu, void* stream);
+
 /* ---- strict sharded parity of the key stabiliser -------------------------
  * fast_attention.py:96-97 takes torch.max over the keys of the WHOLE batch.  When a caller shards the meta-batch over
  * ranks, each rank's launch sequence can be run in two halves around the caller's own collectives on `xchg`

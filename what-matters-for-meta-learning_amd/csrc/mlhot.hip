@@ -26,6 +26,7 @@
 #include "mlp_chain.h"
 #include "linear_rows.h"
 #include "favor_cached.h"
+#include "np_query.h"
 #include "resnet_trunk.h"
 #include "../../include/mlhot.h"
 
@@ -313,6 +314,13 @@ size_t mlhot_favor_query_ws_bytes(int T, int H, int Nq, int Nc, int d, int m) { 
 int mlhot_favor_query_fwd(const float* q, const void* state, const float* v, const float* proj, int T, int H, int Nq, int Nc,
                           int d, int m, float* out, void* ws, size_t ws_bytes, void* stream) {
   return favor_query_forward(q, state, v, proj, T, H, Nq, Nc, d, m, out, ws, ws_bytes, (hipStream_t)stream);
+}
+// the vanilla family's query tail against a conditioned context, one launch (csrc/np_query.h)
+int mlhot_np_query_supported(const mlhot_np_dims* d) { return d && np_query_ok(*d) ? 1 : 0; }
+int mlhot_np_query_fwd(const mlhot_np_dims* d, const mlhot_np_params* p, const float* x_qry, int Nq, const void* key_state, const float* vh,
+                       const float* z, float* mu, void* stream) {
+  if (!d || !p) { set_error("np_query_fwd: null dims/params"); return MLHOT_ERR_ARG; }
+  return np_query_forward(*d, *p, x_qry, Nq, key_state, vh, z, mu, (hipStream_t)stream);
 }
 // Staged passes (strict sharded parity of the key stabiliser, csrc/stab_xchg.h): stage 0 runs up to the rank-local scalar and
 // publishes it in xchg, stage 1 takes the batch-wide scalar from xchg and runs the rest.

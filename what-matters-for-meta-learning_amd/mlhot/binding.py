@@ -263,6 +263,9 @@ SIGNATURES = {
     "mlhot_favor_keys_fwd": (i, [P, P, i, i, i, i, i, P, z, P]),
     "mlhot_favor_query_ws_bytes": (z, [i] * 6),
     "mlhot_favor_query_fwd": (i, _qkvp + [P, P, z, P]),
+    # cached context of the vanilla family: the query tail in one launch
+    "mlhot_np_query_supported": (i, [_p(NpDims)]),
+    "mlhot_np_query_fwd": (i, [_p(NpDims), _p(NpParams), P, i, P, P, P, P, P]),
     # strict sharded parity of the key stabiliser
     "mlhot_favor_fwd_staged": (i, _qkvp + [P, P, z, i, P, P]),
     "mlhot_favor_bwd_staged": (i, _qkvp + [P, P, P, P, P, P, z, i, P, P]),
@@ -1344,6 +1347,45 @@ class MlhotLib:
         self._rc(self.c.mlhot_np_vanilla_fwd(C.byref(dims), C.byref(ps), _ptr(ctx_x), _ptr(ctx_y), _ptr(qry_x), _ptr(mu),
                                              _ptr(saved), _ptr(scratch), sb, _stream(qry_x)), "mlhot_np_vanilla_fwd")
         return mu, saved, scratch
+
+    # ---- cached context of the vanilla family (csrc/np_query.h) ------------------------------------------------
+    def np_query_supported(self, dims):
+        """Whether mlhot_np_query_fwd serves these dimensions (dims.Nq is not looked at; pointers are checked per call)."""
+        return bool(self._fn("np_query_supported", "mlhot_np_query_supported")(C.byref(dims)))
+
+    def np_query_fwd(self, dims, params, x_qry, key_state=None, vh=None, z=None, proj=None):
+        """x_qry [T, Nq, dim_w] (the encoder's target rows) -> mu [T, Nq, y_dim] in ONE launch, any Nq >= 1, against a conditioned
+        context: key_state (favor_keys_fwd's, for 8 heads) + vh [T, Nc, 8, dim_w] + proj for an attention model with dims.Nc > 0,
+        z [T, dim_z] otherwise.  params: state_dict key -> tensor; the query-side ones are read (_W_q, _W, r_to_z, decoder0)."""
+        fn = self._fn("np_query_fwd", "mlhot_np_query_fwd")
+        attend = dims.agg_mode == AGG["attention"] and dims.Nc > 0
+        if x_qry.dtype != torch.float32 or x_qry.dim() != 3 or x_qry.shape[0] != dims.T or x_qry.shape[1] < 1 or x_qry.shape[2] != dims.dim_w:
+            raise MlhotError(f"np_query_fwd: x_qry must be fp32 [T = {dims.T}, Nq >= 1, dim_w = {dims.dim_w}], got {x_qry.dtype} {tuple(x_qry.shape)}")
+        if attend:
+            want = (dims.T, dims.Nc, HEADS, dims.dim_w)
+            if key_state is None or vh is None or proj is None or z is not None or vh.dtype != torch.float32 or tuple(vh.shape) != want or \
+                    proj.dtype != torch.float32 or tuple(proj.shape) != (dims.m_feat, dims.dim_w) or key_state.dtype != torch.uint8:
+                raise MlhotError(f"np_query_fwd: the attention takes key_state (uint8), vh fp32 {want} and proj fp32 [{dims.m_feat}, {dims.dim_w}], no z")
+            if key_state.numel() < self.favor_keys_bytes(dims.T, HEADS, dims.Nc, dims.dim_w, dims.m_feat):
+                raise MlhotError("np_query_fwd: key_state is smaller than mlhot_favor_keys_bytes for these dimensions")
+        elif z is None or key_state is not None or vh is not None or z.dtype != torch.float32 or tuple(z.shape) != (dims.T, dims.dim_z):
+            raise MlhotError(f"np_query_fwd: without attention or context the call takes z fp32 [{dims.T}, {dims.dim_z}], no key_state / vh")
+        ps = NpParams()
+        used = []
+        for path, key in vanilla_param_map(dims.n_hidden, False, attend):
+            if path[0] in ("dec_w", "dec_b") or (attend and path[0] in ("r2z_w", "r2z_b", "wq_w", "wq_b", "wo_w", "wo_b")):
+                _set(ps, path, params[key].data_ptr())
+                used.append(params[key])
+        if attend:
+            ps.proj = proj.data_ptr()
+        live = [t for t in (x_qry, key_state, vh, z, proj, *used) if t is not None]
+        if any(t.device != x_qry.device for t in live):
+            raise MlhotError("np_query_fwd: x_qry, the state and the parameters must lie on one device")
+        _chk(*live)
+        mu = torch.empty(dims.T, x_qry.shape[1], dims.y_dim, device=x_qry.device)
+        self._rc(fn(C.byref(dims), C.byref(ps), _ptr(x_qry), x_qry.shape[1], _ptr(key_state), _ptr(vh), _ptr(z), _ptr(mu), _stream(x_qry)),
+                 "mlhot_np_query_fwd")
+        return mu
 
     def np_vanilla_bwd(self, dims, params, ctx_x, ctx_y, qry_x, mu, dmu, saved, scratch=None, proj=None, exchange=None, loss=None):
         """loss: None, or (kind, gt, dloss[, value]) - the loss whose gradient the call takes itself (mlhot_np_vanilla_bwd_loss): the

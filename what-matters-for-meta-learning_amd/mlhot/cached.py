@@ -1,0 +1,196 @@
+"""Cached-context inference as functions: `condition` once, `predict` for any targets.
+
+    state = mlhot.cached.condition(model, ctx_x, ctx_y)
+    mu = mlhot.cached.predict(model, state, qry_x, chunk=None)        # [T, Nq, y_dim]
+    ok, reason = mlhot.cached.supports(model)
+
+For a ResNetNP instance the two functions are `model.condition` / `model.predict`.  For the vanilla 128x128x1 family (the classes
+whose forward is VanillaNP.forward: CNPVanillaPascal1D, CNPShapeNet1D, ANPVanillaPascal1D, ANPShapeNet1D) they run the path of this
+module - the classes themselves gain no attribute.  `condition` does everything of `forward(..., test=True)` that does not see the
+targets, from existing entries; `predict` runs the encoder on the target images and then ONE launch, mlhot_np_query_fwd
+(csrc/np_query.h; route "fused"), or - for dimensions that kernel does not serve - the same mathematics from linear_rows and
+favor_query (route "composed").  `predict(condition(cx, cy), qx)` equals `model(cx, cy, qx, test=True)[0]` to the kernels'
+tolerance, not to the bit.  Eval mode only; a state serves the T tasks it was conditioned on and dies with the next weight update.
+"""
+import logging
+
+import torch
+
+from mlhot import lib
+from mlhot.binding import HEADS
+from mlhot.ops import LinearFunction, _c, _need_gpu, favor_keys, favor_query, linear_rows
+from networks._resnet_np import ResNetNP
+from networks._vanilla import VanillaNP
+from networks._vanilla_mr import VanillaMR
+
+ROUTES = ("fused", "composed")
+_FRESH_WEIGHTS = ("Bayes-by-backprop draws fresh weights in every forward, so a cached context is not the reference's forward")
+_logged = set()
+
+
+class VanillaContextState:
+    """What condition leaves for predict on a vanilla model.  `kind`: "attention" - `keys` (mlhot.ops.FavorKeyState for 8 heads) and
+    the value heads `vh` [T, Nc, 8, dim_w]; "latent" - `z` [T, dim_z], the aggregated context through r_to_z; "empty" - no context
+    shot, `z` zeros.  `owner` is the model, `fingerprint` its parameters' and buffers' versions when the state was made.  `route`
+    is the route the last predict on this state took ("fused" | "composed"; None before the first)."""
+
+    def __init__(self, owner, T, Nc, fingerprint, kind, keys=None, vh=None, z=None, wq=None):
+        self.owner, self.T, self.Nc, self.fingerprint, self.kind = owner, T, Nc, fingerprint, kind
+        self.keys, self.vh, self.z, self.wq, self.route = keys, vh, z, wq, None
+
+
+def supports(model):
+    """(bool, reason): whether condition / predict serve this model, and through what - or why not."""
+    if isinstance(model, ResNetNP):
+        if model.PREFIX_SWEEP_REFUSAL:
+            return False, _FRESH_WEIGHTS
+        return True, "ResNetNP.condition / predict"
+    if type(model).forward is VanillaNP.forward:
+        return True, "the vanilla family's query tail (mlhot_np_query_fwd)"
+    if isinstance(model, VanillaMR):
+        return False, _FRESH_WEIGHTS
+    return False, "cached-context inference is not built for this class"
+
+
+def _fingerprint(model):
+    return tuple(p._version for p in model.parameters()) + tuple(b._version for b in model.buffers())
+
+
+def _refuse(model, what):
+    ok, reason = supports(model)
+    if not ok:
+        raise ValueError(f"{type(model).__name__}: mlhot.cached.{what}: {reason}")
+    if model.training:
+        raise ValueError(f"{what} is a test-mode path: call model.eval() first")
+
+
+def _enc_params(model):
+    e = model.encoder_w0
+    return tuple(t.detach() for i in (0, 2, 5, 8) for t in (e[i].weight, e[i].bias))
+
+
+def _encode(model, imgs):
+    """[T, N, 1, 128, 128] -> the encoder's rows [T * N, dim_w] (mlhot_enc_vanilla_fwd; its `saved` buffer dies here)."""
+    flat = _c(imgs.reshape(-1, model.img_channels, model.img_size[0], model.img_size[1]).float())
+    return lib().enc_vanilla_fwd(flat, None, _enc_params(model), model.dim_w)[0]
+
+
+def _stacked(mods):
+    return (torch.cat([m.linear.weight.detach() for m in mods], dim=0), torch.cat([m.linear.bias.detach() for m in mods], dim=0))
+
+
+def condition(model, ctx_x, ctx_y):
+    """(ctx images [T, Nc, ...], ctx labels [T, Nc, L]) -> the state for predict: ResNetNP.condition for that family; for the
+    vanilla family the encoder, transform_y and encoder_r, then the key / value heads and mlhot.ops.favor_keys (attention) or the
+    aggregation and r_to_z (mean / max / baco).  No new kernel; the row count is T * Nc whatever follows."""
+    if isinstance(model, ResNetNP):
+        return model.condition(ctx_x, ctx_y)
+    _refuse(model, "condition")
+    T, Nc = ctx_x.shape[0], ctx_x.shape[1]
+    if T != model.task_num:
+        raise ValueError(f"condition: {T} tasks, the model was built for tasks_per_batch = {model.task_num}")
+    _need_gpu(ctx_x, ctx_y, *model.parameters())
+    with torch.no_grad():
+        wq = _stacked(model._W_q) if model.ATTENTION else None
+        if Nc == 0:
+            return VanillaContextState(model, T, 0, _fingerprint(model), "empty", z=torch.zeros(T, model.dim_z, device=ctx_x.device), wq=wq)
+        model._check_agg()
+        x_ctx = _encode(model, ctx_x)
+        ly = LinearFunction.apply(ctx_y.reshape(T * Nc, -1), model.transform_y.weight, model.transform_y.bias, "none")
+        rs = model.encoder_r(torch.cat([x_ctx, ly], dim=1))
+        if model.ATTENTION:
+            kh = LinearFunction.apply(x_ctx, *_stacked(model._W_k), "none").view(T, Nc, HEADS, -1)
+            vh = LinearFunction.apply(rs, *_stacked(model._W_v), "none").view(T, Nc, HEADS, -1)
+            keys = favor_keys(kh, model.attn.projection_matrix)
+            return VanillaContextState(model, T, Nc, _fingerprint(model), "attention", keys=keys, vh=vh.contiguous(), wq=wq)
+        lv = None
+        if model.agg_mode == "baco":         # csrc/np_vanilla.h's order: rs_to_mu, rs_to_var, then the aggregation
+            lv = LinearFunction.apply(rs, model.rs_to_var.weight, model.rs_to_var.bias, "none").view(T, Nc, -1)
+            rs = LinearFunction.apply(rs, model.rs_to_mu.weight, model.rs_to_mu.bias, "none")
+        r = lib().agg_fwd(model.agg_mode, rs.view(T, Nc, -1), lv)[0]
+        z = LinearFunction.apply(r, model.r_to_z.weight, model.r_to_z.bias, "none")
+        return VanillaContextState(model, T, Nc, _fingerprint(model), "latent", z=z)
+
+
+def predict(model, state, qry_x, chunk=None, route=None):
+    """(state, target images [T, Nq, ...]) -> mu [T, Nq, y_dim] = `model(ctx, labels, targets, test=True)[0]` for the context the
+    state was made from, any Nq >= 1.  `chunk` bounds the targets per launch sequence (and the encoder's activations with them).
+    `route`: None picks "fused" where mlhot_np_query_supported says yes and "composed" otherwise; a test may force either.  The
+    state's `route` says which one ran."""
+    if isinstance(model, ResNetNP):
+        if route is not None:
+            raise ValueError("predict: route= belongs to the vanilla family")
+        return model.predict(state, qry_x, chunk=chunk)
+    _refuse(model, "predict")
+    if not isinstance(state, VanillaContextState) or state.owner is not model:
+        raise ValueError("predict: the state was not made by this model's condition()")
+    if qry_x.shape[0] != state.T or state.T != model.task_num:
+        raise ValueError(f"predict: the state holds {state.T} tasks, the targets {qry_x.shape[0]} (the key stabiliser is the maximum "
+                         "over the conditioned batch: predict serves the same tasks)")
+    if state.fingerprint != _fingerprint(model):
+        raise ValueError("predict: the state is stale - a parameter of the model changed since condition()")
+    Nq = qry_x.shape[1]
+    if Nq < 1:
+        raise ValueError("predict needs at least one target")
+    if chunk is not None and int(chunk) < 1:
+        raise ValueError(f"predict: chunk must be a positive number of targets, got {chunk}")
+    if route is not None and route not in ROUTES:
+        raise ValueError(f"predict: route must be one of {ROUTES}, got {route!r}")
+    _need_gpu(qry_x)
+    dims = model._dims(state.Nc, 1)
+    if route is None:
+        route = "fused" if lib().np_query_supported(dims) and (state.keys is None or state.keys.route == "cached") else "composed"
+        if route == "composed" and type(model).__name__ not in _logged:
+            _logged.add(type(model).__name__)
+            logging.getLogger(__name__).info("mlhot.cached.predict: %s's dimensions are outside mlhot_np_query_fwd's envelope; the query tail "
+                                             "runs composed from linear_rows / favor_query", type(model).__name__)
+    state.route = route
+    step = Nq if chunk is None else min(int(chunk), Nq)
+    with torch.no_grad():
+        out = [_predict_targets(model, state, qry_x[:, i:i + step], dims, route) for i in range(0, Nq, step)]
+    return out[0] if len(out) == 1 else torch.cat(out, dim=1)
+
+
+def _rows(sources, lin_w, lin_b, act):
+    """linear_rows, or - for a layer it does not serve (logged once) - LinearFunction on the gathered rows."""
+    k0, k1 = sources[0][0].shape[1], sources[1][0].shape[1] if len(sources) > 1 else 0
+    if lib().linear_rows_supported(k0, k1, lin_w.shape[0]):
+        return linear_rows(sources, lin_w, lin_b, act)
+    if (k0, k1, lin_w.shape[0]) not in _logged:
+        _logged.add((k0, k1, lin_w.shape[0]))
+        logging.getLogger(__name__).info("mlhot.cached.predict: no row-invariant kernel for a Linear [%d | %d] -> %d", k0, k1, lin_w.shape[0])
+    x = torch.cat([x.repeat_interleave(rep, dim=0) if rep > 1 else x for x, rep, _ in sources], dim=1)
+    return LinearFunction.apply(x, lin_w, lin_b, act)
+
+
+def composed_tail(params, x_qry, T, Nq, tanh, keys=None, vh=None, proj=None, z=None, wq=None):
+    """The query tail from the existing row-invariant operators - the yardstick of the fused launch and the route for dimensions
+    it does not serve.  params: state_dict key -> tensor; x_qry [T * Nq, dim_w]; attention: keys (FavorKeyState), vh, proj (wq: the
+    stacked _W_q weight and bias, else stacked here); otherwise z [T, dim_z].  -> mu [T, Nq, y_dim]."""
+    def lin(sources, name, act="none"):
+        return _rows(sources, params[name + ".weight"], params[name + ".bias"], act)
+    if keys is not None:
+        w, b = wq if wq is not None else (torch.cat([params[f"_W_q.{i}.linear.weight"] for i in range(HEADS)]),
+                                          torch.cat([params[f"_W_q.{i}.linear.bias"] for i in range(HEADS)]))
+        qh = _rows([(x_qry, 1, 0)], w, b, "none").view(T, Nq, HEADS, -1)
+        merged = favor_query(qh, keys, vh, proj).view(T * Nq, -1)
+        zq = lin([(lin([(merged, 1, 0)], "_W.linear"), 1, 0)], "r_to_z")
+        h = lin([(x_qry, 1, 0), (zq, 1, 0)], "decoder0.0", "relu")
+    else:
+        h = lin([(x_qry, 1, 0), (z, Nq, 0)], "decoder0.0", "relu")
+    h = lin([(h, 1, 0)], "decoder0.2", "relu")
+    return lin([(h, 1, 0)], "decoder0.4", "tanh" if tanh else "none").view(T, Nq, -1)
+
+
+def _predict_targets(model, state, qry_x, dims, route):
+    T, Nq = qry_x.shape[0], qry_x.shape[1]
+    x_qry = _encode(model, qry_x)
+    proj = _c(model.attn.projection_matrix) if model.ATTENTION else None
+    params = {k: _c(p.detach()) for k, p in model.named_parameters()}
+    if state.kind != "attention":
+        if route == "fused":
+            return lib().np_query_fwd(dims, params, x_qry.view(T, Nq, -1), z=state.z)
+        return composed_tail(params, x_qry, T, Nq, model.OUT_TANH, z=state.z)
+    if route == "fused":
+        return lib().np_query_fwd(dims, params, x_qry.view(T, Nq, -1), key_state=state.keys.buf, vh=state.vh, proj=proj)
+    return composed_tail(params, x_qry, T, Nq, model.OUT_TANH, keys=state.keys, vh=state.vh, proj=proj, wq=state.wq)
