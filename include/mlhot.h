@@ -272,6 +272,22 @@ int mlhot_favor_query_fwd(const float* q, const void* state, const float* v, con
                           int T, int H, int Nq, int Nc, int d, int m, float* out,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* ---- cached context with per-task context sizes: the masked key state (csrc/favor_cached.h) ---------------------
+ * mlhot_favor_keys_ragged_fwd: mlhot_favor_keys_fwd with lens[T] (int32, DEVICE memory, read on the device: no host synchronisation,
+ *   the call stays capturable).  Row n of task t is a context shot iff n < lens[t], 1 <= lens[t] <= Nc (the caller's contract; the
+ *   kernels hold a value outside it to that range).  Layout, mlhot_favor_keys_bytes and envelope are mlhot_favor_keys_fwd's: F_k first,
+ *   then M.  M is the maximum of dd_k over the VALID rows of all T tasks; valid rows hold ratio (exp(dd_k - diag_k - M) + 1e-4), every
+ *   feature (all mp) of an invalid row is exactly 0.0f.  An invalid row of k is never read - it may hold anything, NaN and Inf
+ *   included.  With lens[t] == Nc for every t the state equals mlhot_favor_keys_fwd's bit for bit.
+ * What a zero row means to the query kernels (mlhot_favor_query_fwd, mlhot_np_query_fwd, both unchanged): its column of
+ *   S = F_q F_k^T is exactly 0, so it adds nothing to D = rowsum(S) nor to out = S V / D - the state serves them as any other, with
+ *   the row invariance they guarantee.  v's invalid rows must be FINITE (callers zero-fill them): S is exactly 0 there, and
+ *   0 x NaN is not.
+ * lens == NULL: MLHOT_ERR_ARG.  Outside the envelope: MLHOT_ERR_UNSUPPORTED, nothing written (there is no masked form of
+ * mlhot_favor_fwd to fall back on).  Forward only; GPU build only.  Added within ABI 7: bindings look the symbol up. */
+int mlhot_favor_keys_ragged_fwd(const float* k, const float* proj, const int32_t* lens /* [T], device */,
+                                int T, int H, int Nc, int d, int m, void* state, size_t state_bytes, void* stream);
+
 /* ---- cached context of the vanilla family: everything behind the encoder that sees the targets, ONE launch (csrc/np_query.h) ------
  * mlhot_np_query_fwd: x_qry[T*Nq,dim_w] (the encoder's target rows) -> mu[T*Nq,y_dim] against a conditioned context, any Nq >= 1:
  *   attention models with d->Nc > 0: key_state = mlhot_favor_keys_fwd's state for (T, 8 heads, Nc, dim_w, m_feat) and vh[T,Nc,8,dim_w]

@@ -8,6 +8,8 @@
 //   query  grid (task x head x 16-row query tile), ONE launch for any Nq >= 1:
 //          dd_q = (c q) P^T into LDS, row maxima, F_q in place, S = F_q F_k^T over all m features, D, out = S V / D (merged order)
 // State (floats): F_k [T][H][Nc][mp], mp = m rounded up to 16; then M at offset T H Nc mp; then K1's workgroup maxima.
+// Per-task context sizes: the key launches have a masked instantiation - rows n >= lens[t] are never read, stay
+// out of M and are exact zeros in F_k; such a row's column of S is 0, so the query launch serves that state unchanged.
 //
 // ROW INVARIANCE of the query launch, as for linear_rows.h: the bits of out[t, n, :] depend on q[t, n], the state, v, proj and the
 // dimensions - not on Nq, on n, on the row's place in its tile, on the grid or on the other query rows.  What makes it so:
@@ -130,37 +132,58 @@ __device__ __forceinline__ float stage_row(const float* xrow, float* xs_row, int
 }
 
 // ---- keys, launch 1: dd_k into the state, the workgroup's maximum ------------------------------------------------------------
-template <int RT>
-__global__ __launch_bounds__(256) void keys1_kernel(const Args a) {
+// RAG (mlhot_favor_keys_ragged_fwd): row n of task t is a context shot iff n < lens[t].  Rows behind it are never
+// read (they are staged as zeros), never stored and never enter the maximum - selected by row index, so a NaN there goes nowhere;
+// a 16-row tile wholly behind lens[t] skips its MFMAs (lens[t] is one scalar per workgroup: wave-uniform).  K2 writes their zeros.
+// RAG == false is the code of mlhot_favor_keys_fwd as it was: `len` is Nc at compile time and every masked branch folds away.
+template <int RTA, bool RAG>
+__device__ __forceinline__ float keys1_store(const f32x4_t (&acc)[RTA][NT], const Args& a, int th, int f0, int lr, int lq, int len, float best) {
+  const int m = a.m, mp = a.mp, Nc = a.Nc;
+#pragma unroll
+  for (int i = 0; i < RTA; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 16 * i + 4 * lq + r;
+      if (row >= (RAG ? len : Nc)) continue;
+      float* drow = a.fkw + ((size_t)th * Nc + row) * mp;
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        const int fj = f0 + 16 * j + lr;
+        if (fj < mp) drow[fj] = fj < m ? acc[i][j][r] : 0.f;
+        if (fj < m) best = fmaxf(best, acc[i][j][r]);
+      }
+    }
+  return best;
+}
+
+// lens[t] held to 1 .. Nc: the host checks the values (mlhot.ops.favor_keys); the clamp keeps every index in bounds whatever arrives
+__device__ __forceinline__ int ragged_len(const int32_t* lens, int t, int Nc) { return min(max((int)lens[t], 1), Nc); }
+
+template <int RT, bool RAG>
+__device__ __forceinline__ void keys1_body(const Args& a, const int32_t* lens) {
   __shared__ __attribute__((aligned(16))) float xs[16 * RT * LDX];
   __shared__ float s_w[4];
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, lq = lane >> 4;
   const int th = blockIdx.x, t = th / a.H, h = th % a.H, chunk = blockIdx.y;
   const int d = a.d, m = a.m, Nc = a.Nc, mp = a.mp;
+  const int len = RAG ? ragged_len(lens, t, Nc) : Nc;
   for (int r = tid >> 3; r < 16 * RT; r += 32) {
-    const float* xrow = r < Nc ? a.x + ((size_t)(t * Nc + r) * a.H + h) * d : nullptr;
+    const float* xrow = r < len ? a.x + ((size_t)(t * Nc + r) * a.H + h) * d : nullptr;
     stage_row<8>(xrow, xs + r * LDX, d, tid & 7, a.c);
   }
   __syncthreads();
   const int f0 = chunk * KCH + wv * WF;
   float best = -INFINITY;
   if (f0 < mp) {
-    f32x4_t acc[RT][NT];
-    dd_tiles<RT>(xs, a.proj, d, m, f0, lr, lq, acc);
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * i + 4 * lq + r;
-        if (row >= Nc) continue;
-        float* drow = a.fkw + ((size_t)th * Nc + row) * mp;
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          const int fj = f0 + 16 * j + lr;
-          if (fj < mp) drow[fj] = fj < m ? acc[i][j][r] : 0.f;
-          if (fj < m) best = fmaxf(best, acc[i][j][r]);
-        }
-      }
+    if (RAG && RT == 2 && len <= 16) {          // the second tile holds no context shot: the first tile's chains alone, the same per element
+      f32x4_t acc[1][NT];
+      dd_tiles<1>(xs, a.proj, d, m, f0, lr, lq, acc);
+      best = keys1_store<1, RAG>(acc, a, th, f0, lr, lq, len, best);
+    } else {
+      f32x4_t acc[RT][NT];
+      dd_tiles<RT>(xs, a.proj, d, m, f0, lr, lq, acc);
+      best = keys1_store<RT, RAG>(acc, a, th, f0, lr, lq, len, best);
+    }
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) best = fmaxf(best, __shfl_xor(best, off, 64));
@@ -169,12 +192,21 @@ __global__ __launch_bounds__(256) void keys1_kernel(const Args a) {
   if (tid == 0) a.part[(size_t)th * a.nch + chunk] = fmaxf(fmaxf(s_w[0], s_w[1]), fmaxf(s_w[2], s_w[3]));
 }
 
+template <int RT>
+__global__ __launch_bounds__(256) void keys1_kernel(const Args a) { keys1_body<RT, false>(a, nullptr); }
+template <int RT>
+__global__ __launch_bounds__(256) void keys1_ragged_kernel(const Args a, const int32_t* lens) { keys1_body<RT, true>(a, lens); }
+
 // ---- keys, launch 2: M, diag_k, F_k = ratio exp(dd - diag - M) + ratio 1e-4 in place ----------------------------------------
-__global__ __launch_bounds__(256) void keys2_kernel(const Args a) {
+// RAG: every workgroup of K1 held a valid row (lens[t] >= 1), so the fold of the maxima is unchanged; rows n >= lens[t] get exact
+// zeros over all mp features without a read of k or of the state.
+template <bool RAG>
+__device__ __forceinline__ void keys2_body(const Args& a, const int32_t* lens) {
   __shared__ float s_w[4], s_diag[MAXNC];
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int th = blockIdx.x, t = th / a.H, h = th % a.H;
   const int d = a.d, m = a.m, Nc = a.Nc, mp = a.mp;
+  const int len = RAG ? ragged_len(lens, t, Nc) : Nc;
   float best = -INFINITY;
   for (int i = tid; i < a.T * a.H * a.nch; i += 256) best = fmaxf(best, a.part[i]);
 #pragma unroll
@@ -182,7 +214,7 @@ __global__ __launch_bounds__(256) void keys2_kernel(const Args a) {
   if (lane == 0) s_w[wv] = best;
   {
     const int r = tid >> 3;            // 32 rows x 8 threads
-    const float* xrow = r < Nc ? a.x + ((size_t)(t * Nc + r) * a.H + h) * d : nullptr;
+    const float* xrow = r < len ? a.x + ((size_t)(t * Nc + r) * a.H + h) * d : nullptr;
     const float s = stage_row<8>(xrow, nullptr, d, tid & 7, 0.f);
     if (r < Nc && (tid & 7) == 0) s_diag[r] = 0.5f * a.c * a.c * s;
   }
@@ -193,6 +225,7 @@ __global__ __launch_bounds__(256) void keys2_kernel(const Args a) {
   float* blk = a.fkw + (size_t)th * Nc * mp;
   for (int idx = tid; idx < Nc * q4; idx += 256) {
     const int row = idx / q4, j = 4 * (idx - row * q4);
+    if (RAG && row >= len) { *reinterpret_cast<float4*>(blk + (size_t)row * mp + j) = make_float4(0.f, 0.f, 0.f, 0.f); continue; }
     const float sub = s_diag[row] + M;
     float4 e = *reinterpret_cast<const float4*>(blk + (size_t)row * mp + j);
     e.x = j < m ? a.ratio * expf(e.x - sub) + a.re : 0.f; e.y = j + 1 < m ? a.ratio * expf(e.y - sub) + a.re : 0.f;
@@ -200,6 +233,9 @@ __global__ __launch_bounds__(256) void keys2_kernel(const Args a) {
     *reinterpret_cast<float4*>(blk + (size_t)row * mp + j) = e;
   }
 }
+
+__global__ __launch_bounds__(256) void keys2_kernel(const Args a) { keys2_body<false>(a, nullptr); }
+__global__ __launch_bounds__(256) void keys2_ragged_kernel(const Args a, const int32_t* lens) { keys2_body<true>(a, lens); }
 
 // ---- query: one workgroup per (task, head, 16 query rows) -------------------------------------------------------------------
 __global__ __launch_bounds__(256) void query_kernel(const Args a) {
@@ -351,33 +387,53 @@ inline size_t favor_query_ws_need(int T, int H, int Nq, int Nc, int d, int m) { 
 inline bool fc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 #endif
 
-inline int favor_keys_forward(const float* k, const float* proj, int T, int H, int Nc, int d, int m, void* state, size_t state_bytes,
-                              hipStream_t s) {
-  if (T <= 0 || H <= 0 || Nc <= 0 || d <= 0 || m <= 0 || !k || !proj || !state) { set_error("favor_keys_fwd: bad argument"); return MLHOT_ERR_ARG; }
+// lens == nullptr: mlhot_favor_keys_fwd; otherwise mlhot_favor_keys_ragged_fwd - the same state, the masked instantiations
+inline int favor_keys_launch(const char* what, const float* k, const float* proj, const int32_t* lens, bool ragged, int T, int H, int Nc, int d, int m,
+                             void* state, size_t state_bytes, hipStream_t s) {
+  if (T <= 0 || H <= 0 || Nc <= 0 || d <= 0 || m <= 0 || !k || !proj || !state || (ragged && !lens)) { set_error("%s: bad argument", what); return MLHOT_ERR_ARG; }
   if (!favor_cached_ok(T, H, Nc, d, m)) {
-    set_error("favor_keys_fwd serves Nc <= 32, d %% 16 == 0, d <= 256, 16 <= m <= 1536 on the GPU build (got Nc=%d d=%d m=%d)", Nc, d, m);
+    set_error("%s serves Nc <= 32, d %% 16 == 0, d <= 256, 16 <= m <= 1536 on the GPU build (got Nc=%d d=%d m=%d)", what, Nc, d, m);
     return MLHOT_ERR_UNSUPPORTED;
   }
 #ifdef MLHOT_HOSTSIM
   (void)state_bytes; (void)s; return MLHOT_ERR_UNSUPPORTED;
 #else
   const fc::State st = fc::carve_state(T, H, Nc, m, state);
-  if (state_bytes < st.floats * sizeof(float)) { set_error("favor_keys_fwd: state too small (%zu < %zu)", state_bytes, st.floats * sizeof(float)); return MLHOT_ERR_WORKSPACE; }
-  if (!fc_aligned16(k) || !fc_aligned16(proj) || !fc_aligned16(state)) { set_error("favor_keys_fwd: k, proj and state must be 16-byte aligned"); return MLHOT_ERR_ARG; }
+  if (state_bytes < st.floats * sizeof(float)) { set_error("%s: state too small (%zu < %zu)", what, state_bytes, st.floats * sizeof(float)); return MLHOT_ERR_WORKSPACE; }
+  if (!fc_aligned16(k) || !fc_aligned16(proj) || !fc_aligned16(state)) { set_error("%s: k, proj and state must be 16-byte aligned", what); return MLHOT_ERR_ARG; }
   fc::Args a = fc::make_args(T, H, 0, Nc, d, m, st);
   a.x = k; a.proj = proj;
+  const char* l1 = ragged ? "favor.keys1r" : "favor.keys1";
+  const char* l2 = ragged ? "favor.keys2r" : "favor.keys2";
   {
-    ProfScope ps("favor.keys1", s);
-    if (Nc <= 16) hipLaunchKernelGGL((fc::keys1_kernel<1>), dim3(T * H, st.nch), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((fc::keys1_kernel<2>), dim3(T * H, st.nch), dim3(256), 0, s, a);
+    ProfScope ps(l1, s);
+    if (ragged) {
+      if (Nc <= 16) hipLaunchKernelGGL((fc::keys1_ragged_kernel<1>), dim3(T * H, st.nch), dim3(256), 0, s, a, lens);
+      else hipLaunchKernelGGL((fc::keys1_ragged_kernel<2>), dim3(T * H, st.nch), dim3(256), 0, s, a, lens);
+    } else {
+      if (Nc <= 16) hipLaunchKernelGGL((fc::keys1_kernel<1>), dim3(T * H, st.nch), dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((fc::keys1_kernel<2>), dim3(T * H, st.nch), dim3(256), 0, s, a);
+    }
   }
-  MLHOT_TRY(check_launch("favor.keys1"));
+  MLHOT_TRY(check_launch(l1));
   {
-    ProfScope ps("favor.keys2", s);
-    hipLaunchKernelGGL(fc::keys2_kernel, dim3(T * H), dim3(256), 0, s, a);
+    ProfScope ps(l2, s);
+    if (ragged) hipLaunchKernelGGL(fc::keys2_ragged_kernel, dim3(T * H), dim3(256), 0, s, a, lens);
+    else hipLaunchKernelGGL(fc::keys2_kernel, dim3(T * H), dim3(256), 0, s, a);
   }
-  return check_launch("favor.keys2");
+  return check_launch(l2);
 #endif
+}
+
+inline int favor_keys_forward(const float* k, const float* proj, int T, int H, int Nc, int d, int m, void* state, size_t state_bytes,
+                              hipStream_t s) {
+  return favor_keys_launch("favor_keys_fwd", k, proj, nullptr, false, T, H, Nc, d, m, state, state_bytes, s);
+}
+
+// lens[T] int32 on the device, read there: no host synchronisation, so the call stays capturable
+inline int favor_keys_ragged_forward(const float* k, const float* proj, const int32_t* lens, int T, int H, int Nc, int d, int m, void* state,
+                                     size_t state_bytes, hipStream_t s) {
+  return favor_keys_launch("favor_keys_ragged_fwd", k, proj, lens, true, T, H, Nc, d, m, state, state_bytes, s);
 }
 
 inline int favor_query_forward(const float* q, const void* state, const float* v, const float* proj, int T, int H, int Nq, int Nc, int d, int m,

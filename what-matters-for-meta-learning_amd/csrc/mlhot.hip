@@ -310,6 +310,11 @@ size_t mlhot_favor_keys_bytes(int T, int H, int Nc, int d, int m) { return favor
 int mlhot_favor_keys_fwd(const float* k, const float* proj, int T, int H, int Nc, int d, int m, void* state, size_t state_bytes, void* stream) {
   return favor_keys_forward(k, proj, T, H, Nc, d, m, state, state_bytes, (hipStream_t)stream);
 }
+// the same state for per-task context sizes: rows n >= lens[t] are no context shots
+int mlhot_favor_keys_ragged_fwd(const float* k, const float* proj, const int32_t* lens, int T, int H, int Nc, int d, int m, void* state,
+                                size_t state_bytes, void* stream) {
+  return favor_keys_ragged_forward(k, proj, lens, T, H, Nc, d, m, state, state_bytes, (hipStream_t)stream);
+}
 size_t mlhot_favor_query_ws_bytes(int T, int H, int Nq, int Nc, int d, int m) { return favor_query_ws_need(T, H, Nq, Nc, d, m); }
 int mlhot_favor_query_fwd(const float* q, const void* state, const float* v, const float* proj, int T, int H, int Nq, int Nc,
                           int d, int m, float* out, void* ws, size_t ws_bytes, void* stream) {

@@ -263,6 +263,8 @@ SIGNATURES = {
     "mlhot_favor_keys_fwd": (i, [P, P, i, i, i, i, i, P, z, P]),
     "mlhot_favor_query_ws_bytes": (z, [i] * 6),
     "mlhot_favor_query_fwd": (i, _qkvp + [P, P, z, P]),
+    # cached context with per-task context sizes: the masked key state
+    "mlhot_favor_keys_ragged_fwd": (i, [P, P, P, i, i, i, i, i, P, z, P]),
     # cached context of the vanilla family: the query tail in one launch
     "mlhot_np_query_supported": (i, [_p(NpDims)]),
     "mlhot_np_query_fwd": (i, [_p(NpDims), _p(NpParams), P, i, P, P, P, P, P]),
@@ -1025,6 +1027,26 @@ class MlhotLib:
         state = self._bytes(nb, k)
         fn = self._fn("favor_keys_fwd", "mlhot_favor_keys_fwd")
         self._rc(fn(_ptr(k), _ptr(proj), T, H, Nc, d, m, _ptr(state), state.numel(), _stream(k)), "mlhot_favor_keys_fwd")
+        return state
+
+    def favor_keys_ragged_fwd(self, k, proj, lens):
+        """favor_keys_fwd with lens [T] (int32, on k's device): row n of task t is a context shot iff n < lens[t].  The same state
+        layout; M over the valid rows only, invalid rows exact zeros, their k never read (include/mlhot.h).  The values of lens are
+        the caller's to check (1 .. Nc): they are read on the device.  Forward only."""
+        fn = self._fn("favor_keys_ragged_fwd", "mlhot_favor_keys_ragged_fwd")
+        if k.dtype != torch.float32 or k.dim() != 4 or proj.dtype != torch.float32 or proj.dim() != 2 or proj.shape[1] != k.shape[3] or proj.device != k.device:
+            raise MlhotError(f"favor_keys_ragged_fwd: k must be fp32 [T, Nc, H, d] and proj fp32 [m, d] on one device, got {tuple(k.shape)}, {tuple(proj.shape)}")
+        T, Nc, H, d = k.shape
+        if lens.dtype != torch.int32 or tuple(lens.shape) != (T,) or lens.device != k.device:
+            raise MlhotError(f"favor_keys_ragged_fwd: lens must be int32 [{T}] on {k.device}, got {lens.dtype} {tuple(lens.shape)} on {lens.device}")
+        m = proj.shape[0]
+        nb = self.favor_keys_bytes(T, H, Nc, d, m)
+        if not nb:
+            raise MlhotError(f"favor_keys_ragged_fwd serves Nc <= 32, d % 16 == 0, d <= 256, 16 <= m <= 1536 (got Nc={Nc} d={d} m={m}); "
+                             "there is no masked form outside that envelope")
+        _chk(k, proj, lens)
+        state = self._bytes(nb, k)
+        self._rc(fn(_ptr(k), _ptr(proj), _ptr(lens), T, H, Nc, d, m, _ptr(state), state.numel(), _stream(k)), "mlhot_favor_keys_ragged_fwd")
         return state
 
     @staticmethod

@@ -1,6 +1,7 @@
 """Cached-context inference as functions: `condition` once, `predict` for any targets.
 
-    state = mlhot.cached.condition(model, ctx_x, ctx_y)
+    state = mlhot.cached.condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None)
+    state = mlhot.cached.extend(model, state, new_x, new_y, new_len=None)        # more context shots, only they are encoded (6c-3)
     mu = mlhot.cached.predict(model, state, qry_x, chunk=None)        # [T, Nq, y_dim]
     ok, reason = mlhot.cached.supports(model)
 
@@ -16,7 +17,7 @@ import logging
 
 import torch
 
-from mlhot import lib
+from mlhot import lib, ragged
 from mlhot.binding import HEADS
 from mlhot.ops import LinearFunction, _c, _need_gpu, favor_keys, favor_query, linear_rows
 from networks._resnet_np import ResNetNP
@@ -32,11 +33,17 @@ class VanillaContextState:
     """What condition leaves for predict on a vanilla model.  `kind`: "attention" - `keys` (mlhot.ops.FavorKeyState for 8 heads) and
     the value heads `vh` [T, Nc, 8, dim_w]; "latent" - `z` [T, dim_z], the aggregated context through r_to_z; "empty" - no context
     shot, `z` zeros.  `owner` is the model, `fingerprint` its parameters' and buffers' versions when the state was made.  `route`
-    is the route the last predict on this state took ("fused" | "composed"; None before the first)."""
+    is the route the last predict on this state took ("fused" | "composed"; None before the first).
 
-    def __init__(self, owner, T, Nc, fingerprint, kind, keys=None, vh=None, z=None, wq=None):
+    For extend the state also keeps `lens` (context shots per task, host ints), `capacity` (slots per task: `Nc`
+    is the capacity, what the kernels see) and the per-shot rows in slot order [T, capacity, ...]: `kh` and the zero-filled `vh`
+    (attention), `rs` - baco: rs_to_mu's output - and `lv` (latent), with `r`, the aggregate before r_to_z."""
+
+    def __init__(self, owner, T, Nc, fingerprint, kind, keys=None, vh=None, z=None, wq=None, lens=None, kh=None, rs=None, lv=None, r=None):
         self.owner, self.T, self.Nc, self.fingerprint, self.kind = owner, T, Nc, fingerprint, kind
         self.keys, self.vh, self.z, self.wq, self.route = keys, vh, z, wq, None
+        self.lens, self.capacity = (Nc,) * T if lens is None else tuple(lens), Nc
+        self.kh, self.rs, self.lv, self.r = kh, rs, lv, r
 
 
 def supports(model):
@@ -79,19 +86,29 @@ def _stacked(mods):
     return (torch.cat([m.linear.weight.detach() for m in mods], dim=0), torch.cat([m.linear.bias.detach() for m in mods], dim=0))
 
 
-def condition(model, ctx_x, ctx_y):
+def condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None):
     """(ctx images [T, Nc, ...], ctx labels [T, Nc, L]) -> the state for predict: ResNetNP.condition for that family; for the
     vanilla family the encoder, transform_y and encoder_r, then the key / value heads and mlhot.ops.favor_keys (attention) or the
-    aggregation and r_to_z (mean / max / baco).  No new kernel; the row count is T * Nc whatever follows."""
+    aggregation and r_to_z (mean / max / baco).  No new kernel; the row count is T * Nc whatever follows.
+
+    `ctx_len` (T host ints, 1 .. Nslots): the images are [T, Nslots, ...] and task t's context is its first ctx_len[t] slots; the other
+    slots' images and labels are never read.  `capacity` >= Nslots reserves empty slots for extend (default Nslots; an attention
+    model takes at most 32).  Without either argument this is the call it always was."""
     if isinstance(model, ResNetNP):
-        return model.condition(ctx_x, ctx_y)
+        if ctx_len is None and capacity is None:
+            return model.condition(ctx_x, ctx_y)                  # today's call, as it always went out
+        return model.condition(ctx_x, ctx_y, ctx_len=ctx_len, capacity=capacity)
     _refuse(model, "condition")
     T, Nc = ctx_x.shape[0], ctx_x.shape[1]
     if T != model.task_num:
         raise ValueError(f"condition: {T} tasks, the model was built for tasks_per_batch = {model.task_num}")
+    lens, capacity = ragged.condition_args("condition", T, Nc, ctx_len, capacity, model.ATTENTION)
     _need_gpu(ctx_x, ctx_y, *model.parameters())
     with torch.no_grad():
         wq = _stacked(model._W_q) if model.ATTENTION else None
+        if lens is not None:
+            model._check_agg()
+            return _grow(model, None, (0,) * T, capacity, ctx_x, ctx_y, lens, wq)
         if Nc == 0:
             return VanillaContextState(model, T, 0, _fingerprint(model), "empty", z=torch.zeros(T, model.dim_z, device=ctx_x.device), wq=wq)
         model._check_agg()
@@ -102,14 +119,77 @@ def condition(model, ctx_x, ctx_y):
             kh = LinearFunction.apply(x_ctx, *_stacked(model._W_k), "none").view(T, Nc, HEADS, -1)
             vh = LinearFunction.apply(rs, *_stacked(model._W_v), "none").view(T, Nc, HEADS, -1)
             keys = favor_keys(kh, model.attn.projection_matrix)
-            return VanillaContextState(model, T, Nc, _fingerprint(model), "attention", keys=keys, vh=vh.contiguous(), wq=wq)
+            return VanillaContextState(model, T, Nc, _fingerprint(model), "attention", keys=keys, vh=vh.contiguous(), wq=wq, kh=kh.contiguous())
         lv = None
         if model.agg_mode == "baco":         # csrc/np_vanilla.h's order: rs_to_mu, rs_to_var, then the aggregation
             lv = LinearFunction.apply(rs, model.rs_to_var.weight, model.rs_to_var.bias, "none").view(T, Nc, -1)
             rs = LinearFunction.apply(rs, model.rs_to_mu.weight, model.rs_to_mu.bias, "none")
         r = lib().agg_fwd(model.agg_mode, rs.view(T, Nc, -1), lv)[0]
         z = LinearFunction.apply(r, model.r_to_z.weight, model.r_to_z.bias, "none")
-        return VanillaContextState(model, T, Nc, _fingerprint(model), "latent", z=z)
+        return VanillaContextState(model, T, Nc, _fingerprint(model), "latent", z=z, rs=rs.view(T, Nc, -1), lv=lv, r=r)
+
+
+def extend(model, state, new_x, new_y, new_len=None):
+    """(state, new ctx images [T, n, ...], their labels [T, n, L], new_len) -> a NEW state whose task t holds new_len[t] more context
+    shots (0 .. n each; default n), written behind its current ones; the old state stays valid.  Only the new shots are encoded;
+    then the masked key launches (attention) or the prefix aggregate with its gather and r_to_z (latent) run on the kept rows.  A
+    state needs spare slots: condition with capacity=.  ResNetNP: model.extend."""
+    if isinstance(model, ResNetNP):
+        return model.extend(state, new_x, new_y, new_len=new_len)
+    _refuse(model, "extend")
+    if not isinstance(state, VanillaContextState) or state.owner is not model:
+        raise ValueError("extend: the state was not made by this model's condition()")
+    T, n = new_x.shape[0], new_x.shape[1]
+    if T != state.T or state.T != model.task_num:
+        raise ValueError(f"extend: the state holds {state.T} tasks, the new shots {T} (the key stabiliser is the maximum over the "
+                         "conditioned batch: extend serves the same tasks)")
+    if state.fingerprint != _fingerprint(model):
+        raise ValueError("extend: the state is stale - a parameter of the model changed since condition()")
+    add = ragged.extend_args("extend", state, T, n, new_len)
+    _need_gpu(new_x, new_y, *model.parameters())
+    with torch.no_grad():
+        return _grow(model, state, state.lens, state.capacity, new_x, new_y, add, state.wq)
+
+
+def _shot_rows(model, imgs, labels):
+    """The per-shot part of condition for a packed list of P shots: images [P, 1, 128, 128], labels [P, L] -> (kh, vh) [P, 8, dim_w]
+    for the attention models, (rs, lv) [P, R] for the others (baco: rs_to_mu's and rs_to_var's outputs; else lv None)."""
+    x_ctx = _encode(model, imgs)
+    ly = LinearFunction.apply(labels, model.transform_y.weight, model.transform_y.bias, "none")
+    rs = model.encoder_r(torch.cat([x_ctx, ly], dim=1))
+    if model.ATTENTION:
+        return (LinearFunction.apply(x_ctx, *_stacked(model._W_k), "none").view(-1, HEADS, model.dim_w),
+                LinearFunction.apply(rs, *_stacked(model._W_v), "none").view(-1, HEADS, model.dim_w))
+    if model.agg_mode == "baco":
+        lv = LinearFunction.apply(rs, model.rs_to_var.weight, model.rs_to_var.bias, "none")
+        return LinearFunction.apply(rs, model.rs_to_mu.weight, model.rs_to_mu.bias, "none"), lv
+    return rs, None
+
+
+def _grow(model, state, lens, capacity, images, labels, add, wq):
+    """`add[t]` of the slots of images / labels [T, n, ...] behind task t's lens[t] kept rows (state None: nothing kept yet), then the
+    finishing step on the kept rows.  The valid shots travel as a packed list: a slot that is no shot is never read."""
+    T, dev = model.task_num, images.device
+    plan = ragged.Plan(lens, add, images.shape[1], capacity, dev)
+    total = plan.total
+    a_rows, b_rows = (None, None) if state is None else (state.kh, state.vh) if model.ATTENTION else (state.rs, state.lv)
+    if state is not None and a_rows is None:
+        raise ValueError("extend: the state carries no per-shot rows (it was not made by condition())")
+    if plan.n:
+        src, dst = plan.src, plan.dst
+        imgs = ragged.pack(images.reshape(T, images.shape[1], model.img_channels, model.img_size[0], model.img_size[1]), src)
+        new_a, new_b = _shot_rows(model, imgs, ragged.pack(labels.reshape(T, images.shape[1], -1), src))
+        if state is None:
+            a_rows = torch.zeros(T, capacity, *new_a.shape[1:], device=dev)
+            b_rows = torch.zeros_like(a_rows) if new_b is not None else None
+        a_rows = ragged.scatter(a_rows, dst, new_a)
+        b_rows = ragged.scatter(b_rows, dst, new_b) if new_b is not None else None
+    if model.ATTENTION:
+        keys = ragged.masked_keys(a_rows, model.attn.projection_matrix, plan)
+        return VanillaContextState(model, T, capacity, _fingerprint(model), "attention", keys=keys, vh=b_rows, wq=wq, lens=total, kh=a_rows)
+    r = ragged.gathered_aggregate(model.agg_mode, a_rows, b_rows, plan)
+    z = LinearFunction.apply(r, model.r_to_z.weight, model.r_to_z.bias, "none")
+    return VanillaContextState(model, T, capacity, _fingerprint(model), "latent", z=z, lens=total, rs=a_rows, lv=b_rows, r=r)
 
 
 def predict(model, state, qry_x, chunk=None, route=None):

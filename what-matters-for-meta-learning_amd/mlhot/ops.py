@@ -4,6 +4,8 @@ The Functions are glue only: they hand raw device pointers to libmlhot.so and ke
 opaque `saved` workspace alive between forward and backward.  There is NO eager/CPU
 fallback - a tensor that is not on a HIP device raises.
 """
+import numbers
+
 import torch
 
 from . import lib
@@ -490,10 +492,12 @@ def favor_prefixes(qh, kh, vh, proj):
 class FavorKeyState:
     """What favor_keys leaves for favor_query.  `route` says what it holds: "cached" - `buf` is mlhot_favor_keys_fwd's state (the
     finished key features F_k and the batch-global stabiliser M; features() shows them) and favor_query is row-invariant;
-    "plain" - a shape outside the cached kernels' envelope: `kh` itself, favor_query runs mlhot_favor_fwd, no invariance."""
+    "plain" - a shape outside the cached kernels' envelope: `kh` itself, favor_query runs mlhot_favor_fwd, no invariance.
+    `lens`: None, or the per-task context sizes (a tuple of T ints) of a masked state (mlhot_favor_keys_ragged_fwd): rows
+    n >= lens[t] of F_k are exact zeros."""
 
-    def __init__(self, route, dims, buf=None, kh=None):
-        self.route, self.dims, self.buf, self.kh = route, dims, buf, kh      # dims = (T, Nc, H, d, m)
+    def __init__(self, route, dims, buf=None, kh=None, lens=None):
+        self.route, self.dims, self.buf, self.kh, self.lens = route, dims, buf, kh, lens      # dims = (T, Nc, H, d, m)
 
     def features(self):
         """(F_k [T, H, Nc, mp], M [1]) of a "cached" state, as views."""
@@ -503,15 +507,57 @@ class FavorKeyState:
         return lib().favor_state_views(self.buf, T, H, Nc, m)
 
 
-def favor_keys(kh, proj):
+def host_lens(lens, T, lo, hi, what, exc=MlhotError):
+    """A host int sequence or CPU integer tensor of T values in lo .. hi -> a tuple of ints, or `exc` naming what is wrong.  Host
+    work only: the callers refuse before anything touches the GPU."""
+    if isinstance(lens, torch.Tensor):
+        if lens.is_cuda:
+            raise exc(f"{what} must be a host int sequence or a CPU integer tensor (its values are checked on the host), got a tensor on {lens.device}")
+        if lens.is_floating_point() or lens.is_complex() or lens.dtype == torch.bool:
+            raise exc(f"{what} must hold integers, got a {lens.dtype} tensor")
+        if lens.dim() != 1:
+            raise exc(f"{what} must be one-dimensional with one entry per task, got shape {tuple(lens.shape)}")
+        lens = lens.tolist()
+    try:
+        lens = list(lens)
+    except TypeError:
+        raise exc(f"{what} must be a sequence with one entry per task, got {type(lens).__name__}") from None
+    if len(lens) != T:
+        raise exc(f"{what} has {len(lens)} entries for {T} tasks")
+    vals = []
+    for x in lens:
+        if isinstance(x, bool) or not isinstance(x, numbers.Integral):
+            raise exc(f"{what} must hold integers, got {x!r}")
+        vals.append(int(x))
+    if min(vals) < lo or max(vals) > hi:
+        raise exc(f"{what} must lie in {lo}..{hi}, got {vals}")
+    return tuple(vals)
+
+
+def favor_keys(kh, proj, lens=None, lens_dev=None):
     """The context side of FAVOR+ once: k [T, Nc, H, d] (the head projections' layout), proj [m, d] -> FavorKeyState for any
     number of favor_query calls on the SAME T tasks (the key stabiliser is the maximum over the whole batch of kh).  Two launches
-    (csrc/favor_cached.h) for Nc <= 32, d % 16 == 0, d <= 256, 16 <= m <= 1536; other shapes keep kh.  Forward only."""
+    (csrc/favor_cached.h) for Nc <= 32, d % 16 == 0, d <= 256, 16 <= m <= 1536; other shapes keep kh.  Forward only.
+
+    `lens` (a host int sequence or CPU integer tensor of T values in 1..Nc; checked on the host, then uploaded): row n of task t is
+    a context shot iff n < lens[t].  The stabiliser is the maximum over the valid rows only, the invalid rows of F_k are exact zeros
+    and their kh is never read (mlhot_favor_keys_ragged_fwd).  The state is "cached" and carries `lens`; outside the cached
+    envelope this raises MlhotError - mlhot_favor_fwd has no mask, so there is no "plain" route here.  `lens_dev`: the caller's own
+    int32 copy of `lens` on kh's device, for a caller that uploaded it earlier (mlhot.ragged.Plan); `lens` is still what is checked."""
     _forward_only("favor_keys", kh, proj)
     _need_gpu(kh, proj)
     kh, proj = _c(kh.detach()), _c(proj.detach())
     T, Nc, H, d = kh.shape
     dims = (T, Nc, H, d, proj.shape[0])
+    if lens is not None:
+        lens = host_lens(lens, T, 1, Nc, "favor_keys: lens")
+        if not lib().favor_keys_bytes(T, H, Nc, d, proj.shape[0]):
+            bad = [f"{n}={v}" for n, v, ok in (("Nc", Nc, Nc <= 32), ("d", d, d % 16 == 0 and 16 <= d <= 256),
+                                                ("m", proj.shape[0], 16 <= proj.shape[0] <= 1536)) if not ok] or [f"T*H={T * H}"]
+            raise MlhotError(f"favor_keys: lens needs the cached kernels' envelope (Nc <= 32, d % 16 == 0, d <= 256, 16 <= m <= 1536), "
+                             f"got {', '.join(bad)}; mlhot_favor_fwd has no mask")
+        dev = torch.tensor(lens, dtype=torch.int32).to(kh.device) if lens_dev is None else _c(lens_dev)
+        return FavorKeyState("cached", dims, buf=lib().favor_keys_ragged_fwd(kh, proj, dev), lens=lens)
     if lib().favor_keys_bytes(T, H, Nc, d, proj.shape[0]):
         return FavorKeyState("cached", dims, buf=lib().favor_keys_fwd(kh, proj))
     return FavorKeyState("plain", dims, kh=kh)
@@ -520,7 +566,8 @@ def favor_keys(kh, proj):
 def favor_query(qh, state, vh, proj):
     """FAVOR+ attention of q [T, Nq, H, d] against a favor_keys state and v [T, Nc, H, d] -> merged [T, Nq, d*H], any Nq >= 1 in
     one launch.  On the "cached" route the bits of a row do not depend on the other rows of the call (csrc/favor_cached.h); the
-    "plain" route is mlhot_favor_fwd on the kept keys.  Forward only."""
+    "plain" route is mlhot_favor_fwd on the kept keys.  Forward only.  Against a masked state (favor_keys with lens) the rows of v
+    behind lens[t] must be finite - zero-fill them: their column of S is exactly 0, and 0 x NaN is not."""
     _forward_only("favor_query", qh, vh, proj)
     _need_gpu(qh, vh, proj)
     if not isinstance(state, FavorKeyState):

@@ -1,0 +1,95 @@
+"""Per-task context sizes and growing states for cached-context inference: what ResNetNP.condition / extend and
+mlhot.cached.condition / extend share.  The argument checks are host work only and raise ValueError before anything touches the
+GPU; the device part is index arithmetic on the kept per-shot rows and the two finishing steps - the masked key state
+(mlhot.ops.favor_keys with lens) or the prefix aggregate with a gather of row lens[t] - 1 (mlhot.ops.agg_prefixes)."""
+import numbers
+
+import torch
+
+from mlhot.ops import agg_prefixes, favor_keys, host_lens
+
+MAX_ATTENTION_CAPACITY = 32        # the cached FAVOR+ kernels' envelope on the context side (csrc/favor_cached.h)
+
+
+def condition_args(what, T, Nslots, ctx_len, capacity, attention):
+    """-> (lens, capacity), or (None, Nslots) for the call without ctx_len / capacity (the unmasked path, as before)."""
+    if ctx_len is None and capacity is None:
+        return None, Nslots
+    lens = (Nslots,) * T if ctx_len is None else host_lens(ctx_len, T, 1, Nslots, f"{what}: ctx_len", ValueError)
+    if Nslots < 1:
+        raise ValueError(f"{what}: capacity= needs at least one context shot to start from")
+    if capacity is None:
+        capacity = Nslots
+    if isinstance(capacity, bool) or not isinstance(capacity, numbers.Integral):
+        raise ValueError(f"{what}: capacity must be an integer, got {capacity!r}")
+    capacity = int(capacity)
+    if capacity < Nslots:
+        raise ValueError(f"{what}: capacity = {capacity} is smaller than the {Nslots} context slots handed in")
+    if attention and capacity > MAX_ATTENTION_CAPACITY:
+        raise ValueError(f"{what}: capacity = {capacity} is outside the cached attention kernels' envelope "
+                         f"(at most {MAX_ATTENTION_CAPACITY} context slots per task)")
+    return lens, capacity
+
+
+def extend_args(what, state, T, n, new_len):
+    """-> the new shots per task; the state's own lens / capacity are checked against them."""
+    lens, capacity = getattr(state, "lens", None), getattr(state, "capacity", None)
+    if lens is None or capacity is None:
+        raise ValueError(f"{what}: the state carries no per-shot rows (it was not made by condition())")
+    add = (n,) * T if new_len is None else host_lens(new_len, T, 0, n, f"{what}: new_len", ValueError)
+    over = [(t, l + a) for t, (l, a) in enumerate(zip(lens, add)) if l + a > capacity]
+    if over:
+        t, total = over[0]
+        raise ValueError(f"{what}: task {t} would hold {total} context shots, the state's capacity is {capacity} - condition with "
+                         "capacity= to reserve room for later shots")
+    return add
+
+
+class Plan:
+    """Every index a growth step needs, on the device after ONE upload made before the first launch (an upload from pageable host
+    memory waits for the stream: made later it would hold the host until the encoder is done).  `src` / `dst`: flat indices of the
+    new valid slots, source t * src_stride + j and destination t * capacity + start[t] + j for j < count[t] (int64); `total` =
+    start + count per task, host ints; `lens` the same as int32 on the device (what mlhot_favor_keys_ragged_fwd reads); `last`:
+    row (total[t] - 1) * T + t of mlhot_agg_prefix_fwd's [capacity, T, R] output, flattened (int64)."""
+
+    def __init__(self, start, count, src_stride, capacity, device):
+        T = len(start)
+        self.total = tuple(s + c for s, c in zip(start, count))
+        src = [t * src_stride + j for t, c in enumerate(count) for j in range(c)]
+        dst = [t * capacity + s + j for t, (s, c) in enumerate(zip(start, count)) for j in range(c)]
+        last = [(l - 1) * T + t for t, l in enumerate(self.total)]
+        buf = torch.tensor(src + dst + last + list(self.total), dtype=torch.int32).to(device)
+        P = len(src)
+        idx = buf[:2 * P + T].long()
+        self.n, self.src, self.dst, self.last, self.lens = P, idx[:P], idx[P:2 * P], idx[2 * P:], buf[2 * P + T:]
+
+
+def slot_indices(start, count, src_stride, dst_stride, device):
+    """(src, dst) of a Plan alone."""
+    plan = Plan(start, count, src_stride, dst_stride, device)
+    return plan.src, plan.dst
+
+
+def pack(t, idx):
+    """Rows idx of t flattened over its first two axes [T, N, ...] -> [P, ...]."""
+    return t.reshape(t.shape[0] * t.shape[1], *t.shape[2:]).index_select(0, idx)
+
+
+def scatter(buf, idx, rows):
+    """A copy of buf [T, cap, ...] (None: nothing kept yet - zeros of rows' trailing shape are the caller's to hand in) with
+    rows [P, ...] written at the flat slots idx.  The old buffer stays as it is: the old state stays valid."""
+    out = buf.clone()
+    out.view(buf.shape[0] * buf.shape[1], *buf.shape[2:]).index_copy_(0, idx, rows.reshape(rows.shape[0], *buf.shape[2:]))
+    return out
+
+
+def masked_keys(kh, proj, plan):
+    """The masked key state over the kept key rows kh [T, cap, H, d] (two launches, mlhot_favor_keys_ragged_fwd)."""
+    return favor_keys(kh, proj, lens=plan.total, lens_dev=plan.lens)
+
+
+def gathered_aggregate(mode, rs, lv, plan):
+    """mean / max / baco of every task's first total[t] rows of rs [T, cap, R]: mlhot_agg_prefix_fwd's row (total[t] - 1, t) - the
+    operations of mlhot_agg_fwd on the slice, in its order.  -> r [T, R]"""
+    T, cap, R = rs.shape
+    return agg_prefixes(mode, rs, lv).view(cap * T, R).index_select(0, plan.last)          # of [cap, T, R]

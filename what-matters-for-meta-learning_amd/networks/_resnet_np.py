@@ -9,7 +9,7 @@ from torch import nn
 
 import logging
 
-from mlhot import lib
+from mlhot import lib, ragged
 from mlhot.ops import (AggFunction, FavorFunction, HeadStacksFunction, LinearFunction, StackedLinearFunction, agg_prefixes,
                        favor_keys, favor_prefixes, favor_query, linear_rows)
 from networks.ResNet import run_conv
@@ -48,11 +48,17 @@ def _fold_linear(sources, lin, act, n_prefix):
 class ContextState:
     """What ResNetNP.condition leaves for ResNetNP.predict.  `kind`: "attention" - `keys` (mlhot.ops.FavorKeyState) and the value
     heads `vh` [T, Nc, H, 256]; "latent" - the task embedding `z` [T, 256]; "empty" - no context shot.  `owner` is the model,
-    `fingerprint` its parameters' versions when the state was made: predict refuses a state whose model has moved on."""
+    `fingerprint` its parameters' versions when the state was made: predict refuses a state whose model has moved on.
 
-    def __init__(self, owner, T, Nc, fingerprint, kind, keys=None, vh=None, z=None):
+    For extend the state also keeps `lens` (context shots per task, host ints), `capacity` (slots per task: `Nc`
+    is the capacity, what the kernels see) and the per-shot rows in slot order [T, capacity, ...]: `kh` and the zero-filled `vh`
+    (attention), `rs` - baco: latent_mu's output - and `lv` (latent), with `r` [T, 256], the aggregate before `mu`."""
+
+    def __init__(self, owner, T, Nc, fingerprint, kind, keys=None, vh=None, z=None, lens=None, kh=None, rs=None, lv=None, r=None):
         self.owner, self.T, self.Nc, self.fingerprint, self.kind = owner, T, Nc, fingerprint, kind
         self.keys, self.vh, self.z = keys, vh, z
+        self.lens, self.capacity = (Nc,) * T if lens is None else tuple(lens), Nc
+        self.kh, self.rs, self.lv, self.r = kh, rs, lv, r
 
 
 class _Stacked:
@@ -295,17 +301,20 @@ class ResNetNP(nn.Module):
         merged = FavorFunction.apply(qh, kh, vh, self.attn.projection_matrix)
         return self._W(merged)
 
+    def _latent_rows(self, feats, quirk=False):
+        """What the shot-axis aggregation reads, per shot: (feats, None) for mean / max, (latent_mu, latent_var outputs) for baco."""
+        if self.agg_mode in ("mean", "max"):
+            return feats, None
+        if self.agg_mode == "baco":
+            mu_l = LinearFunction.apply(feats, self.latent_mu.weight, self.latent_mu.bias, "none")
+            return mu_l, LinearFunction.apply(mu_l if quirk else feats, self.latent_var.weight, self.latent_var.bias, "none")
+        raise TypeError("agg_mode is not applicable for CNP, choose from ['mean', 'max', 'baco']")
+
     def _aggregate(self, feats, quirk=False):
         """Shot-axis aggregation of the task-encoder features + `mu` -> task embedding [T, 256].  `quirk`: the target-set path
         of FCLCNPDistractor feeds latent_var with latent_mu's OUTPUT (FCLCNPDistractor.py:133-134); reproduced as is."""
-        if self.agg_mode in ("mean", "max"):
-            r, _ = AggFunction.apply(self.agg_mode, feats, None)
-        elif self.agg_mode == "baco":
-            mu_l = LinearFunction.apply(feats, self.latent_mu.weight, self.latent_mu.bias, "none")
-            lv = LinearFunction.apply(mu_l if quirk else feats, self.latent_var.weight, self.latent_var.bias, "none")
-            r, _ = AggFunction.apply("baco", mu_l, lv)
-        else:
-            raise TypeError("agg_mode is not applicable for CNP, choose from ['mean', 'max', 'baco']")
+        rs, lv = self._latent_rows(feats, quirk)
+        r, _ = AggFunction.apply(self.agg_mode, rs, lv)
         return LinearFunction.apply(r, self.mu.weight, self.mu.bias, "none")
 
     def forward(self, batch_train_images, label_train, batch_test_images, *rest, test=False):
@@ -475,20 +484,27 @@ class ResNetNP(nn.Module):
         if self.training:
             raise ValueError(f"{what} is a test-mode path: call model.eval() first")
 
-    def condition(self, batch_train_images, label_train):
+    def condition(self, batch_train_images, label_train, ctx_len=None, capacity=None):
         """(ctx images [T, Nc, ...], ctx labels) -> ContextState: everything of `forward(..., test=True)` that does not depend on
         the targets, once - the context trunk pass, the task encoder and, for the attention models, the key / value head
         projections and the FAVOR+ key features (mlhot.ops.favor_keys); for the others the aggregation and `mu`.  The key
-        stabiliser is the maximum over all T tasks of THIS batch, so predict reproduces forward on the same T tasks.  Eval mode."""
+        stabiliser is the maximum over all T tasks of THIS batch, so predict reproduces forward on the same T tasks.  Eval mode.
+
+        `ctx_len` (T host ints, 1 .. Nslots): the images are [T, Nslots, ...] and task t's context is its first ctx_len[t] slots; the
+        other slots' images and labels are never read.  `capacity` >= Nslots reserves empty slots for extend (default Nslots; an
+        attention model takes at most 32).  Without either argument this is the call it always was."""
         self._cached_refusals("condition")
         T, Nc = batch_train_images.shape[0], batch_train_images.shape[1]
         if T != self.task_num:
             raise ValueError(f"condition: {T} tasks, the model was built for tasks_per_batch = {self.task_num}")
+        lens, capacity = ragged.condition_args("condition", T, Nc, ctx_len, capacity, self.ATTENTION)
         self._refresh_arena()
         with torch.no_grad():
             if self.ATTENTION:
                 for mods in (self._W_q, self._W_k, self._W_v):       # stack the heads now: re-pointing a parameter must not look like an update later
                     self._stack(mods).tensors()
+            if lens is not None:
+                return self._grow(None, (0,) * T, capacity, batch_train_images, label_train, lens)
             if Nc == 0:
                 return ContextState(self, T, 0, self._fingerprint(), "empty")
             C, H, W = self.img_channels, self.img_size[0], self.img_size[1]
@@ -501,8 +517,69 @@ class ResNetNP(nn.Module):
             if self.ATTENTION:
                 kh, vh = self._heads(x_ctx, self._W_k), self._heads(feats, self._W_v)
                 keys = favor_keys(kh, self.attn.projection_matrix)
-                return ContextState(self, T, Nc, self._fingerprint(), "attention", keys=keys, vh=vh.contiguous())
-            return ContextState(self, T, Nc, self._fingerprint(), "latent", z=self._aggregate(feats))
+                return ContextState(self, T, Nc, self._fingerprint(), "attention", keys=keys, vh=vh.contiguous(), kh=kh.contiguous())
+            rs, lv = self._latent_rows(feats)
+            r, _ = AggFunction.apply(self.agg_mode, rs, lv)
+            z = LinearFunction.apply(r, self.mu.weight, self.mu.bias, "none")
+            return ContextState(self, T, Nc, self._fingerprint(), "latent", z=z, rs=rs.contiguous(), lv=lv, r=r)
+
+    def extend(self, state, new_images, new_labels, new_len=None):
+        """(ContextState, new ctx images [T, n, ...], their labels, new_len) -> a NEW ContextState whose task t holds new_len[t] more
+        context shots (0 .. n each; default n), written behind its current ones; the old state stays valid.  Only the new shots
+        run through the trunk, the task encoder and the head projections; then the masked key launches (attention) or the prefix
+        aggregate with its gather and `mu` (latent) run on the kept rows.  A state needs spare slots: condition with capacity=."""
+        self._cached_refusals("extend")
+        if not isinstance(state, ContextState) or state.owner is not self:
+            raise ValueError("extend: the state was not made by this model's condition()")
+        T, n = new_images.shape[0], new_images.shape[1]
+        if T != state.T or state.T != self.task_num:
+            raise ValueError(f"extend: the state holds {state.T} tasks, the new shots {T} (the key stabiliser is the maximum over the "
+                             "conditioned batch: extend serves the same tasks)")
+        if state.fingerprint != self._fingerprint():
+            raise ValueError("extend: the state is stale - a parameter of the model changed since condition()")
+        add = ragged.extend_args("extend", state, T, n, new_len)
+        self._refresh_arena()
+        with torch.no_grad():
+            return self._grow(state, state.lens, state.capacity, new_images, new_labels, add)
+
+    def _shot_rows(self, imgs, labels):
+        """The per-shot part of condition for a packed list of P shots: images [P, C, H, W], labels [P, L] -> (kh, vh) [P, heads, 256]
+        for the attention models, (rs, lv) [P, 256] for the others (baco: latent_mu's and latent_var's outputs; else lv None)."""
+        maps = run_trunks([self.img_encoder.trunk_job(imgs)])
+        fmap = maps[0] if maps is not None else self.img_encoder.resnet.trunk(run_conv(self.img_encoder.conv1, imgs, relu=True), None)
+        x_ctx = _aggregate_feature_map(fmap, self.img_encoder.aggregate)
+        if self.TRANSFORM_Y:
+            labels = LinearFunction.apply(labels, self.transform_y.weight, self.transform_y.bias, "none")
+        feats = _mlp3(x_ctx, self.task_encoder, last_relu=True, side=labels)
+        if self.ATTENTION:
+            return self._heads(x_ctx[None], self._W_k)[0], self._heads(feats[None], self._W_v)[0]
+        return self._latent_rows(feats)
+
+    def _grow(self, state, lens, capacity, images, labels, add):
+        """`add[t]` of the slots of images / labels [T, n, ...] behind task t's lens[t] kept rows (state None: nothing kept yet), then
+        the finishing step on the kept rows.  The valid shots travel as a packed list: a slot that is no shot is never read."""
+        T, dev = self.task_num, images.device
+        C, H, W = self.img_channels, self.img_size[0], self.img_size[1]
+        plan = ragged.Plan(lens, add, images.shape[1], capacity, dev)
+        total = plan.total
+        a_rows, b_rows = (state.kh, state.vh) if self.ATTENTION and state is not None else (state.rs, state.lv) if state is not None else (None, None)
+        if state is not None and a_rows is None:
+            raise ValueError("extend: the state carries no per-shot rows (it was not made by condition())")
+        if plan.n:
+            src, dst = plan.src, plan.dst
+            imgs = ragged.pack(images.reshape(T, images.shape[1], C, H, W), src)
+            new_a, new_b = self._shot_rows(imgs, ragged.pack(labels, src))
+            if state is None:
+                a_rows = torch.zeros(T, capacity, *new_a.shape[1:], device=dev)
+                b_rows = torch.zeros_like(a_rows) if new_b is not None else None
+            a_rows = ragged.scatter(a_rows, dst, new_a)
+            b_rows = ragged.scatter(b_rows, dst, new_b) if new_b is not None else None
+        if self.ATTENTION:
+            keys = ragged.masked_keys(a_rows, self.attn.projection_matrix, plan)
+            return ContextState(self, T, capacity, self._fingerprint(), "attention", keys=keys, vh=b_rows, lens=total, kh=a_rows)
+        r = ragged.gathered_aggregate(self.agg_mode, a_rows, b_rows, plan)
+        z = LinearFunction.apply(r, self.mu.weight, self.mu.bias, "none")
+        return ContextState(self, T, capacity, self._fingerprint(), "latent", z=z, lens=total, rs=a_rows, lv=b_rows, r=r)
 
     def predict(self, state, batch_test_images, chunk=None):
         """(ContextState, target images [T, Nq, ...]) -> mu [T, Nq, out] = `forward(ctx, labels, targets, test=True)[0]` for the
