@@ -14,6 +14,9 @@
 //             per-workgroup partial sums, a one-workgroup finish kernel divides by the pair count.
 //   backward: S again, H[i][j] = G[i][j] + G[j][i] from the saved per-row statistics (G = dL/ds), dzn = H zn / t on the matrix core
 //             (z read as float4 along d through a column permutation), then the normalisation's backward.
+// Envelope: every d % 16 == 0 from 16 to 256, not only the multiples of 64.  The backward gives wave w the columns [64 w, 64 w + 64);
+// for d % 64 != 0 the last such block is partial and is covered: the wave that owns it runs the product with all 64 lanes (every lane
+// carries an anchor's row of H'), the lanes past d contribute zero columns and store nothing.  tests/ntx_cases.py walks the envelope.
 #pragma once
 #include <vector>
 #include "common.h"
@@ -30,8 +33,9 @@ struct Args {
   float* partial;                       // [ceil(N / 16)] per-workgroup loss sums
 };
 inline long long pair_count(int N, int div, int mod) {      // ordered positive pairs of anchors that have at least one negative
-  std::vector<long long> cnt(mod > 0 ? mod : 1, 0);
-  for (int i = 0; i < N; ++i) cnt[(i / div) % mod]++;
+  const int buckets = mod < N ? (mod > 0 ? mod : 1) : N;     // i / div < N <= mod: (i / div) % mod = i / div, the labels of mod = N (mod = INT_MAX must not size a vector)
+  std::vector<long long> cnt(buckets > 0 ? buckets : 1, 0);
+  for (int i = 0; i < N; ++i) cnt[(i / div) % buckets]++;
   long long p = 0;
   for (long long c : cnt) if (c < N) p += c * (c - 1);
   return p;
@@ -188,11 +192,14 @@ __global__ __launch_bounds__(256) void ntx_bwd_kernel(const BwdArgs b) {
   for (int te = 0; te < 4; ++te) acc[te] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   const int c0 = 64 * wave + 4 * lr;
   const bool colok = c0 < a.d;
-  if (colok) {
+  // The matrix instruction takes A row lr (anchor lr of the tile) from lane (lr, lq) whatever columns that lane owns, and a lane that is
+  // masked off supplies zeros: the loop is entered per WAVE (64 w < d), all 64 lanes load av and issue; in the partial column block
+  // (d % 64 != 0) the lanes past d only load no z (their B columns are zero) and store nothing.
+  if (64 * wave < a.d) {
     for (int jb = 0; jb < (N16 >> 2); ++jb) {
       const int j = 4 * jb + lq;
       f32x4_t zb = {0.f, 0.f, 0.f, 0.f};
-      if (j < a.N) zb = *reinterpret_cast<const f32x4_t*>(a.z + (size_t)j * a.d + c0);
+      if (colok && j < a.N) zb = *reinterpret_cast<const f32x4_t*>(a.z + (size_t)j * a.d + c0);
       const float av = s_S[lr * ldS + j];
 #pragma unroll
       for (int te = 0; te < 4; ++te) acc[te] = mfma4(av, zb[te], acc[te]);
