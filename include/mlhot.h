@@ -306,6 +306,22 @@ int mlhot_np_query_supported(const struct mlhot_np_dims* d);
 int mlhot_np_query_fwd(const struct mlhot_np_dims* d, const struct mlhot_np_params* p, const float* x_qry, int Nq,
                        const void* key_state, const float* vh, const float* z, float* mu, void* stream);
 
+/* ---- prefix sweep of the vanilla family: the query tail for K context prefixes in one launch (csrc/np_prefix.h) ---
+ * mlhot_np_prefix_fwd: x_qry[T*Nq,dim_w] -> mu[K,T,Nq,y_dim]; mu[i] is mlhot_np_query_fwd's result against the first ks[i] of the
+ *   d->Nc context shots of every task.  ks: K ints in HOST memory, strictly increasing, 1 <= ks[i] <= d->Nc (else MLHOT_ERR_ARG).
+ *   attention models: kh, vh[T,Nc,8,dim_w] (the head projections of all shots; z NULL) and ws of mlhot_np_prefix_ws_bytes bytes; the
+ *     call runs the key side itself (two launches into ws), then the sweep launch;
+ *   every other model: z[K,T,dim_z] (the aggregate of each prefix through r_to_z; kh, vh, ws NULL): the sweep launch alone.
+ * INVARIANCE: the bits of mu[i,t,n,:] depend on x_qry[t,n], the first ks[i] shots of the batch, the parameters and the dimensions
+ * only - not on Nq, on n, on the other target rows or on which other prefixes were requested.  Served (mlhot_np_prefix_supported):
+ * mlhot_np_query_supported(d), 1 <= K <= 32, 1 <= Nc <= 32; 16-byte aligned pointers.  Otherwise MLHOT_ERR_UNSUPPORTED, nothing
+ * written.  d->Nq is ignored.  Forward only, test mode; GPU build only.  Added within ABI 7: bindings look the symbols up. */
+int mlhot_np_prefix_supported(const struct mlhot_np_dims* d, int K);
+size_t mlhot_np_prefix_ws_bytes(const struct mlhot_np_dims* d, int K);
+int mlhot_np_prefix_fwd(const struct mlhot_np_dims* d, const struct mlhot_np_params* p, const float* x_qry, int Nq,
+                        const int32_t* ks /* [K], host */, int K, const float* kh, const float* vh, const float* z,
+                        float* mu, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- strict sharded parity of the key stabiliser -------------------------
  * fast_attention.py:96-97 takes torch.max over the keys of the WHOLE batch.  When a caller shards the meta-batch over
  * ranks, each rank's launch sequence can be run in two halves around the caller's own collectives on `xchg`

@@ -27,6 +27,7 @@
 #include "linear_rows.h"
 #include "favor_cached.h"
 #include "np_query.h"
+#include "np_prefix.h"
 #include "resnet_trunk.h"
 #include "../../include/mlhot.h"
 
@@ -326,6 +327,14 @@ int mlhot_np_query_fwd(const mlhot_np_dims* d, const mlhot_np_params* p, const f
                        const float* z, float* mu, void* stream) {
   if (!d || !p) { set_error("np_query_fwd: null dims/params"); return MLHOT_ERR_ARG; }
   return np_query_forward(*d, *p, x_qry, Nq, key_state, vh, z, mu, (hipStream_t)stream);
+}
+// the same tail for K context prefixes of one batch, one sweep launch (csrc/np_prefix.h)
+int mlhot_np_prefix_supported(const mlhot_np_dims* d, int K) { return d && np_prefix_ok(*d, K) ? 1 : 0; }
+size_t mlhot_np_prefix_ws_bytes(const mlhot_np_dims* d, int K) { return d ? np_prefix_ws_need(*d, K) : 0; }
+int mlhot_np_prefix_fwd(const mlhot_np_dims* d, const mlhot_np_params* p, const float* x_qry, int Nq, const int32_t* ks, int K, const float* kh,
+                        const float* vh, const float* z, float* mu, void* ws, size_t ws_bytes, void* stream) {
+  if (!d || !p) { set_error("np_prefix_fwd: null dims/params"); return MLHOT_ERR_ARG; }
+  return np_prefix_forward(*d, *p, x_qry, Nq, ks, K, kh, vh, z, mu, ws, ws_bytes, (hipStream_t)stream);
 }
 // Staged passes (strict sharded parity of the key stabiliser, csrc/stab_xchg.h): stage 0 runs up to the rank-local scalar and
 // publishes it in xchg, stage 1 takes the batch-wide scalar from xchg and runs the rest.

@@ -179,6 +179,10 @@ class ModelEvaluator(BaseEvaluator):
         self._reset(source)
         n, K = self.config.val_iters, self.config.max_ctx_num
         fold = getattr(self.config, "prefix_sweep_fold", False)
+        from networks._vanilla import VanillaNP
+        vanilla = type(self.model).forward is VanillaNP.forward       # its sweep is a function of mlhot.cached
+        if vanilla:
+            from mlhot import cached
         rows = []
         with torch.no_grad():
             def stage():
@@ -189,7 +193,11 @@ class ModelEvaluator(BaseEvaluator):
                     ctx_x, qry_x, ctx_y, qry_y = self._host_batch(source, K)
                 else:
                     ctx_x, qry_x, ctx_y, qry_y = self.ingest.take(ticket)
-                if fold:                                   # each Linear behind the aggregation once, ONE loss launch per batch
+                if vanilla:                                # one encoder pass and one tail launch; fold: ONE loss launch per batch
+                    mu = cached.sweep(self.model, ctx_x, ctx_y, qry_x)
+                    rows.append(self.loss.calc_loss_prefixes(mu, qry_y, test=True) if fold else
+                                torch.stack([self.loss.calc_loss(mu[k], None, qry_y, test=True).view(()) for k in range(K)]))
+                elif fold:                                 # each Linear behind the aggregation once, ONE loss launch per batch
                     mu = self.model.forward_prefixes(ctx_x, ctx_y, qry_x, fold=True)
                     rows.append(self.loss.calc_loss_prefixes(mu, qry_y, test=True))
                 else:

@@ -268,6 +268,10 @@ SIGNATURES = {
     # cached context of the vanilla family: the query tail in one launch
     "mlhot_np_query_supported": (i, [_p(NpDims)]),
     "mlhot_np_query_fwd": (i, [_p(NpDims), _p(NpParams), P, i, P, P, P, P, P]),
+    # prefix sweep of the vanilla family: the query tail for K context prefixes in one launch
+    "mlhot_np_prefix_supported": (i, [_p(NpDims), i]),
+    "mlhot_np_prefix_ws_bytes": (z, [_p(NpDims), i]),
+    "mlhot_np_prefix_fwd": (i, [_p(NpDims), _p(NpParams), P, i, P, i, P, P, P, P, P, z, P]),
     # strict sharded parity of the key stabiliser
     "mlhot_favor_fwd_staged": (i, _qkvp + [P, P, z, i, P, P]),
     "mlhot_favor_bwd_staged": (i, _qkvp + [P, P, P, P, P, P, z, i, P, P]),
@@ -1407,6 +1411,52 @@ class MlhotLib:
         mu = torch.empty(dims.T, x_qry.shape[1], dims.y_dim, device=x_qry.device)
         self._rc(fn(C.byref(dims), C.byref(ps), _ptr(x_qry), x_qry.shape[1], _ptr(key_state), _ptr(vh), _ptr(z), _ptr(mu), _stream(x_qry)),
                  "mlhot_np_query_fwd")
+        return mu
+
+    # ---- prefix sweep of the vanilla family (csrc/np_prefix.h) -------------------------------------------------
+    def np_prefix_supported(self, dims, K):
+        """Whether mlhot_np_prefix_fwd serves these dimensions (dims.Nc: all the context shots) for K prefixes."""
+        return bool(self._fn("np_prefix_supported", "mlhot_np_prefix_supported")(C.byref(dims), int(K)))
+
+    def np_prefix_fwd(self, dims, params, x_qry, ks, kh=None, vh=None, z=None, proj=None):
+        """x_qry [T, Nq, dim_w] -> mu [K, T, Nq, y_dim]: row i is np_query_fwd's result against the first ks[i] of the dims.Nc context
+        shots.  ks: host ints, strictly increasing in 1..Nc.  Attention: kh, vh [T, Nc, 8, dim_w] and proj (the key side runs inside
+        the call); otherwise z [K, T, dim_z].  params: state_dict key -> tensor, the query-side ones are read."""
+        fn = self._fn("np_prefix_fwd", "mlhot_np_prefix_fwd")
+        attend = dims.agg_mode == AGG["attention"]
+        ks = [int(k) for k in ks]
+        K = len(ks)
+        if x_qry.dtype != torch.float32 or x_qry.dim() != 3 or x_qry.shape[0] != dims.T or x_qry.shape[1] < 1 or x_qry.shape[2] != dims.dim_w:
+            raise MlhotError(f"np_prefix_fwd: x_qry must be fp32 [T = {dims.T}, Nq >= 1, dim_w = {dims.dim_w}], got {x_qry.dtype} {tuple(x_qry.shape)}")
+        if not ks or any(k < 1 or k > dims.Nc for k in ks) or any(b <= a for a, b in zip(ks, ks[1:])):
+            raise MlhotError(f"np_prefix_fwd: ks must be strictly increasing in 1..Nc = {dims.Nc}, got {ks}")
+        if not self.np_prefix_supported(dims, K):
+            raise MlhotError(f"np_prefix_fwd serves 1 <= K <= 32 prefixes of 1 <= Nc <= 32 shots within np_query_fwd's envelope (got K={K} Nc={dims.Nc} "
+                             f"dim_w={dims.dim_w} dim_r={dims.dim_r} dim_z={dims.dim_z} dec_hidden={dims.dec_hidden} y_dim={dims.y_dim} m={dims.m_feat})")
+        if attend:
+            want = (dims.T, dims.Nc, HEADS, dims.dim_w)
+            if kh is None or vh is None or proj is None or z is not None or any(t.dtype != torch.float32 or tuple(t.shape) != want for t in (kh, vh)) or \
+                    proj.dtype != torch.float32 or tuple(proj.shape) != (dims.m_feat, dims.dim_w):
+                raise MlhotError(f"np_prefix_fwd: the attention takes kh, vh fp32 {want} and proj fp32 [{dims.m_feat}, {dims.dim_w}], no z")
+        elif z is None or kh is not None or vh is not None or z.dtype != torch.float32 or tuple(z.shape) != (K, dims.T, dims.dim_z):
+            raise MlhotError(f"np_prefix_fwd: without attention the call takes z fp32 [{K}, {dims.T}, {dims.dim_z}], no kh / vh")
+        ps = NpParams()
+        used = []
+        for path, key in vanilla_param_map(dims.n_hidden, False, attend):
+            if path[0] in ("dec_w", "dec_b") or (attend and path[0] in ("r2z_w", "r2z_b", "wq_w", "wq_b", "wo_w", "wo_b")):
+                _set(ps, path, params[key].data_ptr())
+                used.append(params[key])
+        if attend:
+            ps.proj = proj.data_ptr()
+        live = [t for t in (x_qry, kh, vh, z, proj, *used) if t is not None]
+        if any(t.device != x_qry.device for t in live):
+            raise MlhotError("np_prefix_fwd: x_qry, the context rows and the parameters must lie on one device")
+        _chk(*live)
+        nb = self._fn("np_prefix_fwd", "mlhot_np_prefix_ws_bytes")(C.byref(dims), K)
+        ws = self._bytes(nb, x_qry) if attend else None
+        mu = torch.empty(K, dims.T, x_qry.shape[1], dims.y_dim, device=x_qry.device)
+        self._rc(fn(C.byref(dims), C.byref(ps), _ptr(x_qry), x_qry.shape[1], (C.c_int32 * K)(*ks), K, _ptr(kh), _ptr(vh), _ptr(z), _ptr(mu),
+                    _ptr(ws), 0 if ws is None else ws.numel(), _stream(x_qry)), "mlhot_np_prefix_fwd")
         return mu
 
     def np_vanilla_bwd(self, dims, params, ctx_x, ctx_y, qry_x, mu, dmu, saved, scratch=None, proj=None, exchange=None, loss=None):

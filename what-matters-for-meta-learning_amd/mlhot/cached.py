@@ -4,6 +4,8 @@
     state = mlhot.cached.extend(model, state, new_x, new_y, new_len=None)        # more context shots, only they are encoded (6c-3)
     mu = mlhot.cached.predict(model, state, qry_x, chunk=None)        # [T, Nq, y_dim]
     ok, reason = mlhot.cached.supports(model)
+    mu = mlhot.cached.sweep(model, ctx_x, ctx_y, qry_x, ks=None, route=None)      # [len(ks), T, Nq, y_dim]: every context prefix (6b-2)
+    ok, reason = mlhot.cached.supports_sweep(model)
 
 For a ResNetNP instance the two functions are `model.condition` / `model.predict`.  For the vanilla 128x128x1 family (the classes
 whose forward is VanillaNP.forward: CNPVanillaPascal1D, CNPShapeNet1D, ANPVanillaPascal1D, ANPShapeNet1D) they run the path of this
@@ -14,12 +16,13 @@ favor_query (route "composed").  `predict(condition(cx, cy), qx)` equals `model(
 tolerance, not to the bit.  Eval mode only; a state serves the T tasks it was conditioned on and dies with the next weight update.
 """
 import logging
+import numbers
 
 import torch
 
 from mlhot import lib, ragged
 from mlhot.binding import HEADS
-from mlhot.ops import LinearFunction, _c, _need_gpu, favor_keys, favor_query, linear_rows
+from mlhot.ops import LinearFunction, _c, _need_gpu, agg_prefixes, favor_keys, favor_query, linear_rows
 from networks._resnet_np import ResNetNP
 from networks._vanilla import VanillaNP
 from networks._vanilla_mr import VanillaMR
@@ -274,3 +277,119 @@ def _predict_targets(model, state, qry_x, dims, route):
     if route == "fused":
         return lib().np_query_fwd(dims, params, x_qry.view(T, Nq, -1), key_state=state.keys.buf, vh=state.vh, proj=proj)
     return composed_tail(params, x_qry, T, Nq, model.OUT_TANH, keys=state.keys, vh=state.vh, proj=proj, wq=state.wq)
+
+
+# ---- prefix sweep for the vanilla family ---------------------------------------------------------------------------
+def supports_sweep(model):
+    """(bool, reason): whether `sweep` serves this model, and through what - or why not."""
+    if isinstance(model, ResNetNP):
+        if model.PREFIX_SWEEP_REFUSAL:
+            return False, _FRESH_WEIGHTS
+        return True, "ResNetNP.forward_prefixes"
+    if type(model).forward is VanillaNP.forward:
+        return True, "the vanilla family's prefix sweep (mlhot_np_prefix_fwd)"
+    if isinstance(model, VanillaMR):
+        return False, _FRESH_WEIGHTS
+    return False, "the prefix sweep is not built for this class"
+
+
+def _sweep_ks(ks, Nc):
+    if ks is None:
+        return tuple(range(1, Nc + 1))
+    if isinstance(ks, torch.Tensor):
+        if ks.is_cuda or ks.is_floating_point() or ks.dtype == torch.bool or ks.dim() != 1:
+            raise ValueError("sweep: ks must be a host sequence of integers (its values are checked on the host)")
+        ks = ks.tolist()
+    try:
+        ks = list(ks)
+    except TypeError:
+        raise ValueError(f"sweep: ks must be a sequence of context sizes, got {type(ks).__name__}") from None
+    if any(isinstance(k, bool) or not isinstance(k, numbers.Integral) for k in ks):
+        raise ValueError(f"sweep: ks must hold integers, got {ks}")
+    ks = tuple(int(k) for k in ks)
+    if not ks or min(ks) < 1 or max(ks) > Nc or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError(f"sweep: ks must be strictly increasing context sizes in 1..{Nc}, got {list(ks)}")
+    return ks
+
+
+def sweep(model, ctx_x, ctx_y, qry_x, ks=None, route=None):
+    """(ctx images [T, Nc, ...], ctx labels [T, Nc, L], target images [T, Nq, ...]) -> mu [len(ks), T, Nq, y_dim]: row i equals
+    `model(ctx_x[:, :ks[i]], ctx_y[:, :ks[i]], qry_x, test=True)[0]` to the kernels' tolerance.  `ks`: strictly increasing context
+    sizes in 1..Nc (host ints; default 1..Nc).  ONE encoder pass over the context and target images together, the per-shot Linears
+    of `condition`, then route "fused": the prefix aggregate through r_to_z (mean / max / baco) or the key-side launches (attention,
+    inside the call) and ONE mlhot_np_prefix_fwd launch for all prefixes (csrc/np_prefix.h); or route "composed", the parent
+    operators alone: per k the masked state `condition(ctx_len=[k] * T)` builds and `composed_tail` - the yardstick, and the route
+    for dimensions outside the kernel's envelope.  `route=None` picks fused where mlhot_np_prefix_supported says yes; a forced
+    "fused" outside the envelope is an error.  Eval mode only.  A ResNetNP model goes to its forward_prefixes."""
+    if isinstance(model, ResNetNP):
+        if route is not None:
+            raise ValueError("sweep: route= belongs to the vanilla family")
+        return model.forward_prefixes(ctx_x, ctx_y, qry_x, ks=ks)
+    ok, reason = supports_sweep(model)
+    if not ok:
+        raise ValueError(f"{type(model).__name__}: mlhot.cached.sweep: {reason}")
+    if model.training:
+        raise ValueError("sweep is a test-mode path: call model.eval() first")
+    T, Nc, Nq = ctx_x.shape[0], ctx_x.shape[1], qry_x.shape[1]
+    if T != model.task_num or qry_x.shape[0] != T or ctx_y.shape[0] != T:
+        raise ValueError(f"sweep: {T} context and {qry_x.shape[0]} target tasks, the model was built for tasks_per_batch = {model.task_num}")
+    if Nc < 1 or Nq < 1 or ctx_y.shape[1] != Nc:
+        raise ValueError(f"sweep needs at least one context shot with its label and one target (got {Nc} shots, {ctx_y.shape[1]} labels, {Nq} targets)")
+    ks = _sweep_ks(ks, Nc)
+    if route is not None and route not in ROUTES:
+        raise ValueError(f"sweep: route must be one of {ROUTES}, got {route!r}")
+    model._check_agg()
+    _need_gpu(ctx_x, ctx_y, qry_x, *model.parameters())
+    K = len(ks)
+    dims = model._dims(Nc, 1)
+    served = lib().np_prefix_supported(dims, K)
+    if route == "fused" and not served:
+        raise ValueError(f"sweep: route 'fused' - {type(model).__name__}'s dimensions are outside mlhot_np_prefix_fwd's envelope")
+    if route is None:
+        route = "fused" if served else "composed"
+        if route == "composed" and ("sweep", type(model).__name__) not in _logged:
+            _logged.add(("sweep", type(model).__name__))
+            logging.getLogger(__name__).info("mlhot.cached.sweep: %s's dimensions are outside mlhot_np_prefix_fwd's envelope; the sweep runs "
+                                             "composed, one masked state and one composed tail per context size", type(model).__name__)
+    sweep.last_route = route
+    dev = ctx_x.device
+    with torch.no_grad():
+        # the host's one upload goes out before the first launch (an upload from pageable memory waits for the stream)
+        up = None
+        if route == "composed":
+            up = torch.tensor([[k] * T for k in ks] if model.ATTENTION else [[(k - 1) * T + t for t in range(T)] for k in ks], dtype=torch.int32).to(dev)
+        elif not model.ATTENTION and K != Nc:
+            up = torch.tensor([k - 1 for k in ks], dtype=torch.int32).to(dev)
+        shape = (-1, model.img_channels, model.img_size[0], model.img_size[1])
+        x_ctx, x_qry, _ = lib().enc_vanilla_fwd(_c(ctx_x.reshape(shape).float()), _c(qry_x.reshape(shape).float()), _enc_params(model), model.dim_w)
+        ly = LinearFunction.apply(ctx_y.reshape(T * Nc, -1), model.transform_y.weight, model.transform_y.bias, "none")
+        rs = model.encoder_r(torch.cat([x_ctx, ly], dim=1))
+        proj = _c(model.attn.projection_matrix) if model.ATTENTION else None
+        params = {k: _c(p.detach()) for k, p in model.named_parameters()}
+        if model.ATTENTION:
+            kh = _c(LinearFunction.apply(x_ctx, *_stacked(model._W_k), "none").view(T, Nc, HEADS, -1))
+            vh = _c(LinearFunction.apply(rs, *_stacked(model._W_v), "none").view(T, Nc, HEADS, -1))
+            if route == "fused":
+                return lib().np_prefix_fwd(dims, params, x_qry.view(T, Nq, -1), ks, kh=kh, vh=vh, proj=proj)
+            wq = _stacked(model._W_q)
+            return torch.stack([composed_tail(params, x_qry, T, Nq, model.OUT_TANH, keys=favor_keys(kh, proj, lens=(k,) * T, lens_dev=up[i]), vh=vh,
+                                              proj=proj, wq=wq) for i, k in enumerate(ks)])
+        lv = None
+        if model.agg_mode == "baco":
+            lv = LinearFunction.apply(rs, model.rs_to_var.weight, model.rs_to_var.bias, "none").view(T, Nc, -1)
+            rs = LinearFunction.apply(rs, model.rs_to_mu.weight, model.rs_to_mu.bias, "none")
+        r = agg_prefixes(model.agg_mode, rs.view(T, Nc, -1), lv)                          # [Nc, T, R]
+        if route == "fused":
+            if up is not None:
+                r = r.index_select(0, up.long())
+            z = _rows([(r.reshape(K * T, -1), 1, 0)], model.r_to_z.weight.detach(), model.r_to_z.bias.detach(), "none")
+            return lib().np_prefix_fwd(dims, params, x_qry.view(T, Nq, -1), ks, z=z.view(K, T, -1))
+        out = []
+        for i in range(K):                                                                # ragged.gathered_aggregate's rows, then condition's r_to_z
+            rk = r.view(Nc * T, -1).index_select(0, up[i].long())
+            z = LinearFunction.apply(rk, model.r_to_z.weight, model.r_to_z.bias, "none")
+            out.append(composed_tail(params, x_qry, T, Nq, model.OUT_TANH, z=z))
+        return torch.stack(out)
+
+
+sweep.last_route = None

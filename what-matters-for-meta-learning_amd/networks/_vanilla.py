@@ -87,6 +87,10 @@ class VanillaNP(nn.Module):
         return lib().np_grads_layout(self._dims(ctx_num, test_num))
 
     def forward_prefixes(self, *args, **kwargs):
+        """Refuses: the classes of this family gain no sweep method.  Their prefix sweep is `mlhot.cached.sweep(model, ...)` - one
+        encoder pass and one tail launch for every context size - which the evaluator calls under
+        `prefix_sweep = "paired"`.  What still holds of the message below is its second half: the 1D loaders' sweep has no prefix
+        structure, so `prefix_sweep = True` keeps refusing them."""
         raise ValueError(f"{type(self).__name__}.forward_prefixes: the vanilla 128x128x1 family is outside the prefix sweep - its forward is "
                          "one fused call, and its loaders draw shot + shot_max indices from numpy's global generator, so the "
                          "reference's sweep has no prefix structure to reproduce")
