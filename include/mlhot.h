@@ -322,6 +322,40 @@ int mlhot_np_prefix_fwd(const struct mlhot_np_dims* d, const struct mlhot_np_par
                         const int32_t* ks /* [K], host */, int K, const float* kh, const float* vh, const float* z,
                         float* mu, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- cached context beyond 32 shots: a fixed-size FAVOR+ summary state (csrc/favor_summary.h) ---------------------
+ * FAVOR+ is a linear attention, so the context enters the output only through sums over the shots.  With dd[n,j] = (c k_n) . P_j,
+ * diag[n] = |k_n|^2 c^2 / 2, c = d^-1/4, eps = 1e-4 and M = the maximum of dd over every valid shot of all T tasks, all heads and all
+ * features absorbed so far (fast_attention.py:96-97), the state of mlhot_favor_summary_bytes(T, H, d, m) bytes holds, as floats:
+ *   A   [T,H,mp,d]  at 0:                     A[j,e] = sum_n exp(dd[n,j] - diag[n] - M) v[n,e]    (mp = m rounded up to 16)
+ *   a   [T,H,mp]    behind A:                 a[j]   = sum_n exp(dd[n,j] - diag[n] - M)
+ *   vs  [T,H,d]     behind a:                 vs[e]  = sum_n v[n,e]
+ *   M   one float, in a block of 16, behind vs   (kept ONCE per state)
+ *   cnt [T,H] int32 behind M's block:         the shots absorbed by task t (the same for every head)
+ * Features >= m of A and a are exact zeros.  The size does not depend on the number of shots.
+ * mlhot_favor_summary_init: the fresh state - M = -inf, everything else 0.
+ * mlhot_favor_summary_absorb: k, v [T,n,H,d] (n <= 32 NEW shots per task; callers chunk), proj[m,d]; lens[T] (int32, DEVICE memory,
+ *   may be NULL = n for every task) = the valid new shots per task, 0 .. n (a value outside is held to that range).  A row at or
+ *   behind lens[t] of k AND of v is never read - it may hold NaN or Inf.  M' = max(M, max dd of the valid new shots of ALL tasks and
+ *   heads); A <- exp(M - M') A + sum_new exp(dd - diag - M') v, a likewise; vs += sum_new v; cnt += lens.  state_in and state_out may be
+ *   the same pointer (otherwise state_in is left as it is).  ws: mlhot_favor_summary_ws_bytes(T, H, n, d, m) bytes.  Two launches, no
+ *   atomics: every summation order is a function of the dimensions alone, so the same call sequence gives the same bits.
+ * mlhot_favor_summary_query_fwd: q[T,Nq,H,d], state, proj -> out[T,Nq,d*H] in mlhot_favor_fwd's merged order, ONE launch for any Nq:
+ *   out[q,e] = sum_j F_q[q,j] (A[j,e] + eps vs[e]) / sum_j F_q[q,j] (a[j] + eps cnt), F_q as mlhot_favor_query_fwd computes it - equal
+ *   to mlhot_favor_fwd on the concatenated shots in exact arithmetic.  ROW-INVARIANCE guarantee of mlhot_favor_query_fwd: the bits
+ *   of out[t,n,:] depend on q[t,n], the state, proj and the dimensions only.  A task with cnt == 0 has no defined output (0 / 0).
+ * Shapes: d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536, any number of shots; 16-byte aligned pointers.  For others the _bytes
+ * functions return 0 and the calls MLHOT_ERR_UNSUPPORTED, writing nothing.  Forward only; GPU build only.  Added within ABI 7:
+ * bindings look the symbols up. */
+size_t mlhot_favor_summary_bytes(int T, int H, int d, int m);
+size_t mlhot_favor_summary_ws_bytes(int T, int H, int n, int d, int m);
+int mlhot_favor_summary_init(int T, int H, int d, int m, void* state, size_t state_bytes, void* stream);
+int mlhot_favor_summary_absorb(const float* k, const float* v, const float* proj, const int32_t* lens /* [T], device, or NULL */,
+                               int T, int H, int n, int d, int m, const void* state_in, void* state_out, size_t state_bytes,
+                               void* ws, size_t ws_bytes, void* stream);
+size_t mlhot_favor_summary_query_ws_bytes(int T, int H, int Nq, int d, int m);
+int mlhot_favor_summary_query_fwd(const float* q, const void* state, const float* proj, int T, int H, int Nq, int d, int m,
+                                  float* out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- strict sharded parity of the key stabiliser -------------------------
  * fast_attention.py:96-97 takes torch.max over the keys of the WHOLE batch.  When a caller shards the meta-batch over
  * ranks, each rank's launch sequence can be run in two halves around the caller's own collectives on `xchg`

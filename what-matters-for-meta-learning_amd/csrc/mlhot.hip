@@ -28,6 +28,7 @@
 #include "favor_cached.h"
 #include "np_query.h"
 #include "np_prefix.h"
+#include "favor_summary.h"
 #include "resnet_trunk.h"
 #include "../../include/mlhot.h"
 
@@ -335,6 +336,21 @@ int mlhot_np_prefix_fwd(const mlhot_np_dims* d, const mlhot_np_params* p, const 
                         const float* vh, const float* z, float* mu, void* ws, size_t ws_bytes, void* stream) {
   if (!d || !p) { set_error("np_prefix_fwd: null dims/params"); return MLHOT_ERR_ARG; }
   return np_prefix_forward(*d, *p, x_qry, Nq, ks, K, kh, vh, z, mu, ws, ws_bytes, (hipStream_t)stream);
+}
+// the context as a fixed-size summary: any number of shots, absorbed in calls of <= 32 (csrc/favor_summary.h)
+size_t mlhot_favor_summary_bytes(int T, int H, int d, int m) { return favor_summary_need(T, H, d, m); }
+size_t mlhot_favor_summary_ws_bytes(int T, int H, int n, int d, int m) { return favor_summary_ws_need(T, H, n, d, m); }
+int mlhot_favor_summary_init(int T, int H, int d, int m, void* state, size_t state_bytes, void* stream) {
+  return favor_summary_init(T, H, d, m, state, state_bytes, (hipStream_t)stream);
+}
+int mlhot_favor_summary_absorb(const float* k, const float* v, const float* proj, const int32_t* lens, int T, int H, int n, int d, int m,
+                               const void* state_in, void* state_out, size_t state_bytes, void* ws, size_t ws_bytes, void* stream) {
+  return favor_summary_absorb(k, v, proj, lens, T, H, n, d, m, state_in, state_out, state_bytes, ws, ws_bytes, (hipStream_t)stream);
+}
+size_t mlhot_favor_summary_query_ws_bytes(int T, int H, int Nq, int d, int m) { return favor_summary_query_ws_need(T, H, Nq, d, m); }
+int mlhot_favor_summary_query_fwd(const float* q, const void* state, const float* proj, int T, int H, int Nq, int d, int m, float* out,
+                                  void* ws, size_t ws_bytes, void* stream) {
+  return favor_summary_query_forward(q, state, proj, T, H, Nq, d, m, out, ws, ws_bytes, (hipStream_t)stream);
 }
 // Staged passes (strict sharded parity of the key stabiliser, csrc/stab_xchg.h): stage 0 runs up to the rank-local scalar and
 // publishes it in xchg, stage 1 takes the batch-wide scalar from xchg and runs the rest.

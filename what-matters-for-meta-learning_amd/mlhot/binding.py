@@ -272,6 +272,13 @@ SIGNATURES = {
     "mlhot_np_prefix_supported": (i, [_p(NpDims), i]),
     "mlhot_np_prefix_ws_bytes": (z, [_p(NpDims), i]),
     "mlhot_np_prefix_fwd": (i, [_p(NpDims), _p(NpParams), P, i, P, i, P, P, P, P, P, z, P]),
+    # cached context beyond 32 shots: the fixed-size summary state
+    "mlhot_favor_summary_bytes": (z, [i] * 4),
+    "mlhot_favor_summary_ws_bytes": (z, [i] * 5),
+    "mlhot_favor_summary_init": (i, [i, i, i, i, P, z, P]),
+    "mlhot_favor_summary_absorb": (i, [P, P, P, P, i, i, i, i, i, P, P, z, P, z, P]),
+    "mlhot_favor_summary_query_ws_bytes": (z, [i] * 5),
+    "mlhot_favor_summary_query_fwd": (i, [P, P, P, i, i, i, i, i, P, P, z, P]),
     # strict sharded parity of the key stabiliser
     "mlhot_favor_fwd_staged": (i, _qkvp + [P, P, z, i, P, P]),
     "mlhot_favor_bwd_staged": (i, _qkvp + [P, P, P, P, P, P, z, i, P, P]),
@@ -1083,6 +1090,79 @@ class MlhotLib:
         ws = self._bytes(self._fn("favor_query_fwd", "mlhot_favor_query_ws_bytes")(T, H, Nq, Nc, d, m), q)
         fn = self._fn("favor_query_fwd", "mlhot_favor_query_fwd")
         self._rc(fn(_ptr(q), _ptr(state), _ptr(v), _ptr(proj), T, H, Nq, Nc, d, m, _ptr(out), _ptr(ws), ws.numel(), _stream(q)), "mlhot_favor_query_fwd")
+        return out
+
+    # ---- the fixed-size FAVOR+ summary state (csrc/favor_summary.h) ------------------------------
+    def favor_summary_bytes(self, T, H, d, m):
+        """State bytes of the summary kernels; 0 for a shape they do not serve."""
+        return self._fn("favor_summary_init", "mlhot_favor_summary_bytes")(T, H, d, m)
+
+    def favor_summary_init(self, T, H, d, m, device):
+        """A fresh summary state (uint8) for T tasks, H heads, proj [m, d]: M = -inf, everything else 0."""
+        nb = self.favor_summary_bytes(T, H, d, m)
+        if not nb:
+            raise MlhotError(f"favor_summary_init serves d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536 (got d={d} m={m})")
+        state = torch.empty(nb, dtype=torch.uint8, device=device)
+        self._rc(self._fn("favor_summary_init", "mlhot_favor_summary_init")(T, H, d, m, _ptr(state), nb, _stream(state)), "mlhot_favor_summary_init")
+        return state
+
+    def favor_summary_absorb(self, k, v, proj, state, lens=None, out=None):
+        """k, v [T,n,H,d] (n <= 32 new shots per task), proj [m,d], a summary state, lens [T] int32 on k's device or None -> the
+        state with the valid new shots absorbed: `out` (may be `state` itself: in place) or a new buffer; `state` is then left as it
+        is.  Rows at or behind lens[t] of k and v are never read.  The values of lens are the caller's to check (0 .. n)."""
+        fn = self._fn("favor_summary_absorb", "mlhot_favor_summary_absorb")
+        if k.dtype != torch.float32 or k.dim() != 4 or v.dtype != torch.float32 or v.shape != k.shape or proj.dtype != torch.float32 or proj.dim() != 2 \
+                or proj.shape[1] != k.shape[3] or any(t.device != k.device for t in (v, proj, state)):
+            raise MlhotError(f"favor_summary_absorb: k and v must be fp32 [T, n, H, d] and proj fp32 [m, d] on the state's device, got "
+                             f"{tuple(k.shape)}, {tuple(v.shape)}, {tuple(proj.shape)}")
+        T, n, H, d = k.shape
+        m = proj.shape[0]
+        if lens is not None and (lens.dtype != torch.int32 or tuple(lens.shape) != (T,) or lens.device != k.device):
+            raise MlhotError(f"favor_summary_absorb: lens must be int32 [{T}] on {k.device}, got {lens.dtype} {tuple(lens.shape)} on {lens.device}")
+        nb = self.favor_summary_bytes(T, H, d, m)
+        wb = self._fn("favor_summary_absorb", "mlhot_favor_summary_ws_bytes")(T, H, n, d, m)
+        if not nb or not wb:
+            raise MlhotError(f"favor_summary_absorb serves 1 <= n <= 32 new shots per call, d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536 "
+                             f"(got n={n} d={d} m={m}); mlhot.ops.favor_absorb chunks longer inputs")
+        if out is None:
+            out = torch.empty(nb, dtype=torch.uint8, device=k.device)
+        for name, s in (("state", state), ("out", out)):
+            if s.dtype != torch.uint8 or s.numel() < nb or s.device != k.device:
+                raise MlhotError(f"favor_summary_absorb: {name} is not a summary state for T={T} H={H} d={d} m={m} ({s.numel()} bytes, {nb} needed)")
+        _chk(k, v, proj, state, out, *([lens] if lens is not None else []))
+        ws = self._bytes(wb, k)
+        self._rc(fn(_ptr(k), _ptr(v), _ptr(proj), _ptr(lens) if lens is not None else None, T, H, n, d, m, _ptr(state), _ptr(out), nb,
+                    _ptr(ws), ws.numel(), _stream(k)), "mlhot_favor_summary_absorb")
+        return out
+
+    @staticmethod
+    def favor_summary_views(state, T, H, d, m):
+        """(A [T,H,mp,d], a [T,H,mp], vs [T,H,d], cnt [T,H] int32, M [1]) as views of a summary state (include/mlhot.h)."""
+        mp = (m + 15) // 16 * 16
+        f = state.view(torch.float32)
+        nA, na, nv = T * H * mp * d, T * H * mp, T * H * d
+        at = nA + na + nv
+        cnt = state.view(torch.int32)[at + 16:at + 16 + T * H].view(T, H)
+        return f[:nA].view(T, H, mp, d), f[nA:nA + na].view(T, H, mp), f[nA + na:at].view(T, H, d), cnt, f[at:at + 1]
+
+    def favor_summary_query_fwd(self, q, state, proj):
+        """q [T,Nq,H,d], a summary state, proj [m,d] -> out [T,Nq,d*H] (merged order), any Nq >= 1 in one launch, bits per row
+        independent of the other rows (csrc/favor_summary.h).  Forward only."""
+        if q.dtype != torch.float32 or q.dim() != 4 or proj.dtype != torch.float32 or proj.dim() != 2 or proj.shape[1] != q.shape[3] or q.shape[1] < 1:
+            raise MlhotError(f"favor_summary_query_fwd: q must be fp32 [T, Nq, H, d] and proj fp32 [m, d], got {tuple(q.shape)}, {tuple(proj.shape)}")
+        if any(t.device != q.device for t in (state, proj)):
+            raise MlhotError("favor_summary_query_fwd: q, state and proj must lie on one device")
+        T, Nq, H, d = q.shape
+        m = proj.shape[0]
+        nb = self.favor_summary_bytes(T, H, d, m)
+        if not nb or state.dtype != torch.uint8 or state.numel() < nb:
+            raise MlhotError(f"favor_summary_query_fwd: the state is not a summary state for T={T} H={H} d={d} m={m} "
+                             f"({state.numel()} bytes, {nb} needed; 0 = shape not served)")
+        _chk(q, proj, state)
+        out = torch.empty(T, Nq, d * H, device=q.device)
+        ws = self._bytes(self._fn("favor_summary_query_fwd", "mlhot_favor_summary_query_ws_bytes")(T, H, Nq, d, m), q)
+        fn = self._fn("favor_summary_query_fwd", "mlhot_favor_summary_query_fwd")
+        self._rc(fn(_ptr(q), _ptr(state), _ptr(proj), T, H, Nq, d, m, _ptr(out), _ptr(ws), ws.numel(), _stream(q)), "mlhot_favor_summary_query_fwd")
         return out
 
     @staticmethod

@@ -1,6 +1,6 @@
 """Cached-context inference as functions: `condition` once, `predict` for any targets.
 
-    state = mlhot.cached.condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None)
+    state = mlhot.cached.condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys")     # "summary": beyond 32 shots (6c-4)
     state = mlhot.cached.extend(model, state, new_x, new_y, new_len=None)        # more context shots, only they are encoded (6c-3)
     mu = mlhot.cached.predict(model, state, qry_x, chunk=None)        # [T, Nq, y_dim]
     ok, reason = mlhot.cached.supports(model)
@@ -40,12 +40,16 @@ class VanillaContextState:
 
     For extend the state also keeps `lens` (context shots per task, host ints), `capacity` (slots per task: `Nc`
     is the capacity, what the kernels see) and the per-shot rows in slot order [T, capacity, ...]: `kh` and the zero-filled `vh`
-    (attention), `rs` - baco: rs_to_mu's output - and `lv` (latent), with `r`, the aggregate before r_to_z."""
+    (attention), `rs` - baco: rs_to_mu's output - and `lv` (latent), with `r`, the aggregate before r_to_z.
 
-    def __init__(self, owner, T, Nc, fingerprint, kind, keys=None, vh=None, z=None, wq=None, lens=None, kh=None, rs=None, lv=None, r=None):
+    `form` "summary" (DESIGN.md 6c-4): `keys` is a fixed-size summary state (mlhot.ops.favor_absorb), `Nc` the largest of `lens`;
+    there is no capacity and there are no per-shot rows - `vh`, `kh` are None."""
+
+    def __init__(self, owner, T, Nc, fingerprint, kind, keys=None, vh=None, z=None, wq=None, lens=None, kh=None, rs=None, lv=None, r=None,
+                 form="keys"):
         self.owner, self.T, self.Nc, self.fingerprint, self.kind = owner, T, Nc, fingerprint, kind
         self.keys, self.vh, self.z, self.wq, self.route = keys, vh, z, wq, None
-        self.lens, self.capacity = (Nc,) * T if lens is None else tuple(lens), Nc
+        self.lens, self.capacity, self.form = (Nc,) * T if lens is None else tuple(lens), Nc if form == "keys" else None, form
         self.kh, self.rs, self.lv, self.r = kh, rs, lv, r
 
 
@@ -89,15 +93,22 @@ def _stacked(mods):
     return (torch.cat([m.linear.weight.detach() for m in mods], dim=0), torch.cat([m.linear.bias.detach() for m in mods], dim=0))
 
 
-def condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None):
+def condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys"):
     """(ctx images [T, Nc, ...], ctx labels [T, Nc, L]) -> the state for predict: ResNetNP.condition for that family; for the
     vanilla family the encoder, transform_y and encoder_r, then the key / value heads and mlhot.ops.favor_keys (attention) or the
     aggregation and r_to_z (mean / max / baco).  No new kernel; the row count is T * Nc whatever follows.
 
     `ctx_len` (T host ints, 1 .. Nslots): the images are [T, Nslots, ...] and task t's context is its first ctx_len[t] slots; the other
     slots' images and labels are never read.  `capacity` >= Nslots reserves empty slots for extend (default Nslots; an attention
-    model takes at most 32).  Without either argument this is the call it always was."""
+    model takes at most 32).  Without either argument this is the call it always was.
+
+    `form="summary"` (attention models): the state is FAVOR+'s fixed-size summary of the context - any number of
+    shots, `ctx_len` honoured, no `capacity`, no per-shot rows kept; extend absorbs any number of further shots and predict runs
+    the composed route.  The default "keys" is every call as it was."""
+    ragged.check_form("condition", form)
     if isinstance(model, ResNetNP):
+        if form != "keys":
+            return model.condition(ctx_x, ctx_y, ctx_len=ctx_len, capacity=capacity, form=form)
         if ctx_len is None and capacity is None:
             return model.condition(ctx_x, ctx_y)                  # today's call, as it always went out
         return model.condition(ctx_x, ctx_y, ctx_len=ctx_len, capacity=capacity)
@@ -105,6 +116,12 @@ def condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None):
     T, Nc = ctx_x.shape[0], ctx_x.shape[1]
     if T != model.task_num:
         raise ValueError(f"condition: {T} tasks, the model was built for tasks_per_batch = {model.task_num}")
+    if form == "summary":
+        lens = ragged.summary_condition_args("condition", T, Nc, ctx_len, capacity, model.ATTENTION)
+        _need_gpu(ctx_x, ctx_y, *model.parameters())
+        with torch.no_grad():
+            model._check_agg()
+            return _absorb(model, None, ctx_x, ctx_y, lens, _stacked(model._W_q))
     lens, capacity = ragged.condition_args("condition", T, Nc, ctx_len, capacity, model.ATTENTION)
     _need_gpu(ctx_x, ctx_y, *model.parameters())
     with torch.no_grad():
@@ -148,6 +165,11 @@ def extend(model, state, new_x, new_y, new_len=None):
                          "conditioned batch: extend serves the same tasks)")
     if state.fingerprint != _fingerprint(model):
         raise ValueError("extend: the state is stale - a parameter of the model changed since condition()")
+    if state.form == "summary":
+        add = ragged.summary_extend_args("extend", T, n, new_len)
+        _need_gpu(new_x, new_y, *model.parameters())
+        with torch.no_grad():
+            return _absorb(model, state, new_x, new_y, add, state.wq)
     add = ragged.extend_args("extend", state, T, n, new_len)
     _need_gpu(new_x, new_y, *model.parameters())
     with torch.no_grad():
@@ -167,6 +189,20 @@ def _shot_rows(model, imgs, labels):
         lv = LinearFunction.apply(rs, model.rs_to_var.weight, model.rs_to_var.bias, "none")
         return LinearFunction.apply(rs, model.rs_to_mu.weight, model.rs_to_mu.bias, "none"), lv
     return rs, None
+
+
+def _absorb(model, state, images, labels, add, wq):
+    """`add[t]` of the slots of images / labels [T, n, ...] into the summary state (state None: a fresh one): only those shots are
+    encoded, as a packed list, and nothing absorbed earlier is read again."""
+    T, n = model.task_num, images.shape[1]
+    plan = ragged.Plan((0,) * T, add, n, n, images.device)
+    keys = None if state is None else state.keys
+    if plan.n:
+        imgs = ragged.pack(images.reshape(T, n, model.img_channels, model.img_size[0], model.img_size[1]), plan.src)
+        new_k, new_v = _shot_rows(model, imgs, ragged.pack(labels.reshape(T, n, -1), plan.src))
+        keys = ragged.summary_absorb(keys, new_k, new_v, plan, T, n, model.attn.projection_matrix, add)
+    total = keys.lens
+    return VanillaContextState(model, T, max(total), _fingerprint(model), "attention", keys=keys, wq=wq, lens=total, form="summary")
 
 
 def _grow(model, state, lens, capacity, images, labels, add, wq):
@@ -219,6 +255,11 @@ def predict(model, state, qry_x, chunk=None, route=None):
         raise ValueError(f"predict: chunk must be a positive number of targets, got {chunk}")
     if route is not None and route not in ROUTES:
         raise ValueError(f"predict: route must be one of {ROUTES}, got {route!r}")
+    if state.form == "summary":
+        if route == "fused":
+            raise ValueError('predict: route "fused" - mlhot_np_query_fwd reads per-shot key features; a summary state is served by '
+                             "the composed route (linear_rows and favor_query)")
+        route = "composed"
     _need_gpu(qry_x)
     dims = model._dims(state.Nc, 1)
     if route is None:

@@ -490,11 +490,13 @@ def favor_prefixes(qh, kh, vh, proj):
 
 
 class FavorKeyState:
-    """What favor_keys leaves for favor_query.  `route` says what it holds: "cached" - `buf` is mlhot_favor_keys_fwd's state (the
-    finished key features F_k and the batch-global stabiliser M; features() shows them) and favor_query is row-invariant;
-    "plain" - a shape outside the cached kernels' envelope: `kh` itself, favor_query runs mlhot_favor_fwd, no invariance.
+    """What favor_keys / favor_absorb leave for favor_query.  `route` says what it holds: "cached" - `buf` is mlhot_favor_keys_fwd's
+    state (the finished key features F_k and the batch-global stabiliser M; features() shows them) and favor_query is row-invariant;
+    "plain" - a shape outside the cached kernels' envelope: `kh` itself, favor_query runs mlhot_favor_fwd, no invariance;
+    "summary" - favor_absorb's fixed-size state (csrc/favor_summary.h; summary() shows it), any number of shots, row-invariant.
     `lens`: None, or the per-task context sizes (a tuple of T ints) of a masked state (mlhot_favor_keys_ragged_fwd): rows
-    n >= lens[t] of F_k are exact zeros."""
+    n >= lens[t] of F_k are exact zeros.  A summary state always carries `lens`, the shots each task has absorbed so far, and its
+    dims[1] is the largest of them."""
 
     def __init__(self, route, dims, buf=None, kh=None, lens=None):
         self.route, self.dims, self.buf, self.kh, self.lens = route, dims, buf, kh, lens      # dims = (T, Nc, H, d, m)
@@ -502,9 +504,16 @@ class FavorKeyState:
     def features(self):
         """(F_k [T, H, Nc, mp], M [1]) of a "cached" state, as views."""
         if self.route != "cached":
-            raise MlhotError("FavorKeyState.features: this state holds the keys themselves (route 'plain')")
+            raise MlhotError(f"FavorKeyState.features: this state holds no key features (route {self.route!r})")
         T, Nc, H, d, m = self.dims
         return lib().favor_state_views(self.buf, T, H, Nc, m)
+
+    def summary(self):
+        """(A [T, H, mp, d], a [T, H, mp], vs [T, H, d], cnt [T, H] int32, M [1]) of a "summary" state, as views."""
+        if self.route != "summary":
+            raise MlhotError(f"FavorKeyState.summary: this state is no summary (route {self.route!r})")
+        T, _, H, d, m = self.dims
+        return lib().favor_summary_views(self.buf, T, H, d, m)
 
 
 def host_lens(lens, T, lo, hi, what, exc=MlhotError):
@@ -563,11 +572,66 @@ def favor_keys(kh, proj, lens=None, lens_dev=None):
     return FavorKeyState("plain", dims, kh=kh)
 
 
+ABSORB_CHUNK = 32          # new shots per task and mlhot_favor_summary_absorb call
+
+
+def favor_absorb(state, kh, vh, proj, lens=None):
+    """More context shots into a fixed-size FAVOR+ summary: k, v [T, n, H, d] (any n >= 1), proj [m, d] -> a NEW FavorKeyState of
+    route "summary"; `state` (None: a fresh one) stays valid.  The state's size does not depend on the shots it holds and nothing
+    absorbed earlier is read again (csrc/favor_summary.h); the key stabiliser follows the maximum over all valid shots of all T tasks
+    seen so far.  `lens` (a host int sequence or CPU integer tensor of T values in 0..n): task t's new shots are its first lens[t]
+    rows, the others are never read.  Longer inputs go in calls of 32 shots.  d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536, else
+    MlhotError.  Forward only."""
+    _forward_only("favor_absorb", kh, vh, proj)
+    _need_gpu(kh, vh, proj)
+    kh, vh, proj = _c(kh.detach()), _c(vh.detach()), _c(proj.detach())
+    if kh.dim() != 4 or vh.shape != kh.shape or kh.shape[1] < 1 or proj.dim() != 2 or proj.shape[1] != kh.shape[3]:
+        raise MlhotError(f"favor_absorb: k and v must be [T, n >= 1, H, d] and proj [m, d], got {tuple(kh.shape)}, {tuple(vh.shape)}, {tuple(proj.shape)}")
+    T, n, H, d = kh.shape
+    m = proj.shape[0]
+    if state is not None and (not isinstance(state, FavorKeyState) or state.route != "summary"):
+        raise MlhotError("favor_absorb: state must be None or a summary state (favor_keys' states hold per-shot rows: they do not absorb)")
+    if state is not None and (state.dims[0], *state.dims[2:]) != (T, H, d, m):
+        raise MlhotError(f"favor_absorb: the state was built for T={state.dims[0]} H={state.dims[2]} d={state.dims[3]} m={state.dims[4]}; "
+                         f"got k {tuple(kh.shape)}, proj {tuple(proj.shape)}")
+    add = (n,) * T if lens is None else host_lens(lens, T, 0, n, "favor_absorb: lens")
+    if not lib().favor_summary_bytes(T, H, d, m):
+        raise MlhotError(f"favor_absorb serves d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536, got d={d} m={m}")
+    starts = range(0, n, ABSORB_CHUNK)
+    dev = None            # one upload for every chunk's lens, before the first launch
+    if lens is not None:
+        dev = torch.tensor([[min(max(a - s, 0), ABSORB_CHUNK) for a in add] for s in starts], dtype=torch.int32).to(kh.device)
+    buf = lib().favor_summary_init(T, H, d, m, kh.device) if state is None else state.buf
+    for i, s in enumerate(starts):
+        if lens is not None and max(add) <= s:
+            break                                      # nothing valid from here on
+        e = min(s + ABSORB_CHUNK, n)
+        fresh = i > 0 or state is None                 # a buffer of this call's own is updated in place; the caller's state is not
+        buf = lib().favor_summary_absorb(_c(kh[:, s:e]), _c(vh[:, s:e]), proj, buf, lens=None if dev is None else dev[i], out=buf if fresh else None)
+    if state is not None and buf is state.buf:                 # no valid shot at all: still a state of its own
+        buf = buf.clone()
+    total = tuple(a + b for a, b in zip(add, state.lens if state is not None else (0,) * T))
+    return FavorKeyState("summary", (T, max(total), H, d, m), buf=buf, lens=total)
+
+
 def favor_query(qh, state, vh, proj):
     """FAVOR+ attention of q [T, Nq, H, d] against a favor_keys state and v [T, Nc, H, d] -> merged [T, Nq, d*H], any Nq >= 1 in
     one launch.  On the "cached" route the bits of a row do not depend on the other rows of the call (csrc/favor_cached.h); the
     "plain" route is mlhot_favor_fwd on the kept keys.  Forward only.  Against a masked state (favor_keys with lens) the rows of v
-    behind lens[t] must be finite - zero-fill them: their column of S is exactly 0, and 0 x NaN is not."""
+    behind lens[t] must be finite - zero-fill them: their column of S is exactly 0, and 0 x NaN is not.  A "summary" state
+    (favor_absorb) holds what it needs of v: `vh` may be None and is ignored; the call is row-invariant there too
+    (csrc/favor_summary.h) and refuses on the host if a task of the state has absorbed no shot."""
+    if isinstance(state, FavorKeyState) and state.route == "summary":
+        _forward_only("favor_query", qh, proj)
+        T, _, H, d, m = state.dims
+        if min(state.lens) < 1:
+            raise MlhotError(f"favor_query: a task of the summary state has absorbed no shot (shots per task: {list(state.lens)}): "
+                             "its attention is 0 / 0")
+        _need_gpu(qh, proj)
+        qh, proj = _c(qh.detach()), _c(proj.detach())
+        if qh.dim() != 4 or (qh.shape[0], qh.shape[2], qh.shape[3]) != (T, H, d) or tuple(proj.shape) != (m, d):
+            raise MlhotError(f"favor_query: the state was built for T={T} H={H} d={d} m={m}; got q {tuple(qh.shape)}, proj {tuple(proj.shape)}")
+        return lib().favor_summary_query_fwd(qh, state.buf, proj)
     _forward_only("favor_query", qh, vh, proj)
     _need_gpu(qh, vh, proj)
     if not isinstance(state, FavorKeyState):

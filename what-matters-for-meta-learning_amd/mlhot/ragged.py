@@ -6,9 +6,10 @@ import numbers
 
 import torch
 
-from mlhot.ops import agg_prefixes, favor_keys, host_lens
+from mlhot.ops import agg_prefixes, favor_absorb, favor_keys, host_lens
 
 MAX_ATTENTION_CAPACITY = 32        # the cached FAVOR+ kernels' envelope on the context side (csrc/favor_cached.h)
+FORMS = ("keys", "summary")        # what an attention state holds: per-shot key features (<= 32 slots) or the fixed-size summary
 
 
 def condition_args(what, T, Nslots, ctx_len, capacity, attention):
@@ -29,6 +30,41 @@ def condition_args(what, T, Nslots, ctx_len, capacity, attention):
         raise ValueError(f"{what}: capacity = {capacity} is outside the cached attention kernels' envelope "
                          f"(at most {MAX_ATTENTION_CAPACITY} context slots per task)")
     return lens, capacity
+
+
+def check_form(what, form):
+    if form not in FORMS:
+        raise ValueError(f"{what}: form must be one of {FORMS}, got {form!r}")
+    return form
+
+
+def summary_condition_args(what, T, Nslots, ctx_len, capacity, attention):
+    """-> lens for condition(form="summary"): any number of slots, no capacity."""
+    if not attention:
+        raise ValueError(f'{what}: form="summary" serves the attention models; a latent state is one aggregate per task and is not '
+                         "capped at 32 shots - use the default form")
+    if capacity is not None:
+        raise ValueError(f'{what}: form="summary" takes no capacity - a summary state has a fixed size and absorbs any number of shots')
+    if Nslots < 1:
+        raise ValueError(f'{what}: form="summary" needs at least one context shot')
+    return (Nslots,) * T if ctx_len is None else host_lens(ctx_len, T, 1, Nslots, f"{what}: ctx_len", ValueError)
+
+
+def summary_extend_args(what, T, n, new_len):
+    """-> the new shots per task for extend on a summary state: 0 .. n each, no capacity to check."""
+    if n < 1:
+        raise ValueError(f"{what}: no new context slot handed in")
+    return (n,) * T if new_len is None else host_lens(new_len, T, 0, n, f"{what}: new_len", ValueError)
+
+
+def summary_absorb(keys, new_k, new_v, plan, T, n, proj, add):
+    """The packed head rows new_k, new_v [P, H, d] of the valid new shots (plan.dst: their flat slots t * n + j) into the summary
+    state `keys` (None: a fresh one) -> the new summary state (mlhot.ops.favor_absorb; the old one stays valid)."""
+    kh = torch.zeros(T * n, *new_k.shape[1:], device=new_k.device)
+    vh = torch.zeros_like(kh)
+    kh.index_copy_(0, plan.dst, new_k)
+    vh.index_copy_(0, plan.dst, new_v)
+    return favor_absorb(keys, kh.view(T, n, *new_k.shape[1:]), vh.view(T, n, *new_k.shape[1:]), proj, lens=add)
 
 
 def extend_args(what, state, T, n, new_len):

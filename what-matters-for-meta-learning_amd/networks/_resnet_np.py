@@ -52,12 +52,15 @@ class ContextState:
 
     For extend the state also keeps `lens` (context shots per task, host ints), `capacity` (slots per task: `Nc`
     is the capacity, what the kernels see) and the per-shot rows in slot order [T, capacity, ...]: `kh` and the zero-filled `vh`
-    (attention), `rs` - baco: latent_mu's output - and `lv` (latent), with `r` [T, 256], the aggregate before `mu`."""
+    (attention), `rs` - baco: latent_mu's output - and `lv` (latent), with `r` [T, 256], the aggregate before `mu`.
 
-    def __init__(self, owner, T, Nc, fingerprint, kind, keys=None, vh=None, z=None, lens=None, kh=None, rs=None, lv=None, r=None):
+    `form` "summary" (DESIGN.md 6c-4): `keys` is a fixed-size summary state (mlhot.ops.favor_absorb), `Nc` the largest of `lens`;
+    there is no capacity and there are no per-shot rows - `vh`, `kh` are None."""
+
+    def __init__(self, owner, T, Nc, fingerprint, kind, keys=None, vh=None, z=None, lens=None, kh=None, rs=None, lv=None, r=None, form="keys"):
         self.owner, self.T, self.Nc, self.fingerprint, self.kind = owner, T, Nc, fingerprint, kind
         self.keys, self.vh, self.z = keys, vh, z
-        self.lens, self.capacity = (Nc,) * T if lens is None else tuple(lens), Nc
+        self.lens, self.capacity, self.form = (Nc,) * T if lens is None else tuple(lens), Nc if form == "keys" else None, form
         self.kh, self.rs, self.lv, self.r = kh, rs, lv, r
 
 
@@ -484,7 +487,7 @@ class ResNetNP(nn.Module):
         if self.training:
             raise ValueError(f"{what} is a test-mode path: call model.eval() first")
 
-    def condition(self, batch_train_images, label_train, ctx_len=None, capacity=None):
+    def condition(self, batch_train_images, label_train, ctx_len=None, capacity=None, form="keys"):
         """(ctx images [T, Nc, ...], ctx labels) -> ContextState: everything of `forward(..., test=True)` that does not depend on
         the targets, once - the context trunk pass, the task encoder and, for the attention models, the key / value head
         projections and the FAVOR+ key features (mlhot.ops.favor_keys); for the others the aggregation and `mu`.  The key
@@ -492,11 +495,22 @@ class ResNetNP(nn.Module):
 
         `ctx_len` (T host ints, 1 .. Nslots): the images are [T, Nslots, ...] and task t's context is its first ctx_len[t] slots; the
         other slots' images and labels are never read.  `capacity` >= Nslots reserves empty slots for extend (default Nslots; an
-        attention model takes at most 32).  Without either argument this is the call it always was."""
+        attention model takes at most 32).  Without either argument this is the call it always was.
+
+        `form="summary"` (attention models): the state is FAVOR+'s fixed-size summary of the context - any number
+        of shots, `ctx_len` honoured, no `capacity`, no per-shot rows kept; extend absorbs any number of further shots."""
+        ragged.check_form("condition", form)
         self._cached_refusals("condition")
         T, Nc = batch_train_images.shape[0], batch_train_images.shape[1]
         if T != self.task_num:
             raise ValueError(f"condition: {T} tasks, the model was built for tasks_per_batch = {self.task_num}")
+        if form == "summary":
+            lens = ragged.summary_condition_args("condition", T, Nc, ctx_len, capacity, self.ATTENTION)
+            self._refresh_arena()
+            with torch.no_grad():
+                for mods in (self._W_q, self._W_k, self._W_v):
+                    self._stack(mods).tensors()
+                return self._absorb(None, batch_train_images, label_train, lens)
         lens, capacity = ragged.condition_args("condition", T, Nc, ctx_len, capacity, self.ATTENTION)
         self._refresh_arena()
         with torch.no_grad():
@@ -537,6 +551,11 @@ class ResNetNP(nn.Module):
                              "conditioned batch: extend serves the same tasks)")
         if state.fingerprint != self._fingerprint():
             raise ValueError("extend: the state is stale - a parameter of the model changed since condition()")
+        if state.form == "summary":
+            add = ragged.summary_extend_args("extend", T, n, new_len)
+            self._refresh_arena()
+            with torch.no_grad():
+                return self._absorb(state, new_images, new_labels, add)
         add = ragged.extend_args("extend", state, T, n, new_len)
         self._refresh_arena()
         with torch.no_grad():
@@ -554,6 +573,18 @@ class ResNetNP(nn.Module):
         if self.ATTENTION:
             return self._heads(x_ctx[None], self._W_k)[0], self._heads(feats[None], self._W_v)[0]
         return self._latent_rows(feats)
+
+    def _absorb(self, state, images, labels, add):
+        """`add[t]` of the slots of images / labels [T, n, ...] into the summary state (state None: a fresh one): only those shots
+        run through the trunk, the task encoder and the head projections, and nothing absorbed earlier is read again."""
+        T, n = self.task_num, images.shape[1]
+        C, H, W = self.img_channels, self.img_size[0], self.img_size[1]
+        plan = ragged.Plan((0,) * T, add, n, n, images.device)
+        keys = None if state is None else state.keys
+        if plan.n:
+            new_k, new_v = self._shot_rows(ragged.pack(images.reshape(T, n, C, H, W), plan.src), ragged.pack(labels, plan.src))
+            keys = ragged.summary_absorb(keys, new_k, new_v, plan, T, n, self.attn.projection_matrix, add)
+        return ContextState(self, T, max(keys.lens), self._fingerprint(), "attention", keys=keys, lens=keys.lens, form="summary")
 
     def _grow(self, state, lens, capacity, images, labels, add):
         """`add[t]` of the slots of images / labels [T, n, ...] behind task t's lens[t] kept rows (state None: nothing kept yet), then
