@@ -356,6 +356,30 @@ size_t mlhot_favor_summary_query_ws_bytes(int T, int H, int Nq, int d, int m);
 int mlhot_favor_summary_query_fwd(const float* q, const void* state, const float* proj, int T, int H, int Nq, int d, int m,
                                   float* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- prefix sweep beyond 32 context shots: chunked running FAVOR+ prefixes (csrc/favor_prefix_long.h) -------------
+ * mlhot_favor_prefix_long_fwd: q[T,Nq,H,d], k, v[T,Nc,H,d], proj[m,d] -> out[K,T,Nq,d*H] in mlhot_favor_fwd's merged order; out[i]
+ *   is mlhot_favor_fwd on the first ks[i] shots of every task in exact arithmetic, its batch-global key stabiliser included: prefix i
+ *   uses M_i = the maximum of dd over the valid shots < ks[i] of ALL tasks, heads and features (fast_attention.py:96-97), and the key
+ *   feature's +1e-4 floor relative to M_i.  ks: K ints in HOST memory, strictly increasing, 1 <= ks[i] <= Nc (else MLHOT_ERR_ARG).
+ *   lens[T] (int32, DEVICE memory, read on the device; may be NULL = Nc for every task): task t's context is its first lens[t] shots,
+ *   1 <= lens[t] <= Nc (the caller's contract; a value outside is held to 0 .. Nc, and a task without a shot has no defined output);
+ *   a prefix size above lens[t] saturates at lens[t] for that task while M_i still follows every task's valid shots < ks[i].  A row at
+ *   or behind lens[t] of k AND of v is never read - it may hold NaN or Inf.
+ *   Three launches, no atomics, no [mp x d] state: the shots are walked in chunks of 32 with running sums relative to the running
+ *   maximum (rescaled by exp(M_old - M_new) <= 1).  Every summation order is a function of the dimensions and of ks[i] alone, so
+ *   out[i] has the same bits whichever other prefixes are asked for, and the ROW-INVARIANCE guarantee of mlhot_favor_query_fwd holds:
+ *   the bits of out[i,t,n,:] depend on q[t,n], the first ks[i] shots of the batch, proj and the dimensions only.
+ * Served (mlhot_favor_prefix_long_supported): d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536, 1 <= K <= 64, any Nc >= 1, any Nq >= 1
+ * (T H < 2^20; T H ceil(Nc / 32) and T H ceil(Nq / 16) below 2^31); 16-byte aligned pointers; ws of
+ * mlhot_favor_prefix_long_workspace_bytes bytes (0 for a shape not served).  Otherwise MLHOT_ERR_UNSUPPORTED, nothing written.
+ * Forward only; GPU build only.  Added within ABI 7: bindings look the symbols up. */
+int mlhot_favor_prefix_long_supported(int T, int H, int Nq, int Nc, int d, int m, int K);
+size_t mlhot_favor_prefix_long_workspace_bytes(int T, int H, int Nq, int Nc, int d, int m, int K);
+int mlhot_favor_prefix_long_fwd(const float* q, const float* k, const float* v, const float* proj,
+                                const int32_t* ks /* [K], host */, int K, const int32_t* lens /* [T], device, or NULL */,
+                                int T, int H, int Nq, int Nc, int d, int m, float* out,
+                                void* ws, size_t ws_bytes, void* stream);
+
 /* ---- strict sharded parity of the key stabiliser -------------------------
  * fast_attention.py:96-97 takes torch.max over the keys of the WHOLE batch.  When a caller shards the meta-batch over
  * ranks, each rank's launch sequence can be run in two halves around the caller's own collectives on `xchg`

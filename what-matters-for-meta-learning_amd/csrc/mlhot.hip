@@ -29,6 +29,7 @@
 #include "np_query.h"
 #include "np_prefix.h"
 #include "favor_summary.h"
+#include "favor_prefix_long.h"
 #include "resnet_trunk.h"
 #include "../../include/mlhot.h"
 
@@ -351,6 +352,13 @@ size_t mlhot_favor_summary_query_ws_bytes(int T, int H, int Nq, int d, int m) { 
 int mlhot_favor_summary_query_fwd(const float* q, const void* state, const float* proj, int T, int H, int Nq, int d, int m, float* out,
                                   void* ws, size_t ws_bytes, void* stream) {
   return favor_summary_query_forward(q, state, proj, T, H, Nq, d, m, out, ws, ws_bytes, (hipStream_t)stream);
+}
+// K context prefixes of any length: running sums over 32-shot chunks, three launches (csrc/favor_prefix_long.h)
+int mlhot_favor_prefix_long_supported(int T, int H, int Nq, int Nc, int d, int m, int K) { return favor_prefix_long_ok(T, H, Nq, Nc, d, m, K) ? 1 : 0; }
+size_t mlhot_favor_prefix_long_workspace_bytes(int T, int H, int Nq, int Nc, int d, int m, int K) { return favor_prefix_long_ws_need(T, H, Nq, Nc, d, m, K); }
+int mlhot_favor_prefix_long_fwd(const float* q, const float* k, const float* v, const float* proj, const int32_t* ks, int K, const int32_t* lens,
+                                int T, int H, int Nq, int Nc, int d, int m, float* out, void* ws, size_t ws_bytes, void* stream) {
+  return favor_prefix_long_forward(q, k, v, proj, ks, K, lens, T, H, Nq, Nc, d, m, out, ws, ws_bytes, (hipStream_t)stream);
 }
 // Staged passes (strict sharded parity of the key stabiliser, csrc/stab_xchg.h): stage 0 runs up to the rank-local scalar and
 // publishes it in xchg, stage 1 takes the batch-wide scalar from xchg and runs the rest.

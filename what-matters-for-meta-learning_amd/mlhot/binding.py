@@ -279,6 +279,10 @@ SIGNATURES = {
     "mlhot_favor_summary_absorb": (i, [P, P, P, P, i, i, i, i, i, P, P, z, P, z, P]),
     "mlhot_favor_summary_query_ws_bytes": (z, [i] * 5),
     "mlhot_favor_summary_query_fwd": (i, [P, P, P, i, i, i, i, i, P, P, z, P]),
+    # prefix sweep beyond 32 context shots: chunked running FAVOR+ prefixes
+    "mlhot_favor_prefix_long_supported": (i, [i] * 7),
+    "mlhot_favor_prefix_long_workspace_bytes": (z, [i] * 7),
+    "mlhot_favor_prefix_long_fwd": (i, [P, P, P, P, P, i, P, i, i, i, i, i, i, P, P, z, P]),
     # strict sharded parity of the key stabiliser
     "mlhot_favor_fwd_staged": (i, _qkvp + [P, P, z, i, P, P]),
     "mlhot_favor_bwd_staged": (i, _qkvp + [P, P, P, P, P, P, z, i, P, P]),
@@ -1163,6 +1167,49 @@ class MlhotLib:
         ws = self._bytes(self._fn("favor_summary_query_fwd", "mlhot_favor_summary_query_ws_bytes")(T, H, Nq, d, m), q)
         fn = self._fn("favor_summary_query_fwd", "mlhot_favor_summary_query_fwd")
         self._rc(fn(_ptr(q), _ptr(state), _ptr(proj), T, H, Nq, d, m, _ptr(out), _ptr(ws), ws.numel(), _stream(q)), "mlhot_favor_summary_query_fwd")
+        return out
+
+    # ---- prefix sweep beyond 32 context shots (csrc/favor_prefix_long.h) --------------------------
+    def favor_prefix_long_supported(self, T, H, Nq, Nc, d, m, K):
+        """Whether mlhot_favor_prefix_long_fwd serves these dimensions and this number of prefixes."""
+        return bool(self._fn("favor_prefix_long_fwd", "mlhot_favor_prefix_long_supported")(T, H, Nq, Nc, d, m, K))
+
+    def favor_prefix_long_workspace_bytes(self, T, H, Nq, Nc, d, m, K):
+        """Workspace bytes of mlhot_favor_prefix_long_fwd; 0 for a call it does not serve."""
+        return self._fn("favor_prefix_long_fwd", "mlhot_favor_prefix_long_workspace_bytes")(T, H, Nq, Nc, d, m, K)
+
+    def favor_prefix_long_fwd(self, q, k, v, proj, ks, lens=None, out=None):
+        """q [T,Nq,H,d], k/v [T,Nc,H,d], proj [m,d], ks (host ints, strictly increasing in 1..Nc, at most 64) -> out [K,T,Nq,d*H]:
+        out[i] = favor_fwd on the first ks[i] shots.  lens [T] int32 on q's device or None: task t's context is its first lens[t]
+        shots (values 1..Nc are the caller's to check); rows behind it of k and v are never read.  Forward only."""
+        fn = self._fn("favor_prefix_long_fwd", "mlhot_favor_prefix_long_fwd")
+        for name, t in (("q", q), ("k", k), ("v", v)):
+            if t.dtype != torch.float32 or t.dim() != 4:
+                raise MlhotError(f"favor_prefix_long_fwd: {name} must be fp32 [T, N, H, d], got {t.dtype} {tuple(t.shape)}")
+        T, Nq, H, d = q.shape
+        Nc = k.shape[1]
+        if tuple(k.shape) != (T, Nc, H, d) or v.shape != k.shape or proj.dtype != torch.float32 or proj.dim() != 2 or proj.shape[1] != d:
+            raise MlhotError(f"favor_prefix_long_fwd: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, proj {tuple(proj.shape)} do not fit together")
+        if any(t.device != q.device for t in (k, v, proj)):
+            raise MlhotError("favor_prefix_long_fwd: q, k, v and proj must lie on one device")
+        ks = [int(x) for x in ks]
+        K, m = len(ks), proj.shape[0]
+        if not ks or any(x < 1 or x > Nc for x in ks) or any(b <= a for a, b in zip(ks, ks[1:])):
+            raise MlhotError(f"favor_prefix_long_fwd: ks must be strictly increasing in 1..Nc = {Nc}, got {ks}")
+        if lens is not None and (lens.dtype != torch.int32 or tuple(lens.shape) != (T,) or lens.device != q.device):
+            raise MlhotError(f"favor_prefix_long_fwd: lens must be int32 [{T}] on {q.device}, got {lens.dtype} {tuple(lens.shape)} on {lens.device}")
+        wb = self.favor_prefix_long_workspace_bytes(T, H, Nq, Nc, d, m, K)
+        if not wb:
+            raise MlhotError(f"favor_prefix_long_fwd serves d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536, 1 <= K <= 64, Nq, Nc >= 1 "
+                             f"(got Nq={Nq} Nc={Nc} d={d} m={m} K={K})")
+        if out is None:
+            out = torch.empty(K, T, Nq, d * H, device=q.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (K, T, Nq, d * H) or out.device != q.device or not out.is_contiguous():
+            raise MlhotError(f"favor_prefix_long_fwd: out must be contiguous fp32 {(K, T, Nq, d * H)} on {q.device}")
+        _chk(q, k, v, proj, *([lens] if lens is not None else []))
+        ws = self._bytes(wb, q)
+        self._rc(fn(_ptr(q), _ptr(k), _ptr(v), _ptr(proj), (C.c_int32 * K)(*ks), K, _ptr(lens) if lens is not None else None, T, H, Nq, Nc, d, m,
+                    _ptr(out), _ptr(ws), ws.numel(), _stream(q)), "mlhot_favor_prefix_long_fwd")
         return out
 
     @staticmethod

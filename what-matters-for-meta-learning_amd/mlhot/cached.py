@@ -22,7 +22,7 @@ import torch
 
 from mlhot import lib, ragged
 from mlhot.binding import HEADS
-from mlhot.ops import LinearFunction, _c, _need_gpu, agg_prefixes, favor_keys, favor_query, linear_rows
+from mlhot.ops import LinearFunction, _c, _need_gpu, agg_prefixes, favor_keys, favor_prefixes_long, favor_query, linear_rows
 from networks._resnet_np import ResNetNP
 from networks._vanilla import VanillaNP
 from networks._vanilla_mr import VanillaMR
@@ -306,6 +306,19 @@ def composed_tail(params, x_qry, T, Nq, tanh, keys=None, vh=None, proj=None, z=N
     return lin([(h, 1, 0)], "decoder0.4", "tanh" if tanh else "none").view(T, Nq, -1)
 
 
+def _long_tail(params, x_qry, T, Nq, tanh, favor, kh, vh, proj, wq, ks):
+    """composed_tail for the prefixes `ks` of an attention context of any length: the query heads once, `favor` (favor_prefixes_long)
+    once for all prefixes, then every Linear once over the len(ks) * T * Nq rows - row-invariant, so a row has composed_tail's bits."""
+    def lin(sources, name, act="none"):
+        return _rows(sources, params[name + ".weight"], params[name + ".bias"], act)
+    qh = _rows([(x_qry, 1, 0)], wq[0], wq[1], "none").view(T, Nq, HEADS, -1)
+    merged = favor(qh, kh, vh, proj, ks).view(len(ks) * T * Nq, -1)
+    zq = lin([(lin([(merged, 1, 0)], "_W.linear"), 1, 0)], "r_to_z")
+    h = lin([(x_qry, 1, T * Nq), (zq, 1, 0)], "decoder0.0", "relu")
+    h = lin([(h, 1, 0)], "decoder0.2", "relu")
+    return lin([(h, 1, 0)], "decoder0.4", "tanh" if tanh else "none").view(len(ks), T, Nq, -1)
+
+
 def _predict_targets(model, state, qry_x, dims, route):
     T, Nq = qry_x.shape[0], qry_x.shape[1]
     x_qry = _encode(model, qry_x)
@@ -361,7 +374,12 @@ def sweep(model, ctx_x, ctx_y, qry_x, ks=None, route=None):
     inside the call) and ONE mlhot_np_prefix_fwd launch for all prefixes (csrc/np_prefix.h); or route "composed", the parent
     operators alone: per k the masked state `condition(ctx_len=[k] * T)` builds and `composed_tail` - the yardstick, and the route
     for dimensions outside the kernel's envelope.  `route=None` picks fused where mlhot_np_prefix_supported says yes; a forced
-    "fused" outside the envelope is an error.  Eval mode only.  A ResNetNP model goes to its forward_prefixes."""
+    "fused" outside the envelope is an error.  Eval mode only.  A ResNetNP model goes to its forward_prefixes.
+
+    An attention model with Nc > 32 runs composed with mlhot.ops.favor_prefixes_long in place of the per-prefix
+    FAVOR+ stage: the shots are walked once in chunks of 32 for all of `ks`, and the Linears behind it run once over the rows of all
+    prefixes through linear_rows - bit-equal however `ks` is split; route "fused" is an error there.  `sweep.last_attention` says
+    which FAVOR+ stage the last attention sweep ran: "np_prefix" | "favor_keys" | "prefix_long"."""
     if isinstance(model, ResNetNP):
         if route is not None:
             raise ValueError("sweep: route= belongs to the vanilla family")
@@ -383,12 +401,16 @@ def sweep(model, ctx_x, ctx_y, qry_x, ks=None, route=None):
     _need_gpu(ctx_x, ctx_y, qry_x, *model.parameters())
     K = len(ks)
     dims = model._dims(Nc, 1)
-    served = lib().np_prefix_supported(dims, K)
+    long_ctx = model.ATTENTION and Nc > ragged.MAX_ATTENTION_CAPACITY
+    if long_ctx and route == "fused":
+        raise ValueError(f"sweep: route 'fused' - mlhot_np_prefix_fwd serves at most {ragged.MAX_ATTENTION_CAPACITY} context shots (got {Nc}); "
+                         "a longer attention context runs composed, with mlhot.ops.favor_prefixes_long")
+    served = not long_ctx and lib().np_prefix_supported(dims, K)
     if route == "fused" and not served:
         raise ValueError(f"sweep: route 'fused' - {type(model).__name__}'s dimensions are outside mlhot_np_prefix_fwd's envelope")
     if route is None:
         route = "fused" if served else "composed"
-        if route == "composed" and ("sweep", type(model).__name__) not in _logged:
+        if route == "composed" and not long_ctx and ("sweep", type(model).__name__) not in _logged:
             _logged.add(("sweep", type(model).__name__))
             logging.getLogger(__name__).info("mlhot.cached.sweep: %s's dimensions are outside mlhot_np_prefix_fwd's envelope; the sweep runs "
                                              "composed, one masked state and one composed tail per context size", type(model).__name__)
@@ -397,7 +419,7 @@ def sweep(model, ctx_x, ctx_y, qry_x, ks=None, route=None):
     with torch.no_grad():
         # the host's one upload goes out before the first launch (an upload from pageable memory waits for the stream)
         up = None
-        if route == "composed":
+        if route == "composed" and not long_ctx:
             up = torch.tensor([[k] * T for k in ks] if model.ATTENTION else [[(k - 1) * T + t for t in range(T)] for k in ks], dtype=torch.int32).to(dev)
         elif not model.ATTENTION and K != Nc:
             up = torch.tensor([k - 1 for k in ks], dtype=torch.int32).to(dev)
@@ -410,9 +432,12 @@ def sweep(model, ctx_x, ctx_y, qry_x, ks=None, route=None):
         if model.ATTENTION:
             kh = _c(LinearFunction.apply(x_ctx, *_stacked(model._W_k), "none").view(T, Nc, HEADS, -1))
             vh = _c(LinearFunction.apply(rs, *_stacked(model._W_v), "none").view(T, Nc, HEADS, -1))
+            sweep.last_attention = "prefix_long" if long_ctx else "np_prefix" if route == "fused" else "favor_keys"
             if route == "fused":
                 return lib().np_prefix_fwd(dims, params, x_qry.view(T, Nq, -1), ks, kh=kh, vh=vh, proj=proj)
             wq = _stacked(model._W_q)
+            if long_ctx:
+                return _long_tail(params, x_qry, T, Nq, model.OUT_TANH, favor_prefixes_long, kh, vh, proj, wq, ks)
             return torch.stack([composed_tail(params, x_qry, T, Nq, model.OUT_TANH, keys=favor_keys(kh, proj, lens=(k,) * T, lens_dev=up[i]), vh=vh,
                                               proj=proj, wq=wq) for i, k in enumerate(ks)])
         lv = None
@@ -434,3 +459,4 @@ def sweep(model, ctx_x, ctx_y, qry_x, ks=None, route=None):
 
 
 sweep.last_route = None
+sweep.last_attention = None

@@ -489,6 +489,61 @@ def favor_prefixes(qh, kh, vh, proj):
     return torch.stack([lib().favor_fwd(qh, kh[:, :k].contiguous(), vh[:, :k].contiguous(), proj)[0] for k in range(1, Nc + 1)])
 
 
+PREFIX_LONG_MAX_K = 64     # prefixes per mlhot_favor_prefix_long_fwd call
+
+
+def prefix_sizes(ks, Nc, what, exc=MlhotError):
+    """ks (None: 1..Nc; a host int sequence or CPU integer tensor) -> a tuple of strictly increasing context sizes in 1..Nc, or `exc`."""
+    if ks is None:
+        return tuple(range(1, Nc + 1))
+    if isinstance(ks, torch.Tensor):
+        if ks.is_cuda or ks.is_floating_point() or ks.is_complex() or ks.dtype == torch.bool or ks.dim() != 1:
+            raise exc(f"{what}: ks must be a host sequence of integers (its values are checked on the host)")
+        ks = ks.tolist()
+    try:
+        ks = list(ks)
+    except TypeError:
+        raise exc(f"{what}: ks must be a sequence of context sizes, got {type(ks).__name__}") from None
+    if any(isinstance(k, bool) or not isinstance(k, numbers.Integral) for k in ks):
+        raise exc(f"{what}: ks must hold integers, got {ks}")
+    ks = tuple(int(k) for k in ks)
+    if not ks or min(ks) < 1 or max(ks) > Nc or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise exc(f"{what}: ks must be strictly increasing context sizes in 1..{Nc}, got {list(ks)}")
+    return ks
+
+
+def favor_prefixes_long(qh, kh, vh, proj, ks=None, lens=None):
+    """FAVOR+ attention for the context prefixes `ks` of a context of ANY length: q [T, Nq, H, d], k / v [T, Nc, H, d], proj [m, d]
+    -> [K, T, Nq, d*H], element i = FavorFunction on kh[:, :ks[i]], vh[:, :ks[i]] in exact arithmetic - its batch-global key
+    stabiliser taken over those ks[i] shots only, and the key feature's floor relative to it.  `ks`: strictly increasing host ints
+    in 1..Nc (default 1..Nc); more than 64 go out in calls of 64, and an element's bits do not depend on which others are asked for.
+    `lens` (a host int sequence or CPU integer tensor of T values in 1..Nc; checked on the host, then uploaded and read on the
+    device): task t's context is its first lens[t] shots - a prefix size above lens[t] saturates at lens[t] for that task, while the
+    stabiliser of prefix i still follows every task's valid shots < ks[i]; rows of k AND v behind lens[t] are never read.  A task
+    without a shot has no attention (0 / 0): lens = 0 is refused here.  The shots are walked in chunks of 32 with running sums
+    (csrc/favor_prefix_long.h): three launches per call, no state of the context's size times m, row-invariant in the targets.
+    d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536, else MlhotError.  Forward only."""
+    _forward_only("favor_prefixes_long", qh, kh, vh, proj)
+    _need_gpu(qh, kh, vh, proj)
+    qh, kh, vh, proj = _c(qh.detach()), _c(kh.detach()), _c(vh.detach()), _c(proj.detach())
+    if qh.dim() != 4 or kh.dim() != 4 or vh.shape != kh.shape or qh.shape[1] < 1 or kh.shape[1] < 1 or proj.dim() != 2 or \
+            (kh.shape[0], kh.shape[2], kh.shape[3]) != (qh.shape[0], qh.shape[2], qh.shape[3]) or proj.shape[1] != qh.shape[3]:
+        raise MlhotError(f"favor_prefixes_long: q must be [T, Nq >= 1, H, d], k and v [T, Nc >= 1, H, d] and proj [m, d], got "
+                         f"{tuple(qh.shape)}, {tuple(kh.shape)}, {tuple(vh.shape)}, {tuple(proj.shape)}")
+    T, Nq, H, d = qh.shape
+    Nc, m = kh.shape[1], proj.shape[0]
+    ks = prefix_sizes(ks, Nc, "favor_prefixes_long")
+    if lens is not None:
+        lens = host_lens(lens, T, 1, Nc, "favor_prefixes_long: lens")
+    if not lib().favor_prefix_long_supported(T, H, Nq, Nc, d, m, min(len(ks), PREFIX_LONG_MAX_K)):
+        raise MlhotError(f"favor_prefixes_long serves d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536, got d={d} m={m} (T={T} H={H} Nq={Nq} Nc={Nc})")
+    dev = None if lens is None else torch.tensor(lens, dtype=torch.int32).to(qh.device)      # the one upload, before the first launch
+    out = torch.empty(len(ks), T, Nq, d * H, device=qh.device)
+    for i in range(0, len(ks), PREFIX_LONG_MAX_K):
+        lib().favor_prefix_long_fwd(qh, kh, vh, proj, ks[i:i + PREFIX_LONG_MAX_K], lens=dev, out=out[i:i + PREFIX_LONG_MAX_K])
+    return out
+
+
 class FavorKeyState:
     """What favor_keys / favor_absorb leave for favor_query.  `route` says what it holds: "cached" - `buf` is mlhot_favor_keys_fwd's
     state (the finished key features F_k and the batch-global stabiliser M; features() shows them) and favor_query is row-invariant;

@@ -11,7 +11,7 @@ import logging
 
 from mlhot import lib, ragged
 from mlhot.ops import (AggFunction, FavorFunction, HeadStacksFunction, LinearFunction, StackedLinearFunction, agg_prefixes,
-                       favor_keys, favor_prefixes, favor_query, linear_rows)
+                       favor_keys, favor_prefixes, favor_prefixes_long, favor_query, linear_rows)
 from networks.ResNet import run_conv
 from networks.fast_attention import FastAttention
 from networks.models import AttnLinear, ImageEncoder, NPDecoder, _aggregate_feature_map, _mlp3, run_trunks
@@ -452,13 +452,21 @@ class ResNetNP(nn.Module):
             feats = _mlp3(x_ctx, self.task_encoder, last_relu=True, side=label_train)
             if self.ATTENTION:
                 qh, kh, vh = self._head_projections(x_ctx, feats, x_tgt)
-                merged = favor_prefixes(qh, kh, vh, self.attn.projection_matrix)             # [Nc, T, Nq, heads * 256]
+                sel = ks                                                                      # merged[k - 1] for k in sel
+                if Nc > ragged.MAX_ATTENTION_CAPACITY:        # one walk over the shots, the asked-for sizes only
+                    sizes = sorted(set(ks))
+                    merged = favor_prefixes_long(qh, kh, vh, self.attn.projection_matrix, sizes)
+                    sel = [sizes.index(k) + 1 for k in ks]
+                    self.last_prefix_attention = "prefix_long"
+                else:
+                    merged = favor_prefixes(qh, kh, vh, self.attn.projection_matrix)         # [Nc, T, Nq, heads * 256]
+                    self.last_prefix_attention = "prefix"
                 if fold:
-                    rows = _take_prefixes(merged, ks).reshape(len(ks) * self.task_num * Nq, -1)
+                    rows = _take_prefixes(merged, sel).reshape(len(ks) * self.task_num * Nq, -1)
                     sample = _fold_linear([(rows, 1, 0)], self._W.linear, "none", len(ks))
                     sample = _fold_linear([(sample, 1, 0)], self.mu, "none", len(ks))
                     return self._fold_head(x_dec, sample, 1, len(ks), Nq)
-                samples, pre = (self._W(merged[k - 1]) for k in ks), self.mu
+                samples, pre = (self._W(merged[k - 1]) for k in sel), self.mu
             else:
                 if self.agg_mode in ("mean", "max"):
                     r = agg_prefixes(self.agg_mode, feats)
