@@ -49,7 +49,8 @@ const char* mlhot_last_error(void);
  * split-K partial results, 128 phase C' takes the loss's gradient itself when handed a loss descriptor, 512 phase B' as two
  * workgroups per (task, head), 1024 / 2048 phases C' / A' as two workgroups per task, 4096 four instead of two, 256 unassigned;
  * default 7935 = all, 0 = the run-time-shaped csrc/tail_fused.h / tail_cnp.h; "favor2" = 1
- * (default) the two-launch FAVOR+ kernels, 0 the operator chain; "materialize_a1" = 1 additionally stores the conv1 output
+ * (default) the two-launch FAVOR+ kernels, 0 the operator chain; "favor_linear" = 1 (default 0) FAVOR+ in linear form above 32 shots
+ * (mlhot_favor_linear_supported); "materialize_a1" = 1 additionally stores the conv1 output
  * (debug / tests; the fused conv1+conv2 kernels never need it); "conv2_split" = 1 (default 0) runs the vanilla encoder's conv1 +
  * conv2 + pool forward with conv2 on the bf16 matrix pipe over exact hi / mid / lo splits of the fp32 operands (csrc/conv_split.h:
  * same outputs' layout, same parity tolerances, 1.5 x the fp32 kernel; the benchmark's headline stays on the fp32 kernels).      */
@@ -221,6 +222,14 @@ int mlhot_favor_fwd(const float* q, const float* k, const float* v, const float*
 int mlhot_favor_bwd(const float* q, const float* k, const float* v, const float* proj,
                     int T, int H, int Nq, int Nc, int d, int m, const float* out, const float* dout,
                     float* dq, float* dk, float* dv, void* ws, size_t ws_bytes, void* stream);
+/* Above 32 shots on either side the two calls above run favor.h's operator chain (quadratic in the shot counts); with the option
+ * "favor_linear" = 1 (default 0) they run the linear form instead (csrc/favor_linear.h): Ctx = F_k^T (v - c) and
+ * sum_n F_k on the matrix core, out = c + F_q Ctx / (F_q . ksum), and the backward through the same [m, d] sums.  Same operands,
+ * same results within the tolerances of tests/favor_linear_cases.py, same workspace query.  mlhot_favor_linear_supported reports the
+ * route's envelope - max(Nq, Nc) > 32, d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536, GPU build - whatever the option says; the
+ * staged entries below keep the older routes.  The option must not change between a forward and the backward on its workspace.
+ * Added within ABI 7: bindings look the symbol up. */
+int mlhot_favor_linear_supported(int T, int H, int Nq, int Nc, int d, int m);
 
 /* ---- every context prefix of one batch, forward only (the evaluator's loss-versus-context-size sweep) -------------------
  * Row k-1 of an output is what the plain operator returns for the first k shots of every task, k = 1..Nc.

@@ -201,13 +201,10 @@ struct SumRed {
   MLHOT_HD void finish(float s) const { out[0] = s; }
 };
 
-inline int favor_forward(const FavorDims& f, const float* q, const float* k, const float* v, const float* proj,
-                         float* out, void* ws, size_t ws_bytes, hipStream_t s, const Stage& st = Stage{}) {
-  FavorWs w = favor_carve(f, ws, ws_bytes);
-  if (!w.ok) { set_error("favor_fwd: workspace too small"); return MLHOT_ERR_WORKSPACE; }
-  const float c = powf((float)f.d, -0.25f), ratio = 1.0f / sqrtf((float)f.m), eps = 1e-4f;
+// The feature front, shared by the chain below and the linear route (favor_linear.h): dd = (c x) P^T, the row statistics and the
+// batch-global key maximum; then, behind the staged exchange, E in place.
+inline int favor_front_dd(const FavorDims& f, const FavorWs& w, const float* q, const float* k, const float* proj, float c, hipStream_t s) {
   const size_t rq = f.rows_q(), rk = f.rows_k();
-  if (st.first()) {
   MLHOT_TRY(run_foreach(ScaleCopy{proj, w.pc, c}, (size_t)f.m * f.d, s, "favor.scale_proj"));
   WBlocks pb{}; pb.w[0] = w.pc; pb.b[0] = nullptr; pb.rows = f.m;
   LinearFwd lq{(int)rq, f.m, f.d, q, f.d, pb, w.qf, f.m, ACT_NONE};
@@ -218,15 +215,38 @@ inline int favor_forward(const FavorDims& f, const float* q, const float* k, con
   MLHOT_TRY(run_reduce_seg(FavorRowDiag{k, f.d, 0.5f * c * c, w.diag_k}, (int)rk, f.d, s, "favor.rowdiag_k"));
   MLHOT_TRY(run_reduce_seg(FavorRowMax{w.qf, f.m, w.max_q, w.arg_q}, (int)rq, f.m, s, "favor.rowmax_q"));
   MLHOT_TRY(run_reduce_seg(FavorRowMax{w.kf, f.m, w.max_k, w.arg_k}, (int)rk, f.m, s, "favor.rowmax_k"));
-  MLHOT_TRY(run_reduce1(FavorGlobalMax{w.max_k, w.arg_k, w.gmax, w.gpos}, (int)rk, s, "favor.gmax"));
-  }
+  return run_reduce1(FavorGlobalMax{w.max_k, w.arg_k, w.gmax, w.gpos}, (int)rk, s, "favor.gmax");
+}
+inline int favor_front_feat(const FavorDims& f, const FavorWs& w, float ratio, hipStream_t s) {
+  MLHOT_TRY(run_foreach(FavorFeat{w.qf, w.diag_q, w.max_q, nullptr, f.m, ratio}, f.rows_q() * f.m, s, "favor.feat_q"));
+  return run_foreach(FavorFeat{w.kf, w.diag_k, nullptr, w.gmax, f.m, ratio}, f.rows_k() * f.m, s, "favor.feat_k");
+}
+// The back, shared likewise: the row sums of G_q and G_k and the stabiliser's gradient; then, behind the staged exchange, dq and dk.
+inline int favor_back_sums(const FavorDims& f, const FavorWs& w, hipStream_t s) {
+  const size_t rq = f.rows_q(), rk = f.rows_k();
+  MLHOT_TRY(run_reduce_seg(RowSum{w.Gq, f.m, w.rsum_q}, (int)rq, f.m, s, "favor.bwd.rsum_q"));
+  MLHOT_TRY(run_reduce_seg(RowSum{w.Gk, f.m, w.rsum_k}, (int)rk, f.m, s, "favor.bwd.rsum_k"));
+  return run_reduce1(SumRed{w.rsum_k, w.gtotal}, (int)rk, s, "favor.bwd.gtotal");
+}
+inline int favor_back_dx(const FavorDims& f, const FavorWs& w, const float* q, const float* k, float c, float* dq, float* dk, hipStream_t s) {
+  FavorDx xq{(int)f.rows_q(), f.d, f.m, w.Gq, w.rsum_q, w.arg_q, nullptr, nullptr, w.pc, q, c * c, dq};
+  FavorDx xk{(int)f.rows_k(), f.d, f.m, w.Gk, w.rsum_k, nullptr, w.gpos, w.gtotal, w.pc, k, c * c, dk};
+  MLHOT_TRY(run_igemm_auto(xq, s, "favor.bwd.dq"));
+  return run_igemm_auto(xk, s, "favor.bwd.dk");
+}
+
+inline int favor_forward(const FavorDims& f, const float* q, const float* k, const float* v, const float* proj,
+                         float* out, void* ws, size_t ws_bytes, hipStream_t s, const Stage& st = Stage{}) {
+  FavorWs w = favor_carve(f, ws, ws_bytes);
+  if (!w.ok) { set_error("favor_fwd: workspace too small"); return MLHOT_ERR_WORKSPACE; }
+  const float c = powf((float)f.d, -0.25f), ratio = 1.0f / sqrtf((float)f.m), eps = 1e-4f;
+  if (st.first()) MLHOT_TRY(favor_front_dd(f, w, q, k, proj, c, s));
 #ifndef MLHOT_HOSTSIM
   // strict sharded parity (stab_xchg.h): the rank's maximum goes out, the batch's comes back (and the position with it)
   if (st.stage == 0) return sx::max_publish(w.gmax, 1, st.x, s);
   if (st.stage == 1) MLHOT_TRY(sx::max_apply(w.gmax, w.gpos, 1, st.x, s));
 #endif
-  MLHOT_TRY(run_foreach(FavorFeat{w.qf, w.diag_q, w.max_q, nullptr, f.m, ratio}, rq * f.m, s, "favor.feat_q"));
-  MLHOT_TRY(run_foreach(FavorFeat{w.kf, w.diag_k, nullptr, w.gmax, f.m, ratio}, rk * f.m, s, "favor.feat_k"));
+  MLHOT_TRY(favor_front_feat(f, w, ratio, s));
   MLHOT_TRY(run_reduce_seg(FavorS{f, w.qf, w.kf, ratio * eps, w.S}, f.T * f.H * f.Nq * f.Nc, f.m, s, "favor.S"));
   MLHOT_TRY(run_foreach(FavorD{f.Nc, w.S, w.D}, (size_t)f.T * f.H * f.Nq, s, "favor.D"));
   MLHOT_TRY(run_foreach(FavorOut{f, w.S, w.D, v, out}, (size_t)f.T * f.Nq * f.d * f.H, s, "favor.out"));
@@ -245,19 +265,13 @@ inline int favor_backward(const FavorDims& f, const float* q, const float* k, co
   MLHOT_TRY(run_foreach(FavorBwdDV{f, w.S, w.D, dout, dv}, rk * f.d, s, "favor.bwd.dv"));
   MLHOT_TRY(run_foreach(FavorBwdG{f, 1, w.dS, w.qf, w.kf, ratio * eps, w.Gq}, rq * f.m, s, "favor.bwd.Gq"));
   MLHOT_TRY(run_foreach(FavorBwdG{f, 0, w.dS, w.kf, w.qf, ratio * eps, w.Gk}, rk * f.m, s, "favor.bwd.Gk"));
-  MLHOT_TRY(run_reduce_seg(RowSum{w.Gq, f.m, w.rsum_q}, (int)rq, f.m, s, "favor.bwd.rsum_q"));
-  MLHOT_TRY(run_reduce_seg(RowSum{w.Gk, f.m, w.rsum_k}, (int)rk, f.m, s, "favor.bwd.rsum_k"));
-  MLHOT_TRY(run_reduce1(SumRed{w.rsum_k, w.gtotal}, (int)rk, s, "favor.bwd.gtotal"));
+  MLHOT_TRY(favor_back_sums(f, w, s));
   }
 #ifndef MLHOT_HOSTSIM
   if (st.stage == 0) return sx::sum_publish(w.gtotal, 1, st.x, s);
   if (st.stage == 1) MLHOT_TRY(sx::sum_apply(w.gtotal, 1, st.x, w.gtotal, 1, s));
 #endif
-  FavorDx xq{(int)rq, f.d, f.m, w.Gq, w.rsum_q, w.arg_q, nullptr, nullptr, w.pc, q, c * c, dq};
-  FavorDx xk{(int)rk, f.d, f.m, w.Gk, w.rsum_k, nullptr, w.gpos, w.gtotal, w.pc, k, c * c, dk};
-  MLHOT_TRY(run_igemm_auto(xq, s, "favor.bwd.dq"));
-  MLHOT_TRY(run_igemm_auto(xk, s, "favor.bwd.dk"));
-  return MLHOT_OK;
+  return favor_back_dx(f, w, q, k, c, dq, dk, s);
 }
 
 }  // namespace mlhot

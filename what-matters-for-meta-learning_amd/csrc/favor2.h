@@ -700,8 +700,12 @@ inline int backward(const FavorDims& f, const float* q, const float* k, const fl
 }  // namespace mlhot
 #endif
 
+#include "favor_linear.h"
+
 namespace mlhot {
-// Which FAVOR+ implementation runs: the two-launch kernels above when the shot counts fit (and "favor2" is on), else favor.h's.
+// Which FAVOR+ implementation runs: the two-launch kernels above when the shot counts fit (and "favor2" is on); above 32 shots on
+// either side favor_linear.h's linear form when "favor_linear" is on; else favor.h's chain.  A staged pass (strict sharded parity)
+// keeps the two older routes whatever "favor_linear" says: the linear route has no exchange point.
 inline bool favor2_on(const FavorDims& f) {
 #ifndef MLHOT_HOSTSIM
   return g_opt.favor2 && fv::applies(f);
@@ -709,16 +713,26 @@ inline bool favor2_on(const FavorDims& f) {
   (void)f; return false;
 #endif
 }
+inline bool favor_linear_on(const FavorDims& f, const Stage& st) {
+#ifndef MLHOT_HOSTSIM
+  return g_opt.favor_linear && !st.staged() && fl::applies(f);
+#else
+  (void)f; (void)st; return false;
+#endif
+}
+// The maximum over every route the shape can take: the options are process-global and may change between the size query and the call.
 inline size_t favor_ws_need(const FavorDims& f) {
-  size_t a = 0, b = 0;
+  size_t a = 0, b = 0, c = 0;
   favor_carve(f, nullptr, 0, &a);
 #ifndef MLHOT_HOSTSIM
   if (fv::applies(f)) fv::carve(f, nullptr, 0, &b);
+  if (fl::applies(f)) fl::carve(f, nullptr, 0, &c);
 #endif
-  return a > b ? a : b;
+  if (b > a) a = b;
+  return a > c ? a : c;
 }
 // The contract of mlhot_favor_ws_bytes: a workspace smaller than the reported size is refused before anything is launched, whichever
-// implementation would run (the two carve differently, and each carve's own check leaves the 256-byte slack and the other's excess unseen).
+// implementation would run (they carve differently, and each carve's own check leaves the 256-byte slack and the others' excess unseen).
 inline int favor_ws_check(const FavorDims& f, const void* ws, size_t ws_bytes, const char* what) {
   const size_t need = favor_ws_need(f);
   if (ws == nullptr || ws_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", what, ws_bytes, need); return MLHOT_ERR_WORKSPACE; }
@@ -729,6 +743,7 @@ inline int favor_fwd_any(const FavorDims& f, const float* q, const float* k, con
   MLHOT_TRY(favor_ws_check(f, ws, ws_bytes, "favor_fwd"));
 #ifndef MLHOT_HOSTSIM
   if (favor2_on(f)) return fv::forward(f, q, k, v, proj, out, ws, ws_bytes, s, st);
+  if (favor_linear_on(f, st)) return fl::forward(f, q, k, v, proj, out, ws, ws_bytes, s);
 #endif
   return favor_forward(f, q, k, v, proj, out, ws, ws_bytes, s, st);
 }
@@ -738,6 +753,7 @@ inline int favor_bwd_any(const FavorDims& f, const float* q, const float* k, con
   MLHOT_TRY(favor_ws_check(f, ws, ws_bytes, "favor_bwd"));
 #ifndef MLHOT_HOSTSIM
   if (favor2_on(f)) return fv::backward(f, q, k, v, proj, out, dout, dq, dk, dv, ws, ws_bytes, s, st);
+  if (favor_linear_on(f, st)) return fl::backward(f, q, k, v, out, dout, dq, dk, dv, ws, ws_bytes, s);
 #endif
   return favor_backward(f, q, k, v, out, dout, dq, dk, dv, ws, ws_bytes, s, st);
 }

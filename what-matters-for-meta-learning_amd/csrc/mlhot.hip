@@ -81,6 +81,7 @@ int mlhot_set_option(const char* name, int value) {
     {"materialize_a1", &Options::materialize_a1, INT_MIN, INT_MAX},
     {"dbg", &Options::dbg, INT_MIN, INT_MAX},
     {"favor2", &Options::favor2, INT_MIN, INT_MAX},
+    {"favor_linear", &Options::favor_linear, INT_MIN, INT_MAX},
 #ifndef MLHOT_HOSTSIM      // the host simulation has no trunk
     {"trunk_dual_dgrad", &Options::trunk_dual_dgrad, INT_MIN, INT_MAX},
     {"trunk_wg_rows", &Options::trunk_wg_rows, 16, 128},
@@ -290,6 +291,8 @@ int mlhot_favor_bwd(const float* q, const float* k, const float* v, const float*
   if (T <= 0 || H <= 0 || Nq <= 0 || Nc <= 0 || d <= 0 || m <= 0) { set_error("favor_bwd: bad argument"); return MLHOT_ERR_ARG; }
   return favor_bwd_any(FavorDims{T, H, Nq, Nc, d, m}, q, k, v, proj, out, dout, dq, dk, dv, ws, ws_bytes, (hipStream_t)stream);
 }
+// the envelope of the linear-form route (csrc/favor_linear.h), whatever the option "favor_linear" says
+int mlhot_favor_linear_supported(int T, int H, int Nq, int Nc, int d, int m) { return favor_linear_ok(FavorDims{T, H, Nq, Nc, d, m}) ? 1 : 0; }
 // every context prefix 1..Nc in three launches (csrc/prefix.h): out[k-1] is mlhot_favor_fwd's result for the first k keys / values
 size_t mlhot_favor_prefix_ws_bytes(int T, int H, int Nq, int Nc, int d, int m) {
 #ifndef MLHOT_HOSTSIM

@@ -1,7 +1,7 @@
 // Run-time switches (mlhot_set_option): which implementation of a hot-path row runs.  The generic igemm problems are always
 // available as the A/B reference of the specialised kernels.  Every switch lives here, with its default; mlhot_set_option's table
 // (mlhot.hip) is the only writer.  Readers: enc_route() (encoder.h) for the encoder's, np_route() (np_vanilla.h) for the tail's,
-// trunk_route() (resnet_trunk.h) for the three trunk_* ones, favor2.h for its own.
+// trunk_route() (resnet_trunk.h) for the three trunk_* ones, favor2.h for its own and favor_linear's.
 #pragma once
 
 namespace mlhot {
@@ -39,6 +39,8 @@ struct Options {
   int materialize_a1 = 0;    // the fused conv1 + conv2 forward never stores conv1's output; 1: a launch of its own keeps it (tests)
   int dbg = 0;               // timing experiments only (results become wrong)
   int favor2 = 1;            // FAVOR+: the two-launch kernels (favor2.h); 0: favor.h's chain
+  int favor_linear = 0;      // FAVOR+ above 32 shots on either side: 1 the linear form (favor_linear.h), 0 favor.h's chain.  As with favor2, it
+                             // must not change between a forward and the backward that reuses its workspace: the routes carve differently
   int trunk_dual_dgrad = 1;  // a 3x3-skip block's two stride-2 data gradients in one 512-thread launch (resnet_ws.h dgrad2_dual_kernel)
   int trunk_wg_rows = 128;   // slab rows (x 4 channel tiles = workgroups) a trunk weight-gradient launch is planned against; 16 .. 128
   int trunk_fuse34 = 1;      // blocks 3-4 of a 64 x 64 trunk as one launch per direction (resnet_ws.h tail34_*)

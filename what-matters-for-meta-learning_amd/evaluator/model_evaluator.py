@@ -26,6 +26,8 @@ class ModelEvaluator(BaseEvaluator):
         super().__init__(model=model, loss=loss, config=config, optimizer=optimizer)
         self.data = data
         self.ingest = None
+        from mlhot.ops import apply_config_switches
+        apply_config_switches(config)          # config.favor_linear
         if hasattr(data, "get_batch_u8") and torch.device(config.device).type == "cuda" and getattr(config, "ingest_u8", True):
             from mlhot.ingest import BatchIngest
             self.ingest = BatchIngest(config.device)

@@ -251,6 +251,7 @@ SIGNATURES = {
     "mlhot_favor_ws_bytes": (z, [i] * 6),
     "mlhot_favor_fwd": (i, _qkvp + [P, P, z, P]),
     "mlhot_favor_bwd": (i, _qkvp + [P, P, P, P, P, P, z, P]),
+    "mlhot_favor_linear_supported": (i, [i] * 6),
     # every context prefix of one batch; the Linears and the loss behind the prefix operators
     "mlhot_agg_prefix_fwd": (i, [i, P, P, i, i, i, P, P, P]),
     "mlhot_favor_prefix_ws_bytes": (z, [i] * 6),
@@ -353,6 +354,7 @@ class MlhotLib:
             raise MlhotError(f"mlhot: shared library not found: {path} (run __graft_entry__.build())")
         self.path = path
         self.c = c = C.CDLL(path)
+        self.options = {}     # what set_option() has been told since loading (the library has no getter); absent = csrc/options.h's default
         MlhotLib._last = self
         if c.mlhot_version() != ABI_VERSION:       # before any other symbol is touched: an older prebuilt library lacks the newer ones
             raise MlhotError(f"mlhot: libmlhot.so has ABI version {c.mlhot_version()}, this binding needs {ABI_VERSION} "
@@ -390,6 +392,7 @@ class MlhotLib:
 
     def set_option(self, name, value):
         self._rc(self.c.mlhot_set_option(name.encode(), int(value)), "mlhot_set_option")
+        self.options[name] = int(value)
 
     # ---- bench-only launch profiler -----------------------------------------------------------
     def prof_begin(self, max_records=4096):
@@ -1221,6 +1224,11 @@ class MlhotLib:
         call(0, _ptr(x))
         (ex.forward if direction == "fwd" else ex.backward)(x)
         call(1, _ptr(x))
+
+    def favor_linear_supported(self, T, H, Nq, Nc, d, m):
+        """Whether the linear-form route of favor_fwd / favor_bwd (option "favor_linear", csrc/favor_linear.h) serves these dimensions:
+        the envelope alone, whatever the option says."""
+        return bool(self._fn("favor_linear_supported", "mlhot_favor_linear_supported")(T, H, Nq, Nc, d, m))
 
     def favor_fwd(self, q, k, v, proj, exchange=None):
         """q [T,Nq,H,d], k/v [T,Nc,H,d], proj [m,d] -> out [T,Nq,d*H] (merged order), ws"""

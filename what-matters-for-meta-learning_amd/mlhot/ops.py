@@ -461,6 +461,28 @@ class FavorFunction(torch.autograd.Function):
         return dq, dk, dv, None
 
 
+def favor_route(T, H, Nq, Nc, d, m):
+    """Which implementation FavorFunction (lib().favor_fwd / favor_bwd) runs for these dimensions under the options as they stand:
+    "two_launch" (csrc/favor2.h: both sides <= 32 shots), "linear" (csrc/favor_linear.h: option "favor_linear", above 32 shots) or
+    "chain" (csrc/favor.h).  Options are read from what MlhotLib.set_option was told (MLHOT_OPTS included); under a stabiliser
+    exchange (strict sharded parity) the passes are staged and never take the linear route."""
+    L = lib()
+    two = Nq <= 32 and Nc <= 32 and d % 16 == 0 and d <= 256 and 16 <= m <= 1536        # fv::applies (tests/test_favor_cases_cpu.py)
+    if L.options.get("favor2", 1) and two:
+        return "two_launch"
+    if L.options.get("favor_linear", 0) and _stab_exchange is None and L.favor_linear_supported(T, H, Nq, Nc, d, m):
+        return "linear"
+    return "chain"
+
+
+def apply_config_switches(config):
+    """The library switches a run's config may set, read once by the trainer and the evaluator: config.favor_linear (absent = off)
+    turns the option "favor_linear" on - FAVOR+ forward and backward in linear form above 32 shots.  It is set once,
+    before any step, because a backward must run the route of its forward."""
+    if getattr(config, "favor_linear", False) and torch.device(config.device).type == "cuda":
+        lib().set_option("favor_linear", 1)
+
+
 def _forward_only(what, *ts):
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
         raise MlhotError(f"{what} is forward-only (the evaluator's prefix sweep): call it under torch.no_grad() or on detached tensors")

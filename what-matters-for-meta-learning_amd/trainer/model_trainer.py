@@ -328,6 +328,7 @@ class ModelTrainer(BaseTrainer):
         self.bucket = GradBucket(model.parameters(), side_stream=torch.device(config.device).type == "cuda", early=early)
         if not self.bucket._single() and hasattr(model, "enable_flat_grads") and torch.device(config.device).type == "cuda":
             model.enable_flat_grads()      # more than one rank: the ResNet / BBB family's gradients in one flat buffer, reduced in place
+        ops.apply_config_switches(config)      # config.favor_linear
         if getattr(config, "strict_sharded_parity", False):
             if getattr(config, "graph_steps", False):
                 raise ValueError("config.strict_sharded_parity runs a collective between two C calls of the forward: not with config.graph_steps")
