@@ -10,6 +10,7 @@ import torch.nn.functional as F
 
 from oracle import ref_cpu as O
 from tests import split_cases as SC
+from tests.autograd_cases import _bbb_ref, _chain_reference, _trunk_weights
 from tests import util as U
 
 pytestmark = pytest.mark.gpu
@@ -82,17 +83,6 @@ def test_two_source_linear_vs_autograd(gpulib, M, Ka, Kb, N, act, grads):
         assert U.rel_err(bd.grad, br.grad) <= U.RTOL
     else:
         assert bd.grad is None
-
-
-def _chain_reference(x0, layers):
-    """torch autograd restatement of a chain: layers = [(w, b, act, side | None, side_first)]."""
-    h = x0
-    for w, b, act, side, side_first in layers:
-        if side is not None:
-            h = torch.cat([side, h] if side_first else [h, side], dim=-1)
-        h = F.linear(h, w, b)
-        h = torch.relu(h) if act == "relu" else torch.tanh(h) if act == "tanh" else h
-    return h
 
 
 @pytest.mark.parametrize("M", [120, 7, 240, 16])
@@ -1165,16 +1155,6 @@ def test_mr_vanilla_models_vs_reference(gpulib, name):
 
 
 # ---- E2 / D2 / B1 trunk kernels in isolation (csrc/resnet_ws.h, resnet_trunk.h) -----------------------------------------
-def _trunk_weights(C, skip_k, seed):
-    g = torch.Generator().manual_seed(seed)
-    shapes = [(64, C, 5, 5)] + [s_ for _ in range(4) for s_ in ((64, 64, 3, 3), (64, 64, 3, 3), (64, 64, skip_k, skip_k))]
-    out = []
-    for sh in shapes:
-        fan = sh[1] * sh[2] * sh[3]
-        out += [torch.randn(*sh, generator=g) * (1.5 / fan) ** 0.5, torch.randn(sh[0], generator=g) * 0.1]
-    return out
-
-
 def _trunk_dict(ws):
     d = {"t.conv1.weight": ws[0], "t.conv1.bias": ws[1]}
     for i in range(4):
@@ -1239,22 +1219,6 @@ def test_resnet_trunk_fwd_bwd_vs_torch(gpulib, C, H, skips, ns, share, opts):
 
 
 # ---- B1 in isolation: sample + KL and their backward against torch autograd ------------------------------------
-def _bbb_ref(mus, rhos, epss, wouts, dkl):
-    """autograd of sum_i <w_i, wout_i> + dkl * kl with w = mu + eps * softplus(rho), kl as bbb/BBBConv.py:33-35,100-108."""
-    mr = [(m.clone().requires_grad_(), r.clone().requires_grad_()) for m, r in zip(mus, rhos)]
-    ws, kl = [], 0.0
-    for (m, r), e in zip(mr, epss):
-        sigma = torch.log1p(torch.exp(r))
-        ws.append(m + e * sigma)
-        kl = kl + 0.5 * (2 * torch.log(sigma / 0.1) - 1 + (0.1 / sigma).pow(2) + (m / sigma).pow(2)).sum()
-    total = dkl * kl
-    for w, wo in zip(ws, wouts):
-        if wo is not None:
-            total = total + (w * wo).sum()
-    total.backward()
-    return [w.detach() for w in ws], kl.detach(), [m.grad for m, _ in mr], [r.grad for _, r in mr]
-
-
 @pytest.mark.parametrize("shape", [(7,), (64, 3, 5, 5), (64, 64, 3, 3), (64, 4096)])
 @pytest.mark.parametrize("dkl", [0.0, 1e-7, 0.3])
 def test_bbb_sample_fwd_bwd_vs_autograd(gpulib, shape, dkl):
@@ -2651,7 +2615,7 @@ def test_grad_bucket_side_stream_and_early_bucket_on_cuda(gpulib):
             assert [k for k, _ in early_log] == ["early", "rest"] and [k for k, _ in side_log] == ["all"]
 
 
-@pytest.mark.parametrize("method", ["ANPMRShapeNet3D", "ANP", "CondNeuralProcess"])
+@pytest.mark.parametrize("method", ["ANPMRShapeNet3D", "ANP", "CondNeuralProcess", "ANPDistractor", "CNPDistractor"])
 def test_flat_gradient_arena_for_the_resnet_family(gpulib, method):
     """VERDICT r3 item 5 i (train.py:52-56: one optimizer over all parameters): with model.enable_flat_grads() every gradient of a
     ResNet / Bayes-by-backprop model is a view of ONE flat buffer (mlhot/arena.py) - the trunk backward, the linears, the head
@@ -2663,8 +2627,8 @@ def test_flat_gradient_arena_for_the_resnet_family(gpulib, method):
     from trainer.losses import LossFunc
     T, Nc, Nq = 2, 5, 6
     cfg = types.SimpleNamespace(device=torch.device(DEV), seed=2578, img_size=[64, 64, 4], tasks_per_batch=T, input_dim=4, output_dim=4,
-                                agg_mode="attention" if method != "CondNeuralProcess" else "max", img_agg="reshape" if method == "ANPMRShapeNet3D" else "max",
-                                task="shapenet_3d", temperature=0.07)
+                                agg_mode="attention" if method.startswith("ANP") else "max", img_agg="reshape" if method == "ANPMRShapeNet3D" else "max",
+                                task="shapenet_3d", temperature=0.07, dim_w=64)
     model = getattr(importlib.import_module("networks." + method), method)(cfg).to(DEV)
     g = torch.Generator().manual_seed(7)
     cx, qx = torch.rand(T, Nc, 3, 64, 64, generator=g).to(DEV), torch.rand(T, Nq, 3, 64, 64, generator=g).to(DEV)

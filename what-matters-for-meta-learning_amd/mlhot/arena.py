@@ -13,7 +13,18 @@ installed (mlhot.binding.set_grad_arena), every binding call that is about to al
 slot of the tensor the gradient belongs to (looked up by storage pointer + offset: detached views of a parameter hit, temporaries
 such as sampled Bayes-by-backprop weights miss and get a fresh tensor as before).  autograd then hands the kernels' output views to
 the parameters' .grad as they are, GradBucket finds every live gradient inside one storage and all-reduces the range in place.
-`first`: parameters whose segments come first (GradBucket's early bucket: one contiguous range of its own)."""
+`first`: parameters whose segments come first (GradBucket's early bucket: one contiguous range of its own).
+
+The contract (take()): a kernel is handed a slot only while no live `.grad` of a covered parameter aliases it and no other call of
+the same backward pass has been handed it; otherwise the kernel writes a fresh tensor and autograd accumulates as it always does.
+So a step that starts from `.grad is None` with one consumer per parameter (the shipped trainer: zero_grad(set_to_none=True)) keeps
+every gradient at its fixed address in `flat`, and zero_grad(set_to_none=False), accumulation over several backwards and a
+parameter shared by several nodes give the gradients they give without an arena.  The contract covers `.backward()` passes that
+accumulate into `.grad`, one pass at a time: what is handed out is remembered per autograd graph task, so a re-entrant backward
+(checkpointing) starts a record of its own, and the tensors `torch.autograd.grad` returns - nothing is stolen into a `.grad` - are
+views of the slots that the next pass writes again: copy them if they must outlive it."""
+import bisect
+
 import torch
 
 
@@ -25,6 +36,7 @@ class GradArena:
         self.params = head + [p for p in params if id(p) not in ids]
         self.n_first = len(head)
         self.flat, self._base, self._sig, self.first_numel = None, {}, None, 0
+        self._cover, self._pass, self._out = ([], [], []), -1, set()
 
     def _signature(self):
         return tuple((p.untyped_storage().data_ptr(), p.storage_offset(), p.numel(), str(p.device)) for p in self.params)
@@ -61,6 +73,10 @@ class GradArena:
                 self.first_numel = total
         self.flat = torch.zeros(total, dtype=torch.float32, device=self.params[0].device)
         self._base, self._sig = base, sig
+        # the parameters by their position in `flat` (take() asks which of them a slot covers)
+        cover = sorted(((base[p.untyped_storage().data_ptr()] + p.storage_offset(), p) for p in self.params), key=lambda c: c[0])
+        self._cover = ([a for a, _ in cover], [a + p.numel() for a, p in cover], [p for _, p in cover])
+        self._pass, self._out = -1, set()
         return self
 
     def slot(self, t):
@@ -76,3 +92,32 @@ class GradArena:
         if a < lo or e > hi:
             return None
         return self.flat[b + a:b + e].view(t.shape)
+
+    def take(self, t):
+        """slot(t) for a kernel to WRITE: None (the caller allocates) while the `.grad` of a parameter the slot covers lives in this
+        buffer - the kernel would overwrite what autograd is about to add to - or when the slot has already been handed out in the
+        running backward pass (a parameter consumed by two nodes: the second gradient must not land on the first).  A pass is one
+        autograd graph task (torch._C._current_graph_task_id, what torch.utils.checkpoint tells passes apart by: unlike an
+        end-of-pass callback it cannot leave a stale record behind a pass that raised); calls outside a backward stand each on their own."""
+        v = self.slot(t)
+        if v is None:
+            return None
+        lo = v.storage_offset()
+        hi = lo + v.numel()
+        starts, ends, params = self._cover
+        mine = self.flat.untyped_storage().data_ptr()
+        task = torch._C._current_graph_task_id()
+        if task != self._pass:
+            self._pass, self._out = task, set()
+        covered = []
+        i = max(bisect.bisect_right(starts, lo) - 1, 0)
+        while i < len(starts) and starts[i] < hi:
+            if ends[i] > lo:
+                g = params[i].grad
+                if i in self._out or (g is not None and g.untyped_storage().data_ptr() == mine):
+                    return None
+                covered.append(i)
+            i += 1
+        if task >= 0:
+            self._out.update(covered)
+        return v

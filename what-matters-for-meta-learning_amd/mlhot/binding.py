@@ -158,9 +158,10 @@ def get_grad_arena():
 
 
 def _grad_like(t):
-    """Storage for the gradient of `t`: its slot in the installed arena, or a fresh tensor."""
+    """Storage a kernel writes the gradient of `t` into: its slot in the installed arena while the arena may hand it out
+    (GradArena.take: no live .grad in it, not handed out before in this backward pass), else a fresh tensor."""
     if _GRAD_ARENA is not None:
-        v = _GRAD_ARENA.slot(t)
+        v = _GRAD_ARENA.take(t)
         if v is not None:
             return v
     return torch.empty_like(t)

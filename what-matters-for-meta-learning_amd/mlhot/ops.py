@@ -119,8 +119,25 @@ def _need_gpu(*ts):
                              "(got a CPU tensor); there is no CPU fallback")
 
 
-def _c(t):
+def _c4(t):
+    """Contiguous, at the tensor's own address: for mlhot_linear_fwd / _bwd, whose operands need 4-byte alignment only."""
     return t if t is None or t.is_contiguous() else t.contiguous()
+
+
+def _c(t):
+    """What every other entry may be handed (include/mlhot.h: all pointers 16-byte aligned): `t` itself when it is contiguous and
+    aligned, else a copy - a contiguous tensor that starts inside its buffer (flat[1:].view(...)) is copied like a strided view."""
+    if t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0):
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
+
+
+def _need_aligned(what, *ts):
+    """For operands that cannot be copied - buffers the kernels update in place or whose storage the caller's parameters are views
+    of: refuse before anything is launched."""
+    for t in ts:
+        if t is not None and (not t.is_contiguous() or t.data_ptr() % 16):
+            raise MlhotError(f"{what} must be contiguous and 16-byte aligned (include/mlhot.h); it cannot be copied on the way in")
 
 
 class VanillaNPFunction(torch.autograd.Function):
@@ -132,6 +149,7 @@ class VanillaNPFunction(torch.autograd.Function):
         L = lib()
         ctx_x, ctx_y, qry_x = _c(ctx_x.float()), _c(ctx_y.float()), _c(qry_x.float())
         pd = {k: _c(p.detach()) for k, p in zip(keys, params)}
+        proj = _c(proj)
         # the exchange only concerns the attention models with a context (the empty-context branch has no keys)
         ctx.xchg = (_stab_exchange, torch.zeros(4, device=qry_x.device)) if _stab_exchange is not None and proj is not None and dims.Nc > 0 else None
         mu, saved, scratch = L.np_vanilla_fwd(dims, pd, ctx_x, ctx_y, qry_x, proj, exchange=ctx.xchg)
@@ -197,16 +215,16 @@ class LinearFunction(torch.autograd.Function):
     def forward(ctx, x, w, b, act):
         _need_gpu(x, w, b)
         shp = x.shape
-        x2 = _c(x.reshape(-1, shp[-1]).float())
-        y = lib().linear_fwd(x2, _c(w.detach()), _c(b.detach()) if b is not None else None, act)
+        x2 = _c4(x.reshape(-1, shp[-1]).float())
+        y = lib().linear_fwd(x2, _c4(w.detach()), _c4(b.detach()) if b is not None else None, act)
         ctx.act, ctx.shp, ctx.has_b = act, shp, b is not None
-        ctx.save_for_backward(x2, _c(w.detach()), y, *([b.detach()] if b is not None else []))
+        ctx.save_for_backward(x2, _c4(w.detach()), y, *([_c4(b.detach())] if b is not None else []))
         return y.view(*shp[:-1], w.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
         x2, w, y, *bias = ctx.saved_tensors
-        dx, dw, db = lib().linear_bwd(x2, w, y, _c(dy.reshape(-1, w.shape[0])), ctx.act, need_dx=ctx.needs_input_grad[0],
+        dx, dw, db = lib().linear_bwd(x2, w, y, _c4(dy.reshape(-1, w.shape[0])), ctx.act, need_dx=ctx.needs_input_grad[0],
                                       b=bias[0] if bias else None)
         return (dx.view(ctx.shp) if dx is not None else None), dw, (db if ctx.has_b else None), None
 
@@ -221,7 +239,7 @@ class StackedLinearFunction(torch.autograd.Function):
     def forward(ctx, x, stack_w, stack_b, n_heads, *head_params):
         _need_gpu(x, stack_w, stack_b)
         shp = x.shape
-        x2 = _c(x.reshape(-1, shp[-1]).float())
+        x2 = _c4(x.reshape(-1, shp[-1]).float())
         y = lib().linear_fwd(x2, stack_w, stack_b, "none")
         ctx.shp, ctx.n_heads = shp, n_heads
         ctx.save_for_backward(x2, stack_w, y, stack_b)
@@ -230,7 +248,7 @@ class StackedLinearFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x2, w, y, b = ctx.saved_tensors
-        dx, dw, db = lib().linear_bwd(x2, w, y, _c(dy.reshape(-1, w.shape[0])), "none", need_dx=ctx.needs_input_grad[0], b=b)
+        dx, dw, db = lib().linear_bwd(x2, w, y, _c4(dy.reshape(-1, w.shape[0])), "none", need_dx=ctx.needs_input_grad[0], b=b)
         h = ctx.n_heads
         return ((dx.view(ctx.shp) if dx is not None else None), None, None, None,
                 *dw.view(h, w.shape[0] // h, w.shape[1]).unbind(0), *db.view(h, -1).unbind(0))
@@ -256,9 +274,11 @@ class Linear2Function(torch.autograd.Function):
     def backward(ctx, dy):
         a2, b2, w, y, *bias = ctx.saved_tensors
         need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        # the entry computes dW beside an input gradient (include/mlhot.h: the backward needs dx): with both inputs frozen it still
+        # writes dxa, which is dropped here
         ((dxa, dw, db, dxb),) = lib().linear_multi_bwd([(a2, w, y, _c(dy.reshape(-1, w.shape[0]).float()), ctx.act, bias[0] if bias else None,
-                                                         b2, need_a, need_b)])
-        return (dxa.view(ctx.shp_a) if dxa is not None else None, dxb.view(ctx.shp_b) if dxb is not None else None, dw,
+                                                         b2, need_a or not need_b, need_b)])
+        return (dxa.view(ctx.shp_a) if need_a else None, dxb.view(ctx.shp_b) if dxb is not None else None, dw,
                 db if ctx.has_b else None, None)
 
 
@@ -376,6 +396,7 @@ class HeadStacksFunction(torch.autograd.Function):
     def forward(ctx, n_heads, n_stacks, *args):
         xs, ws, bs = args[0:3 * n_stacks:3], args[1:3 * n_stacks:3], args[2:3 * n_stacks:3]
         _need_gpu(*xs, *ws, *bs)
+        _need_aligned("HeadStacksFunction: a stacked weight / bias", *ws, *bs)
         x2 = [_c(x.reshape(-1, x.shape[-1]).float()) for x in xs]
         ys = lib().linear_multi_fwd([(x, w, b, "none") for x, w, b in zip(x2, ws, bs)])
         ctx.n_heads, ctx.n_stacks, ctx.shapes = n_heads, n_stacks, [x.shape for x in xs]
@@ -974,6 +995,7 @@ class BatchNormReluFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, run_mean, run_var, momentum, eps):
         _need_gpu(x, gamma, beta, run_mean, run_var)
+        _need_aligned("BatchNormReluFunction: run_mean / run_var (updated in place)", run_mean, run_var)
         x = _c(x)
         y, mean, var = lib().bn_relu_fwd(x, _c(gamma.detach()), _c(beta.detach()), run_mean, run_var, momentum, eps)
         ctx.eps = eps
