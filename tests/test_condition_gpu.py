@@ -20,7 +20,7 @@ DEV = "cuda:0"
 T, H = 2, 2
 DM = [(16, 16), (64, 266), (256, 1419), (256, 1536)]
 NCS = [1, 15, 32]
-TILE = 16                      # query rows per workgroup (csrc/favor_cached.h QT)
+TILE = 16                      # query rows per workgroup (csrc/favor_tile.h QT)
 
 
 @functools.lru_cache(maxsize=None)

@@ -13,6 +13,7 @@
 #include "common.h"
 #include "favor.h"
 #include "options.h"
+#include "favor_tile.h"
 
 #ifndef MLHOT_HOSTSIM
 namespace mlhot {
@@ -21,8 +22,8 @@ namespace tf { extern __device__ long long* g_ts_dev; }
 #endif
 namespace fv {
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4_t mfma4(float a, float b, f32x4_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+using ft::f32x4_t;
+using ft::mfma4;
 constexpr int F1_TPW = 3;         // 16-feature tiles per F1 wave
 constexpr int FCH = 4 * 16 * F1_TPW;   // features per F1 workgroup (4 waves x 3 tiles of 16 = 192: m = 1419 -> 8 chunks x 64 (task, head) blocks =
                                        // 512 workgroups, two per CU; with 256 features it was 384 - half the CUs carried two, and the kernel ran at their pace)
@@ -647,7 +648,8 @@ __global__ __launch_bounds__(B2_TH) void b2_kernel(const Args a) {
 inline Args make_args(const FavorDims& f, const Ws& w, const float* q, const float* k, const float* v, const float* proj) {
   Args a{};
   a.f = f; a.w = w; a.q = q; a.k = k; a.v = v; a.proj = proj;
-  a.c = powf((float)f.d, -0.25f); a.ratio = 1.0f / sqrtf((float)f.m); a.re = a.ratio * 1e-4f;
+  const ft::Scales sc(f.d, f.m);
+  a.c = sc.c; a.ratio = sc.ratio; a.re = sc.re;
   return a;
 }
 inline int forward(const FavorDims& f, const float* q, const float* k, const float* v, const float* proj, float* out, void* ws, size_t ws_bytes,

@@ -29,25 +29,24 @@
 #include "common.h"
 #include "favor.h"
 #include "options.h"
-// Included by favor2.h, behind its namespace fv (mfma4, f32x4_t) and in front of the route decision: include favor2.h, not this file.
+#include "favor_tile.h"
 
 #ifndef MLHOT_HOSTSIM
 namespace mlhot {
 namespace fl {
 
-using fv::f32x4_t;
-using fv::mfma4;
+using ft::f32x4_t;
+using ft::mfma4;
+using ft::LDX;
+using ft::ldf;
+using ft::ldo;
 
 constexpr int MINN = 32;                  // the route serves max(Nq, Nc) > MINN: up to there favor2.h's two launches do
-constexpr int MIND = 16;
-constexpr int MAXD = 256;
-constexpr int MINM = 16;
-constexpr int MAXM = 1536;
-constexpr int RT = 16;                    // rows per workgroup of apply / gw / grad
+constexpr int MIND = 16; constexpr int MAXD = 256; constexpr int MINM = 16; constexpr int MAXM = 1536;      // a CPU test reads these and applies()
+static_assert(MIND == ft::MIND && MAXD == ft::MAXD && MINM == ft::MINM && MAXM == ft::MAXM, "favor_tile.h's envelope");
+constexpr int RT = ft::QT;                // rows per workgroup of apply / gw / grad
 constexpr int FC = 64;                    // features per sum workgroup: 16 per wave
 constexpr int MSMALL = 320;               // apply: F's LDS tile is sized for mp <= MSMALL or for MAXM
-constexpr int LDX = MAXD + 8;             // LDS row stride of a [16 x d] tile: 8 mod 32, so a b128 read of lanes (lr, lq) is conflict-free
-constexpr int ldf(int mp) { return (mp + 31) / 32 * 32 + 8; }      // LDS row stride of F, 8 mod 32 as well
 
 // blockIdx.x = (task x head) x 16-row tile, and favor.h's launches count rows in an int
 inline bool grid_ok(const FavorDims& f) {
@@ -162,7 +161,6 @@ struct ApplyArgs {
   float re;
 };
 
-constexpr int ldo(int d) { return d + 4; }           // row stride of a wave's partial tile in LDS
 constexpr int apply_lds(int ng, int mcap) { return RT * ldf(mcap) > 4 * RT * ldo(64 * ng) ? RT * ldf(mcap) : 4 * RT * ldo(64 * ng); }
 
 template <int NG, int MCAP>
@@ -178,76 +176,25 @@ __global__ __launch_bounds__(256) void apply_kernel(const ApplyArgs a) {
     s_f[row * LD + j] = (n < N && j < m) ? a.F[(((size_t)t * N + n) * H + h) * m + j] + a.re : 0.f;
   }
   __syncthreads();
-  // 2. forward: D = sum_j F[j] cs[j]: 16 threads per row, thread p takes j = p, p + 16, .. in order, then a butterfly over the 16 lanes
+  // 2. forward: D = sum_j F[j] cs[j]
   if (a.fwd) {
     const int row = tid >> 4, p = tid & 15;
     const float* cs = a.cs + (size_t)th * mp;
-    float den = 0.f;
-    for (int j = p; j < mp; j += 16) den += s_f[row * LD + j] * cs[j];
-#pragma unroll
-    for (int off = 1; off < 16; off <<= 1) den += __shfl_xor(den, off, 64);
+    float den[1];
+    ft::row_sums(mp, p, den, [&](int j, float (&u)[1]) { u[0] += s_f[row * LD + j] * cs[j]; });
     if (p == 0) {
-      s_den[row] = den;
-      if (n0 + row < N) a.D[((size_t)t * N + n0 + row) * H + h] = den;
+      s_den[row] = den[0];
+      if (n0 + row < N) a.D[((size_t)t * N + n0 + row) * H + h] = den[0];
     }
   }
-  // 3. F C: wave w takes the 16-feature chunks w, w + 4, .. in ascending order for every column group; the next chunk's rows of C
-  //    are in flight while this one's MFMAs run
-  f32x4_t acc[NG][4];
-#pragma unroll
-  for (int g = 0; g < NG; ++g)
-#pragma unroll
-    for (int y = 0; y < 4; ++y) acc[g][y] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  {
-    const int nch16 = mp / 16;
-    const float* Cb = a.C + (size_t)th * mp * d + 4 * lr;
-    float4 cur[NG][4], nxt[NG][4];
-    auto load = [&](float4 (&b)[NG][4], int ch) {
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int x = 0; x < 4; ++x)
-          b[g][x] = (ch < nch16 && 64 * g + 4 * lr < d) ? *reinterpret_cast<const float4*>(Cb + (size_t)(16 * ch + 4 * lq + x) * d + 64 * g)
-                                                        : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    load(cur, wv);
-    for (int ch = wv; ch < nch16; ch += 4) {
-      load(nxt, ch + 4);
-      const float4 fa = *reinterpret_cast<const float4*>(s_f + lr * LD + 16 * ch + 4 * lq);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        acc[g][0] = mfma4(fa.x, cur[g][0].x, acc[g][0]); acc[g][1] = mfma4(fa.x, cur[g][0].y, acc[g][1]);
-        acc[g][2] = mfma4(fa.x, cur[g][0].z, acc[g][2]); acc[g][3] = mfma4(fa.x, cur[g][0].w, acc[g][3]);
-        acc[g][0] = mfma4(fa.y, cur[g][1].x, acc[g][0]); acc[g][1] = mfma4(fa.y, cur[g][1].y, acc[g][1]);
-        acc[g][2] = mfma4(fa.y, cur[g][1].z, acc[g][2]); acc[g][3] = mfma4(fa.y, cur[g][1].w, acc[g][3]);
-        acc[g][0] = mfma4(fa.z, cur[g][2].x, acc[g][0]); acc[g][1] = mfma4(fa.z, cur[g][2].y, acc[g][1]);
-        acc[g][2] = mfma4(fa.z, cur[g][2].z, acc[g][2]); acc[g][3] = mfma4(fa.z, cur[g][2].w, acc[g][3]);
-        acc[g][0] = mfma4(fa.w, cur[g][3].x, acc[g][0]); acc[g][1] = mfma4(fa.w, cur[g][3].y, acc[g][1]);
-        acc[g][2] = mfma4(fa.w, cur[g][3].z, acc[g][2]); acc[g][3] = mfma4(fa.w, cur[g][3].w, acc[g][3]);
-      }
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int x = 0; x < 4; ++x) cur[g][x] = nxt[g][x];
-    }
-  }
-  __syncthreads();                          // F is dead: its space takes the four partial tiles [wave][16][ldo(d)]
-  float* red = s_f;
-  const int LDO = ldo(d);
-#pragma unroll
-  for (int g = 0; g < NG; ++g)
-    if (64 * g + 4 * lr < d) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        *reinterpret_cast<float4*>(red + (wv * RT + 4 * lq + r) * LDO + 64 * g + 4 * lr) = make_float4(acc[g][0][r], acc[g][1][r], acc[g][2][r], acc[g][3][r]);
-    }
-  __syncthreads();
+  // 3. F C into the four partial tiles (fsum::query_kernel's step 5)
+  ft::stream_product<NG>(s_f, LD, a.C + (size_t)th * mp * d, mp, d, wv, lr, lq);
   // 4. fold the waves 0, 1, 2, 3; forward: divide, add the centre, store in mlhot_favor_fwd's merged order
   const float* cen = a.fwd ? a.v + ((size_t)t * a.Nc * H + h) * d : nullptr;
   for (int idx = tid; idx < RT * d; idx += 256) {
     const int row = idx / d, e = idx - row * d, n = n0 + row;
     if (n >= N) continue;
-    const float s = ((red[row * LDO + e] + red[(RT + row) * LDO + e]) + red[(2 * RT + row) * LDO + e]) + red[(3 * RT + row) * LDO + e];
+    const float s = ft::fold_tiles(s_f, ldo(d), row, e);
     if (a.fwd) a.out[((size_t)t * N + n) * ((size_t)d * H) + (size_t)e * H + h] = cen[e] + s / s_den[row];
     else a.out[(((size_t)t * N + n) * H + h) * d + e] = s;
   }
@@ -368,31 +315,31 @@ inline int forward(const FavorDims& f, const float* q, const float* k, const flo
                    hipStream_t s) {
   const Ws r = carve(f, ws, ws_bytes);
   if (!r.ok) { set_error("favor_fwd: workspace too small"); return MLHOT_ERR_WORKSPACE; }
-  const float c = powf((float)f.d, -0.25f), ratio = 1.0f / sqrtf((float)f.m), re = ratio * 1e-4f;
+  const ft::Scales sc(f.d, f.m);
   const int th = f.T * f.H;
-  MLHOT_TRY(favor_front_dd(f, r.w, q, k, proj, c, s));
-  MLHOT_TRY(favor_front_feat(f, r.w, ratio, s));
-  MLHOT_TRY(run_sum(SumArgs{r.w.kf, v, nullptr, r.ctx, r.ksum, f.H, f.Nc, f.d, f.m, r.mp, 1, re}, th, s, "favor.lin.ctx"));
-  return run_apply(ApplyArgs{r.w.qf, r.ctx, r.ksum, v, out, r.w.D, f.H, f.Nq, f.Nc, f.d, f.m, r.mp, (f.Nq + RT - 1) / RT, 1, re}, th, s, "favor.lin.out");
+  MLHOT_TRY(favor_front_dd(f, r.w, q, k, proj, sc.c, s));
+  MLHOT_TRY(favor_front_feat(f, r.w, sc.ratio, s));
+  MLHOT_TRY(run_sum(SumArgs{r.w.kf, v, nullptr, r.ctx, r.ksum, f.H, f.Nc, f.d, f.m, r.mp, 1, sc.re}, th, s, "favor.lin.ctx"));
+  return run_apply(ApplyArgs{r.w.qf, r.ctx, r.ksum, v, out, r.w.D, f.H, f.Nq, f.Nc, f.d, f.m, r.mp, (f.Nq + RT - 1) / RT, 1, sc.re}, th, s, "favor.lin.out");
 }
 
 inline int backward(const FavorDims& f, const float* q, const float* k, const float* v, const float* out, const float* dout, float* dq, float* dk,
                     float* dv, void* ws, size_t ws_bytes, hipStream_t s) {
   const Ws r = carve(f, ws, ws_bytes);
   if (!r.ok) { set_error("favor_bwd: workspace too small"); return MLHOT_ERR_WORKSPACE; }
-  const float c = powf((float)f.d, -0.25f), ratio = 1.0f / sqrtf((float)f.m), re = ratio * 1e-4f;
+  const ft::Scales sc(f.d, f.m);
   const int th = f.T * f.H, ntq = (f.Nq + RT - 1) / RT, ntk = (f.Nc + RT - 1) / RT;
   {
     ProfScope ps("favor.lin.bwd.gw", s);
     hipLaunchKernelGGL(gw_kernel, dim3((unsigned)(th * ntq)), dim3(256), 0, s, GwArgs{dout, out, r.w.D, v, r.g, r.nw, f.H, f.Nq, f.Nc, f.d, ntq});
   }
   MLHOT_TRY(check_launch("favor.lin.bwd.gw"));
-  MLHOT_TRY(run_sum(SumArgs{r.w.qf, r.g, r.nw, r.dctx, r.dks, f.H, f.Nq, f.d, f.m, r.mp, 0, re}, th, s, "favor.lin.bwd.dctx"));
+  MLHOT_TRY(run_sum(SumArgs{r.w.qf, r.g, r.nw, r.dctx, r.dks, f.H, f.Nq, f.d, f.m, r.mp, 0, sc.re}, th, s, "favor.lin.bwd.dctx"));
   MLHOT_TRY(run_grad(GradArgs{r.g, r.ctx, r.ksum, r.nw, r.w.qf, r.w.Gq, f.H, f.Nq, f.d, f.m, r.mp, ntq, 0}, th, s, "favor.lin.bwd.Gq"));
   MLHOT_TRY(run_grad(GradArgs{v, r.dctx, r.dks, nullptr, r.w.kf, r.w.Gk, f.H, f.Nc, f.d, f.m, r.mp, ntk, 1}, th, s, "favor.lin.bwd.Gk"));
-  MLHOT_TRY(run_apply(ApplyArgs{r.w.kf, r.dctx, nullptr, v, dv, nullptr, f.H, f.Nc, f.Nc, f.d, f.m, r.mp, ntk, 0, re}, th, s, "favor.lin.bwd.dv"));
+  MLHOT_TRY(run_apply(ApplyArgs{r.w.kf, r.dctx, nullptr, v, dv, nullptr, f.H, f.Nc, f.Nc, f.d, f.m, r.mp, ntk, 0, sc.re}, th, s, "favor.lin.bwd.dv"));
   MLHOT_TRY(favor_back_sums(f, r.w, s));
-  return favor_back_dx(f, r.w, q, k, c, dq, dk, s);
+  return favor_back_dx(f, r.w, q, k, sc.c, dq, dk, s);
 }
 
 }  // namespace fl

@@ -8,12 +8,12 @@
 //   out_k[q, e] = sum_n (S_k[q, n] + eps fs[q]) v[n, e] / sum_n (S_k[q, n] + eps fs[q]),   S_k[q, n] = sum_j F_q[q, j] exp(dd[n, j] - diag[n] - M_k),
 // fs = rowsum(F_q): the numerator is  P_k + eps fs vs_k,  the denominator  p_k + eps fs cnt_k  of favor_summary.h, shot by shot.
 //
-//   D  grid (task x head x 32-shot chunk, 256-feature chunk): dd of the chunk's shots through fc::dd_tiles - the bits favor_keys
+//   D  grid (task x head x 32-shot chunk, 256-feature chunk): dd of the chunk's shots through ft::keys_dd - the bits favor_keys
 //      gives an element - into the workspace, and per shot the maximum over the workgroup's features
 //   X  grid (256 shots): smax[n] = the maximum over tasks, heads and feature chunks of shot n's maxima.  M_k is a running maximum
 //      of smax, which the sweep takes as it walks.  (A fold inside D needs an atomic or a last-workgroup flag, a fold inside S
 //      re-reads T H ceil(mp / 256) floats per shot in every workgroup: a third, tiny launch is the cheaper form.)
-//   S  grid (task x head x 16-row target tile): fc::query_kernel's front half step for step (F_q in LDS once), then the shots in
+//   S  grid (task x head x 16-row target tile): ft::query_front (F_q in LDS once, fc::query_kernel's), then the shots in
 //      chunks of 32, ascending.  Per chunk: diag of its keys, the running maxima Mref[n] = max(smax[0 .. n]),
 //      S[q, n] = sum_j F_q[q, j] exp(dd[n, j] - diag[n] - Mref[n])  (every exponent <= 0) on the matrix core - wave w takes the
 //      16-feature chunks w, w + 4, .. ascending, the waves fold 0, 1, 2, 3 - and the chunk's 32 rows of v in registers.  A member
@@ -38,25 +38,24 @@ inline bool favor_prefix_long_ok(int T, int H, int Nq, int Nc, int d, int m, int
 #ifdef MLHOT_HOSTSIM
   (void)T; (void)H; (void)Nq; (void)Nc; (void)d; (void)m; (void)K; return false;
 #else
-  return T >= 1 && H >= 1 && Nq >= 1 && Nc >= 1 && K >= 1 && K <= FAVOR_PREFIX_LONG_MAXK && d >= 16 && d % 16 == 0 && d <= 256 && m >= 16 &&
-         m <= 1536 && (long long)T * H < (1 << 20) && (long long)T * H * ((Nc + 31) / 32) < (1ll << 31) &&
-         (long long)T * H * (((long long)Nq + 15) / 16) < (1ll << 31);
+  return Nq >= 1 && Nc >= 1 && K >= 1 && K <= FAVOR_PREFIX_LONG_MAXK && ft::envelope_ok(T, H, d, m) &&
+         (long long)T * H * ((Nc + 31) / 32) < (1ll << 31) && (long long)T * H * (((long long)Nq + 15) / 16) < (1ll << 31);
 #endif
 }
 
 #ifndef MLHOT_HOSTSIM
 namespace fpl {
 
-using fv::f32x4_t;
-using fv::mfma4;
+using ft::f32x4_t;
+using ft::mfma4;
+using ft::EPS;
 
 constexpr int CH = 32;                    // shots per chunk
-constexpr float EPS = 1e-4f;
 
 struct Ws { float *dd, *part, *smax; int Ncp, nch, mp; size_t floats; };
 inline Ws carve_ws(int T, int H, int Nc, int m, void* ws) {
   Ws w{};
-  w.mp = (m + 15) / 16 * 16; w.nch = (w.mp + fc::KCH - 1) / fc::KCH; w.Ncp = (Nc + CH - 1) / CH * CH;
+  w.mp = (m + 15) / 16 * 16; w.nch = (w.mp + ft::KCH - 1) / ft::KCH; w.Ncp = (Nc + CH - 1) / CH * CH;
   const size_t th = (size_t)T * H;
   w.dd = (float*)ws; w.part = w.dd + th * w.Ncp * w.mp; w.smax = w.part + th * w.nch * w.Ncp;
   w.floats = th * w.Ncp * w.mp + th * w.nch * w.Ncp + w.Ncp;
@@ -69,73 +68,21 @@ struct Args {
   float* out;
   Ws ws;
   int T, H, Nq, Nc, d, m, mp, ntile, K, nsc;      // nsc: the chunks that hold a shot < ks[K - 1]
-  float c, ratio, re;
+  ft::Scales sc;
   int ks[FAVOR_PREFIX_LONG_MAXK];
 };
 
 // lens[t] held to 0 .. Nc (the host checks 1 .. Nc; the clamp keeps every index in bounds whatever arrives); NULL: all Nc
-__device__ __forceinline__ int task_len(const int32_t* lens, int t, int Nc) { return lens ? min(max((int)lens[t], 0), Nc) : Nc; }
+__device__ __forceinline__ int task_len(const int32_t* lens, int t, int Nc) { return ft::clamp_len(lens, t, 0, Nc); }
 
 // ---- D: dd of one chunk's shots into the workspace, per shot the maximum over this workgroup's features ----------------------
-template <int RT>
-__device__ __forceinline__ void dd_store(const f32x4_t (&acc)[RT][fc::NT], float* ddb, int mp, int m, int f0, int lr, int lq, int ll, float (&best)[2][4]) {
-#pragma unroll
-  for (int i = 0; i < RT; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * i + 4 * lq + r;
-      if (row >= ll) continue;
-      float* drow = ddb + (size_t)row * mp;
-#pragma unroll
-      for (int j = 0; j < fc::NT; ++j) {
-        const int fj = f0 + 16 * j + lr;
-        if (fj < mp) drow[fj] = fj < m ? acc[i][j][r] : 0.f;
-        if (fj < m) best[i][r] = fmaxf(best[i][r], acc[i][j][r]);
-      }
-    }
-}
-
 __global__ __launch_bounds__(256) void dd_kernel(const Args a) {
-  __shared__ __attribute__((aligned(16))) float xs[CH * fc::LDX];
-  __shared__ float s_w[4][CH];
-  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, lq = lane >> 4;
-  const int th = blockIdx.x / a.nsc, sc = blockIdx.x % a.nsc, t = th / a.H, h = th % a.H, chunk = blockIdx.y;
-  const int d = a.d, n0 = CH * sc;
-  const int ll = min(max(task_len(a.lens, t, a.Nc) - n0, 0), CH);        // the chunk's valid shots
-  for (int r = tid >> 3; r < CH; r += 32) {
-    const float* xrow = r < ll ? a.k + (((size_t)t * a.Nc + n0 + r) * a.H + h) * d : nullptr;
-    fc::stage_row<8>(xrow, xs + r * fc::LDX, d, tid & 7, a.c);
-  }
-  __syncthreads();
-  const int f0 = chunk * fc::KCH + wv * fc::WF;
-  float best[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) best[i][r] = -INFINITY;
-  if (f0 < a.mp && ll > 0) {
-    float* ddb = a.ws.dd + ((size_t)th * a.ws.Ncp + n0) * a.mp;
-    if (ll <= 16) {                              // the second tile holds no shot: the first tile's chains alone, the same per element
-      f32x4_t acc[1][fc::NT];
-      fc::dd_tiles<1>(xs, a.proj, d, a.m, f0, lr, lq, acc);
-      dd_store<1>(acc, ddb, a.mp, a.m, f0, lr, lq, ll, best);
-    } else {
-      f32x4_t acc[2][fc::NT];
-      fc::dd_tiles<2>(xs, a.proj, d, a.m, f0, lr, lq, acc);
-      dd_store<2>(acc, ddb, a.mp, a.m, f0, lr, lq, ll, best);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1) best[i][r] = fmaxf(best[i][r], __shfl_xor(best[i][r], off, 64));
-      if (lr == 0) s_w[wv][16 * i + 4 * lq + r] = best[i][r];
-    }
-  __syncthreads();
-  if (tid < CH)                                  // a shot behind lens[t] leaves -inf: it enters no maximum
-    a.ws.part[((size_t)th * a.ws.nch + chunk) * a.ws.Ncp + n0 + tid] = fmaxf(fmaxf(s_w[0][tid], s_w[1][tid]), fmaxf(s_w[2][tid], s_w[3][tid]));
+  __shared__ __attribute__((aligned(16))) float xs[CH * ft::LDX];
+  __shared__ float s_w[4 * CH];
+  const int th = blockIdx.x / a.nsc, sc = blockIdx.x % a.nsc, t = th / a.H, h = th % a.H, n0 = CH * sc;
+  const int ll = min(max(task_len(a.lens, t, a.Nc) - n0, 0), CH);        // the chunk's valid shots; a shot behind lens[t] leaves -inf
+  ft::keys_dd<2, true, true>([&](int r) { return a.k + (((size_t)t * a.Nc + n0 + r) * a.H + h) * a.d; }, ll, a.proj, a.sc.c, a.d, a.m, a.mp,
+                       a.ws.dd + ((size_t)th * a.ws.Ncp + n0) * a.mp, a.ws.part + ((size_t)th * a.ws.nch + blockIdx.y) * a.ws.Ncp + n0, xs, s_w);
 }
 
 // ---- X: per shot the maximum over every task, head and feature chunk ----------------------------------------------------------
@@ -152,64 +99,21 @@ __global__ __launch_bounds__(256) void smax_kernel(const Args a) {
 // NG: the 16-column tiles of d a wave owns (tile wv + 4 i)
 template <int NG>
 __global__ __launch_bounds__(256) void sweep_kernel(const Args a) {
-  __shared__ __attribute__((aligned(16))) float s_f[fc::QT * fc::ldf(fc::MAXM)];
-  __shared__ __attribute__((aligned(16))) float xs[fc::QT * fc::LDX];
+  __shared__ __attribute__((aligned(16))) float s_f[ft::QT * ft::ldf(ft::MAXM)];
+  __shared__ __attribute__((aligned(16))) float xs[ft::QT * ft::LDX];
   __shared__ __attribute__((aligned(16))) float red[4 * 2 * 64 * 4];
-  __shared__ float s_S[fc::QT * fc::LDS_S], s_diag[fc::QT], s_pm[4][fc::QT], s_fs[fc::QT], s_kd[CH], s_sm[CH], s_mref[CH];
+  __shared__ float s_S[ft::QT * ft::LDS_S], s_diag[ft::QT], s_pm[4][ft::QT], s_fs[ft::QT], s_kd[CH], s_sm[CH], s_mref[CH];
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, lq = lane >> 4;
-  const int th = blockIdx.x / a.ntile, tile = blockIdx.x % a.ntile, t = th / a.H, h = th % a.H, q0 = tile * fc::QT;
-  const int d = a.d, m = a.m, Nq = a.Nq, Nc = a.Nc, H = a.H, mp = a.mp, LD = fc::ldf(mp);
-  // 1. - 3.: fc::query_kernel's front half, step for step: c q and diag, dd and the row maxima, F_q in place
-  {
-    const int r = tid >> 4, n = q0 + r;
-    const float* xrow = n < Nq ? a.q + (((size_t)t * Nq + n) * H + h) * d : nullptr;
-    const float s = fc::stage_row<16>(xrow, xs + r * fc::LDX, d, tid & 15, a.c);
-    if ((tid & 15) == 0) s_diag[r] = 0.5f * a.c * a.c * s;
-  }
-  __syncthreads();
-  {
-    float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    for (int f0 = wv * fc::WF; f0 < mp; f0 += 4 * fc::WF) {
-      f32x4_t acc[1][fc::NT];
-      fc::dd_tiles<1>(xs, a.proj, d, m, f0, lr, lq, acc);
-#pragma unroll
-      for (int j = 0; j < fc::NT; ++j) {
-        const int fj = f0 + 16 * j + lr;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (fj < mp) s_f[(4 * lq + r) * LD + fj] = fj < m ? acc[0][j][r] : 0.f;
-          if (fj < m) best[r] = fmaxf(best[r], acc[0][j][r]);
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1) best[r] = fmaxf(best[r], __shfl_xor(best[r], off, 64));
-      if (lr == 0) s_pm[wv][4 * lq + r] = best[r];
-    }
-  }
-  __syncthreads();
-  {
-    const int q4 = mp / 4;
-    for (int idx = tid; idx < fc::QT * q4; idx += 256) {
-      const int row = idx / q4, j = 4 * (idx - row * q4);
-      const float sub = s_diag[row] + fmaxf(fmaxf(s_pm[0][row], s_pm[1][row]), fmaxf(s_pm[2][row], s_pm[3][row]));
-      float4 e = *reinterpret_cast<const float4*>(s_f + row * LD + j);
-      e.x = j < m ? a.ratio * expf(e.x - sub) + a.re : 0.f; e.y = j + 1 < m ? a.ratio * expf(e.y - sub) + a.re : 0.f;
-      e.z = j + 2 < m ? a.ratio * expf(e.z - sub) + a.re : 0.f; e.w = j + 3 < m ? a.ratio * expf(e.w - sub) + a.re : 0.f;
-      *reinterpret_cast<float4*>(s_f + row * LD + j) = e;
-    }
-  }
-  __syncthreads();
-  // 4. fs = rowsum(F_q): 16 threads per row, thread p takes j = p, p + 16, .. in order, then a butterfly (favor_summary.h's step 4)
+  const int th = blockIdx.x / a.ntile, tile = blockIdx.x % a.ntile, t = th / a.H, h = th % a.H, q0 = tile * ft::QT;
+  const int d = a.d, m = a.m, Nq = a.Nq, Nc = a.Nc, H = a.H, mp = a.mp, LD = ft::ldf(mp);
+  // 1. - 3. c q and diag, dd and the row maxima, F_q in place
+  ft::query_front([&](int r) { return q0 + r < Nq ? a.q + (((size_t)t * Nq + q0 + r) * H + h) * d : nullptr; }, a.proj, d, m, mp, a.sc, xs, s_f, s_diag, s_pm);
+  // 4. fs = rowsum(F_q)
   {
     const int row = tid >> 4, p = tid & 15;
-    float fs = 0.f;
-    for (int j = p; j < mp; j += 16) fs += s_f[row * LD + j];
-#pragma unroll
-    for (int off = 1; off < 16; off <<= 1) fs += __shfl_xor(fs, off, 64);
-    if (p == 0) s_fs[row] = fs;
+    float fs[1];
+    ft::row_sums(mp, p, fs, [&](int j, float (&u)[1]) { u[0] += s_f[row * LD + j]; });
+    if (p == 0) s_fs[row] = fs[0];
   }
   // 5. the walk.  Carried, relative to Mprev = the running maximum at the end of the last chunk: P (this wave's NG tiles of the
   //    [16 x d] numerator, rows 4 lq + r, column 16 (wv + 4 i) + lr), p (rows 4 lq + r), vs (this lane's columns) and cnt
@@ -223,10 +127,9 @@ __global__ __launch_bounds__(256) void sweep_kernel(const Args a) {
     const int n0 = CH * sc, ll = min(max(len - n0, 0), CH);
     __syncthreads();                            // the last chunk's members have read s_S, s_mref (and, first, s_fs is written)
     {
-      const int r = tid >> 3;                   // 32 shots x 8 threads: keys2's diag
-      const float* xrow = r < ll ? a.k + (((size_t)t * Nc + n0 + r) * H + h) * d : nullptr;
-      const float s = fc::stage_row<8>(xrow, nullptr, d, tid & 7, 0.f);
-      if ((tid & 7) == 0) s_kd[r] = 0.5f * a.c * a.c * s;
+      const int r = tid >> 3;
+      const float dg = ft::key_diag(r < ll ? a.k + (((size_t)t * Nc + n0 + r) * H + h) * d : nullptr, d, a.sc.c, tid);
+      if ((tid & 7) == 0) s_kd[r] = dg;
     }
     if (tid < CH) s_sm[tid] = a.ws.smax[n0 + tid];
     // the chunk's rows of v for this lane's columns: slot 4 s8 + lq, zeros behind lens[t] (never read)
@@ -247,7 +150,6 @@ __global__ __launch_bounds__(256) void sweep_kernel(const Args a) {
     __syncthreads();
     // S[q, n] = sum_j F_q[q, j] exp(dd[n, j] - diag[n] - Mref[n]); features >= m and shots behind lens[t] are zeros by index
     {
-      const int tk = (ll + 15) / 16, nch16 = ll > 0 ? mp / 16 : 0;
       const float* drow[2];
       float sub[2];
 #pragma unroll
@@ -256,46 +158,9 @@ __global__ __launch_bounds__(256) void sweep_kernel(const Args a) {
         drow[jj] = n < ll ? a.ws.dd + ((size_t)th * a.ws.Ncp + n0 + n) * mp + 4 * lq : nullptr;
         sub[jj] = s_kd[n] + s_mref[n];
       }
-      f32x4_t acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-      for (int ch = wv; ch < nch16; ch += 16) {
-        float4 fb[4][2];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int jj = 0; jj < 2; ++jj)
-            fb[u][jj] = (ch + 4 * u < nch16 && drow[jj]) ? *reinterpret_cast<const float4*>(drow[jj] + 16 * (ch + 4 * u)) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (ch + 4 * u >= nch16) break;
-          const int j0 = 16 * (ch + 4 * u) + 4 * lq;
-          const float4 fa = *reinterpret_cast<const float4*>(s_f + lr * LD + j0);
-#pragma unroll
-          for (int jj = 0; jj < 2; ++jj) {
-            if (jj >= tk) continue;
-            const bool on = drow[jj] != nullptr;
-            const float ex = (on && j0 < m) ? expf(fb[u][jj].x - sub[jj]) : 0.f, ey = (on && j0 + 1 < m) ? expf(fb[u][jj].y - sub[jj]) : 0.f;
-            const float ez = (on && j0 + 2 < m) ? expf(fb[u][jj].z - sub[jj]) : 0.f, ew = (on && j0 + 3 < m) ? expf(fb[u][jj].w - sub[jj]) : 0.f;
-            acc[jj] = mfma4(fa.x, ex, acc[jj]); acc[jj] = mfma4(fa.y, ey, acc[jj]);
-            acc[jj] = mfma4(fa.z, ez, acc[jj]); acc[jj] = mfma4(fa.w, ew, acc[jj]);
-          }
-        }
-      }
-#pragma unroll
-      for (int jj = 0; jj < 2; ++jj) *reinterpret_cast<f32x4_t*>(red + ((wv * 2 + jj) * 64 + lane) * 4) = acc[jj];
+      ft::s_tile(s_f, LD, drow, (ll + 15) / 16, ll > 0 ? mp / 16 : 0, CH,
+                 [&](int jj, int j0, bool on, float4 b) { return on ? ft::exp4(b, sub[jj], j0, m) : make_float4(0.f, 0.f, 0.f, 0.f); }, red, s_S);
     }
-    __syncthreads();
-    if (wv < 2) {
-      const int jj = wv;
-      f32x4_t s = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const f32x4_t vv = *reinterpret_cast<const f32x4_t*>(red + ((k * 2 + jj) * 64 + lane) * 4);
-        s[0] += vv[0]; s[1] += vv[1]; s[2] += vv[2]; s[3] += vv[3];
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) s_S[(4 * lq + r) * fc::LDS_S + 16 * jj + lr] = s[r];
-    }
-    __syncthreads();
     // the chunk's part of a prefix that ends p shots into it, relative to Mk: one chain over the shot slots per tile, one against
     // ones for the denominator; slots at or behind min(p, ll) are zeros by index, their MFMAs (which would add +0) are skipped
     auto product = [&](int p, float Mk, float eps, f32x4_t (&o)[NG], f32x4_t& od) {
@@ -306,7 +171,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(const Args a) {
         const int np = 4 * s8 + lq;
         const float mr = s_mref[np];
         const float w = mr == Mk ? 1.f : expf(mr - Mk);
-        av[s8] = np < cut ? s_S[lr * fc::LDS_S + np] * w + eps * s_fs[lr] : 0.f;
+        av[s8] = np < cut ? s_S[lr * ft::LDS_S + np] * w + eps * s_fs[lr] : 0.f;
       }
       od = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -398,14 +263,14 @@ inline int favor_prefix_long_forward(const float* q, const float* k, const float
   fpl::Args a{};
   a.ws = fpl::carve_ws(T, H, Nc, m, ws);
   if (!ws || ws_bytes < a.ws.floats * sizeof(float)) { set_error("favor_prefix_long_fwd: workspace too small (%zu < %zu)", ws_bytes, a.ws.floats * sizeof(float)); return MLHOT_ERR_WORKSPACE; }
-  if (!fc_aligned16(q) || !fc_aligned16(k) || !fc_aligned16(v) || !fc_aligned16(proj) || !fc_aligned16(ws)) {
+  if (!ft::aligned16(q) || !ft::aligned16(k) || !ft::aligned16(v) || !ft::aligned16(proj) || !ft::aligned16(ws)) {
     set_error("favor_prefix_long_fwd: q, k, v, proj and ws must be 16-byte aligned"); return MLHOT_ERR_ARG;
   }
   a.q = q; a.k = k; a.v = v; a.proj = proj; a.lens = lens; a.out = out;
   a.T = T; a.H = H; a.Nq = Nq; a.Nc = Nc; a.d = d; a.m = m; a.mp = a.ws.mp; a.K = K;
-  a.ntile = (Nq + fc::QT - 1) / fc::QT;
+  a.ntile = (Nq + ft::QT - 1) / ft::QT;
   a.nsc = (ks[K - 1] + fpl::CH - 1) / fpl::CH;
-  a.c = powf((float)d, -0.25f); a.ratio = 1.0f / sqrtf((float)m); a.re = a.ratio * 1e-4f;
+  a.sc = ft::Scales(d, m);
   for (int i = 0; i < K; ++i) a.ks[i] = ks[i];
   {
     ProfScope ps("favor.plong_dd", s);

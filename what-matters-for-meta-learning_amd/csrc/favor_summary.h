@@ -6,18 +6,18 @@
 // of all tasks, heads and features absorbed so far - fast_attention.py:96-97's batch-global rule):
 //   A[j, e] = sum_n exp(dd[n, j] - diag[n] - M) v[n, e]   [mp, d]      a[j] = sum_n exp(dd[n, j] - diag[n] - M)   [mp]
 //   vs[e]   = sum_n v[n, e]                                [d]          cnt  = the number of shots
-//   out[q, e] = sum_j F_q[q, j] (A[j, e] + eps vs[e]) / sum_j F_q[q, j] (a[j] + eps cnt),   F_q exactly fc::query_kernel's.
+//   out[q, e] = sum_j F_q[q, j] (A[j, e] + eps vs[e]) / sum_j F_q[q, j] (a[j] + eps cnt),   F_q exactly fc::query_kernel's (ft::query_front).
 // State (floats): A [T][H][mp][d], a [T][H][mp], vs [T][H][d], M (one float in a block of 16), cnt [T][H] (int32), mp = m rounded
 // up to 16; features >= m are exact zeros.  A fresh state has M = -inf and everything else 0.
 //
 //   absorb A1 grid (task x head, 256-feature chunk): dd of the NEW shots (<= 32 per task) on the matrix core into the workspace -
-//             fc::dd_tiles, so an element has the bits favor_keys gives it - and the workgroup's maximum; one workgroup copies the
+//             ft::keys_dd, so an element has the bits favor_keys gives it - and the workgroup's maximum; one workgroup copies the
 //             state's M into the workspace, so that no workgroup of A2 reads what another one writes (state_in may be state_out)
 //          A2 grid (task x head, 64-feature chunk): M' = max(M, the maxima), s = exp(M - M') (1 where M' == M, so a fresh state's
 //             -inf - -inf never forms), e[n, j] = exp(dd - diag - M') in LDS (0 behind lens[t] and at features >= m - selected by
 //             index, never by a product), then A <- s A + e^T v on the matrix core (K = the 32 shot slots), a <- s a + the row sums of
 //             e^T; chunk 0 of a (task, head) adds vs and cnt, chunk 0 of (0, 0) writes M'
-//   query  grid (task x head x 16-row query tile), ONE launch for any Nq: F_q in LDS (fc::query_kernel's front half), then
+//   query  grid (task x head x 16-row query tile), ONE launch for any Nq: F_q in LDS (ft::query_front), then
 //             [16 x mp] [mp x d] against A streamed from memory: wave w takes the 16-feature chunks w, w + 4, .. in ascending order
 //             for all d columns, the four partial tiles fold 0, 1, 2, 3 through LDS (F_q's space, dead by then); the row sums of
 //             F_q and of F_q a give the eps terms and the denominator.
@@ -34,20 +34,20 @@ inline bool favor_summary_ok(int T, int H, int d, int m) {
 #ifdef MLHOT_HOSTSIM
   (void)T; (void)H; (void)d; (void)m; return false;
 #else
-  return T >= 1 && H >= 1 && d >= 16 && d % 16 == 0 && d <= 256 && m >= 16 && m <= 1536 && (long long)T * H < (1 << 20);
+  return ft::envelope_ok(T, H, d, m);
 #endif
 }
 
 #ifndef MLHOT_HOSTSIM
 namespace fsum {
 
-using fv::f32x4_t;
-using fv::mfma4;
+using ft::f32x4_t;
+using ft::mfma4;
+using ft::EPS;
 
 constexpr int MAXN = 32;                  // new shots per task and absorb call
 constexpr int FC = 64;                    // features per A2 workgroup: 16 per wave
 constexpr int LDE = FC + 8;               // LDS row stride of e
-constexpr float EPS = 1e-4f;
 
 struct State { float *A, *a, *vs, *M; int32_t* cnt; int mp; size_t floats; };
 inline State carve_state(int T, int H, int d, int m, void* state) {
@@ -64,7 +64,7 @@ struct Ws { float *dd, *part, *Mold; int nch; size_t floats; };
 inline Ws carve_ws(int T, int H, int n, int mp, void* ws) {
   Ws w{};
   const size_t th = (size_t)T * H;
-  w.nch = (mp + fc::KCH - 1) / fc::KCH;
+  w.nch = (mp + ft::KCH - 1) / ft::KCH;
   w.dd = (float*)ws; w.part = w.dd + th * n * mp; w.Mold = w.part + align_up(th * w.nch, 64);
   w.floats = th * n * mp + align_up(th * w.nch, 64) + 64;
   return w;
@@ -80,7 +80,7 @@ struct AbsorbArgs {
 };
 
 // lens[t] held to 0 .. n; NULL: every one of the n rows is a shot
-__device__ __forceinline__ int new_len(const int32_t* lens, int t, int n) { return lens ? min(max((int)lens[t], 0), n) : n; }
+__device__ __forceinline__ int new_len(const int32_t* lens, int t, int n) { return ft::clamp_len(lens, t, 0, n); }
 
 __global__ __launch_bounds__(256) void init_kernel(float* st, size_t floats, size_t m_at) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < floats; i += (size_t)gridDim.x * 256) st[i] = i == m_at ? -INFINITY : 0.f;
@@ -89,38 +89,12 @@ __global__ __launch_bounds__(256) void init_kernel(float* st, size_t floats, siz
 // ---- absorb, launch 1: dd of the new shots into the workspace, the workgroup's maximum ---------------------------------------
 template <int RT>
 __global__ __launch_bounds__(256) void absorb1_kernel(const AbsorbArgs a) {
-  __shared__ __attribute__((aligned(16))) float xs[16 * RT * fc::LDX];
+  __shared__ __attribute__((aligned(16))) float xs[16 * RT * ft::LDX];
   __shared__ float s_w[4];
-  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, lq = lane >> 4;
-  const int th = blockIdx.x, t = th / a.H, h = th % a.H, chunk = blockIdx.y;
-  const int d = a.d, n = a.n;
-  const int len = new_len(a.lens, t, n);
-  if (th == 0 && chunk == 0 && tid == 0) a.ws.Mold[0] = a.in.M[0];
-  for (int r = tid >> 3; r < 16 * RT; r += 32) {
-    const float* xrow = r < len ? a.k + ((size_t)(t * n + r) * a.H + h) * d : nullptr;
-    fc::stage_row<8>(xrow, xs + r * fc::LDX, d, tid & 7, a.c);
-  }
-  __syncthreads();
-  fc::Args ka{};                            // what fc::keys1_store reads: rows of the workspace in place of the key state
-  ka.fkw = a.ws.dd; ka.Nc = n; ka.m = a.m; ka.mp = a.mp;
-  const int f0 = chunk * fc::KCH + wv * fc::WF;
-  float best = -INFINITY;
-  if (f0 < a.mp && len > 0) {
-    if (RT == 2 && len <= 16) {
-      f32x4_t acc[1][fc::NT];
-      fc::dd_tiles<1>(xs, a.proj, d, a.m, f0, lr, lq, acc);
-      best = fc::keys1_store<1, true>(acc, ka, th, f0, lr, lq, len, best);
-    } else {
-      f32x4_t acc[RT][fc::NT];
-      fc::dd_tiles<RT>(xs, a.proj, d, a.m, f0, lr, lq, acc);
-      best = fc::keys1_store<RT, true>(acc, ka, th, f0, lr, lq, len, best);
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) best = fmaxf(best, __shfl_xor(best, off, 64));
-  if (lane == 0) s_w[wv] = best;
-  __syncthreads();
-  if (tid == 0) a.ws.part[(size_t)th * a.ws.nch + chunk] = fmaxf(fmaxf(s_w[0], s_w[1]), fmaxf(s_w[2], s_w[3]));
+  const int th = blockIdx.x, t = th / a.H, h = th % a.H;
+  if (th == 0 && blockIdx.y == 0 && threadIdx.x == 0) a.ws.Mold[0] = a.in.M[0];
+  ft::keys_dd<RT, false, true>([&](int r) { return a.k + ((size_t)(t * a.n + r) * a.H + h) * a.d; }, new_len(a.lens, t, a.n), a.proj, a.c, a.d, a.m, a.mp,
+                         a.ws.dd + (size_t)th * a.n * a.mp, a.ws.part + (size_t)th * a.ws.nch + blockIdx.y, xs, s_w);
 }
 
 // ---- absorb, launch 2: M', the rescale, A += e^T v, a += rowsum(e^T); vs, cnt and M by designated workgroups ---------------------
@@ -131,20 +105,15 @@ __global__ __launch_bounds__(256) void absorb2_kernel(const AbsorbArgs a) {
   const int th = blockIdx.x, t = th / a.H, h = th % a.H, chunk = blockIdx.y;
   const int d = a.d, n = a.n, m = a.m, mp = a.mp, H = a.H;
   const int len = new_len(a.lens, t, n);
-  float best = -INFINITY;
-  for (int i = tid; i < a.T * H * a.ws.nch; i += 256) best = fmaxf(best, a.ws.part[i]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) best = fmaxf(best, __shfl_xor(best, off, 64));
-  if (lane == 0) s_w[wv] = best;
+  ft::part_max(a.ws.part, a.T * H * a.ws.nch, s_w, tid);
   {
-    const int r = tid >> 3;            // 32 rows x 8 threads
-    const float* xrow = r < len ? a.k + ((size_t)(t * n + r) * H + h) * d : nullptr;
-    const float s = fc::stage_row<8>(xrow, nullptr, d, tid & 7, 0.f);
-    if ((tid & 7) == 0) s_diag[r] = 0.5f * a.c * a.c * s;
+    const int r = tid >> 3;
+    const float dg = ft::key_diag(r < len ? a.k + ((size_t)(t * n + r) * H + h) * d : nullptr, d, a.c, tid);
+    if ((tid & 7) == 0) s_diag[r] = dg;
   }
   __syncthreads();
   const float Mold = a.ws.Mold[0];
-  const float M = fmaxf(Mold, fmaxf(fmaxf(s_w[0], s_w[1]), fmaxf(s_w[2], s_w[3])));
+  const float M = fmaxf(Mold, ft::max4(s_w[0], s_w[1], s_w[2], s_w[3]));
   const float scale = M == Mold ? 1.f : expf(Mold - M);         // a fresh state (Mold = -inf) with no valid shot keeps M = -inf
   const int j0 = chunk * FC;
   const float* ddb = a.ws.dd + (size_t)th * n * mp;
@@ -198,133 +167,38 @@ struct QueryArgs {
   State st;
   float* out;
   int T, H, Nq, d, m, mp, ntile;
-  float c, ratio, re;
+  ft::Scales sc;
 };
 
-constexpr int ldo(int d) { return d + 4; }  // row stride of a wave's partial out tile in LDS
-
-// NG: 64-column groups of d.  A lane's float4 of A[j][64 g + 4 lr ..] serves four MFMAs whose 16 output columns are 64 g + 4 lr' + y.
+// NG: 64-column groups of d (ft::stream_product)
 template <int NG>
 __global__ __launch_bounds__(256) void query_kernel(const QueryArgs a) {
-  __shared__ __attribute__((aligned(16))) float s_f[fc::QT * fc::ldf(fc::MAXM)];
-  __shared__ __attribute__((aligned(16))) float xs[fc::QT * fc::LDX];
-  __shared__ float s_diag[fc::QT], s_pm[4][fc::QT], s_fs[fc::QT], s_den[fc::QT];
-  static_assert(4 * fc::QT * ldo(fc::MAXD) <= fc::QT * fc::ldf(fc::MAXM), "the four partial tiles must fit into F_q's space");
+  __shared__ __attribute__((aligned(16))) float s_f[ft::QT * ft::ldf(ft::MAXM)];
+  __shared__ __attribute__((aligned(16))) float xs[ft::QT * ft::LDX];
+  __shared__ float s_diag[ft::QT], s_pm[4][ft::QT], s_fs[ft::QT], s_den[ft::QT];
+  static_assert(4 * ft::QT * ft::ldo(ft::MAXD) <= ft::QT * ft::ldf(ft::MAXM), "the four partial tiles must fit into F_q's space");
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, lq = lane >> 4;
-  const int th = blockIdx.x / a.ntile, tile = blockIdx.x % a.ntile, t = th / a.H, h = th % a.H, n0 = tile * fc::QT;
-  const int d = a.d, m = a.m, Nq = a.Nq, H = a.H, mp = a.mp, LD = fc::ldf(mp);
-  // 1. - 3.: fc::query_kernel's front half, step for step: c q and diag, dd and the row maxima, F_q in place
-  {
-    const int r = tid >> 4, n = n0 + r;
-    const float* xrow = n < Nq ? a.q + (((size_t)t * Nq + n) * H + h) * d : nullptr;
-    const float s = fc::stage_row<16>(xrow, xs + r * fc::LDX, d, tid & 15, a.c);
-    if ((tid & 15) == 0) s_diag[r] = 0.5f * a.c * a.c * s;
-  }
-  __syncthreads();
-  {
-    float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    for (int f0 = wv * fc::WF; f0 < mp; f0 += 4 * fc::WF) {
-      f32x4_t acc[1][fc::NT];
-      fc::dd_tiles<1>(xs, a.proj, d, m, f0, lr, lq, acc);
-#pragma unroll
-      for (int j = 0; j < fc::NT; ++j) {
-        const int fj = f0 + 16 * j + lr;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (fj < mp) s_f[(4 * lq + r) * LD + fj] = fj < m ? acc[0][j][r] : 0.f;
-          if (fj < m) best[r] = fmaxf(best[r], acc[0][j][r]);
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1) best[r] = fmaxf(best[r], __shfl_xor(best[r], off, 64));
-      if (lr == 0) s_pm[wv][4 * lq + r] = best[r];
-    }
-  }
-  __syncthreads();
-  {
-    const int q4 = mp / 4;
-    for (int idx = tid; idx < fc::QT * q4; idx += 256) {
-      const int row = idx / q4, j = 4 * (idx - row * q4);
-      const float sub = s_diag[row] + fmaxf(fmaxf(s_pm[0][row], s_pm[1][row]), fmaxf(s_pm[2][row], s_pm[3][row]));
-      float4 e = *reinterpret_cast<const float4*>(s_f + row * LD + j);
-      e.x = j < m ? a.ratio * expf(e.x - sub) + a.re : 0.f; e.y = j + 1 < m ? a.ratio * expf(e.y - sub) + a.re : 0.f;
-      e.z = j + 2 < m ? a.ratio * expf(e.z - sub) + a.re : 0.f; e.w = j + 3 < m ? a.ratio * expf(e.w - sub) + a.re : 0.f;
-      *reinterpret_cast<float4*>(s_f + row * LD + j) = e;
-    }
-  }
-  __syncthreads();
-  // 4. per row: fs = sum_j F_q[j], fa = sum_j F_q[j] a[j]: 16 threads per row, thread p takes j = p, p + 16, .. in order, then a
-  //    butterfly over the 16 lanes (commutative at every level: every lane ends with the same bits)
+  const int th = blockIdx.x / a.ntile, tile = blockIdx.x % a.ntile, t = th / a.H, h = th % a.H, n0 = tile * ft::QT;
+  const int d = a.d, Nq = a.Nq, H = a.H, mp = a.mp, LD = ft::ldf(mp);
+  // 1. - 3. c q and diag, dd and the row maxima, F_q in place
+  ft::query_front([&](int r) { return n0 + r < Nq ? a.q + (((size_t)t * Nq + n0 + r) * H + h) * d : nullptr; }, a.proj, d, a.m, mp, a.sc, xs, s_f, s_diag, s_pm);
+  // 4. per row: fs = sum_j F_q[j], fa = sum_j F_q[j] a[j]
   {
     const int row = tid >> 4, p = tid & 15;
     const float* av = a.st.a + (size_t)th * mp;
-    float fs = 0.f, fa = 0.f;
-    for (int j = p; j < mp; j += 16) { const float f = s_f[row * LD + j]; fs += f; fa += f * av[j]; }
-#pragma unroll
-    for (int off = 1; off < 16; off <<= 1) { fs += __shfl_xor(fs, off, 64); fa += __shfl_xor(fa, off, 64); }
-    if (p == 0) { s_fs[row] = fs; s_den[row] = fa + (EPS * (float)a.st.cnt[th]) * fs; }
+    float s[2];
+    ft::row_sums(mp, p, s, [&](int j, float (&u)[2]) { const float f = s_f[row * LD + j]; u[0] += f; u[1] += f * av[j]; });
+    if (p == 0) { s_fs[row] = s[0]; s_den[row] = s[1] + (EPS * (float)a.st.cnt[th]) * s[0]; }
   }
-  // 5. F_q A: wave w takes the 16-feature chunks w, w + 4, .. in ascending order for every column group; the next chunk's rows of A
-  //    are in flight while this one's MFMAs run
-  f32x4_t acc[NG][4];
-#pragma unroll
-  for (int g = 0; g < NG; ++g)
-#pragma unroll
-    for (int y = 0; y < 4; ++y) acc[g][y] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  {
-    const int nch16 = mp / 16;
-    const float* Ab = a.st.A + (size_t)th * mp * d + 4 * lr;
-    float4 cur[NG][4], nxt[NG][4];
-    auto load = [&](float4 (&b)[NG][4], int ch) {
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int x = 0; x < 4; ++x)
-          b[g][x] = (ch < nch16 && 64 * g + 4 * lr < d) ? *reinterpret_cast<const float4*>(Ab + (size_t)(16 * ch + 4 * lq + x) * d + 64 * g)
-                                                        : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    load(cur, wv);
-    for (int ch = wv; ch < nch16; ch += 4) {
-      load(nxt, ch + 4);
-      const float4 fa = *reinterpret_cast<const float4*>(s_f + lr * LD + 16 * ch + 4 * lq);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        acc[g][0] = mfma4(fa.x, cur[g][0].x, acc[g][0]); acc[g][1] = mfma4(fa.x, cur[g][0].y, acc[g][1]);
-        acc[g][2] = mfma4(fa.x, cur[g][0].z, acc[g][2]); acc[g][3] = mfma4(fa.x, cur[g][0].w, acc[g][3]);
-        acc[g][0] = mfma4(fa.y, cur[g][1].x, acc[g][0]); acc[g][1] = mfma4(fa.y, cur[g][1].y, acc[g][1]);
-        acc[g][2] = mfma4(fa.y, cur[g][1].z, acc[g][2]); acc[g][3] = mfma4(fa.y, cur[g][1].w, acc[g][3]);
-        acc[g][0] = mfma4(fa.z, cur[g][2].x, acc[g][0]); acc[g][1] = mfma4(fa.z, cur[g][2].y, acc[g][1]);
-        acc[g][2] = mfma4(fa.z, cur[g][2].z, acc[g][2]); acc[g][3] = mfma4(fa.z, cur[g][2].w, acc[g][3]);
-        acc[g][0] = mfma4(fa.w, cur[g][3].x, acc[g][0]); acc[g][1] = mfma4(fa.w, cur[g][3].y, acc[g][1]);
-        acc[g][2] = mfma4(fa.w, cur[g][3].z, acc[g][2]); acc[g][3] = mfma4(fa.w, cur[g][3].w, acc[g][3]);
-      }
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int x = 0; x < 4; ++x) cur[g][x] = nxt[g][x];
-    }
-  }
-  __syncthreads();                          // F_q is dead: its space takes the four partial tiles [wave][16][ldo(d)]
-  float* red = s_f;
-  const int LDO = ldo(d);
-#pragma unroll
-  for (int g = 0; g < NG; ++g)
-    if (64 * g + 4 * lr < d) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        *reinterpret_cast<float4*>(red + (wv * fc::QT + 4 * lq + r) * LDO + 64 * g + 4 * lr) = make_float4(acc[g][0][r], acc[g][1][r], acc[g][2][r], acc[g][3][r]);
-    }
-  __syncthreads();
+  // 5. F_q A into the four partial tiles
+  ft::stream_product<NG>(s_f, LD, a.st.A + (size_t)th * mp * d, mp, d, wv, lr, lq);
   // 6. fold the waves 0, 1, 2, 3, add eps vs[e] fs, divide, store in mlhot_favor_fwd's merged order
   {
     const float* vs = a.st.vs + (size_t)th * d;
-    for (int idx = tid; idx < fc::QT * d; idx += 256) {
+    for (int idx = tid; idx < ft::QT * d; idx += 256) {
       const int row = idx / d, e = idx - row * d, n = n0 + row;
       if (n >= Nq) continue;
-      const float s = ((red[row * LDO + e] + red[(fc::QT + row) * LDO + e]) + red[(2 * fc::QT + row) * LDO + e]) + red[(3 * fc::QT + row) * LDO + e];
+      const float s = ft::fold_tiles(s_f, ft::ldo(d), row, e);
       a.out[((size_t)t * Nq + n) * ((size_t)d * H) + (size_t)e * H + h] = (s + (EPS * vs[e]) * s_fs[row]) / s_den[row];
     }
   }
@@ -362,7 +236,7 @@ inline int favor_summary_init(int T, int H, int d, int m, void* state, size_t st
 #else
   const fsum::State st = fsum::carve_state(T, H, d, m, state);
   if (state_bytes < st.floats * sizeof(float)) { set_error("favor_summary_init: state too small (%zu < %zu)", state_bytes, st.floats * sizeof(float)); return MLHOT_ERR_WORKSPACE; }
-  if (!fc_aligned16(state)) { set_error("favor_summary_init: state must be 16-byte aligned"); return MLHOT_ERR_ARG; }
+  if (!ft::aligned16(state)) { set_error("favor_summary_init: state must be 16-byte aligned"); return MLHOT_ERR_ARG; }
   ProfScope ps("favor.sum_init", s);
   const size_t want = (st.floats + 255) / 256;
   const unsigned blocks = (unsigned)(want < 4096 ? want : 4096);
@@ -385,12 +259,12 @@ inline int favor_summary_absorb(const float* k, const float* v, const float* pro
   a.ws = fsum::carve_ws(T, H, n, a.in.mp, ws);
   if (state_bytes < a.in.floats * sizeof(float)) { set_error("favor_summary_absorb: state too small (%zu < %zu)", state_bytes, a.in.floats * sizeof(float)); return MLHOT_ERR_WORKSPACE; }
   if (!ws || ws_bytes < a.ws.floats * sizeof(float)) { set_error("favor_summary_absorb: workspace too small"); return MLHOT_ERR_WORKSPACE; }
-  if (!fc_aligned16(k) || !fc_aligned16(v) || !fc_aligned16(proj) || !fc_aligned16(state_in) || !fc_aligned16(state_out) || !fc_aligned16(ws)) {
+  if (!ft::aligned16(k) || !ft::aligned16(v) || !ft::aligned16(proj) || !ft::aligned16(state_in) || !ft::aligned16(state_out) || !ft::aligned16(ws)) {
     set_error("favor_summary_absorb: k, v, proj, the states and ws must be 16-byte aligned"); return MLHOT_ERR_ARG;
   }
   a.k = k; a.v = v; a.proj = proj; a.lens = lens;
   a.T = T; a.H = H; a.n = n; a.d = d; a.m = m; a.mp = a.in.mp;
-  a.c = powf((float)d, -0.25f);
+  a.c = ft::Scales(d, m).c;
   {
     ProfScope ps("favor.sum_absorb1", s);
     if (n <= 16) hipLaunchKernelGGL((fsum::absorb1_kernel<1>), dim3(T * H, a.ws.nch), dim3(256), 0, s, a);
@@ -413,14 +287,14 @@ inline int favor_summary_query_forward(const float* q, const void* state, const 
   (void)ws; (void)ws_bytes; (void)s; return MLHOT_ERR_UNSUPPORTED;
 #else
   if (ws == nullptr || ws_bytes < favor_summary_query_ws_need(T, H, Nq, d, m)) { set_error("favor_summary_query_fwd: workspace too small"); return MLHOT_ERR_WORKSPACE; }
-  const long long ntile = ((long long)Nq + fc::QT - 1) / fc::QT;
+  const long long ntile = ((long long)Nq + ft::QT - 1) / ft::QT;
   if (ntile * T * H >= (1ll << 31)) { set_error("favor_summary_query_fwd: T H ceil(Nq / 16) must stay below 2^31 (chunk the query rows)"); return MLHOT_ERR_ARG; }
-  if (!fc_aligned16(q) || !fc_aligned16(proj) || !fc_aligned16(state)) { set_error("favor_summary_query_fwd: q, proj and state must be 16-byte aligned"); return MLHOT_ERR_ARG; }
+  if (!ft::aligned16(q) || !ft::aligned16(proj) || !ft::aligned16(state)) { set_error("favor_summary_query_fwd: q, proj and state must be 16-byte aligned"); return MLHOT_ERR_ARG; }
   fsum::QueryArgs a{};
   a.st = fsum::carve_state(T, H, d, m, const_cast<void*>(state));
   a.q = q; a.proj = proj; a.out = out;
   a.T = T; a.H = H; a.Nq = Nq; a.d = d; a.m = m; a.mp = a.st.mp; a.ntile = (int)ntile;
-  a.c = powf((float)d, -0.25f); a.ratio = 1.0f / sqrtf((float)m); a.re = a.ratio * 1e-4f;
+  a.sc = ft::Scales(d, m);
   ProfScope ps("favor.sum_query", s);
   const dim3 grid((unsigned)(ntile * T * H));
   switch ((d + 63) / 64) {

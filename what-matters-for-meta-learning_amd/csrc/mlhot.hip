@@ -11,6 +11,7 @@
 #include "problems.h"
 #include "ops_direct.h"
 #include "favor.h"
+#include "favor_tile.h"
 #include "favor2.h"
 #include "prefix.h"
 #include "encoder.h"

@@ -93,14 +93,13 @@ inline Ws carve_ws(int T, int Nc, int m, void* ws) {
 __global__ __launch_bounds__(256) void keys_kernel(const fc::Args a, float* diag, float* pmax) {
   const int tid = threadIdx.x, th = blockIdx.x, t = th / a.H, h = th % a.H;
   const int r = tid >> 3, part = tid & 7;          // 32 rows x 8 threads
-  const float* xrow = r < a.Nc ? a.x + ((size_t)(t * a.Nc + r) * a.H + h) * a.d : nullptr;
-  const float s = fc::stage_row<8>(xrow, nullptr, a.d, part, 0.f);
+  const float dg = ft::key_diag(r < a.Nc ? a.x + ((size_t)(t * a.Nc + r) * a.H + h) * a.d : nullptr, a.d, a.sc.c, tid);
   float best = -INFINITY;
   if (r < a.Nc)
     for (int f = part; f < a.m; f += 8) best = fmaxf(best, a.fk[((size_t)th * a.Nc + r) * a.mp + f]);
 #pragma unroll
   for (int off = 1; off < 8; off <<= 1) best = fmaxf(best, __shfl_xor(best, off, 64));
-  if (r < a.Nc && part == 0) { diag[(size_t)th * a.Nc + r] = 0.5f * a.c * a.c * s; pmax[(size_t)th * a.Nc + r] = best; }
+  if (r < a.Nc && part == 0) { diag[(size_t)th * a.Nc + r] = dg; pmax[(size_t)th * a.Nc + r] = best; }
 }
 
 // nq::tile_linear with a row stride of W of its own (ldw) and the chain's start value: store(r, row, n, chain from init(row, n) + b[n])
@@ -179,43 +178,24 @@ __global__ __launch_bounds__(256) void sweep_kernel(const Args pa) {
     for (int h = 0; h < H; ++h) {
       const size_t th = (size_t)t * H + h;
       // 1. - 3. of np_query.h: c q_h (and q_h itself for diag), dd_q with the row maxima, F_q in place
-      nq::tile_linear<1>(s_xz, LDXZ, a.wq_w[h], a.wq_b[h], d, d, wv, lr, lq, [&](int, int row, int n, float v) { s_q[row * LDQ + n] = a.c * v; s_o[row * LDQ + n] = v; });
+      nq::tile_linear<1>(s_xz, LDXZ, a.wq_w[h], a.wq_b[h], d, d, wv, lr, lq, [&](int, int row, int n, float v) { s_q[row * LDQ + n] = a.sc.c * v; s_o[row * LDQ + n] = v; });
       __syncthreads();
       {
         const int r = tid >> 4;
-        const float s = fc::stage_row<16>(s_o + r * LDQ, nullptr, d, tid & 15, 0.f);      // fc::query_kernel's diag: its sum, then its scale
-        if ((tid & 15) == 0) s_diag[r] = 0.5f * a.c * a.c * s;
+        const float s = ft::stage_row<16>(s_o + r * LDQ, nullptr, d, tid & 15, 0.f);      // fc::query_kernel's diag: its sum, then its scale
+        if ((tid & 15) == 0) s_diag[r] = 0.5f * a.sc.c * a.sc.c * s;
       }
       {
         float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         nq::tile_linear<4>(s_q, LDQ, a.proj, nullptr, d, m, wv, lr, lq, [&](int r, int row, int n, float v) { s_f[row * LDF + n] = v; best[r] = fmaxf(best[r], v); });
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-          for (int off = 1; off < 16; off <<= 1) best[r] = fmaxf(best[r], __shfl_xor(best[r], off, 64));
-          if (lr == 0) s_pm[wv][4 * lq + r] = best[r];
-        }
+        ft::rowmax_fold(best, s_pm, wv, lr, lq);
       }
       __syncthreads();
-      {
-        const int q4 = mp / 4;
-        for (int idx = tid; idx < QT * q4; idx += 256) {
-          const int row = idx / q4, j = 4 * (idx - row * q4);
-          const float sub = s_diag[row] + fmaxf(fmaxf(s_pm[0][row], s_pm[1][row]), fmaxf(s_pm[2][row], s_pm[3][row]));
-          float4 e = *reinterpret_cast<const float4*>(s_f + row * LDF + j);
-          e.x = j < m ? a.ratio * expf(e.x - sub) + a.re : 0.f; e.y = j + 1 < m ? a.ratio * expf(e.y - sub) + a.re : 0.f;
-          e.z = j + 2 < m ? a.ratio * expf(e.z - sub) + a.re : 0.f; e.w = j + 3 < m ? a.ratio * expf(e.w - sub) + a.re : 0.f;
-          *reinterpret_cast<float4*>(s_f + row * LDF + j) = e;
-        }
-      }
+      ft::features_inplace(s_f, LDF, m, mp, s_diag, s_pm, a.sc, tid);
       // head h's value rows (wave = the 16-channel tile of e) in registers
       const bool mine = 16 * wv < d;
       float bv[MAXNC / 4];
-#pragma unroll
-      for (int ks = 0; ks < MAXNC / 4; ++ks) {
-        const int np = 4 * ks + lq;
-        bv[ks] = mine && np < Nc ? a.v[(((size_t)t * Nc + np) * H + h) * d + 16 * wv + lr] : 0.f;
-      }
+      ft::load_v(bv, a.v + ((size_t)t * Nc * H + h) * d, (size_t)H * d, Nc, 16 * wv + lr, lq, mine);
       __syncthreads();
       int Mprev = 0;
       for (int pi = 0; pi < npre; ++pi) {
@@ -225,7 +205,6 @@ __global__ __launch_bounds__(256) void sweep_kernel(const Args pa) {
           // 4. S = F_q F_k^T with F_k built from dd_k for this M_k (favor_cached.h's K2 formula), np_query.h's chunk order and fold
           Mprev = Mbits;
           const float Mk = __int_as_float(Mbits);
-          const int tk = (khi + 15) / 16, nch16 = mp / 16;
           const float* krow[2]; float sub[2];
 #pragma unroll
           for (int jj = 0; jj < 2; ++jj) {
@@ -233,50 +212,8 @@ __global__ __launch_bounds__(256) void sweep_kernel(const Args pa) {
             krow[jj] = np < khi ? pa.dd + (th * Nc + np) * mp + 4 * lq : nullptr;
             sub[jj] = np < khi ? pa.diag[th * Nc + np] + Mk : 0.f;
           }
-          f32x4_t acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-          for (int ch = wv; ch < nch16; ch += 16) {
-            float4 fb[4][2];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-              for (int jj = 0; jj < 2; ++jj) {
-                const bool on = ch + 4 * u < nch16 && krow[jj] != nullptr;
-                float4 e = ld4(krow[jj] + 16 * (ch + 4 * u), on);
-                const int f = 16 * (ch + 4 * u) + 4 * lq;
-                e.x = on && f < m ? a.ratio * expf(e.x - sub[jj]) + a.re : 0.f; e.y = on && f + 1 < m ? a.ratio * expf(e.y - sub[jj]) + a.re : 0.f;
-                e.z = on && f + 2 < m ? a.ratio * expf(e.z - sub[jj]) + a.re : 0.f; e.w = on && f + 3 < m ? a.ratio * expf(e.w - sub[jj]) + a.re : 0.f;
-                fb[u][jj] = e;
-              }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              if (ch + 4 * u >= nch16) break;
-              const float4 fa = *reinterpret_cast<const float4*>(s_f + lr * LDF + 16 * (ch + 4 * u) + 4 * lq);
-#pragma unroll
-              for (int jj = 0; jj < 2; ++jj) {
-                if (jj >= tk) continue;
-                acc[jj] = mfma4(fa.x, fb[u][jj].x, acc[jj]); acc[jj] = mfma4(fa.y, fb[u][jj].y, acc[jj]);
-                acc[jj] = mfma4(fa.z, fb[u][jj].z, acc[jj]); acc[jj] = mfma4(fa.w, fb[u][jj].w, acc[jj]);
-              }
-            }
-          }
-#pragma unroll
-          for (int jj = 0; jj < 2; ++jj) *reinterpret_cast<f32x4_t*>(s_red + ((wv * 2 + jj) * 64 + lane) * 4) = acc[jj];
-          __syncthreads();
-          if (wv < 2) {
-            const int jj = wv;
-            f32x4_t s = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-              const f32x4_t vv = *reinterpret_cast<const f32x4_t*>(s_red + ((kk * 2 + jj) * 64 + lane) * 4);
-              s[0] += vv[0]; s[1] += vv[1]; s[2] += vv[2]; s[3] += vv[3];
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int np = 16 * jj + lr;
-              if (np < Nc) s_S[(4 * lq + r) * LDS_S + np] = s[r];
-            }
-          }
-          __syncthreads();
+          ft::s_tile(s_f, LDF, krow, (khi + 15) / 16, mp / 16, Nc,
+                     [&](int jj, int f, bool on, float4 b) { return on ? ft::feature4(b, sub[jj], f, m, a.sc) : make_float4(0.f, 0.f, 0.f, 0.f); }, s_red, s_S);
           if (tid < QT) {                                      // D of every prefix: the running sum over the columns, in shot order
             float s = 0.f;
             for (int np = 0; np < Nc; ++np) { s += s_S[tid * LDS_S + np]; s_Dc[tid * LDS_S + np] = s; }
@@ -285,12 +222,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(const Args pa) {
         }
         // 5. out_h = S[:, :k] V_h[:k] / D_k into prefix pi's merged tile: one chain over the 32 key slots, zeros from k on
         if (mine) {
-          f32x4_t o = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int ks = 0; ks < MAXNC / 4; ++ks) {
-            const int np = 4 * ks + lq;
-            o = mfma4(np < k ? s_S[lr * LDS_S + np] : 0.f, bv[ks], o);
-          }
+          const f32x4_t o = ft::sv_chain(s_S, bv, k, lr, lq);
 #pragma unroll
           for (int r = 0; r < 4; ++r) s_mg[(pi * QT + 4 * lq + r) * LDM + (16 * wv + lr) * H + h] = o[r] / s_Dc[(4 * lq + r) * LDS_S + k - 1];
         }
@@ -394,7 +326,7 @@ inline int np_prefix_forward(const mlhot_np_dims& d, const mlhot_np_params& p, c
     MLHOT_TRY(check_launch("np.prefix_keys"));
     pa.dd = w.dd; pa.diag = w.diag; pa.pmax = w.pmax;
     a.m = d.m_feat; a.mp = w.st.mp;
-    a.c = powf((float)d.dim_w, -0.25f); a.ratio = 1.0f / sqrtf((float)d.m_feat); a.re = a.ratio * 1e-4f;
+    a.sc = ft::Scales(d.dim_w, d.m_feat);
     ProfScope ps("np.prefix", s);
     hipLaunchKernelGGL(npx::sweep_kernel<true>, grid, dim3(256), 0, s, pa);
   } else {

@@ -56,10 +56,10 @@ constexpr int QT = 16, H = MLHOT_HEADS;
 constexpr int MAXD = 64, MAXZ = 64, MAXH = 128, MAXNC = 32, MAXM = 272;
 constexpr int LDXZ = MAXD + MAXZ + 8;      // [x | z]
 constexpr int LDQ = MAXD + 8;              // c q_h, later r
-constexpr int LDF = fc::ldf(MAXM);         // dd / F_q
+constexpr int LDF = ft::ldf(MAXM);         // dd / F_q
 constexpr int LDM = H * MAXD + 8;          // the merged tile
 constexpr int LDH = MAXH + 8;              // the decoder's hidden tiles (they lie in the dd buffer)
-constexpr int LDS_S = MAXNC + 1;
+constexpr int LDS_S = ft::LDS_S;
 static_assert(LDXZ % 32 == 8 && LDQ % 32 == 8 && LDF % 32 == 8 && LDM % 32 == 8 && LDH % 32 == 8, "row strides are 8 mod 32 dwords");
 static_assert(QT * LDF >= 2 * QT * LDH, "the hidden tiles fit the dd buffer");
 
@@ -69,7 +69,7 @@ struct Args {
   const float *wq_w[H], *wq_b[H];
   const float *wo_w, *wo_b, *r2z_w, *r2z_b, *dec_w[3], *dec_b[3];
   int T, Nq, Nc, ntile, dw, dz, dh, y, m, mp, out_act;
-  float c, ratio, re;                      // d^-1/4, m^-1/2, ratio * 1e-4
+  ft::Scales sc;
 };
 
 // acc[j] += A[16][K] (LDS; arow = this lane's row + 4 lq) x B_j[16][K]^T (global; brow[j] = this lane's row + 4 lq, nullptr: zeros)
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void query_kernel(const Args a) {
     const int d = dw, m = a.m, mp = a.mp, Nc = a.Nc;
     for (int h = 0; h < H; ++h) {
       // 1. c q_h into LDS
-      tile_linear<1>(s_xz, LDXZ, a.wq_w[h], a.wq_b[h], d, d, wv, lr, lq, [&](int, int row, int n, float v) { s_q[row * LDQ + n] = a.c * v; });
+      tile_linear<1>(s_xz, LDXZ, a.wq_w[h], a.wq_b[h], d, d, wv, lr, lq, [&](int, int row, int n, float v) { s_q[row * LDQ + n] = a.sc.c * v; });
       __syncthreads();
       // 2. diag = 0.5 |c q|^2; dd = (c q) P^T into LDS with the row maxima
       {
@@ -161,92 +161,20 @@ __global__ __launch_bounds__(256) void query_kernel(const Args a) {
       {
         float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         tile_linear<4>(s_q, LDQ, a.proj, nullptr, d, m, wv, lr, lq, [&](int r, int row, int n, float v) { s_f[row * LDF + n] = v; best[r] = fmaxf(best[r], v); });
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-          for (int off = 1; off < 16; off <<= 1) best[r] = fmaxf(best[r], __shfl_xor(best[r], off, 64));
-          if (lr == 0) s_pm[wv][4 * lq + r] = best[r];
-        }
+        ft::rowmax_fold(best, s_pm, wv, lr, lq);
       }
       __syncthreads();
       // 3. F_q = ratio exp(dd - diag - rowmax) + ratio 1e-4 in place, zeros at features >= m
-      {
-        const int q4 = mp / 4;
-        for (int idx = tid; idx < QT * q4; idx += 256) {
-          const int row = idx / q4, j = 4 * (idx - row * q4);
-          const float sub = s_diag[row] + fmaxf(fmaxf(s_pm[0][row], s_pm[1][row]), fmaxf(s_pm[2][row], s_pm[3][row]));
-          float4 e = *reinterpret_cast<const float4*>(s_f + row * LDF + j);
-          e.x = j < m ? a.ratio * expf(e.x - sub) + a.re : 0.f; e.y = j + 1 < m ? a.ratio * expf(e.y - sub) + a.re : 0.f;
-          e.z = j + 2 < m ? a.ratio * expf(e.z - sub) + a.re : 0.f; e.w = j + 3 < m ? a.ratio * expf(e.w - sub) + a.re : 0.f;
-          *reinterpret_cast<float4*>(s_f + row * LDF + j) = e;
-        }
-      }
+      ft::features_inplace(s_f, LDF, m, mp, s_diag, s_pm, a.sc, tid);
       __syncthreads();
-      // 4. S = F_q F_k^T: wave w takes the 16-feature chunks w, w + 4, .. ascending (four in flight); then the waves fold 0, 1, 2, 3
-      {
-        const int tk = (Nc + 15) / 16, nch16 = mp / 16;
-        const float* krow[2];
+      // 4. S = F_q F_k^T (favor_cached.h's chunk order and fold), D = rowsum(S)
+      const float* krow[2];
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj) krow[jj] = 16 * jj + lr < Nc ? a.fk + (((size_t)t * H + h) * Nc + 16 * jj + lr) * mp + 4 * lq : nullptr;
-        f32x4_t acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-        for (int ch = wv; ch < nch16; ch += 16) {
-          float4 fb[4][2];
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj) fb[u][jj] = ld4(krow[jj] + 16 * (ch + 4 * u), ch + 4 * u < nch16 && krow[jj] != nullptr);
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            if (ch + 4 * u >= nch16) break;
-            const float4 fa = *reinterpret_cast<const float4*>(s_f + lr * LDF + 16 * (ch + 4 * u) + 4 * lq);
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj) {
-              if (jj >= tk) continue;
-              acc[jj] = mfma4(fa.x, fb[u][jj].x, acc[jj]); acc[jj] = mfma4(fa.y, fb[u][jj].y, acc[jj]);
-              acc[jj] = mfma4(fa.z, fb[u][jj].z, acc[jj]); acc[jj] = mfma4(fa.w, fb[u][jj].w, acc[jj]);
-            }
-          }
-        }
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) *reinterpret_cast<f32x4_t*>(s_red + ((wv * 2 + jj) * 64 + lane) * 4) = acc[jj];
-      }
-      __syncthreads();
-      if (wv < 2) {
-        const int jj = wv;
-        f32x4_t s = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const f32x4_t vv = *reinterpret_cast<const f32x4_t*>(s_red + ((k * 2 + jj) * 64 + lane) * 4);
-          s[0] += vv[0]; s[1] += vv[1]; s[2] += vv[2]; s[3] += vv[3];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int np = 16 * jj + lr;
-          if (np < Nc) s_S[(4 * lq + r) * LDS_S + np] = s[r];
-        }
-      }
-      __syncthreads();
-      if (tid < QT) {
-        float s = 0.f;
-        for (int np = 0; np < Nc; ++np) s += s_S[tid * LDS_S + np];
-        s_D[tid] = s;
-      }
-      __syncthreads();
-      // 5. merged[row][e H + h] = sum_n' S[row][n'] v[(t, n', h)][e] / D[row]: wave = 16-channel tiles of e, K = 32 key slots (zeros beyond Nc)
-      for (int et = wv; et * 16 < d; et += 4) {
-        const int e = 16 * et + lr;
-        float bv[MAXNC / 4];
-#pragma unroll
-        for (int ks = 0; ks < MAXNC / 4; ++ks) { const int np = 4 * ks + lq; bv[ks] = np < Nc ? a.v[(((size_t)t * Nc + np) * H + h) * d + e] : 0.f; }
-        f32x4_t o = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < MAXNC / 4; ++ks) {
-          const int np = 4 * ks + lq;
-          o = mfma4(np < Nc ? s_S[lr * LDS_S + np] : 0.f, bv[ks], o);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s_mg[(4 * lq + r) * LDM + e * H + h] = o[r] / s_D[4 * lq + r];
-      }
+      for (int jj = 0; jj < 2; ++jj) krow[jj] = 16 * jj + lr < Nc ? a.fk + (((size_t)t * H + h) * Nc + 16 * jj + lr) * mp + 4 * lq : nullptr;
+      ft::s_tile(s_f, LDF, krow, (Nc + 15) / 16, mp / 16, Nc, ft::BPlain{}, s_red, s_S);
+      ft::s_rowsum(s_S, Nc, s_D);
+      // 5. merged[row][e H + h] = sum_n' S[row][n'] v[(t, n', h)][e] / D[row]
+      ft::sv_tiles(s_S, s_D, a.v + ((size_t)t * Nc * H + h) * d, (size_t)H * d, Nc, d, wv, lr, lq, [&](int row, int e, float o) { s_mg[row * LDM + e * H + h] = o; });
     }
     __syncthreads();
     // r = merged Wo^T + b (dim_r == dw), then z = r_to_z(r) behind x
@@ -267,7 +195,7 @@ __global__ __launch_bounds__(256) void query_kernel(const Args a) {
   });
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+using ft::aligned16;
 
 }  // namespace nq
 #endif
@@ -311,7 +239,7 @@ inline int np_query_forward(const mlhot_np_dims& d, const mlhot_np_params& p, co
   if (attn) {
     const fc::State st = fc::carve_state(d.T, MLHOT_HEADS, d.Nc, d.m_feat, const_cast<void*>(key_state));
     a.fk = st.fk; a.m = d.m_feat; a.mp = st.mp;
-    a.c = powf((float)d.dim_w, -0.25f); a.ratio = 1.0f / sqrtf((float)d.m_feat); a.re = a.ratio * 1e-4f;
+    a.sc = ft::Scales(d.dim_w, d.m_feat);
     hipLaunchKernelGGL(nq::query_kernel<true>, dim3((unsigned)(ntile * d.T)), dim3(256), 0, s, a);
   } else {
     hipLaunchKernelGGL(nq::query_kernel<false>, dim3((unsigned)(ntile * d.T)), dim3(256), 0, s, a);
