@@ -99,9 +99,29 @@ __global__ __launch_bounds__(256) void bbb_sample_multi_bwd_kernel(const BbbMult
       it.dmu[e] = dwe + dw2 + g * mu * inv * inv;
       float dsig = dwe * e1[u] + g * (inv - 0.01f * inv * inv * inv - mu * mu * inv * inv * inv);
       if (it.eps2 != nullptr) dsig += dw2 * e2[u];
-      it.drho[e] = dsig / (1.f + expf(-rho[u]));
+      it.drho[e] = bbb_drho(sg, dsig, rho[u]);
     }
   }
+}
+#else
+// The hostsim build sums the KL terms in the kernels' order (a 256-wide strided accumulation and tree per 1024-element chunk, then
+// run_reduce1's 4 x 1024 stride and 1024-wide tree over the partials): one float32 accumulator over a million terms is 1e-5 of the
+// sum off, thirty times what the table of tests/bbb_cases.py allows and what the kernels deliver.
+inline float host_tree(float* sm, int width) {
+  for (int s = width / 2; s > 0; s >>= 1)
+    for (int t = 0; t < s; ++t) sm[t] += sm[t + s];
+  return sm[0];
+}
+inline float host_reduce1_sum(const float* v, int n) {          // reduce1_block (foreach.h) with R = SumRed
+  float sm[1024];
+  for (int t = 0; t < 1024; ++t) {
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    int i = t;
+    for (; i + 3072 < n; i += 4096) { a0 += v[i]; a1 += v[i + 1024]; a2 += v[i + 2048]; a3 += v[i + 3072]; }
+    for (; i < n; i += 1024) a0 += v[i];
+    sm[t] = (a0 + a1) + (a2 + a3);
+  }
+  return host_tree(sm, 1024);
 }
 #endif
 
@@ -111,19 +131,27 @@ inline int bbb_sample_multi_fwd(const mlhot_bbb_item* items, int n_items, float*
   for (int i = 0; i < n_items; ++i) if (!items[i].w || (items[i].eps2 && !items[i].w2)) { set_error("bbb_sample_multi_fwd: null output"); return MLHOT_ERR_ARG; }
   const int blocks = m.first[m.n];
 #ifdef MLHOT_HOSTSIM
-  (void)s; (void)partial;
-  float tot = 0.f;
+  (void)s;
+  if (blocks == 0) { kl[0] = 0.f; return MLHOT_OK; }
   for (int i = 0; i < n_items; ++i) {
     const mlhot_bbb_item& it = items[i];
-    for (size_t e = 0; e < it.n; ++e) {
-      const float sg = log1pf(expf(it.rho[e]));
-      it.w[e] = it.mu[e] + it.eps[e] * sg;
-      if (it.eps2) it.w2[e] = it.mu[e] + it.eps2[e] * sg;
-      const float q = 0.1f / sg, z = it.mu[e] / sg;
-      tot += 0.5f * (2.f * logf(sg / 0.1f) - 1.f + q * q + z * z);
+    for (size_t base = 0; base < it.n; base += BBB_CHUNK) {       // one workgroup of bbb_sample_multi_kernel
+      float sm[256];
+      for (int t = 0; t < 256; ++t) {
+        float acc = 0.f;
+        for (size_t e = base + t; e < it.n && e < base + BBB_CHUNK; e += 256) {
+          const float sg = log1pf(expf(it.rho[e]));
+          it.w[e] = it.mu[e] + it.eps[e] * sg;
+          if (it.eps2) it.w2[e] = it.mu[e] + it.eps2[e] * sg;
+          const float q = 0.1f / sg, z = it.mu[e] / sg;
+          acc += 0.5f * (2.f * logf(sg / 0.1f) - 1.f + q * q + z * z);
+        }
+        sm[t] = acc;
+      }
+      partial[m.first[i] + base / BBB_CHUNK] = host_tree(sm, 256);
     }
   }
-  kl[0] = tot;
+  kl[0] = host_reduce1_sum(partial, blocks);
   return MLHOT_OK;
 #else
   if (blocks == 0) return run_foreach(FillZero{kl}, 1, s, "bbb.multi.zero");
@@ -148,7 +176,7 @@ inline int bbb_sample_multi_bwd(const mlhot_bbb_item* items, int n_items, const 
       const float sg = log1pf(expf(it.rho[e])), inv = 1.f / sg, mu = it.mu[e], g = dkl[0];
       const float dwe = it.dw ? it.dw[e] : 0.f, dw2 = (it.eps2 && it.dw2) ? it.dw2[e] : 0.f;
       it.dmu[e] = dwe + dw2 + g * mu * inv * inv;
-      it.drho[e] = (dwe * it.eps[e] + (it.eps2 ? dw2 * it.eps2[e] : 0.f) + g * (inv - 0.01f * inv * inv * inv - mu * mu * inv * inv * inv)) / (1.f + expf(-it.rho[e]));
+      it.drho[e] = bbb_drho(sg, dwe * it.eps[e] + (it.eps2 ? dw2 * it.eps2[e] : 0.f) + g * (inv - 0.01f * inv * inv * inv - mu * mu * inv * inv * inv), it.rho[e]);
     }
   }
   return MLHOT_OK;

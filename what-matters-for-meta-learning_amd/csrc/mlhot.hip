@@ -463,7 +463,12 @@ int mlhot_pool2_bwd(const float* dy, const uint8_t* amax, float* dx, int planes,
 }
 int mlhot_bbb_sample_fwd(const float* mu, const float* rho, const float* eps, float* w, float* klterm, float* kl, size_t n, void* stream) {
   MLHOT_TRY(run_foreach(BbbSample{mu, rho, eps, w, klterm}, n, (hipStream_t)stream, "bbb.sample"));
+#ifdef MLHOT_HOSTSIM
+  kl[0] = host_reduce1_sum(klterm, (int)n);       // in the kernel's order (bbb_multi.h)
+  return MLHOT_OK;
+#else
   return run_reduce1(SumRed{klterm, kl}, (int)n, (hipStream_t)stream, "bbb.kl");
+#endif
 }
 int mlhot_bbb_sample_bwd(const float* mu, const float* rho, const float* eps, const float* dw, const float* dkl, float* dmu, float* drho,
                          size_t n, void* stream) {

@@ -12,7 +12,8 @@
 //      r = sqrt(-2 log u1), th = 2 pi u2 -> x[j] = r cos th, x[j + 8] = r sin th; a tensor whose size is not a multiple of
 //      16 takes 16 MORE outputs for its last 16 elements.
 // The uniforms and the engine state are bit-identical to torch's; the normals differ from ATen's (Sleef u10 log / sincos) by the
-// last few ulp of the device's logf / sincosf.  Checked against torch itself in tests/ (1 M draws, odd sizes, state round trip).
+// last ulps of the device's logf / sincosf: the tests assert <= 6 ulp and measure 3 (tests/test_mt_stream_gpu.py: every branch of the
+// kernels below, uniforms and engine compared in bits) and 4 (tests/test_gpu_parity.py: 1.3 M draws, state round trip).
 #pragma once
 #include "common.h"
 #include "../../include/mlhot.h"

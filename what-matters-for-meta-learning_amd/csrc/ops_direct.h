@@ -103,6 +103,11 @@ struct BbbSample {
     klterm[i] = 0.5f * (2.f * logf(sg / 0.1f) - 1.f + q * q + z * z);
   }
 };
+// d rho = d sigma * sigmoid(rho).  Where expf(rho) overflows (rho > 88.72: sigma = inf) the reference's autograd has d sigma / d rho =
+// exp(rho) / (1 + exp(rho)) = inf / inf: its d rho is nan there, and so is this one (not the finite d sigma).
+MLHOT_HD float bbb_drho(float sg, float dsig, float rho) {
+  return __builtin_isinf(sg) ? __builtin_nanf("") : dsig / (1.f + expf(-rho));
+}
 struct BbbSampleBwd {   // dmu = dw + dkl * mu/sigma^2 ; drho = (dw*eps + dkl * (1/sigma - 0.01/sigma^3 - mu^2/sigma^3)) * sigmoid(rho)
   const float* mu; const float* rho; const float* eps; const float* dw; const float* dkl; float* dmu; float* drho;
   MLHOT_HD void operator()(size_t i) const {
@@ -110,7 +115,7 @@ struct BbbSampleBwd {   // dmu = dw + dkl * mu/sigma^2 ; drho = (dw*eps + dkl * 
     const float inv = 1.f / sg;
     dmu[i] = dw[i] + g * mu[i] * inv * inv;
     const float dsig = dw[i] * eps[i] + g * (inv - 0.01f * inv * inv * inv - mu[i] * mu[i] * inv * inv * inv);
-    drho[i] = dsig / (1.f + expf(-rho[i]));
+    drho[i] = bbb_drho(sg, dsig, rho[i]);
   }
 };
 
