@@ -14,14 +14,18 @@ targets, from existing entries; `predict` runs the encoder on the target images 
 (csrc/np_query.h; route "fused"), or - for dimensions that kernel does not serve - the same mathematics from linear_rows and
 favor_query (route "composed").  `predict(condition(cx, cy), qx)` equals `model(cx, cy, qx, test=True)[0]` to the kernels'
 tolerance, not to the bit.  Eval mode only; a state serves the T tasks it was conditioned on and dies with the next weight update.
+The state class and the lifecycle (entry checks, growth, absorption, the chunk loop) are mlhot/context.py's, shared with ResNetNP;
+this module supplies the vanilla family's adapter (_Vanilla).
 """
 import logging
 import numbers
 
 import torch
 
-from mlhot import lib, ragged
+from mlhot import context, lib, ragged
 from mlhot.binding import HEADS
+from mlhot.context import ContextState as VanillaContextState          # noqa: F401  one class for both families; the name stays importable
+from mlhot.context import fingerprint as _fingerprint                  # noqa: F401
 from mlhot.ops import LinearFunction, _c, _need_gpu, agg_prefixes, favor_keys, favor_prefixes_long, favor_query, linear_rows
 from networks._resnet_np import ResNetNP
 from networks._vanilla import VanillaNP
@@ -29,51 +33,39 @@ from networks._vanilla_mr import VanillaMR
 
 ROUTES = ("fused", "composed")
 _FRESH_WEIGHTS = ("Bayes-by-backprop draws fresh weights in every forward, so a cached context is not the reference's forward")
+# what serves a family (_family) at each entry point, or why nothing does
+_CACHED = {"resnet": "ResNetNP.condition / predict", "vanilla": "the vanilla family's query tail (mlhot_np_query_fwd)",
+           "fresh": _FRESH_WEIGHTS, None: "cached-context inference is not built for this class"}
+_SWEEP = {"resnet": "ResNetNP.forward_prefixes", "vanilla": "the vanilla family's prefix sweep (mlhot_np_prefix_fwd)",
+          "fresh": _FRESH_WEIGHTS, None: "the prefix sweep is not built for this class"}
 _logged = set()
 
 
-class VanillaContextState:
-    """What condition leaves for predict on a vanilla model.  `kind`: "attention" - `keys` (mlhot.ops.FavorKeyState for 8 heads) and
-    the value heads `vh` [T, Nc, 8, dim_w]; "latent" - `z` [T, dim_z], the aggregated context through r_to_z; "empty" - no context
-    shot, `z` zeros.  `owner` is the model, `fingerprint` its parameters' and buffers' versions when the state was made.  `route`
-    is the route the last predict on this state took ("fused" | "composed"; None before the first).
-
-    For extend the state also keeps `lens` (context shots per task, host ints), `capacity` (slots per task: `Nc`
-    is the capacity, what the kernels see) and the per-shot rows in slot order [T, capacity, ...]: `kh` and the zero-filled `vh`
-    (attention), `rs` - baco: rs_to_mu's output - and `lv` (latent), with `r`, the aggregate before r_to_z.
-
-    `form` "summary" (DESIGN.md 6c-4): `keys` is a fixed-size summary state (mlhot.ops.favor_absorb), `Nc` the largest of `lens`;
-    there is no capacity and there are no per-shot rows - `vh`, `kh` are None."""
-
-    def __init__(self, owner, T, Nc, fingerprint, kind, keys=None, vh=None, z=None, wq=None, lens=None, kh=None, rs=None, lv=None, r=None,
-                 form="keys"):
-        self.owner, self.T, self.Nc, self.fingerprint, self.kind = owner, T, Nc, fingerprint, kind
-        self.keys, self.vh, self.z, self.wq, self.route = keys, vh, z, wq, None
-        self.lens, self.capacity, self.form = (Nc,) * T if lens is None else tuple(lens), Nc if form == "keys" else None, form
-        self.kh, self.rs, self.lv, self.r = kh, rs, lv, r
+def _family(model):
+    """"resnet" | "vanilla": who serves the model; "fresh": a Bayes-by-backprop class of either; None: another class."""
+    if isinstance(model, ResNetNP):
+        return "fresh" if model.PREFIX_SWEEP_REFUSAL else "resnet"
+    if type(model).forward is VanillaNP.forward:
+        return "vanilla"
+    return "fresh" if isinstance(model, VanillaMR) else None
 
 
 def supports(model):
     """(bool, reason): whether condition / predict serve this model, and through what - or why not."""
-    if isinstance(model, ResNetNP):
-        if model.PREFIX_SWEEP_REFUSAL:
-            return False, _FRESH_WEIGHTS
-        return True, "ResNetNP.condition / predict"
-    if type(model).forward is VanillaNP.forward:
-        return True, "the vanilla family's query tail (mlhot_np_query_fwd)"
-    if isinstance(model, VanillaMR):
-        return False, _FRESH_WEIGHTS
-    return False, "cached-context inference is not built for this class"
+    family = _family(model)
+    return family in ("resnet", "vanilla"), _CACHED[family]
 
 
-def _fingerprint(model):
-    return tuple(p._version for p in model.parameters()) + tuple(b._version for b in model.buffers())
+def supports_sweep(model):
+    """(bool, reason): whether `sweep` serves this model, and through what - or why not."""
+    family = _family(model)
+    return family in ("resnet", "vanilla"), _SWEEP[family]
 
 
-def _refuse(model, what):
-    ok, reason = supports(model)
-    if not ok:
-        raise ValueError(f"{type(model).__name__}: mlhot.cached.{what}: {reason}")
+def _refuse(model, what, reasons=_CACHED):
+    family = _family(model)
+    if family not in ("resnet", "vanilla"):
+        raise ValueError(f"{type(model).__name__}: mlhot.cached.{what}: {reasons[family]}")
     if model.training:
         raise ValueError(f"{what} is a test-mode path: call model.eval() first")
 
@@ -93,10 +85,88 @@ def _stacked(mods):
     return (torch.cat([m.linear.weight.detach() for m in mods], dim=0), torch.cat([m.linear.bias.detach() for m in mods], dim=0))
 
 
+def _encoded_rows(model, x_ctx, labels):
+    """The per-shot stage behind the encoder: its rows x_ctx [P, dim_w], labels [P, L] -> (kh, vh) [P, 8, dim_w] for the attention
+    models, (rs, lv) [P, R] for the others (baco: rs_to_mu's and rs_to_var's outputs, rs_to_var first; else lv None)."""
+    ly = LinearFunction.apply(labels, model.transform_y.weight, model.transform_y.bias, "none")
+    rs = model.encoder_r(torch.cat([x_ctx, ly], dim=1))
+    if model.ATTENTION:
+        return (LinearFunction.apply(x_ctx, *_stacked(model._W_k), "none").view(-1, HEADS, model.dim_w),
+                LinearFunction.apply(rs, *_stacked(model._W_v), "none").view(-1, HEADS, model.dim_w))
+    if model.agg_mode == "baco":
+        lv = LinearFunction.apply(rs, model.rs_to_var.weight, model.rs_to_var.bias, "none")
+        return LinearFunction.apply(rs, model.rs_to_mu.weight, model.rs_to_mu.bias, "none"), lv
+    return rs, None
+
+
+def _shot_rows(model, imgs, labels):
+    """The per-shot part of condition for a packed list of P shots: images [P, 1, 128, 128], labels [P, L] -> _encoded_rows."""
+    return _encoded_rows(model, _encode(model, imgs), labels)
+
+
+class _Vanilla:
+    """mlhot.context's adapter for the vanilla family; `route` is what predict's caller asked for."""
+
+    def __init__(self, model, route=None):
+        self.model, self.asked, self.dims = model, route, None
+
+    finish = property(lambda self: self.model.r_to_z)
+
+    def refuse(self, what):
+        _refuse(self.model, what)
+
+    def prepare(self, *tensors):
+        _need_gpu(*tensors, *self.model.parameters())
+
+    def begin(self, launches):
+        if launches:
+            self.model._check_agg()
+        return _stacked(self.model._W_q) if self.model.ATTENTION else None
+
+    def shot_rows(self, imgs, labels):
+        return _shot_rows(self.model, imgs, labels)
+
+    def empty_z(self, device):
+        return torch.zeros(self.model.task_num, self.model.dim_z, device=device)
+
+    def route(self, state, qry_x):
+        model, route = self.model, self.asked
+        if route is not None and route not in ROUTES:
+            raise ValueError(f"predict: route must be one of {ROUTES}, got {route!r}")
+        if state.form == "summary":
+            if route == "fused":
+                raise ValueError('predict: route "fused" - mlhot_np_query_fwd reads per-shot key features; a summary state is served by '
+                                 "the composed route (linear_rows and favor_query)")
+            route = "composed"
+        _need_gpu(qry_x)
+        self.dims = model._dims(state.Nc, 1)
+        if route is None:
+            route = "fused" if lib().np_query_supported(self.dims) and (state.keys is None or state.keys.route == "cached") else "composed"
+            if route == "composed" and type(model).__name__ not in _logged:
+                _logged.add(type(model).__name__)
+                logging.getLogger(__name__).info("mlhot.cached.predict: %s's dimensions are outside mlhot_np_query_fwd's envelope; the query tail "
+                                                 "runs composed from linear_rows / favor_query", type(model).__name__)
+        state.route = route
+
+    def predict_targets(self, state, qry_x):
+        model, T, Nq = self.model, qry_x.shape[0], qry_x.shape[1]
+        x_qry = _encode(model, qry_x)
+        proj = _c(model.attn.projection_matrix) if model.ATTENTION else None
+        params = {k: _c(p.detach()) for k, p in model.named_parameters()}
+        if state.kind != "attention":
+            if state.route == "fused":
+                return lib().np_query_fwd(self.dims, params, x_qry.view(T, Nq, -1), z=state.z)
+            return composed_tail(params, x_qry, T, Nq, model.OUT_TANH, z=state.z)
+        if state.route == "fused":
+            return lib().np_query_fwd(self.dims, params, x_qry.view(T, Nq, -1), key_state=state.keys.buf, vh=state.vh, proj=proj)
+        return composed_tail(params, x_qry, T, Nq, model.OUT_TANH, keys=state.keys, vh=state.vh, proj=proj, wq=state.wq)
+
+
 def condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys"):
     """(ctx images [T, Nc, ...], ctx labels [T, Nc, L]) -> the state for predict: ResNetNP.condition for that family; for the
     vanilla family the encoder, transform_y and encoder_r, then the key / value heads and mlhot.ops.favor_keys (attention) or the
-    aggregation and r_to_z (mean / max / baco).  No new kernel; the row count is T * Nc whatever follows.
+    aggregation and r_to_z (mean / max / baco) - mlhot.context.condition with this module's per-shot stage.  No new kernel; the row
+    count is T * Nc whatever follows.
 
     `ctx_len` (T host ints, 1 .. Nslots): the images are [T, Nslots, ...] and task t's context is its first ctx_len[t] slots; the other
     slots' images and labels are never read.  `capacity` >= Nslots reserves empty slots for extend (default Nslots; an attention
@@ -112,41 +182,7 @@ def condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys"):
         if ctx_len is None and capacity is None:
             return model.condition(ctx_x, ctx_y)                  # today's call, as it always went out
         return model.condition(ctx_x, ctx_y, ctx_len=ctx_len, capacity=capacity)
-    _refuse(model, "condition")
-    T, Nc = ctx_x.shape[0], ctx_x.shape[1]
-    if T != model.task_num:
-        raise ValueError(f"condition: {T} tasks, the model was built for tasks_per_batch = {model.task_num}")
-    if form == "summary":
-        lens = ragged.summary_condition_args("condition", T, Nc, ctx_len, capacity, model.ATTENTION)
-        _need_gpu(ctx_x, ctx_y, *model.parameters())
-        with torch.no_grad():
-            model._check_agg()
-            return _absorb(model, None, ctx_x, ctx_y, lens, _stacked(model._W_q))
-    lens, capacity = ragged.condition_args("condition", T, Nc, ctx_len, capacity, model.ATTENTION)
-    _need_gpu(ctx_x, ctx_y, *model.parameters())
-    with torch.no_grad():
-        wq = _stacked(model._W_q) if model.ATTENTION else None
-        if lens is not None:
-            model._check_agg()
-            return _grow(model, None, (0,) * T, capacity, ctx_x, ctx_y, lens, wq)
-        if Nc == 0:
-            return VanillaContextState(model, T, 0, _fingerprint(model), "empty", z=torch.zeros(T, model.dim_z, device=ctx_x.device), wq=wq)
-        model._check_agg()
-        x_ctx = _encode(model, ctx_x)
-        ly = LinearFunction.apply(ctx_y.reshape(T * Nc, -1), model.transform_y.weight, model.transform_y.bias, "none")
-        rs = model.encoder_r(torch.cat([x_ctx, ly], dim=1))
-        if model.ATTENTION:
-            kh = LinearFunction.apply(x_ctx, *_stacked(model._W_k), "none").view(T, Nc, HEADS, -1)
-            vh = LinearFunction.apply(rs, *_stacked(model._W_v), "none").view(T, Nc, HEADS, -1)
-            keys = favor_keys(kh, model.attn.projection_matrix)
-            return VanillaContextState(model, T, Nc, _fingerprint(model), "attention", keys=keys, vh=vh.contiguous(), wq=wq, kh=kh.contiguous())
-        lv = None
-        if model.agg_mode == "baco":         # csrc/np_vanilla.h's order: rs_to_mu, rs_to_var, then the aggregation
-            lv = LinearFunction.apply(rs, model.rs_to_var.weight, model.rs_to_var.bias, "none").view(T, Nc, -1)
-            rs = LinearFunction.apply(rs, model.rs_to_mu.weight, model.rs_to_mu.bias, "none")
-        r = lib().agg_fwd(model.agg_mode, rs.view(T, Nc, -1), lv)[0]
-        z = LinearFunction.apply(r, model.r_to_z.weight, model.r_to_z.bias, "none")
-        return VanillaContextState(model, T, Nc, _fingerprint(model), "latent", z=z, rs=rs.view(T, Nc, -1), lv=lv, r=r)
+    return context.condition(_Vanilla(model), ctx_x, ctx_y, ctx_len, capacity, form)
 
 
 def extend(model, state, new_x, new_y, new_len=None):
@@ -156,79 +192,7 @@ def extend(model, state, new_x, new_y, new_len=None):
     state needs spare slots: condition with capacity=.  ResNetNP: model.extend."""
     if isinstance(model, ResNetNP):
         return model.extend(state, new_x, new_y, new_len=new_len)
-    _refuse(model, "extend")
-    if not isinstance(state, VanillaContextState) or state.owner is not model:
-        raise ValueError("extend: the state was not made by this model's condition()")
-    T, n = new_x.shape[0], new_x.shape[1]
-    if T != state.T or state.T != model.task_num:
-        raise ValueError(f"extend: the state holds {state.T} tasks, the new shots {T} (the key stabiliser is the maximum over the "
-                         "conditioned batch: extend serves the same tasks)")
-    if state.fingerprint != _fingerprint(model):
-        raise ValueError("extend: the state is stale - a parameter of the model changed since condition()")
-    if state.form == "summary":
-        add = ragged.summary_extend_args("extend", T, n, new_len)
-        _need_gpu(new_x, new_y, *model.parameters())
-        with torch.no_grad():
-            return _absorb(model, state, new_x, new_y, add, state.wq)
-    add = ragged.extend_args("extend", state, T, n, new_len)
-    _need_gpu(new_x, new_y, *model.parameters())
-    with torch.no_grad():
-        return _grow(model, state, state.lens, state.capacity, new_x, new_y, add, state.wq)
-
-
-def _shot_rows(model, imgs, labels):
-    """The per-shot part of condition for a packed list of P shots: images [P, 1, 128, 128], labels [P, L] -> (kh, vh) [P, 8, dim_w]
-    for the attention models, (rs, lv) [P, R] for the others (baco: rs_to_mu's and rs_to_var's outputs; else lv None)."""
-    x_ctx = _encode(model, imgs)
-    ly = LinearFunction.apply(labels, model.transform_y.weight, model.transform_y.bias, "none")
-    rs = model.encoder_r(torch.cat([x_ctx, ly], dim=1))
-    if model.ATTENTION:
-        return (LinearFunction.apply(x_ctx, *_stacked(model._W_k), "none").view(-1, HEADS, model.dim_w),
-                LinearFunction.apply(rs, *_stacked(model._W_v), "none").view(-1, HEADS, model.dim_w))
-    if model.agg_mode == "baco":
-        lv = LinearFunction.apply(rs, model.rs_to_var.weight, model.rs_to_var.bias, "none")
-        return LinearFunction.apply(rs, model.rs_to_mu.weight, model.rs_to_mu.bias, "none"), lv
-    return rs, None
-
-
-def _absorb(model, state, images, labels, add, wq):
-    """`add[t]` of the slots of images / labels [T, n, ...] into the summary state (state None: a fresh one): only those shots are
-    encoded, as a packed list, and nothing absorbed earlier is read again."""
-    T, n = model.task_num, images.shape[1]
-    plan = ragged.Plan((0,) * T, add, n, n, images.device)
-    keys = None if state is None else state.keys
-    if plan.n:
-        imgs = ragged.pack(images.reshape(T, n, model.img_channels, model.img_size[0], model.img_size[1]), plan.src)
-        new_k, new_v = _shot_rows(model, imgs, ragged.pack(labels.reshape(T, n, -1), plan.src))
-        keys = ragged.summary_absorb(keys, new_k, new_v, plan, T, n, model.attn.projection_matrix, add)
-    total = keys.lens
-    return VanillaContextState(model, T, max(total), _fingerprint(model), "attention", keys=keys, wq=wq, lens=total, form="summary")
-
-
-def _grow(model, state, lens, capacity, images, labels, add, wq):
-    """`add[t]` of the slots of images / labels [T, n, ...] behind task t's lens[t] kept rows (state None: nothing kept yet), then the
-    finishing step on the kept rows.  The valid shots travel as a packed list: a slot that is no shot is never read."""
-    T, dev = model.task_num, images.device
-    plan = ragged.Plan(lens, add, images.shape[1], capacity, dev)
-    total = plan.total
-    a_rows, b_rows = (None, None) if state is None else (state.kh, state.vh) if model.ATTENTION else (state.rs, state.lv)
-    if state is not None and a_rows is None:
-        raise ValueError("extend: the state carries no per-shot rows (it was not made by condition())")
-    if plan.n:
-        src, dst = plan.src, plan.dst
-        imgs = ragged.pack(images.reshape(T, images.shape[1], model.img_channels, model.img_size[0], model.img_size[1]), src)
-        new_a, new_b = _shot_rows(model, imgs, ragged.pack(labels.reshape(T, images.shape[1], -1), src))
-        if state is None:
-            a_rows = torch.zeros(T, capacity, *new_a.shape[1:], device=dev)
-            b_rows = torch.zeros_like(a_rows) if new_b is not None else None
-        a_rows = ragged.scatter(a_rows, dst, new_a)
-        b_rows = ragged.scatter(b_rows, dst, new_b) if new_b is not None else None
-    if model.ATTENTION:
-        keys = ragged.masked_keys(a_rows, model.attn.projection_matrix, plan)
-        return VanillaContextState(model, T, capacity, _fingerprint(model), "attention", keys=keys, vh=b_rows, wq=wq, lens=total, kh=a_rows)
-    r = ragged.gathered_aggregate(model.agg_mode, a_rows, b_rows, plan)
-    z = LinearFunction.apply(r, model.r_to_z.weight, model.r_to_z.bias, "none")
-    return VanillaContextState(model, T, capacity, _fingerprint(model), "latent", z=z, lens=total, rs=a_rows, lv=b_rows, r=r)
+    return context.extend(_Vanilla(model), state, new_x, new_y, new_len)
 
 
 def predict(model, state, qry_x, chunk=None, route=None):
@@ -240,39 +204,7 @@ def predict(model, state, qry_x, chunk=None, route=None):
         if route is not None:
             raise ValueError("predict: route= belongs to the vanilla family")
         return model.predict(state, qry_x, chunk=chunk)
-    _refuse(model, "predict")
-    if not isinstance(state, VanillaContextState) or state.owner is not model:
-        raise ValueError("predict: the state was not made by this model's condition()")
-    if qry_x.shape[0] != state.T or state.T != model.task_num:
-        raise ValueError(f"predict: the state holds {state.T} tasks, the targets {qry_x.shape[0]} (the key stabiliser is the maximum "
-                         "over the conditioned batch: predict serves the same tasks)")
-    if state.fingerprint != _fingerprint(model):
-        raise ValueError("predict: the state is stale - a parameter of the model changed since condition()")
-    Nq = qry_x.shape[1]
-    if Nq < 1:
-        raise ValueError("predict needs at least one target")
-    if chunk is not None and int(chunk) < 1:
-        raise ValueError(f"predict: chunk must be a positive number of targets, got {chunk}")
-    if route is not None and route not in ROUTES:
-        raise ValueError(f"predict: route must be one of {ROUTES}, got {route!r}")
-    if state.form == "summary":
-        if route == "fused":
-            raise ValueError('predict: route "fused" - mlhot_np_query_fwd reads per-shot key features; a summary state is served by '
-                             "the composed route (linear_rows and favor_query)")
-        route = "composed"
-    _need_gpu(qry_x)
-    dims = model._dims(state.Nc, 1)
-    if route is None:
-        route = "fused" if lib().np_query_supported(dims) and (state.keys is None or state.keys.route == "cached") else "composed"
-        if route == "composed" and type(model).__name__ not in _logged:
-            _logged.add(type(model).__name__)
-            logging.getLogger(__name__).info("mlhot.cached.predict: %s's dimensions are outside mlhot_np_query_fwd's envelope; the query tail "
-                                             "runs composed from linear_rows / favor_query", type(model).__name__)
-    state.route = route
-    step = Nq if chunk is None else min(int(chunk), Nq)
-    with torch.no_grad():
-        out = [_predict_targets(model, state, qry_x[:, i:i + step], dims, route) for i in range(0, Nq, step)]
-    return out[0] if len(out) == 1 else torch.cat(out, dim=1)
+    return context.predict(_Vanilla(model, route), state, qry_x, chunk)
 
 
 def _rows(sources, lin_w, lin_b, act):
@@ -287,66 +219,32 @@ def _rows(sources, lin_w, lin_b, act):
     return LinearFunction.apply(x, lin_w, lin_b, act)
 
 
-def composed_tail(params, x_qry, T, Nq, tanh, keys=None, vh=None, proj=None, z=None, wq=None):
+def composed_tail(params, x_qry, T, Nq, tanh, keys=None, vh=None, proj=None, z=None, wq=None, favor=None, prefixes=None):
     """The query tail from the existing row-invariant operators - the yardstick of the fused launch and the route for dimensions
     it does not serve.  params: state_dict key -> tensor; x_qry [T * Nq, dim_w]; attention: keys (FavorKeyState), vh, proj (wq: the
-    stacked _W_q weight and bias, else stacked here); otherwise z [T, dim_z].  -> mu [T, Nq, y_dim]."""
+    stacked _W_q weight and bias, else stacked here); otherwise z [T, dim_z].  -> mu [T, Nq, y_dim].
+
+    `favor` (attention): the FAVOR+ stage, query heads [T, Nq, 8, dim_w] -> merged; default favor_query on `keys`.  With `prefixes`
+    = K it answers for K context prefixes at once (favor_prefixes_long) and every Linear behind it runs once over the K * T * Nq
+    rows, x_qry wrapping every T * Nq - row-invariant, so a row has the single tail's bits.  -> mu [K, T, Nq, y_dim]."""
     def lin(sources, name, act="none"):
         return _rows(sources, params[name + ".weight"], params[name + ".bias"], act)
-    if keys is not None:
+    K = 1 if prefixes is None else prefixes
+    if keys is not None or favor is not None:
         w, b = wq if wq is not None else (torch.cat([params[f"_W_q.{i}.linear.weight"] for i in range(HEADS)]),
                                           torch.cat([params[f"_W_q.{i}.linear.bias"] for i in range(HEADS)]))
         qh = _rows([(x_qry, 1, 0)], w, b, "none").view(T, Nq, HEADS, -1)
-        merged = favor_query(qh, keys, vh, proj).view(T * Nq, -1)
+        merged = (favor_query(qh, keys, vh, proj) if favor is None else favor(qh)).view(K * T * Nq, -1)
         zq = lin([(lin([(merged, 1, 0)], "_W.linear"), 1, 0)], "r_to_z")
-        h = lin([(x_qry, 1, 0), (zq, 1, 0)], "decoder0.0", "relu")
+        h = lin([(x_qry, 1, T * Nq), (zq, 1, 0)], "decoder0.0", "relu")
     else:
-        h = lin([(x_qry, 1, 0), (z, Nq, 0)], "decoder0.0", "relu")
+        h = lin([(x_qry, 1, T * Nq), (z, Nq, 0)], "decoder0.0", "relu")
     h = lin([(h, 1, 0)], "decoder0.2", "relu")
-    return lin([(h, 1, 0)], "decoder0.4", "tanh" if tanh else "none").view(T, Nq, -1)
-
-
-def _long_tail(params, x_qry, T, Nq, tanh, favor, kh, vh, proj, wq, ks):
-    """composed_tail for the prefixes `ks` of an attention context of any length: the query heads once, `favor` (favor_prefixes_long)
-    once for all prefixes, then every Linear once over the len(ks) * T * Nq rows - row-invariant, so a row has composed_tail's bits."""
-    def lin(sources, name, act="none"):
-        return _rows(sources, params[name + ".weight"], params[name + ".bias"], act)
-    qh = _rows([(x_qry, 1, 0)], wq[0], wq[1], "none").view(T, Nq, HEADS, -1)
-    merged = favor(qh, kh, vh, proj, ks).view(len(ks) * T * Nq, -1)
-    zq = lin([(lin([(merged, 1, 0)], "_W.linear"), 1, 0)], "r_to_z")
-    h = lin([(x_qry, 1, T * Nq), (zq, 1, 0)], "decoder0.0", "relu")
-    h = lin([(h, 1, 0)], "decoder0.2", "relu")
-    return lin([(h, 1, 0)], "decoder0.4", "tanh" if tanh else "none").view(len(ks), T, Nq, -1)
-
-
-def _predict_targets(model, state, qry_x, dims, route):
-    T, Nq = qry_x.shape[0], qry_x.shape[1]
-    x_qry = _encode(model, qry_x)
-    proj = _c(model.attn.projection_matrix) if model.ATTENTION else None
-    params = {k: _c(p.detach()) for k, p in model.named_parameters()}
-    if state.kind != "attention":
-        if route == "fused":
-            return lib().np_query_fwd(dims, params, x_qry.view(T, Nq, -1), z=state.z)
-        return composed_tail(params, x_qry, T, Nq, model.OUT_TANH, z=state.z)
-    if route == "fused":
-        return lib().np_query_fwd(dims, params, x_qry.view(T, Nq, -1), key_state=state.keys.buf, vh=state.vh, proj=proj)
-    return composed_tail(params, x_qry, T, Nq, model.OUT_TANH, keys=state.keys, vh=state.vh, proj=proj, wq=state.wq)
+    mu = lin([(h, 1, 0)], "decoder0.4", "tanh" if tanh else "none")
+    return mu.view(T, Nq, -1) if prefixes is None else mu.view(K, T, Nq, -1)
 
 
 # ---- prefix sweep for the vanilla family (DESIGN.md 6b-2) ---------------------------------------------------------------------------
-def supports_sweep(model):
-    """(bool, reason): whether `sweep` serves this model, and through what - or why not."""
-    if isinstance(model, ResNetNP):
-        if model.PREFIX_SWEEP_REFUSAL:
-            return False, _FRESH_WEIGHTS
-        return True, "ResNetNP.forward_prefixes"
-    if type(model).forward is VanillaNP.forward:
-        return True, "the vanilla family's prefix sweep (mlhot_np_prefix_fwd)"
-    if isinstance(model, VanillaMR):
-        return False, _FRESH_WEIGHTS
-    return False, "the prefix sweep is not built for this class"
-
-
 def _sweep_ks(ks, Nc):
     if ks is None:
         return tuple(range(1, Nc + 1))
@@ -384,11 +282,7 @@ def sweep(model, ctx_x, ctx_y, qry_x, ks=None, route=None):
         if route is not None:
             raise ValueError("sweep: route= belongs to the vanilla family")
         return model.forward_prefixes(ctx_x, ctx_y, qry_x, ks=ks)
-    ok, reason = supports_sweep(model)
-    if not ok:
-        raise ValueError(f"{type(model).__name__}: mlhot.cached.sweep: {reason}")
-    if model.training:
-        raise ValueError("sweep is a test-mode path: call model.eval() first")
+    _refuse(model, "sweep", _SWEEP)
     T, Nc, Nq = ctx_x.shape[0], ctx_x.shape[1], qry_x.shape[1]
     if T != model.task_num or qry_x.shape[0] != T or ctx_y.shape[0] != T:
         raise ValueError(f"sweep: {T} context and {qry_x.shape[0]} target tasks, the model was built for tasks_per_batch = {model.task_num}")
@@ -425,26 +319,21 @@ def sweep(model, ctx_x, ctx_y, qry_x, ks=None, route=None):
             up = torch.tensor([k - 1 for k in ks], dtype=torch.int32).to(dev)
         shape = (-1, model.img_channels, model.img_size[0], model.img_size[1])
         x_ctx, x_qry, _ = lib().enc_vanilla_fwd(_c(ctx_x.reshape(shape).float()), _c(qry_x.reshape(shape).float()), _enc_params(model), model.dim_w)
-        ly = LinearFunction.apply(ctx_y.reshape(T * Nc, -1), model.transform_y.weight, model.transform_y.bias, "none")
-        rs = model.encoder_r(torch.cat([x_ctx, ly], dim=1))
+        a_rows, b_rows = _encoded_rows(model, x_ctx, ctx_y.reshape(T * Nc, -1))           # condition's per-shot stage
         proj = _c(model.attn.projection_matrix) if model.ATTENTION else None
         params = {k: _c(p.detach()) for k, p in model.named_parameters()}
         if model.ATTENTION:
-            kh = _c(LinearFunction.apply(x_ctx, *_stacked(model._W_k), "none").view(T, Nc, HEADS, -1))
-            vh = _c(LinearFunction.apply(rs, *_stacked(model._W_v), "none").view(T, Nc, HEADS, -1))
+            kh, vh = _c(a_rows.view(T, Nc, HEADS, -1)), _c(b_rows.view(T, Nc, HEADS, -1))
             sweep.last_attention = "prefix_long" if long_ctx else "np_prefix" if route == "fused" else "favor_keys"
             if route == "fused":
                 return lib().np_prefix_fwd(dims, params, x_qry.view(T, Nq, -1), ks, kh=kh, vh=vh, proj=proj)
             wq = _stacked(model._W_q)
             if long_ctx:
-                return _long_tail(params, x_qry, T, Nq, model.OUT_TANH, favor_prefixes_long, kh, vh, proj, wq, ks)
+                return composed_tail(params, x_qry, T, Nq, model.OUT_TANH, wq=wq, prefixes=K,
+                                     favor=lambda qh: favor_prefixes_long(qh, kh, vh, proj, ks))
             return torch.stack([composed_tail(params, x_qry, T, Nq, model.OUT_TANH, keys=favor_keys(kh, proj, lens=(k,) * T, lens_dev=up[i]), vh=vh,
                                               proj=proj, wq=wq) for i, k in enumerate(ks)])
-        lv = None
-        if model.agg_mode == "baco":
-            lv = LinearFunction.apply(rs, model.rs_to_var.weight, model.rs_to_var.bias, "none").view(T, Nc, -1)
-            rs = LinearFunction.apply(rs, model.rs_to_mu.weight, model.rs_to_mu.bias, "none")
-        r = agg_prefixes(model.agg_mode, rs.view(T, Nc, -1), lv)                          # [Nc, T, R]
+        r = agg_prefixes(model.agg_mode, a_rows.view(T, Nc, -1), None if b_rows is None else b_rows.view(T, Nc, -1))      # [Nc, T, R]
         if route == "fused":
             if up is not None:
                 r = r.index_select(0, up.long())

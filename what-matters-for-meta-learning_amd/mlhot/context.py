@@ -1,0 +1,169 @@
+"""Cached-context inference, the part both model families share: the state `condition` leaves for `predict`, and
+the lifecycle condition -> extend -> predict with its entry checks, written once.  ResNetNP.condition / extend / predict
+(networks/_resnet_np.py) and mlhot.cached.condition / extend / predict (the vanilla family) are thin callers of the functions here.
+
+What differs per family comes in as an adapter `ad`, a small object with
+    model                               the owner: task_num, ATTENTION, agg_mode, img_channels, img_size, attn.projection_matrix
+    refuse(what)                        raises, in the family's own words, for a model or a mode the path does not serve
+    prepare(*tensors)                   host work before the first launch (the gradient arena / the device check)
+    begin(launches)                     inside no_grad, before condition's launches -> what the state carries as `wq`
+    shot_rows(imgs [P, C, H, W], labels [P, L])     the per-shot stage -> (kh, vh) [P, H, d] or (rs, lv) [P, R], lv None but for baco
+    finish                              the Linear behind the aggregate (`mu` / `r_to_z`)
+    empty_z(device)                     `z` of the state without a context shot
+    route(state, qry_x)                 predict's own checks and choices, behind the shared ones
+    predict_targets(state, qry_x)       one launch sequence for the targets of one chunk -> mu [T, n, y_dim]
+This module imports nothing from networks/: both families import it."""
+import torch
+
+from mlhot import lib, ragged
+from mlhot.ops import LinearFunction, favor_keys
+
+
+class ContextState:
+    """What condition leaves for predict.  `kind`: "attention" - `keys` (mlhot.ops.FavorKeyState) and the value heads `vh`
+    [T, Nc, H, d]; "latent" - the task embedding `z` [T, dim_z], the aggregated context through the finishing Linear; "empty" - no
+    context shot (`z` zeros or None).  `owner` is the model, `fingerprint` its parameters' and buffers' versions when the state
+    was made: extend and predict refuse a state whose model has moved on.  `wq`: the stacked query-head weight and bias where the
+    family keeps them with the state (vanilla), `route` the route the last vanilla predict on this state took ("fused" |
+    "composed"; None before the first).
+
+    For extend the state also keeps `lens` (context shots per task, host ints), `capacity` (slots per task: `Nc`
+    is the capacity, what the kernels see) and the per-shot rows in slot order [T, capacity, ...]: `kh` and the zero-filled `vh`
+    (attention), `rs` - baco: the mean Linear's output - and `lv` (latent), with `r`, the aggregate before the finishing Linear.
+
+    `form` "summary" (DESIGN.md 6c-4): `keys` is a fixed-size summary state (mlhot.ops.favor_absorb), `Nc` the largest of `lens`;
+    there is no capacity and there are no per-shot rows - `vh`, `kh` are None."""
+
+    def __init__(self, owner, T, Nc, fingerprint, kind, keys=None, vh=None, z=None, lens=None, kh=None, rs=None, lv=None, r=None,
+                 form="keys", wq=None):
+        self.owner, self.T, self.Nc, self.fingerprint, self.kind = owner, T, Nc, fingerprint, kind
+        self.keys, self.vh, self.z, self.wq, self.route = keys, vh, z, wq, None
+        self.lens, self.capacity, self.form = (Nc,) * T if lens is None else tuple(lens), Nc if form == "keys" else None, form
+        self.kh, self.rs, self.lv, self.r = kh, rs, lv, r
+
+
+def fingerprint(model):
+    return tuple(p._version for p in model.parameters()) + tuple(b._version for b in model.buffers())
+
+
+def _images(model, images):
+    """[T, n, ...] -> [T, n, C, H, W]"""
+    return images.reshape(images.shape[0], images.shape[1], model.img_channels, model.img_size[0], model.img_size[1])
+
+
+def _enter(ad, what, state, rows, noun):
+    """The checks extend and predict share; `rows` [T, n, ...] are the new shots / the targets."""
+    ad.refuse(what)
+    if not isinstance(state, ContextState) or state.owner is not ad.model:
+        raise ValueError(f"{what}: the state was not made by this model's condition()")
+    if rows.shape[0] != state.T or state.T != ad.model.task_num:
+        raise ValueError(f"{what}: the state holds {state.T} tasks, the {noun} {rows.shape[0]} (the key stabiliser is the maximum over the "
+                         f"conditioned batch: {what} serves the same tasks)")
+    if state.fingerprint != fingerprint(ad.model):
+        raise ValueError(f"{what}: the state is stale - a parameter of the model changed since condition()")
+
+
+def condition(ad, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys"):
+    """(ctx images [T, Nc, ...], ctx labels [T, Nc, L]) -> ContextState: the per-shot stage, then the FAVOR+ key features
+    (attention) or the aggregation and the finishing Linear.  `ctx_len` / `capacity`: the masked path (_grow); `form="summary"`:
+    _absorb; neither: the call as it always was."""
+    model = ad.model
+    ragged.check_form("condition", form)
+    ad.refuse("condition")
+    T, Nc = ctx_x.shape[0], ctx_x.shape[1]
+    if T != model.task_num:
+        raise ValueError(f"condition: {T} tasks, the model was built for tasks_per_batch = {model.task_num}")
+    if form == "summary":
+        lens = ragged.summary_condition_args("condition", T, Nc, ctx_len, capacity, model.ATTENTION)
+    else:
+        lens, capacity = ragged.condition_args("condition", T, Nc, ctx_len, capacity, model.ATTENTION)
+    ad.prepare(ctx_x, ctx_y)
+    with torch.no_grad():
+        if form == "summary":
+            return _absorb(ad, None, ctx_x, ctx_y, lens, ad.begin(True))
+        wq = ad.begin(lens is not None or Nc > 0)
+        if lens is not None:
+            return _grow(ad, None, (0,) * T, capacity, ctx_x, ctx_y, lens, wq)
+        if Nc == 0:
+            return ContextState(model, T, 0, fingerprint(model), "empty", z=ad.empty_z(ctx_x.device), wq=wq)
+        a_rows, b_rows = ad.shot_rows(ctx_x.reshape(T * Nc, model.img_channels, model.img_size[0], model.img_size[1]), ctx_y.reshape(T * Nc, -1))
+        a_rows = a_rows.view(T, Nc, *a_rows.shape[1:])
+        b_rows = b_rows.view(T, Nc, *b_rows.shape[1:]) if b_rows is not None else None
+        if model.ATTENTION:
+            keys = favor_keys(a_rows, model.attn.projection_matrix)
+            return ContextState(model, T, Nc, fingerprint(model), "attention", keys=keys, vh=b_rows.contiguous(), wq=wq, kh=a_rows.contiguous())
+        return _latent(ad, Nc, a_rows, b_rows, lib().agg_fwd(model.agg_mode, a_rows, b_rows)[0])
+
+
+def extend(ad, state, new_x, new_y, new_len=None):
+    """(state, new ctx images [T, n, ...], their labels [T, n, L], new_len) -> a NEW state whose task t holds new_len[t] more context
+    shots (0 .. n each; default n), written behind its current ones; the old state stays valid.  Only the new shots go through the
+    per-shot stage."""
+    _enter(ad, "extend", state, new_x, "new shots")
+    T, n = new_x.shape[0], new_x.shape[1]
+    if state.form == "summary":
+        add = ragged.summary_extend_args("extend", T, n, new_len)
+    else:
+        add = ragged.extend_args("extend", state, T, n, new_len)
+    ad.prepare(new_x, new_y)
+    with torch.no_grad():
+        if state.form == "summary":
+            return _absorb(ad, state, new_x, new_y, add, state.wq)
+        return _grow(ad, state, state.lens, state.capacity, new_x, new_y, add, state.wq)
+
+
+def _absorb(ad, state, images, labels, add, wq):
+    """`add[t]` of the slots of images / labels [T, n, ...] into the summary state (state None: a fresh one): only those shots go
+    through the per-shot stage, as a packed list, and nothing absorbed earlier is read again."""
+    model = ad.model
+    T, n = model.task_num, images.shape[1]
+    plan = ragged.Plan((0,) * T, add, n, n, images.device)
+    keys = None if state is None else state.keys
+    if plan.n:
+        new_k, new_v = ad.shot_rows(ragged.pack(_images(model, images), plan.src), ragged.pack(labels.reshape(T, n, -1), plan.src))
+        keys = ragged.summary_absorb(keys, new_k, new_v, plan, T, n, model.attn.projection_matrix, add)
+    return ContextState(model, T, max(keys.lens), fingerprint(model), "attention", keys=keys, wq=wq, lens=keys.lens, form="summary")
+
+
+def _grow(ad, state, lens, capacity, images, labels, add, wq):
+    """`add[t]` of the slots of images / labels [T, n, ...] behind task t's lens[t] kept rows (state None: nothing kept yet), then the
+    finishing step on the kept rows.  The valid shots travel as a packed list: a slot that is no shot is never read."""
+    model = ad.model
+    T, n, dev = model.task_num, images.shape[1], images.device
+    plan = ragged.Plan(lens, add, n, capacity, dev)
+    a_rows, b_rows = (None, None) if state is None else (state.kh, state.vh) if model.ATTENTION else (state.rs, state.lv)
+    if state is not None and a_rows is None:
+        raise ValueError("extend: the state carries no per-shot rows (it was not made by condition())")
+    if plan.n:
+        new_a, new_b = ad.shot_rows(ragged.pack(_images(model, images), plan.src), ragged.pack(labels.reshape(T, n, -1), plan.src))
+        if state is None:
+            a_rows = torch.zeros(T, capacity, *new_a.shape[1:], device=dev)
+            b_rows = torch.zeros_like(a_rows) if new_b is not None else None
+        a_rows = ragged.scatter(a_rows, plan.dst, new_a)
+        b_rows = ragged.scatter(b_rows, plan.dst, new_b) if new_b is not None else None
+    if model.ATTENTION:
+        keys = ragged.masked_keys(a_rows, model.attn.projection_matrix, plan)
+        return ContextState(model, T, capacity, fingerprint(model), "attention", keys=keys, vh=b_rows, wq=wq, lens=plan.total, kh=a_rows)
+    return _latent(ad, capacity, a_rows, b_rows, ragged.gathered_aggregate(model.agg_mode, a_rows, b_rows, plan), plan.total)
+
+
+def _latent(ad, Nc, rs, lv, r, lens=None):
+    """The latent state behind the aggregate r [T, R] of the per-shot rows rs, lv [T, Nc, R]."""
+    z = LinearFunction.apply(r, ad.finish.weight, ad.finish.bias, "none")
+    return ContextState(ad.model, rs.shape[0], Nc, fingerprint(ad.model), "latent", z=z, lens=lens, rs=rs, lv=lv, r=r)
+
+
+def predict(ad, state, qry_x, chunk=None):
+    """(state, target images [T, Nq, ...]) -> mu [T, Nq, y_dim] for the context the state was made from, any Nq >= 1.  `chunk` bounds
+    the targets per launch sequence."""
+    _enter(ad, "predict", state, qry_x, "targets")
+    Nq = qry_x.shape[1]
+    if Nq < 1:
+        raise ValueError("predict needs at least one target")
+    if chunk is not None and int(chunk) < 1:
+        raise ValueError(f"predict: chunk must be a positive number of targets, got {chunk}")
+    ad.route(state, qry_x)
+    step = Nq if chunk is None else min(int(chunk), Nq)
+    with torch.no_grad():
+        out = [ad.predict_targets(state, qry_x[:, i:i + step]) for i in range(0, Nq, step)]
+    return out[0] if len(out) == 1 else torch.cat(out, dim=1)

@@ -9,9 +9,10 @@ from torch import nn
 
 import logging
 
-from mlhot import lib, ragged
+from mlhot import context, lib, ragged
+from mlhot.context import ContextState         # noqa: F401  one class for both families; the name stays importable from here
 from mlhot.ops import (AggFunction, FavorFunction, HeadStacksFunction, LinearFunction, StackedLinearFunction, agg_prefixes,
-                       favor_keys, favor_prefixes, favor_prefixes_long, favor_query, linear_rows)
+                       favor_prefixes, favor_prefixes_long, favor_query, linear_rows)
 from networks.ResNet import run_conv
 from networks.fast_attention import FastAttention
 from networks.models import AttnLinear, ImageEncoder, NPDecoder, _aggregate_feature_map, _mlp3, run_trunks
@@ -43,25 +44,6 @@ def _fold_linear(sources, lin, act, n_prefix):
     cols = [x[(idx // rep) % period if period else idx // rep] for x, rep, period in sources]
     x = torch.cat(cols, dim=1) if len(cols) > 1 else cols[0]
     return torch.cat([LinearFunction.apply(c, lin.weight, lin.bias, act) for c in x.chunk(n_prefix)])
-
-
-class ContextState:
-    """What ResNetNP.condition leaves for ResNetNP.predict.  `kind`: "attention" - `keys` (mlhot.ops.FavorKeyState) and the value
-    heads `vh` [T, Nc, H, 256]; "latent" - the task embedding `z` [T, 256]; "empty" - no context shot.  `owner` is the model,
-    `fingerprint` its parameters' versions when the state was made: predict refuses a state whose model has moved on.
-
-    For extend the state also keeps `lens` (context shots per task, host ints), `capacity` (slots per task: `Nc`
-    is the capacity, what the kernels see) and the per-shot rows in slot order [T, capacity, ...]: `kh` and the zero-filled `vh`
-    (attention), `rs` - baco: latent_mu's output - and `lv` (latent), with `r` [T, 256], the aggregate before `mu`.
-
-    `form` "summary" (DESIGN.md 6c-4): `keys` is a fixed-size summary state (mlhot.ops.favor_absorb), `Nc` the largest of `lens`;
-    there is no capacity and there are no per-shot rows - `vh`, `kh` are None."""
-
-    def __init__(self, owner, T, Nc, fingerprint, kind, keys=None, vh=None, z=None, lens=None, kh=None, rs=None, lv=None, r=None, form="keys"):
-        self.owner, self.T, self.Nc, self.fingerprint, self.kind = owner, T, Nc, fingerprint, kind
-        self.keys, self.vh, self.z = keys, vh, z
-        self.lens, self.capacity, self.form = (Nc,) * T if lens is None else tuple(lens), Nc if form == "keys" else None, form
-        self.kh, self.rs, self.lv, self.r = kh, rs, lv, r
 
 
 class _Stacked:
@@ -127,6 +109,30 @@ class HeadStack:
 
     def params(self):
         return [m.linear.weight for m in self.mods] + [m.linear.bias for m in self.mods]
+
+
+class _CachedContext:
+    """mlhot.context's adapter for ResNetNP: what its condition / extend / predict do differently from the vanilla family's."""
+
+    def __init__(self, model):
+        self.model, self.finish, self.refuse, self.shot_rows = model, model.mu, model._cached_refusals, model._shot_rows
+
+    def prepare(self, *tensors):
+        self.model._refresh_arena()
+
+    def begin(self, launches):
+        if self.model.ATTENTION:
+            for mods in (self.model._W_q, self.model._W_k, self.model._W_v):   # stack the heads now: re-pointing a parameter must not look like an update later
+                self.model._stack(mods).tensors()
+
+    def empty_z(self, device):
+        return None
+
+    def route(self, state, qry_x):
+        pass
+
+    def predict_targets(self, state, qry_x):
+        return self.model._predict_targets(state, qry_x.contiguous())
 
 
 class ResNetNP(nn.Module):
@@ -447,9 +453,7 @@ class ResNetNP(nn.Module):
                 x_ctx = self.img_encoder.features(fm["ctx"])
                 x_tgt = self.img_encoder.features(fm["tgt"]) if self.ATTENTION else None
             x_dec = _aggregate_feature_map(dec_map, self.decoder.aggregate).reshape(self.task_num, Nq, -1)
-            if self.TRANSFORM_Y:
-                label_train = LinearFunction.apply(label_train, self.transform_y.weight, self.transform_y.bias, "none")
-            feats = _mlp3(x_ctx, self.task_encoder, last_relu=True, side=label_train)
+            feats = self._task_features(x_ctx, label_train)
             if self.ATTENTION:
                 qh, kh, vh = self._head_projections(x_ctx, feats, x_tgt)
                 sel = ks                                                                      # merged[k - 1] for k in sel
@@ -468,14 +472,7 @@ class ResNetNP(nn.Module):
                     return self._fold_head(x_dec, sample, 1, len(ks), Nq)
                 samples, pre = (self._W(merged[k - 1]) for k in sel), self.mu
             else:
-                if self.agg_mode in ("mean", "max"):
-                    r = agg_prefixes(self.agg_mode, feats)
-                elif self.agg_mode == "baco":
-                    mu_l = LinearFunction.apply(feats, self.latent_mu.weight, self.latent_mu.bias, "none")
-                    lv = LinearFunction.apply(feats, self.latent_var.weight, self.latent_var.bias, "none")
-                    r = agg_prefixes("baco", mu_l, lv)
-                else:
-                    raise TypeError("agg_mode is not applicable for CNP, choose from ['mean', 'max', 'baco']")
+                r = agg_prefixes(self.agg_mode, *self._latent_rows(feats))
                 if fold:
                     z = _fold_linear([(_take_prefixes(r, ks).reshape(len(ks) * self.task_num, -1), 1, 0)], self.mu, "none", len(ks))
                     return self._fold_head(x_dec, z, Nq, len(ks), Nq)
@@ -484,9 +481,9 @@ class ResNetNP(nn.Module):
             out = [_mlp3(sample, self.decoder.fc_mu, last_relu=False, side=x_dec, side_first=True, pre=pre) for sample in samples]
             return torch.stack(out)
 
-    # ---- cached context: condition once, predict for any targets --------------------------------------------------
+    # ---- cached context: condition once, predict for any targets; the lifecycle itself is mlhot/context.py ---------
     def _fingerprint(self):
-        return tuple(p._version for p in self.parameters()) + tuple(b._version for b in self.buffers())
+        return context.fingerprint(self)
 
     def _cached_refusals(self, what):
         if self.PREFIX_SWEEP_REFUSAL:
@@ -507,118 +504,32 @@ class ResNetNP(nn.Module):
 
         `form="summary"` (attention models): the state is FAVOR+'s fixed-size summary of the context - any number
         of shots, `ctx_len` honoured, no `capacity`, no per-shot rows kept; extend absorbs any number of further shots."""
-        ragged.check_form("condition", form)
-        self._cached_refusals("condition")
-        T, Nc = batch_train_images.shape[0], batch_train_images.shape[1]
-        if T != self.task_num:
-            raise ValueError(f"condition: {T} tasks, the model was built for tasks_per_batch = {self.task_num}")
-        if form == "summary":
-            lens = ragged.summary_condition_args("condition", T, Nc, ctx_len, capacity, self.ATTENTION)
-            self._refresh_arena()
-            with torch.no_grad():
-                for mods in (self._W_q, self._W_k, self._W_v):
-                    self._stack(mods).tensors()
-                return self._absorb(None, batch_train_images, label_train, lens)
-        lens, capacity = ragged.condition_args("condition", T, Nc, ctx_len, capacity, self.ATTENTION)
-        self._refresh_arena()
-        with torch.no_grad():
-            if self.ATTENTION:
-                for mods in (self._W_q, self._W_k, self._W_v):       # stack the heads now: re-pointing a parameter must not look like an update later
-                    self._stack(mods).tensors()
-            if lens is not None:
-                return self._grow(None, (0,) * T, capacity, batch_train_images, label_train, lens)
-            if Nc == 0:
-                return ContextState(self, T, 0, self._fingerprint(), "empty")
-            C, H, W = self.img_channels, self.img_size[0], self.img_size[1]
-            ctx_imgs = batch_train_images.reshape(-1, C, H, W)
-            maps = run_trunks([self.img_encoder.trunk_job(ctx_imgs)])
-            x_ctx = self.img_encoder.features(maps[0]) if maps is not None else self.img_encoder(ctx_imgs)
-            if self.TRANSFORM_Y:
-                label_train = LinearFunction.apply(label_train, self.transform_y.weight, self.transform_y.bias, "none")
-            feats = _mlp3(x_ctx, self.task_encoder, last_relu=True, side=label_train)
-            if self.ATTENTION:
-                kh, vh = self._heads(x_ctx, self._W_k), self._heads(feats, self._W_v)
-                keys = favor_keys(kh, self.attn.projection_matrix)
-                return ContextState(self, T, Nc, self._fingerprint(), "attention", keys=keys, vh=vh.contiguous(), kh=kh.contiguous())
-            rs, lv = self._latent_rows(feats)
-            r, _ = AggFunction.apply(self.agg_mode, rs, lv)
-            z = LinearFunction.apply(r, self.mu.weight, self.mu.bias, "none")
-            return ContextState(self, T, Nc, self._fingerprint(), "latent", z=z, rs=rs.contiguous(), lv=lv, r=r)
+        return context.condition(_CachedContext(self), batch_train_images, label_train, ctx_len, capacity, form)
 
     def extend(self, state, new_images, new_labels, new_len=None):
         """(ContextState, new ctx images [T, n, ...], their labels, new_len) -> a NEW ContextState whose task t holds new_len[t] more
         context shots (0 .. n each; default n), written behind its current ones; the old state stays valid.  Only the new shots
         run through the trunk, the task encoder and the head projections; then the masked key launches (attention) or the prefix
         aggregate with its gather and `mu` (latent) run on the kept rows.  A state needs spare slots: condition with capacity=."""
-        self._cached_refusals("extend")
-        if not isinstance(state, ContextState) or state.owner is not self:
-            raise ValueError("extend: the state was not made by this model's condition()")
-        T, n = new_images.shape[0], new_images.shape[1]
-        if T != state.T or state.T != self.task_num:
-            raise ValueError(f"extend: the state holds {state.T} tasks, the new shots {T} (the key stabiliser is the maximum over the "
-                             "conditioned batch: extend serves the same tasks)")
-        if state.fingerprint != self._fingerprint():
-            raise ValueError("extend: the state is stale - a parameter of the model changed since condition()")
-        if state.form == "summary":
-            add = ragged.summary_extend_args("extend", T, n, new_len)
-            self._refresh_arena()
-            with torch.no_grad():
-                return self._absorb(state, new_images, new_labels, add)
-        add = ragged.extend_args("extend", state, T, n, new_len)
-        self._refresh_arena()
-        with torch.no_grad():
-            return self._grow(state, state.lens, state.capacity, new_images, new_labels, add)
+        return context.extend(_CachedContext(self), state, new_images, new_labels, new_len)
+
+    def _task_features(self, x_ctx, labels):
+        """transform_y (the *Distractor classes) and the task encoder over [x_ctx | labels], per shot."""
+        if self.TRANSFORM_Y:
+            labels = LinearFunction.apply(labels, self.transform_y.weight, self.transform_y.bias, "none")
+        return _mlp3(x_ctx, self.task_encoder, last_relu=True, side=labels)
 
     def _shot_rows(self, imgs, labels):
         """The per-shot part of condition for a packed list of P shots: images [P, C, H, W], labels [P, L] -> (kh, vh) [P, heads, 256]
         for the attention models, (rs, lv) [P, 256] for the others (baco: latent_mu's and latent_var's outputs; else lv None)."""
         maps = run_trunks([self.img_encoder.trunk_job(imgs)])
-        fmap = maps[0] if maps is not None else self.img_encoder.resnet.trunk(run_conv(self.img_encoder.conv1, imgs, relu=True), None)
-        x_ctx = _aggregate_feature_map(fmap, self.img_encoder.aggregate)
-        if self.TRANSFORM_Y:
-            labels = LinearFunction.apply(labels, self.transform_y.weight, self.transform_y.bias, "none")
-        feats = _mlp3(x_ctx, self.task_encoder, last_relu=True, side=labels)
+        enc = self.img_encoder
+        fmap = maps[0] if maps is not None else enc.resnet.trunk(run_conv(enc.conv1, imgs, relu=True), enc._taps())
+        x_ctx = _aggregate_feature_map(fmap, enc.aggregate)
+        feats = self._task_features(x_ctx, labels)
         if self.ATTENTION:
             return self._heads(x_ctx[None], self._W_k)[0], self._heads(feats[None], self._W_v)[0]
         return self._latent_rows(feats)
-
-    def _absorb(self, state, images, labels, add):
-        """`add[t]` of the slots of images / labels [T, n, ...] into the summary state (state None: a fresh one): only those shots
-        run through the trunk, the task encoder and the head projections, and nothing absorbed earlier is read again."""
-        T, n = self.task_num, images.shape[1]
-        C, H, W = self.img_channels, self.img_size[0], self.img_size[1]
-        plan = ragged.Plan((0,) * T, add, n, n, images.device)
-        keys = None if state is None else state.keys
-        if plan.n:
-            new_k, new_v = self._shot_rows(ragged.pack(images.reshape(T, n, C, H, W), plan.src), ragged.pack(labels, plan.src))
-            keys = ragged.summary_absorb(keys, new_k, new_v, plan, T, n, self.attn.projection_matrix, add)
-        return ContextState(self, T, max(keys.lens), self._fingerprint(), "attention", keys=keys, lens=keys.lens, form="summary")
-
-    def _grow(self, state, lens, capacity, images, labels, add):
-        """`add[t]` of the slots of images / labels [T, n, ...] behind task t's lens[t] kept rows (state None: nothing kept yet), then
-        the finishing step on the kept rows.  The valid shots travel as a packed list: a slot that is no shot is never read."""
-        T, dev = self.task_num, images.device
-        C, H, W = self.img_channels, self.img_size[0], self.img_size[1]
-        plan = ragged.Plan(lens, add, images.shape[1], capacity, dev)
-        total = plan.total
-        a_rows, b_rows = (state.kh, state.vh) if self.ATTENTION and state is not None else (state.rs, state.lv) if state is not None else (None, None)
-        if state is not None and a_rows is None:
-            raise ValueError("extend: the state carries no per-shot rows (it was not made by condition())")
-        if plan.n:
-            src, dst = plan.src, plan.dst
-            imgs = ragged.pack(images.reshape(T, images.shape[1], C, H, W), src)
-            new_a, new_b = self._shot_rows(imgs, ragged.pack(labels, src))
-            if state is None:
-                a_rows = torch.zeros(T, capacity, *new_a.shape[1:], device=dev)
-                b_rows = torch.zeros_like(a_rows) if new_b is not None else None
-            a_rows = ragged.scatter(a_rows, dst, new_a)
-            b_rows = ragged.scatter(b_rows, dst, new_b) if new_b is not None else None
-        if self.ATTENTION:
-            keys = ragged.masked_keys(a_rows, self.attn.projection_matrix, plan)
-            return ContextState(self, T, capacity, self._fingerprint(), "attention", keys=keys, vh=b_rows, lens=total, kh=a_rows)
-        r = ragged.gathered_aggregate(self.agg_mode, a_rows, b_rows, plan)
-        z = LinearFunction.apply(r, self.mu.weight, self.mu.bias, "none")
-        return ContextState(self, T, capacity, self._fingerprint(), "latent", z=z, lens=total, rs=a_rows, lv=b_rows, r=r)
 
     def predict(self, state, batch_test_images, chunk=None):
         """(ContextState, target images [T, Nq, ...]) -> mu [T, Nq, out] = `forward(ctx, labels, targets, test=True)[0]` for the
@@ -626,23 +537,7 @@ class ResNetNP(nn.Module):
         the query head projection, `_W`, `mu` and the decoder head go through mlhot.ops.linear_rows and the attention through
         mlhot.ops.favor_query, so nothing behind the trunks depends on how many targets share the call.  `chunk` bounds the
         targets per launch sequence.  Against forward the result agrees to the kernels' tolerance, not to the bit."""
-        self._cached_refusals("predict")
-        if not isinstance(state, ContextState) or state.owner is not self:
-            raise ValueError("predict: the state was not made by this model's condition()")
-        if batch_test_images.shape[0] != state.T or state.T != self.task_num:
-            raise ValueError(f"predict: the state holds {state.T} tasks, the targets {batch_test_images.shape[0]} (the key stabiliser "
-                             "is the maximum over the conditioned batch: predict serves the same tasks)")
-        if state.fingerprint != self._fingerprint():
-            raise ValueError("predict: the state is stale - a parameter of the model changed since condition()")
-        Nq = batch_test_images.shape[1]
-        if Nq < 1:
-            raise ValueError("predict needs at least one target")
-        if chunk is not None and int(chunk) < 1:
-            raise ValueError(f"predict: chunk must be a positive number of targets, got {chunk}")
-        if chunk is None or int(chunk) >= Nq:
-            return self._predict_targets(state, batch_test_images)
-        chunk = int(chunk)
-        return torch.cat([self._predict_targets(state, batch_test_images[:, i:i + chunk].contiguous()) for i in range(0, Nq, chunk)], dim=1)
+        return context.predict(_CachedContext(self), state, batch_test_images, chunk)
 
     def _predict_targets(self, state, batch_test_images):
         self._refresh_arena()
