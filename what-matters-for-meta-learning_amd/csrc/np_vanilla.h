@@ -17,6 +17,7 @@
 #include "cnp_spec.h"
 #include "linear_skinny.h"
 #include "favor2.h"
+#include <initializer_list>
 #include <type_traits>
 
 namespace mlhot {
@@ -105,6 +106,29 @@ struct NpRoute {
   bool bwd_B_split;     // B' as two workgroups per (task, head): query side | key / value side
   int bwd_C_wg, bwd_A_wg;   // workgroups per task of C' (the CNP backward) and A': 1, 2 or 4
 };
+// gfx950 (CDNA4): 160 KB of LDS per compute unit, and one workgroup may have all of it.  A launch that asks for more is refused by
+// hipFuncSetAttribute (tail_launch), so a family whose kernels need more is never picked.
+constexpr size_t LDS_PER_WORKGROUP = 160 * 1024;
+static_assert(LDS_PER_WORKGROUP == 163840, "gfx950: 160 KB of LDS per workgroup");
+#ifndef MLHOT_HOSTSIM
+inline bool lds_fits(std::initializer_list<size_t> launches) {
+  for (size_t bytes : launches) if (bytes > LDS_PER_WORKGROUP) return false;
+  return true;
+}
+// every launch of the attention family, forward and backward, with the kernels the bits `spec` select
+inline bool tail_lds_fits(const tf::TailDims& td, int spec) {
+  return lds_fits({(spec & TAIL_SPEC_FWD_A) ? ts::phaseA_lds_bytes() : tf::phaseA_lds_bytes(td),
+                   (spec & TAIL_SPEC_FWD_B) ? ts::phaseB_lds_bytes() : tf::phaseB_lds_bytes(td),
+                   (spec & TAIL_SPEC_FWD_C) ? ts::phaseC_lds_bytes() : tf::phaseC_lds_bytes(td),
+                   (spec & TAIL_SPEC_BWD_C) ? ts::phaseC_bwd_lds_bytes() : tf::phaseC_bwd_lds_bytes(td),
+                   (spec & TAIL_SPEC_BWD_B) ? ts::phaseB_bwd_lds_bytes() : tf::phaseB_bwd_lds_bytes(td),
+                   (spec & TAIL_SPEC_BWD_A) ? ts::phaseA_bwd_lds_bytes() : tf::phaseA_bwd_lds_bytes(td)});
+}
+inline bool cnp_lds_fits(const tf::CnpDims& cd, int spec) {
+  return lds_fits({(spec & TAIL_SPEC_FWD_A) ? ts::cnp_fwd_lds_bytes() : tf::cnp_fwd_lds_bytes(cd),
+                   (spec & TAIL_SPEC_BWD_C) ? ts::cnp_bwd_lds_bytes() : tf::cnp_bwd_lds_bytes(cd)});
+}
+#endif
 inline NpRoute np_route(const mlhot_np_dims& d) {
   NpRoute r{};
   r.bwd_C_wg = r.bwd_A_wg = 1;
@@ -113,15 +137,19 @@ inline NpRoute np_route(const mlhot_np_dims& d) {
   const bool attn = d.agg_mode == MLHOT_AGG_ATTENTION, pooled = d.agg_mode == MLHOT_AGG_MEAN || d.agg_mode == MLHOT_AGG_MAX;
   if (d.Nc > 0 && d.n_hidden == 2) r.slab = attn ? Tail::Attention : pooled ? Tail::Cnp : Tail::Generic;
   const bool one_tile = g_opt.tail_fused && d.Nc >= 1 && d.Nc <= 16 && d.Nq <= 16 && d.n_hidden == 2;   // a task's rows fit one 16-row tile
+  // One decision for both directions (they share the saved and scratch layouts): a fused family is picked only when EVERY launch of
+  // it, forward and backward, gets its LDS; otherwise the operator chain runs.
   int spec = 0;
-  if (one_tile && attn && d.dim_w % 64 == 0 && d.dim_r == d.dim_w && d.m_feat <= 4096 &&
+  if (one_tile && attn && d.dim_w % 64 == 0 && d.dim_w <= tf::KEYHEAD_MAX_DW && d.dim_r == d.dim_w && d.m_feat <= tf::KMAX_COLS &&
       (long long)d.T * d.Nc * MLHOT_HEADS < (1ll << 19)) {      // key arg-max positions are packed row * 4096 + col
-    r.family = Tail::Attention;
-    if (ts::applies(tail_dims(d))) spec = g_opt.tail_spec;
+    const tf::TailDims td = tail_dims(d);
+    const int sp = ts::applies(td) ? g_opt.tail_spec : 0;
+    if (tail_lds_fits(td, sp)) { r.family = Tail::Attention; spec = sp; }
   } else if (one_tile && pooled && d.dim_w % 16 == 0 && d.dim_r <= 128) {
-    r.family = Tail::Cnp;
-    if (ts::cnp_applies(cnp_dims(d)))
-      spec = g_opt.tail_spec & (TAIL_SPEC_FWD_A | TAIL_SPEC_BWD_C | TAIL_SPEC_ENC_FOLD | TAIL_SPEC_LOSS | TAIL_SPEC_BWD_C_WG2 | TAIL_SPEC_WG4);
+    const tf::CnpDims cd = cnp_dims(d);
+    const int sp = ts::cnp_applies(cd)
+        ? g_opt.tail_spec & (TAIL_SPEC_FWD_A | TAIL_SPEC_BWD_C | TAIL_SPEC_ENC_FOLD | TAIL_SPEC_LOSS | TAIL_SPEC_BWD_C_WG2 | TAIL_SPEC_WG4) : 0;
+    if (cnp_lds_fits(cd, sp)) { r.family = Tail::Cnp; spec = sp; }
   }
   r.fwd_A = spec & TAIL_SPEC_FWD_A; r.fwd_B = spec & TAIL_SPEC_FWD_B; r.fwd_C = spec & TAIL_SPEC_FWD_C;
   r.bwd_C = spec & TAIL_SPEC_BWD_C; r.bwd_B = spec & TAIL_SPEC_BWD_B; r.bwd_A = spec & TAIL_SPEC_BWD_A;
@@ -219,13 +247,36 @@ inline NpScratch np_scratch_carve(const mlhot_np_dims& d, const NpRoute& rt, voi
   return s;
 }
 
+// What every route needs of the dims; a refusal names the width it is about.  Which widths must be multiples of 4: dim_w (rows of
+// kh / vh / qh and of the projection matrix are read as float4 by FAVOR+, favor2.h) and dim_z (rows of d_dec_in, dim_w + dim_z wide,
+// are read as float4 by the encoder Linear's backward, enc_linear.h).  hidden[], dec_hidden and dim_r need not be: linear_skinny.h is
+// entered only with K % 4 == 0 / N % 4 == 0 and 16-byte aligned rows (lin_fwd, lin_dgrad below), and the fused tails' layer function
+// reads weights as float4 only when its K % 4 == 0 (wg_linear_t, tail_fused.h).
 inline int np_check_dims(const mlhot_np_dims& d) {
-  if (d.T <= 0 || d.Nq <= 0 || d.Nc < 0 || d.n_hidden < 1 || d.n_hidden > MLHOT_MAX_HIDDEN || d.dim_w % 4 ||
+  if (d.T <= 0 || d.Nq <= 0 || d.Nc < 0 || d.n_hidden < 1 || d.n_hidden > MLHOT_MAX_HIDDEN ||
       d.agg_mode < 0 || d.agg_mode > 3 || d.y_dim < 1 || d.y_dim > 8) {
-    set_error("np_vanilla: bad dims"); return MLHOT_ERR_ARG;
+    set_error("np_vanilla: bad dims (T %d, Nc %d, Nq %d, n_hidden %d, agg_mode %d, y_dim %d)", d.T, d.Nc, d.Nq, d.n_hidden, d.agg_mode, d.y_dim);
+    return MLHOT_ERR_ARG;
   }
+  if (d.dim_w < 4 || d.dim_w % 4) { set_error("np_vanilla: dim_w = %d must be a positive multiple of 4", d.dim_w); return MLHOT_ERR_ARG; }
+  if (d.dim_z < 4 || d.dim_z % 4) { set_error("np_vanilla: dim_z = %d must be a positive multiple of 4", d.dim_z); return MLHOT_ERR_ARG; }
+  if (d.dim_r < 1) { set_error("np_vanilla: dim_r = %d must be positive", d.dim_r); return MLHOT_ERR_ARG; }
+  if (d.dec_hidden < 1) { set_error("np_vanilla: dec_hidden = %d must be positive", d.dec_hidden); return MLHOT_ERR_ARG; }
+  if (d.label_dim < 1) { set_error("np_vanilla: label_dim = %d must be positive", d.label_dim); return MLHOT_ERR_ARG; }
+  for (int i = 0; i < d.n_hidden; ++i)
+    if (d.hidden[i] < 1) { set_error("np_vanilla: hidden[%d] = %d must be positive", i, d.hidden[i]); return MLHOT_ERR_ARG; }
   if (d.agg_mode == MLHOT_AGG_ATTENTION && (d.dim_r != d.dim_w || d.m_feat <= 0)) {
-    set_error("np_vanilla: attention needs dim_r == dim_w and m_feat > 0"); return MLHOT_ERR_ARG;
+    set_error("np_vanilla: attention needs dim_r == dim_w and m_feat > 0 (dim_r %d, dim_w %d, m_feat %d)", d.dim_r, d.dim_w, d.m_feat); return MLHOT_ERR_ARG;
+  }
+  // row counts and row * width products are ints in the launches' arguments (T * Nc, T * Nq rows; the widest row is the head stack's)
+  long long widest = (long long)d.dim_w + (d.dim_z > d.dim_w / 4 ? d.dim_z : d.dim_w / 4);
+  if (d.agg_mode == MLHOT_AGG_ATTENTION) widest = (long long)MLHOT_HEADS * d.dim_w > widest ? (long long)MLHOT_HEADS * d.dim_w : widest;
+  if (d.dim_r > widest) widest = d.dim_r;
+  if (d.dec_hidden > widest) widest = d.dec_hidden;
+  for (int i = 0; i < d.n_hidden; ++i) if (d.hidden[i] > widest) widest = d.hidden[i];
+  if (((long long)d.T * d.Nc + (long long)d.T * d.Nq) * widest >= (1ll << 31)) {
+    set_error("np_vanilla: T * (Nc + Nq) = %lld rows of up to %lld floats overflow the kernels' 32-bit indices", (long long)d.T * ((long long)d.Nc + d.Nq), widest);
+    return MLHOT_ERR_UNSUPPORTED;
   }
   return MLHOT_OK;
 }

@@ -28,6 +28,11 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4_t mfma4(float a, float b, f32x4_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 constexpr int H = 8;
+// Bounds of the run-time-shaped attention kernels that are not LDS (np_route(), np_vanilla.h, keeps every shape beyond them on the
+// operator chain): phaseA_keyhead computes kh as ONE 16-column tile per wave of its 8-wave workgroup, and the key arg-max position is
+// packed as row * 4096 + column.
+constexpr int KEYHEAD_MAX_DW = 16 * 8;
+constexpr int KMAX_COLS = 4096;
 
 // stage timestamps for latency hunting (build with -DMLHOT_TS; see scripts/tail_ts.py).  Compiled out otherwise.
 #ifdef MLHOT_TS

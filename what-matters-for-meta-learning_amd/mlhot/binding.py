@@ -512,6 +512,9 @@ class MlhotLib:
             if dims.agg_mode != AGG["attention"]:
                 out["r"], out["zt"] = take(dims.T, dims.dim_r), take(dims.T, dims.dim_z)
                 out["amax"] = take(dims.T, dims.dim_r, torch.int32)
+            else:
+                out["kh"], out["vh"], out["qh"] = take(Rc, HEADS * dw), take(Rc, HEADS * dw), take(Rq, HEADS * dw)
+                out["merged"], out["rr"] = take(Rq, HEADS * dw), take(Rq, dw)
         return out
 
     def enc_vanilla_bwd(self, img0, img1, params, dim_w, dfeat0, dfeat1, saved):
@@ -1595,22 +1598,23 @@ class MlhotLib:
                     _ptr(ws), 0 if ws is None else ws.numel(), _stream(x_qry)), "mlhot_np_prefix_fwd")
         return mu
 
-    def np_vanilla_bwd(self, dims, params, ctx_x, ctx_y, qry_x, mu, dmu, saved, scratch=None, proj=None, exchange=None, loss=None):
+    def np_vanilla_bwd(self, dims, params, ctx_x, ctx_y, qry_x, mu, dmu, saved, scratch=None, proj=None, exchange=None, loss=None, flat=True):
         """loss: None, or (kind, gt, dloss[, value]) - the loss whose gradient the call takes itself (mlhot_np_vanilla_bwd_loss): the
         gradient of mu is then dmu (may be None) + d loss / d mu * dloss; `value`: None, or the scalar tensor that receives the loss
-        VALUE from the same call (what loss_fwd would have written)."""
+        VALUE from the same call (what loss_fwd would have written).  flat = False: every gradient is a tensor of its own instead of
+        a view of one buffer in the library's flat layout (the tail's slabs then reduce segment by segment)."""
         _chk(dmu, mu)
         if loss is not None and exchange is not None:
             raise MlhotError("np_vanilla_bwd: the staged pass takes dmu, not a loss descriptor")
         # one flat gradient buffer in the library's preferred order; the per-parameter gradients are views of it
         offs = NpGrads()
         total = self.c.mlhot_np_grads_flat_layout(C.byref(dims), C.byref(offs))
-        flat = torch.empty(total, dtype=torch.float32, device=qry_x.device)
+        buf = torch.empty(total if flat else 0, dtype=torch.float32, device=qry_x.device)
         pm = vanilla_param_map(dims.n_hidden, dims.agg_mode == AGG["baco"], dims.agg_mode == AGG["attention"])
         grads = {}
         for path, key in pm:
             off = (_get(offs, path) or 0) // 4
-            grads[key] = flat[off:off + params[key].numel()].view_as(params[key])
+            grads[key] = buf[off:off + params[key].numel()].view_as(params[key]) if flat else torch.empty_like(params[key])
         sb = self.c.mlhot_np_scratch_bytes(C.byref(dims))
         if scratch is None or scratch.numel() < sb:
             scratch = self._bytes(sb, qry_x)
