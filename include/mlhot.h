@@ -270,6 +270,14 @@ int mlhot_loss_prefix_fwd(int kind, const float* mu, const float* gt, int P, int
  * mlhot_favor_query_fwd: q[T,Nq,H,d], state, v[T,Nc,H,d], proj -> out[T,Nq,d*H] in mlhot_favor_fwd's merged order, for ANY Nq >= 1
  *   in one launch, with a ROW-INVARIANCE guarantee: the bits of out[t,n,:] depend on q[t,n], state, v, proj and the dimensions -
  *   not on Nq, on n, on the grid or on the other query rows (so a caller may chunk, pad or reorder the rows freely).
+ * mlhot_favor_query_weights_fwd: mlhot_favor_query_fwd that also reads out FAVOR+'s implied attention,
+ *   w[T,H,Nq,Nc] contiguous fp32 (row length Nc), w[t,h,n,n'] = S[n,n'] / D[n] with the S = F_q F_k^T and D = rowsum(S) the launch
+ *   forms for out = S V / D: every w >= 0, sum_n' w = 1 and out[t,n,e*H+h] = sum_n' w[t,h,n,n'] v[t,n',h,e] up to rounding.  It is
+ *   FAVOR+'s own weighting - the 1e-4 floors and the state's batch-global stabiliser included - not a softmax.  Against a masked
+ *   state (mlhot_favor_keys_ragged_fwd) the columns n' >= lens[t] are exactly 0.0f.  w carries out's ROW-INVARIANCE guarantee (one
+ *   IEEE divide per element, the same at every row of a tile), and out is BIT-EQUAL to mlhot_favor_query_fwd's on the same
+ *   arguments.  Envelope, workspace (mlhot_favor_query_ws_bytes), alignment of q / state / v / proj / out and error codes are
+ *   mlhot_favor_query_fwd's; w needs 4-byte alignment only; w == NULL is MLHOT_ERR_ARG; unsupported shapes write neither out nor w.
  * Shapes: Nc <= 32, d % 16 == 0, d <= 256, 16 <= m <= 1536 (favor2.h's, on the context side), 16-byte aligned pointers; for others
  * the _bytes functions return 0 and the calls MLHOT_ERR_UNSUPPORTED, writing nothing (callers keep k and run mlhot_favor_fwd).
  * Forward only; GPU build only.  Added within ABI 7: bindings look the symbols up. */
@@ -280,6 +288,9 @@ size_t mlhot_favor_query_ws_bytes(int T, int H, int Nq, int Nc, int d, int m);
 int mlhot_favor_query_fwd(const float* q, const void* state, const float* v, const float* proj,
                           int T, int H, int Nq, int Nc, int d, int m, float* out,
                           void* ws, size_t ws_bytes, void* stream);
+int mlhot_favor_query_weights_fwd(const float* q, const void* state, const float* v, const float* proj,
+                                  int T, int H, int Nq, int Nc, int d, int m, float* out, float* w /* [T,H,Nq,Nc] */,
+                                  void* ws, size_t ws_bytes, void* stream);
 
 /* ---- cached context with per-task context sizes: the masked key state (csrc/favor_cached.h) ---------------------
  * mlhot_favor_keys_ragged_fwd: mlhot_favor_keys_fwd with lens[T] (int32, DEVICE memory, read on the device: no host synchronisation,

@@ -116,7 +116,14 @@ __global__ __launch_bounds__(256) void keys2_kernel(const Args a) { keys2_body<f
 __global__ __launch_bounds__(256) void keys2_ragged_kernel(const Args a, const int32_t* lens) { keys2_body<true>(a, lens); }
 
 // ---- query: one workgroup per (task, head, 16 query rows) -------------------------------------------------------------------
-__global__ __launch_bounds__(256) void query_kernel(const Args a) {
+// WOUT (mlhot_favor_query_weights_fwd): behind D the workgroup also stores FAVOR+'s implied attention
+// w[t][h][n][n'] = S[n][n'] / D[n] of its rows n < Nq and the columns n' < Nc - the tile's rows are one contiguous block of
+// min(16, Nq - n0) x Nc floats of w [T][H][Nq][Nc], thread i takes the floats i, i + 256: consecutive lanes, consecutive addresses
+// (a row of Nc floats has no alignment to speak of: scalar stores).  One IEEE divide per element, the same expression at every
+// row of the tile, so w has out's row invariance; a zero row of F_k (a masked slot) is an exactly zero column.  Nothing of the
+// S V chain, its fold or its division moves: out has the bits of the plain instantiation.
+template <bool WOUT>
+__device__ __forceinline__ void query_body(const Args& a, float* w) {
   __shared__ __attribute__((aligned(16))) float s_f[QT * ft::ldf(ft::MAXM)];
   __shared__ __attribute__((aligned(16))) float xs[QT * ft::LDX];
   __shared__ __attribute__((aligned(16))) float red[4 * 2 * 64 * 4];
@@ -132,12 +139,23 @@ __global__ __launch_bounds__(256) void query_kernel(const Args a) {
   for (int jj = 0; jj < 2; ++jj) krow[jj] = 16 * jj + lr < Nc ? a.fk + ((size_t)th * Nc + 16 * jj + lr) * mp + 4 * lq : nullptr;
   ft::s_tile(s_f, ft::ldf(mp), krow, (Nc + 15) / 16, mp / 16, Nc, ft::BPlain{}, red, s_S);
   ft::s_rowsum(s_S, Nc, s_D);
+  if constexpr (WOUT) {
+    float* wt = w + ((size_t)th * Nq + n0) * Nc;
+    const int lim = min(QT, Nq - n0) * Nc;
+    for (int idx = tid; idx < lim; idx += 256) {
+      const int row = idx / Nc, np = idx - row * Nc;
+      wt[idx] = s_S[row * ft::LDS_S + np] / s_D[row];
+    }
+  }
   // 5. out[t][n][e H + h] = sum_n' S[n][n'] v[(t, n', h)][e] / D[n]
   ft::sv_tiles(s_S, s_D, a.v + ((size_t)t * Nc * H + h) * d, (size_t)H * d, Nc, d, wv, lr, lq, [&](int row, int e, float o) {
     const int n = n0 + row;
     if (n < Nq) a.out[((size_t)t * Nq + n) * ((size_t)d * H) + (size_t)e * H + h] = o;
   });
 }
+
+__global__ __launch_bounds__(256) void query_kernel(const Args a) { query_body<false>(a, nullptr); }
+__global__ __launch_bounds__(256) void query_weights_kernel(const Args a, float* w) { query_body<true>(a, w); }
 
 inline Args make_args(int T, int H, int Nq, int Nc, int d, int m, const State& st) {
   Args a{};
@@ -209,27 +227,43 @@ inline int favor_keys_ragged_forward(const float* k, const float* proj, const in
   return favor_keys_launch("favor_keys_ragged_fwd", k, proj, lens, true, T, H, Nc, d, m, state, state_bytes, s);
 }
 
-inline int favor_query_forward(const float* q, const void* state, const float* v, const float* proj, int T, int H, int Nq, int Nc, int d, int m,
-                               float* out, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (T <= 0 || H <= 0 || Nq <= 0 || Nc <= 0 || d <= 0 || m <= 0 || !q || !state || !v || !proj || !out) { set_error("favor_query_fwd: bad argument"); return MLHOT_ERR_ARG; }
+// w == nullptr with weights == false: mlhot_favor_query_fwd; otherwise mlhot_favor_query_weights_fwd - the same launch with the
+// read-out instantiation, which also writes w [T][H][Nq][Nc] (4-byte aligned, as every float*)
+inline int favor_query_launch(const char* what, const float* q, const void* state, const float* v, const float* proj, int T, int H, int Nq, int Nc, int d,
+                              int m, float* out, float* w, bool weights, void* ws, size_t ws_bytes, hipStream_t s) {
+  if (T <= 0 || H <= 0 || Nq <= 0 || Nc <= 0 || d <= 0 || m <= 0 || !q || !state || !v || !proj || !out || (weights && !w)) { set_error("%s: bad argument", what); return MLHOT_ERR_ARG; }
   if (!favor_cached_ok(T, H, Nc, d, m)) {
-    set_error("favor_query_fwd serves Nc <= 32, d %% 16 == 0, d <= 256, 16 <= m <= 1536 on the GPU build (got Nc=%d d=%d m=%d)", Nc, d, m);
+    set_error("%s serves Nc <= 32, d %% 16 == 0, d <= 256, 16 <= m <= 1536 on the GPU build (got Nc=%d d=%d m=%d)", what, Nc, d, m);
     return MLHOT_ERR_UNSUPPORTED;
   }
 #ifdef MLHOT_HOSTSIM
   (void)ws; (void)ws_bytes; (void)s; return MLHOT_ERR_UNSUPPORTED;
 #else
-  if (ws == nullptr || ws_bytes < favor_query_ws_need(T, H, Nq, Nc, d, m)) { set_error("favor_query_fwd: workspace too small"); return MLHOT_ERR_WORKSPACE; }
+  if (ws == nullptr || ws_bytes < favor_query_ws_need(T, H, Nq, Nc, d, m)) { set_error("%s: workspace too small", what); return MLHOT_ERR_WORKSPACE; }
   const long long ntile = ((long long)Nq + fc::QT - 1) / fc::QT;
-  if (ntile * T * H >= (1ll << 31)) { set_error("favor_query_fwd: T H ceil(Nq / 16) must stay below 2^31 (chunk the query rows)"); return MLHOT_ERR_ARG; }
-  if (!ft::aligned16(q) || !ft::aligned16(proj) || !ft::aligned16(state)) { set_error("favor_query_fwd: q, proj and state must be 16-byte aligned"); return MLHOT_ERR_ARG; }
+  if (ntile * T * H >= (1ll << 31)) { set_error("%s: T H ceil(Nq / 16) must stay below 2^31 (chunk the query rows)", what); return MLHOT_ERR_ARG; }
+  if (!ft::aligned16(q) || !ft::aligned16(proj) || !ft::aligned16(state)) { set_error("%s: q, proj and state must be 16-byte aligned", what); return MLHOT_ERR_ARG; }
+  if (weights && (reinterpret_cast<uintptr_t>(w) & 3) != 0) { set_error("%s: w must be 4-byte aligned", what); return MLHOT_ERR_ARG; }
   const fc::State st = fc::carve_state(T, H, Nc, m, const_cast<void*>(state));
   fc::Args a = fc::make_args(T, H, Nq, Nc, d, m, st);
   a.x = q; a.proj = proj; a.v = v; a.out = out; a.ntile = (int)ntile;
-  ProfScope ps("favor.query", s);
-  hipLaunchKernelGGL(fc::query_kernel, dim3((unsigned)(ntile * T * H)), dim3(256), 0, s, a);
-  return check_launch("favor.query");
+  const char* label = weights ? "favor.queryw" : "favor.query";
+  ProfScope ps(label, s);
+  if (weights) hipLaunchKernelGGL(fc::query_weights_kernel, dim3((unsigned)(ntile * T * H)), dim3(256), 0, s, a, w);
+  else hipLaunchKernelGGL(fc::query_kernel, dim3((unsigned)(ntile * T * H)), dim3(256), 0, s, a);
+  return check_launch(label);
 #endif
+}
+
+inline int favor_query_forward(const float* q, const void* state, const float* v, const float* proj, int T, int H, int Nq, int Nc, int d, int m,
+                               float* out, void* ws, size_t ws_bytes, hipStream_t s) {
+  return favor_query_launch("favor_query_fwd", q, state, v, proj, T, H, Nq, Nc, d, m, out, nullptr, false, ws, ws_bytes, s);
+}
+
+// the same with FAVOR+'s per-shot weights w = S / D read out beside out
+inline int favor_query_weights_forward(const float* q, const void* state, const float* v, const float* proj, int T, int H, int Nq, int Nc, int d,
+                                       int m, float* out, float* w, void* ws, size_t ws_bytes, hipStream_t s) {
+  return favor_query_launch("favor_query_weights_fwd", q, state, v, proj, T, H, Nq, Nc, d, m, out, w, true, ws, ws_bytes, s);
 }
 
 }  // namespace mlhot

@@ -327,6 +327,11 @@ int mlhot_favor_query_fwd(const float* q, const void* state, const float* v, con
                           int d, int m, float* out, void* ws, size_t ws_bytes, void* stream) {
   return favor_query_forward(q, state, v, proj, T, H, Nq, Nc, d, m, out, ws, ws_bytes, (hipStream_t)stream);
 }
+// the same launch with FAVOR+'s per-shot weights w = S / D read out beside out
+int mlhot_favor_query_weights_fwd(const float* q, const void* state, const float* v, const float* proj, int T, int H, int Nq, int Nc,
+                                  int d, int m, float* out, float* w, void* ws, size_t ws_bytes, void* stream) {
+  return favor_query_weights_forward(q, state, v, proj, T, H, Nq, Nc, d, m, out, w, ws, ws_bytes, (hipStream_t)stream);
+}
 // the vanilla family's query tail against a conditioned context, one launch (csrc/np_query.h)
 int mlhot_np_query_supported(const mlhot_np_dims* d) { return d && np_query_ok(*d) ? 1 : 0; }
 int mlhot_np_query_fwd(const mlhot_np_dims* d, const mlhot_np_params* p, const float* x_qry, int Nq, const void* key_state, const float* vh,

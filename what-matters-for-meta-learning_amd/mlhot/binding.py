@@ -265,6 +265,7 @@ SIGNATURES = {
     "mlhot_favor_keys_fwd": (i, [P, P, i, i, i, i, i, P, z, P]),
     "mlhot_favor_query_ws_bytes": (z, [i] * 6),
     "mlhot_favor_query_fwd": (i, _qkvp + [P, P, z, P]),
+    "mlhot_favor_query_weights_fwd": (i, _qkvp + [P, P, P, z, P]),
     # cached context with per-task context sizes: the masked key state
     "mlhot_favor_keys_ragged_fwd": (i, [P, P, P, i, i, i, i, i, P, z, P]),
     # cached context of the vanilla family: the query tail in one launch
@@ -1079,29 +1080,47 @@ class MlhotLib:
         n = T * H * Nc * mp
         return f[:n].view(T, H, Nc, mp), f[n:n + 1]
 
-    def favor_query_fwd(self, q, state, v, proj):
-        """q [T,Nq,H,d], a mlhot_favor_keys_fwd state, v [T,Nc,H,d], proj [m,d] -> out [T,Nq,d*H] (merged order), any Nq >= 1, bits
-        per row independent of the other rows (csrc/favor_cached.h).  Forward only."""
+    def _favor_query_dims(self, what, q, state, v, proj):
+        """The checks favor_query_fwd and favor_query_weights_fwd share -> (T, H, Nq, Nc, d, m)."""
         for name, t in (("q", q), ("v", v)):
             if t.dtype != torch.float32 or t.dim() != 4:
-                raise MlhotError(f"favor_query_fwd: {name} must be fp32 [T, N, H, d], got {t.dtype} {tuple(t.shape)}")
+                raise MlhotError(f"{what}: {name} must be fp32 [T, N, H, d], got {t.dtype} {tuple(t.shape)}")
         T, Nq, H, d = q.shape
         Nc = v.shape[1]
         if tuple(v.shape) != (T, Nc, H, d) or proj.dtype != torch.float32 or proj.dim() != 2 or proj.shape[1] != d or Nq < 1:
-            raise MlhotError(f"favor_query_fwd: q {tuple(q.shape)}, v {tuple(v.shape)}, proj {tuple(proj.shape)} do not fit together")
+            raise MlhotError(f"{what}: q {tuple(q.shape)}, v {tuple(v.shape)}, proj {tuple(proj.shape)} do not fit together")
         if any(t.device != q.device for t in (state, v, proj)):
-            raise MlhotError("favor_query_fwd: q, state, v and proj must lie on one device")
+            raise MlhotError(f"{what}: q, state, v and proj must lie on one device")
         m = proj.shape[0]
         nb = self.favor_keys_bytes(T, H, Nc, d, m)
         if not nb or state.dtype != torch.uint8 or state.numel() < nb:
-            raise MlhotError(f"favor_query_fwd: the state is not mlhot_favor_keys_fwd's for T={T} H={H} Nc={Nc} d={d} m={m} "
+            raise MlhotError(f"{what}: the state is not mlhot_favor_keys_fwd's for T={T} H={H} Nc={Nc} d={d} m={m} "
                              f"({state.numel()} bytes, {nb} needed; 0 = shape not served)")
         _chk(q, v, proj, state)
+        return T, H, Nq, Nc, d, m
+
+    def favor_query_fwd(self, q, state, v, proj):
+        """q [T,Nq,H,d], a mlhot_favor_keys_fwd state, v [T,Nc,H,d], proj [m,d] -> out [T,Nq,d*H] (merged order), any Nq >= 1, bits
+        per row independent of the other rows (csrc/favor_cached.h).  Forward only."""
+        T, H, Nq, Nc, d, m = self._favor_query_dims("favor_query_fwd", q, state, v, proj)
         out = torch.empty(T, Nq, d * H, device=q.device)
         ws = self._bytes(self._fn("favor_query_fwd", "mlhot_favor_query_ws_bytes")(T, H, Nq, Nc, d, m), q)
         fn = self._fn("favor_query_fwd", "mlhot_favor_query_fwd")
         self._rc(fn(_ptr(q), _ptr(state), _ptr(v), _ptr(proj), T, H, Nq, Nc, d, m, _ptr(out), _ptr(ws), ws.numel(), _stream(q)), "mlhot_favor_query_fwd")
         return out
+
+    def favor_query_weights_fwd(self, q, state, v, proj):
+        """favor_query_fwd with FAVOR+'s per-shot weights read out: -> (out [T,Nq,d*H], w [T,H,Nq,Nc]), w = S / D of the same launch
+        (include/mlhot.h).  out has favor_query_fwd's bits; the columns of w behind a masked state's lens[t] are exact
+        zeros.  Forward only."""
+        fn = self._fn("favor_query_weights_fwd", "mlhot_favor_query_weights_fwd")
+        T, H, Nq, Nc, d, m = self._favor_query_dims("favor_query_weights_fwd", q, state, v, proj)
+        out = torch.empty(T, Nq, d * H, device=q.device)
+        w = torch.empty(T, H, Nq, Nc, device=q.device)
+        ws = self._bytes(self._fn("favor_query_weights_fwd", "mlhot_favor_query_ws_bytes")(T, H, Nq, Nc, d, m), q)
+        self._rc(fn(_ptr(q), _ptr(state), _ptr(v), _ptr(proj), T, H, Nq, Nc, d, m, _ptr(out), _ptr(w), _ptr(ws), ws.numel(), _stream(q)),
+                 "mlhot_favor_query_weights_fwd")
+        return out, w
 
     # ---- the fixed-size FAVOR+ summary state (csrc/favor_summary.h) ------------------------------
     def favor_summary_bytes(self, T, H, d, m):

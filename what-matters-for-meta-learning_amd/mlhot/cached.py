@@ -3,6 +3,8 @@
     state = mlhot.cached.condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys")     # "summary": beyond 32 shots (6c-4)
     state = mlhot.cached.extend(model, state, new_x, new_y, new_len=None)        # more context shots, only they are encoded (6c-3)
     mu = mlhot.cached.predict(model, state, qry_x, chunk=None)        # [T, Nq, y_dim]
+    mu, attn = mlhot.cached.predict(model, state, qry_x, return_attention=True)      # attn [T, 8, Nq, Nc slots]: FAVOR+'s weight per context
+                                                                                      # slot, head and target (attention models; 6c-5)
     ok, reason = mlhot.cached.supports(model)
     mu = mlhot.cached.sweep(model, ctx_x, ctx_y, qry_x, ks=None, route=None)      # [len(ks), T, Nq, y_dim]: every context prefix (6b-2)
     ok, reason = mlhot.cached.supports_sweep(model)
@@ -107,8 +109,8 @@ def _shot_rows(model, imgs, labels):
 class _Vanilla:
     """mlhot.context's adapter for the vanilla family; `route` is what predict's caller asked for."""
 
-    def __init__(self, model, route=None):
-        self.model, self.asked, self.dims = model, route, None
+    def __init__(self, model, route=None, attention=False):
+        self.model, self.asked, self.dims, self.attention = model, route, None, attention
 
     finish = property(lambda self: self.model.r_to_z)
 
@@ -133,6 +135,11 @@ class _Vanilla:
         model, route = self.model, self.asked
         if route is not None and route not in ROUTES:
             raise ValueError(f"predict: route must be one of {ROUTES}, got {route!r}")
+        if self.attention:           # the one-launch tail forms no weights to read out
+            if route == "fused":
+                raise ValueError('predict: return_attention=True with route "fused" - mlhot_np_query_fwd keeps S and D inside its one launch '
+                                 "and stays as it is; the attention read-out runs the composed route (linear_rows and favor_query)")
+            route = "composed"
         if state.form == "summary":
             if route == "fused":
                 raise ValueError('predict: route "fused" - mlhot_np_query_fwd reads per-shot key features; a summary state is served by '
@@ -148,7 +155,7 @@ class _Vanilla:
                                                  "runs composed from linear_rows / favor_query", type(model).__name__)
         state.route = route
 
-    def predict_targets(self, state, qry_x):
+    def predict_targets(self, state, qry_x, attention=False):
         model, T, Nq = self.model, qry_x.shape[0], qry_x.shape[1]
         x_qry = _encode(model, qry_x)
         proj = _c(model.attn.projection_matrix) if model.ATTENTION else None
@@ -159,7 +166,7 @@ class _Vanilla:
             return composed_tail(params, x_qry, T, Nq, model.OUT_TANH, z=state.z)
         if state.route == "fused":
             return lib().np_query_fwd(self.dims, params, x_qry.view(T, Nq, -1), key_state=state.keys.buf, vh=state.vh, proj=proj)
-        return composed_tail(params, x_qry, T, Nq, model.OUT_TANH, keys=state.keys, vh=state.vh, proj=proj, wq=state.wq)
+        return composed_tail(params, x_qry, T, Nq, model.OUT_TANH, keys=state.keys, vh=state.vh, proj=proj, wq=state.wq, weights=attention)
 
 
 def condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys"):
@@ -195,16 +202,24 @@ def extend(model, state, new_x, new_y, new_len=None):
     return context.extend(_Vanilla(model), state, new_x, new_y, new_len)
 
 
-def predict(model, state, qry_x, chunk=None, route=None):
+def predict(model, state, qry_x, chunk=None, route=None, return_attention=False):
     """(state, target images [T, Nq, ...]) -> mu [T, Nq, y_dim] = `model(ctx, labels, targets, test=True)[0]` for the context the
     state was made from, any Nq >= 1.  `chunk` bounds the targets per launch sequence (and the encoder's activations with them).
     `route`: None picks "fused" where mlhot_np_query_supported says yes and "composed" otherwise; a test may force either.  The
-    state's `route` says which one ran."""
+    state's `route` says which one ran.
+
+    `return_attention=True` -> (mu, attn): attn [T, 8, Nq, Nc slots] is FAVOR+'s weight of every context slot per
+    head and target (rows sum to 1; slots behind a task's ctx_len are exact zeros), concatenated over the chunks like mu.  The
+    vanilla family runs the composed route for it - `route=None` picks it, a forced "fused" is a ValueError - and mu is bit-equal
+    to `predict(..., route="composed")`; for a ResNetNP model mu is bit-equal to the call without the keyword.  A model without
+    attention and a summary state refuse with ValueError."""
     if isinstance(model, ResNetNP):
         if route is not None:
             raise ValueError("predict: route= belongs to the vanilla family")
+        if return_attention:
+            return model.predict(state, qry_x, chunk=chunk, return_attention=True)
         return model.predict(state, qry_x, chunk=chunk)
-    return context.predict(_Vanilla(model, route), state, qry_x, chunk)
+    return context.predict(_Vanilla(model, route, return_attention), state, qry_x, chunk, return_attention)
 
 
 def _rows(sources, lin_w, lin_b, act):
@@ -219,14 +234,16 @@ def _rows(sources, lin_w, lin_b, act):
     return LinearFunction.apply(x, lin_w, lin_b, act)
 
 
-def composed_tail(params, x_qry, T, Nq, tanh, keys=None, vh=None, proj=None, z=None, wq=None, favor=None, prefixes=None):
+def composed_tail(params, x_qry, T, Nq, tanh, keys=None, vh=None, proj=None, z=None, wq=None, favor=None, prefixes=None, weights=False):
     """The query tail from the existing row-invariant operators - the yardstick of the fused launch and the route for dimensions
     it does not serve.  params: state_dict key -> tensor; x_qry [T * Nq, dim_w]; attention: keys (FavorKeyState), vh, proj (wq: the
     stacked _W_q weight and bias, else stacked here); otherwise z [T, dim_z].  -> mu [T, Nq, y_dim].
 
     `favor` (attention): the FAVOR+ stage, query heads [T, Nq, 8, dim_w] -> merged; default favor_query on `keys`.  With `prefixes`
     = K it answers for K context prefixes at once (favor_prefixes_long) and every Linear behind it runs once over the K * T * Nq
-    rows, x_qry wrapping every T * Nq - row-invariant, so a row has the single tail's bits.  -> mu [K, T, Nq, y_dim]."""
+    rows, x_qry wrapping every T * Nq - row-invariant, so a row has the single tail's bits.  -> mu [K, T, Nq, y_dim].
+
+    `weights` (with `keys`, the default FAVOR+ stage): -> (mu, w), w [T, 8, Nq, Nc] from favor_query(weights=True); mu's bits stay."""
     def lin(sources, name, act="none"):
         return _rows(sources, params[name + ".weight"], params[name + ".bias"], act)
     K = 1 if prefixes is None else prefixes
@@ -234,14 +251,20 @@ def composed_tail(params, x_qry, T, Nq, tanh, keys=None, vh=None, proj=None, z=N
         w, b = wq if wq is not None else (torch.cat([params[f"_W_q.{i}.linear.weight"] for i in range(HEADS)]),
                                           torch.cat([params[f"_W_q.{i}.linear.bias"] for i in range(HEADS)]))
         qh = _rows([(x_qry, 1, 0)], w, b, "none").view(T, Nq, HEADS, -1)
-        merged = (favor_query(qh, keys, vh, proj) if favor is None else favor(qh)).view(K * T * Nq, -1)
+        att = None
+        if weights:
+            merged, att = favor_query(qh, keys, vh, proj, weights=True)
+            merged = merged.view(K * T * Nq, -1)
+        else:
+            merged = (favor_query(qh, keys, vh, proj) if favor is None else favor(qh)).view(K * T * Nq, -1)
         zq = lin([(lin([(merged, 1, 0)], "_W.linear"), 1, 0)], "r_to_z")
         h = lin([(x_qry, 1, T * Nq), (zq, 1, 0)], "decoder0.0", "relu")
     else:
         h = lin([(x_qry, 1, T * Nq), (z, Nq, 0)], "decoder0.0", "relu")
     h = lin([(h, 1, 0)], "decoder0.2", "relu")
     mu = lin([(h, 1, 0)], "decoder0.4", "tanh" if tanh else "none")
-    return mu.view(T, Nq, -1) if prefixes is None else mu.view(K, T, Nq, -1)
+    mu = mu.view(T, Nq, -1) if prefixes is None else mu.view(K, T, Nq, -1)
+    return (mu, att) if weights else mu
 
 
 # ---- prefix sweep for the vanilla family ---------------------------------------------------------------------------

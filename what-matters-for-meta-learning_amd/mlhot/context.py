@@ -11,7 +11,8 @@ What differs per family comes in as an adapter `ad`, a small object with
     finish                              the Linear behind the aggregate (`mu` / `r_to_z`)
     empty_z(device)                     `z` of the state without a context shot
     route(state, qry_x)                 predict's own checks and choices, behind the shared ones
-    predict_targets(state, qry_x)       one launch sequence for the targets of one chunk -> mu [T, n, y_dim]
+    predict_targets(state, qry_x)       one launch sequence for the targets of one chunk -> mu [T, n, y_dim]; called with
+                                        attention=True for predict(return_attention=True) -> (mu, attn [T, H, n, Nc])
 This module imports nothing from networks/: both families import it."""
 import torch
 
@@ -153,17 +154,37 @@ def _latent(ad, Nc, rs, lv, r, lens=None):
     return ContextState(ad.model, rs.shape[0], Nc, fingerprint(ad.model), "latent", z=z, lens=lens, rs=rs, lv=lv, r=r)
 
 
-def predict(ad, state, qry_x, chunk=None):
+def _refuse_attention(ad, state):
+    """predict(return_attention=True): what has no per-shot weights to read out.  Host checks only."""
+    if state.kind != "attention":
+        raise ValueError(f"predict: return_attention=True - {type(ad.model).__name__} (agg_mode {ad.model.agg_mode!r}) has no attention: its "
+                         f"state is {state.kind!r}, the context enters the prediction as one aggregate")
+    if state.form == "summary":
+        raise ValueError("predict: return_attention=True - a summary state keeps no per-shot rows, so there is no weight per context shot to "
+                         'read out (condition with the default form="keys" for at most 32 shots)')
+    if state.keys.route != "cached":
+        raise ValueError("predict: return_attention=True needs the cached kernels' envelope (Nc <= 32, d % 16 == 0, d <= 256, "
+                         f"16 <= m <= 1536); this state's keys are kept {state.keys.route!r} (T, Nc, H, d, m = {state.keys.dims})")
+
+
+def predict(ad, state, qry_x, chunk=None, return_attention=False):
     """(state, target images [T, Nq, ...]) -> mu [T, Nq, y_dim] for the context the state was made from, any Nq >= 1.  `chunk` bounds
-    the targets per launch sequence."""
+    the targets per launch sequence.  `return_attention`: -> (mu, attn), attn [T, H, Nq, Nc slots] FAVOR+'s weight of
+    every context slot per head and target (mlhot.ops.favor_query(weights=True)), exact zeros at the slots behind a task's ctx_len,
+    concatenated over the chunks like mu; mu has the bits of the call without it on the same route."""
     _enter(ad, "predict", state, qry_x, "targets")
     Nq = qry_x.shape[1]
     if Nq < 1:
         raise ValueError("predict needs at least one target")
     if chunk is not None and int(chunk) < 1:
         raise ValueError(f"predict: chunk must be a positive number of targets, got {chunk}")
+    if return_attention:
+        _refuse_attention(ad, state)
     ad.route(state, qry_x)
     step = Nq if chunk is None else min(int(chunk), Nq)
     with torch.no_grad():
+        if return_attention:
+            out, att = zip(*[ad.predict_targets(state, qry_x[:, i:i + step], attention=True) for i in range(0, Nq, step)])
+            return (out[0], att[0]) if len(out) == 1 else (torch.cat(out, dim=1), torch.cat(att, dim=2))
         out = [ad.predict_targets(state, qry_x[:, i:i + step]) for i in range(0, Nq, step)]
     return out[0] if len(out) == 1 else torch.cat(out, dim=1)

@@ -712,13 +712,25 @@ def favor_absorb(state, kh, vh, proj, lens=None):
     return FavorKeyState("summary", (T, max(total), H, d, m), buf=buf, lens=total)
 
 
-def favor_query(qh, state, vh, proj):
+def favor_query(qh, state, vh, proj, weights=False):
     """FAVOR+ attention of q [T, Nq, H, d] against a favor_keys state and v [T, Nc, H, d] -> merged [T, Nq, d*H], any Nq >= 1 in
     one launch.  On the "cached" route the bits of a row do not depend on the other rows of the call (csrc/favor_cached.h); the
     "plain" route is mlhot_favor_fwd on the kept keys.  Forward only.  Against a masked state (favor_keys with lens) the rows of v
     behind lens[t] must be finite - zero-fill them: their column of S is exactly 0, and 0 x NaN is not.  A "summary" state
     (favor_absorb) holds what it needs of v: `vh` may be None and is ignored; the call is row-invariant there too
-    (csrc/favor_summary.h) and refuses on the host if a task of the state has absorbed no shot."""
+    (csrc/favor_summary.h) and refuses on the host if a task of the state has absorbed no shot.
+
+    `weights=True` -> (merged, w): w [T, H, Nq, Nc] = S / D of the same launch (mlhot_favor_query_weights_fwd),
+    FAVOR+'s implied attention per head, query row and context slot - non-negative, rows summing to 1, exact zeros behind a masked
+    state's lens[t], row-invariant like merged; merged has the bits of the call without it.  "cached" states only: a "plain" or a
+    "summary" state raises MlhotError.  Without it the call launches what it always did."""
+    if weights and isinstance(state, FavorKeyState) and state.route != "cached":
+        if state.route == "summary":
+            raise MlhotError("favor_query: weights=True - a summary state keeps no per-shot rows, so there is no weight per context shot to "
+                             "read out (condition with the default form for at most 32 shots)")
+        T, Nc, H, d, m = state.dims
+        raise MlhotError(f"favor_query: weights=True needs the cached kernels' envelope (Nc <= 32, d % 16 == 0, d <= 256, 16 <= m <= 1536), "
+                         f"got Nc={Nc} d={d} m={m}: mlhot_favor_fwd on the kept keys forms no per-shot weights")
     if isinstance(state, FavorKeyState) and state.route == "summary":
         _forward_only("favor_query", qh, proj)
         T, _, H, d, m = state.dims
@@ -739,6 +751,8 @@ def favor_query(qh, state, vh, proj):
     if tuple(vh.shape) != (T, Nc, H, d) or qh.dim() != 4 or (qh.shape[0], qh.shape[2], qh.shape[3]) != (T, H, d) or tuple(proj.shape) != (m, d):
         raise MlhotError(f"favor_query: the state was built for T={T} Nc={Nc} H={H} d={d} m={m}; got q {tuple(qh.shape)}, v {tuple(vh.shape)}, proj {tuple(proj.shape)}")
     if state.route == "cached":
+        if weights:
+            return lib().favor_query_weights_fwd(qh, state.buf, vh, proj)
         return lib().favor_query_fwd(qh, state.buf, vh, proj)
     return lib().favor_fwd(qh, state.kh, vh, proj)[0]
 

@@ -131,7 +131,9 @@ class _CachedContext:
     def route(self, state, qry_x):
         pass
 
-    def predict_targets(self, state, qry_x):
+    def predict_targets(self, state, qry_x, attention=False):
+        if attention:
+            return self.model._predict_targets(state, qry_x.contiguous(), return_attention=True)
         return self.model._predict_targets(state, qry_x.contiguous())
 
 
@@ -531,15 +533,20 @@ class ResNetNP(nn.Module):
             return self._heads(x_ctx[None], self._W_k)[0], self._heads(feats[None], self._W_v)[0]
         return self._latent_rows(feats)
 
-    def predict(self, state, batch_test_images, chunk=None):
+    def predict(self, state, batch_test_images, chunk=None, return_attention=False):
         """(ContextState, target images [T, Nq, ...]) -> mu [T, Nq, out] = `forward(ctx, labels, targets, test=True)[0]` for the
         context the state was made from, any Nq >= 1.  One run_trunks call does the target (attention models) and decoder passes;
         the query head projection, `_W`, `mu` and the decoder head go through mlhot.ops.linear_rows and the attention through
         mlhot.ops.favor_query, so nothing behind the trunks depends on how many targets share the call.  `chunk` bounds the
-        targets per launch sequence.  Against forward the result agrees to the kernels' tolerance, not to the bit."""
-        return context.predict(_CachedContext(self), state, batch_test_images, chunk)
+        targets per launch sequence.  Against forward the result agrees to the kernels' tolerance, not to the bit.
 
-    def _predict_targets(self, state, batch_test_images):
+        `return_attention=True` (attention models, the default state form) -> (mu, attn): attn [T, heads, Nq, Nc
+        slots] is FAVOR+'s weight of every context slot for every head and target, read out of the same favor_query launch - rows
+        sum to 1, slots behind a task's ctx_len are exact zeros, and mu has the bits of the call without the keyword.  A model
+        without attention and a summary state refuse with ValueError."""
+        return context.predict(_CachedContext(self), state, batch_test_images, chunk, return_attention)
+
+    def _predict_targets(self, state, batch_test_images, return_attention=False):
         self._refresh_arena()
         with torch.no_grad():
             T, Nq = self.task_num, batch_test_images.shape[1]
@@ -558,10 +565,15 @@ class ResNetNP(nn.Module):
             if attend:
                 w, b = self._stack(self._W_q).tensors()
                 qh = _fold_linear([(x_tgt.reshape(T * Nq, -1), 1, 0)], _Stacked(w, b), "none", 1).view(T, Nq, self.N_HEADS, -1)
-                merged = favor_query(qh, state.keys, state.vh, self.attn.projection_matrix)
+                attn = None
+                if return_attention:
+                    merged, attn = favor_query(qh, state.keys, state.vh, self.attn.projection_matrix, weights=True)
+                else:
+                    merged = favor_query(qh, state.keys, state.vh, self.attn.projection_matrix)
                 sample = _fold_linear([(merged.reshape(T * Nq, -1), 1, 0)], self._W.linear, "none", 1)
                 sample = _fold_linear([(sample, 1, 0)], self.mu, "none", 1)
-                return self._fold_head(x_dec, sample, 1, 1, Nq)[0]
+                mu = self._fold_head(x_dec, sample, 1, 1, Nq)[0]
+                return (mu, attn) if return_attention else mu
             if state.kind == "latent":
                 return self._fold_head(x_dec, state.z, Nq, 1, Nq)[0]
             return self._fold_head(x_dec, torch.zeros(T * Nq, 256, device=batch_test_images.device), 1, 1, Nq)[0]
