@@ -180,13 +180,17 @@ typedef struct {
 } mlhot_chain_grads;
 int mlhot_mlp_chain_fwd(const float* x0, int ldx0, int M, const mlhot_chain_layer* layers, int n_layers, void* stream);
 /* dy[M][lddy]: gradient of the last layer's output; dx0 (NULL: not wanted) (+)= the gradient of x0's columns.  Two launches:
- * the data-gradient walk (also fills every g) and ONE weight + bias gradient launch for all layers.                             */
+ * the data-gradient walk (also fills every g) and ONE weight + bias gradient launch for all layers.
+ * M == 0 is a valid call of both entries (x0, side, y, g, dy may then be NULL): the forward launches nothing; the backward leaves dx0
+ * and every dside untouched and writes every dw and db as zeros (the gradient of an empty sum) - its weight-gradient launch alone. */
 int mlhot_mlp_chain_bwd(const float* x0, int ldx0, int M, const mlhot_chain_layer* layers, const mlhot_chain_grads* grads,
                         int n_layers, const float* dy, int lddy, float* dx0, int lddx0, int dx0_accumulate, void* stream);
 
 /* Up to 8 INDEPENDENT few-row Linear layers in one launch (the K / V / Q head stacks of the attention, ANP.py:80-93: one
  * Linear(256 -> 8 x 256) each over the stacked head weights): forward y = act(x w^T + b); backward dx (+)= (dy act'(y)) w,
- * dw = (dy act'(y))^T x, db.  M <= 512, K % 4 == 0, rows 16-byte aligned; the backward needs N % 4 == 0 and all of dy, dx, dw.  */
+ * dw = (dy act'(y))^T x, db.  M <= 512, K % 4 == 0, rows 16-byte aligned, ldy >= N; the backward needs N % 4 == 0, lddy >= N and all
+ * of dy, dx, dw.  A job with M == 0 is valid (its x, x2, y, dy, dx, dx2 may be NULL): the forward skips it (a table of such jobs
+ * launches nothing); the backward leaves its dx and dx2 untouched and writes its dw and db as zeros, as mlhot_linear_bwd does.  */
 typedef struct {
   const float* x; int ldx; const float* w; const float* b; float* y; int ldy; int M, K, N, act;
   const float* dy; int lddy; float* dx; int lddx, dx_accumulate; float* dw; float* db;      /* backward only */

@@ -295,13 +295,13 @@ __global__ __launch_bounds__(256) void multi_bwd_kernel(const LJobs t) {
 inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 inline int check_chain(const float* x0, int ldx0, int M, const mlhot_chain_layer* L, int n, const char* what) {
-  if (!x0 || !L || n < 1 || n > MAXL || M < 0 || M > sk::MAX_ROWS || !a16(x0) || ldx0 % 4) { set_error("%s: bad argument", what); return MLHOT_ERR_ARG; }
+  if ((!x0 && M != 0) || !L || n < 1 || n > MAXL || M < 0 || M > sk::MAX_ROWS || !a16(x0) || ldx0 % 4) { set_error("%s: bad argument", what); return MLHOT_ERR_ARG; }
   int prev = -1;
   for (int k = 0; k < n; ++k) {
     const mlhot_chain_layer& l = L[k];
     const int pw = l.K - l.side_w;
-    if (!l.w || !l.y || l.K < 4 || l.K > KMAX || l.K % 4 || l.N < 1 || l.N > NMAX || l.act < 0 || l.act > 2 || l.side_w < 0 || l.side_w % 4 || pw < 4 ||
-        pw % 4 || (l.side_w && (!l.side || !a16(l.side) || l.side_ld % 4)) || !a16(l.w) || l.ldy < l.N) {
+    if (!l.w || (!l.y && M != 0) || l.K < 4 || l.K > KMAX || l.K % 4 || l.N < 1 || l.N > NMAX || l.act < 0 || l.act > 2 || l.side_w < 0 || l.side_w % 4 || pw < 4 ||
+        pw % 4 || (l.side_w && ((!l.side && M != 0) || !a16(l.side) || l.side_ld % 4)) || !a16(l.w) || l.ldy < l.N) {
       set_error("%s: layer %d: needs 4 <= K <= %d (K, side_w %% 4 == 0), N <= %d, 16-byte aligned operands", what, k, KMAX, NMAX);
       return MLHOT_ERR_ARG;
     }
@@ -338,8 +338,7 @@ inline int chain_forward(const float* x0, int ldx0, int M, const mlhot_chain_lay
 inline int chain_backward(const float* x0, int ldx0, int M, const mlhot_chain_layer* L, const mlhot_chain_grads* G, int n, const float* dy, int lddy,
                           float* dx0, int lddx0, int dx0_acc, hipStream_t s) {
   MLHOT_TRY(check_chain(x0, ldx0, M, L, n, "mlp_chain_bwd"));
-  if (!G || !dy || lddy < L[n - 1].N) { set_error("mlp_chain_bwd: bad argument"); return MLHOT_ERR_ARG; }
-  if (M == 0) return MLHOT_OK;
+  if (!G || (!dy && M != 0) || lddy < L[n - 1].N) { set_error("mlp_chain_bwd: bad argument"); return MLHOT_ERR_ARG; }
   Args a;
   fill_args(a, x0, ldx0, M, L, n);
   a.dy = dy; a.lddy = lddy; a.dx0 = dx0; a.lddx0 = lddx0; a.dx0_acc = dx0_acc;
@@ -352,7 +351,7 @@ inline int chain_backward(const float* x0, int ldx0, int M, const mlhot_chain_la
   };
   for (int k = 0; k < n; ++k) {
     const mlhot_chain_grads& gk = G[k];
-    if (!gk.g || !gk.dw || gk.ldg < L[k].N || gk.ldg % 4 || !a16(gk.g)) { set_error("mlp_chain_bwd: layer %d: needs g (ldg %% 4 == 0, >= N) and dw", k); return MLHOT_ERR_ARG; }
+    if ((!gk.g && M != 0) || !gk.dw || gk.ldg < L[k].N || gk.ldg % 4 || !a16(gk.g)) { set_error("mlp_chain_bwd: layer %d: needs g (ldg %% 4 == 0, >= N) and dw", k); return MLHOT_ERR_ARG; }
     Layer& d = a.L[k];
     d.g = gk.g; d.ldg = gk.ldg; d.dside = gk.dside; d.dside_ld = gk.dside_ld; d.dside_acc = gk.dside_accumulate;
     // weight gradient: the previous-layer columns and the side columns of dW are two jobs (two operand tensors)
@@ -361,11 +360,13 @@ inline int chain_backward(const float* x0, int ldx0, int M, const mlhot_chain_la
     add(gk.g, gk.ldg, xin, ldin, gk.dw + d.off_prev(), d.K, gk.db, d.prev_w(), d.N);
     if (d.side_w) add(gk.g, gk.ldg, d.side, d.side_ld, gk.dw + d.off_side(), d.K, nullptr, d.side_w, d.N);
   }
-  {
+  // no rows: dx0 and the sides' gradients have nothing to write, but dw / db are the gradient of an empty sum - the weight
+  // gradient's table alone runs and writes the zeros (as sk::run_bwd does)
+  if (M > 0) {
     ProfScope ps("chain.bwd.dgrad", s);
     hipLaunchKernelGGL(chain_dgrad_kernel, dim3((M + 15) / 16), dim3(NT), 0, s, a);
   }
-  MLHOT_TRY(check_launch("mlp_chain_bwd (dgrad)"));
+  if (M > 0) MLHOT_TRY(check_launch("mlp_chain_bwd (dgrad)"));
   {
     ProfScope ps("chain.bwd.wgrad", s);
     hipLaunchKernelGGL(multi_wgrad_kernel, dim3(jobs.total), dim3(256), 0, s, jobs);
@@ -377,10 +378,11 @@ inline int check_multi(const mlhot_linear_job* J, int n, bool bwd, const char* w
   if (!J || n < 1 || n > MAXJ) { set_error("%s: 1 .. %d jobs", what, MAXJ); return MLHOT_ERR_ARG; }
   for (int i = 0; i < n; ++i) {
     const mlhot_linear_job& j = J[i];
-    bool ok = j.x && j.w && j.y && j.M >= 0 && j.M <= sk::MAX_ROWS && j.K >= 4 && j.K % 4 == 0 && j.N >= 1 && j.act >= 0 && j.act <= 2 &&
-              sk::aligned4(j.x, j.ldx) && a16(j.w);
+    const bool rows = j.M != 0;            // no rows: the row operands (x, x2, y, dy, dx, dx2) are never read or written and may be NULL
+    bool ok = (j.x || !rows) && j.w && (j.y || !rows) && j.M >= 0 && j.M <= sk::MAX_ROWS && j.K >= 4 && j.K % 4 == 0 && j.N >= 1 && j.act >= 0 && j.act <= 2 &&
+              sk::aligned4(j.x, j.ldx) && a16(j.w) && j.ldy >= j.N;
     if (j.x2) ok = ok && j.K2 >= 4 && j.K2 % 4 == 0 && j.K2 < j.K && sk::aligned4(j.x2, j.ldx2);
-    if (bwd) ok = ok && j.dy && (j.dx || (j.x2 && j.dx2)) && j.dw && j.N % 4 == 0 && sk::aligned4(j.dy, j.lddy) && (j.act == ACT_NONE || sk::aligned4(j.y, j.ldy)) &&
+    if (bwd) ok = ok && (!rows || (j.dy && (j.dx || (j.x2 && j.dx2)))) && j.dw && j.N % 4 == 0 && sk::aligned4(j.dy, j.lddy) && j.lddy >= j.N && (j.act == ACT_NONE || sk::aligned4(j.y, j.ldy)) &&
                   (!j.dx || sk::aligned4(j.dx, j.lddx)) && (!j.dx2 || sk::aligned4(j.dx2, j.lddx2));
     if (!ok) { set_error("%s: job %d: few-row Linear jobs need M <= %d, K %% 4 == 0, 16-byte aligned rows%s", what, i, sk::MAX_ROWS, bwd ? ", N % 4 == 0, dx and dw" : ""); return MLHOT_ERR_ARG; }
   }
@@ -393,7 +395,9 @@ inline void fill_jobs(LJobs& t, const mlhot_linear_job* J, int n, bool bwd) {
     LJob& j = t.j[t.n];
     j = LJob{s.x, s.w, s.b, s.y, s.dy, s.dx, s.dw, s.db, s.x2, s.dx2, s.ldx, s.ldy, s.lddy, s.lddx, s.M, s.K, s.N, s.act, s.dx_accumulate, (s.M + 31) / 32, 0,
              (s.N + 15) / 16, t.total, s.ldx2, s.lddx2, s.x2 ? s.K - s.K2 : (1 << 30)};
-    if (s.M == 0) continue;
+    // no rows: the forward skips the job; the backward keeps its weight-gradient blocks alone (nd = 0), which write dw / db as
+    // zeros - the gradient of an empty sum, as sk::run_bwd does
+    if (s.M == 0 && !bwd) continue;
     if (!bwd) t.total += j.gdx * ((s.N + 15) / 16);
     else { j.nd = j.gdx * ((s.K + 15) / 16); t.total += j.nd + j.gwx * ((s.K + 63) / 64); }
     ++t.n;

@@ -401,7 +401,7 @@ class HeadStacksFunction(torch.autograd.Function):
         ys = lib().linear_multi_fwd([(x, w, b, "none") for x, w, b in zip(x2, ws, bs)])
         ctx.n_heads, ctx.n_stacks, ctx.shapes = n_heads, n_stacks, [x.shape for x in xs]
         ctx.save_for_backward(*x2, *ws, *ys, *bs)
-        return tuple(y.view(*x.shape[:-1], n_heads, -1) for y, x in zip(ys, xs))
+        return tuple(y.view(*x.shape[:-1], n_heads, w.shape[0] // n_heads) for y, x, w in zip(ys, xs, ws))      # no -1: x may have no rows
 
     @staticmethod
     def backward(ctx, *dys):
