@@ -379,6 +379,20 @@ int mlhot_favor_summary_absorb(const float* k, const float* v, const float* proj
 size_t mlhot_favor_summary_query_ws_bytes(int T, int H, int Nq, int d, int m);
 int mlhot_favor_summary_query_fwd(const float* q, const void* state, const float* proj, int T, int H, int Nq, int d, int m,
                                   float* out, void* ws, size_t ws_bytes, void* stream);
+/* mlhot_favor_summary_merge: n summary states of the same (T, H, d, m) that were absorbed apart -> out, the state
+ *   of all their shots.  states: n device pointers in HOST memory, 1 <= n <= 8 (callers fold more in groups); m_floor: ONE float in
+ *   DEVICE memory or NULL - "the stabiliser is at least this".  All fp32:  M' = max(M_0 .. M_{n-1}, *m_floor);  s_i = 1.0f exactly
+ *   where M_i == M' (also when both are -inf), else expf(M_i - M') - 0 for a fresh state against a finite M';  A' = sum_i s_i A_i and
+ *   a' likewise, ONE chain per element in the order i = 0, 1, .. (a function of n alone; no atomics);  vs' = sum_i vs_i and
+ *   cnt' = sum_i cnt_i (int32) in the same order.  Features >= m come out as exact zeros and EVERY float of out is written (M's
+ *   block and cnt's padding as mlhot_favor_summary_init leaves them), whatever out held.  The inputs are only read.  out must be a
+ *   buffer of its own: one that overlaps an input is MLHOT_ERR_ARG.  state_bytes must equal mlhot_favor_summary_bytes(T, H, d, m)
+ *   (else MLHOT_ERR_WORKSPACE).  One launch; equal to absorbing all the shots into one state in exact arithmetic, one stabiliser
+ *   for the whole (fast_attention.py:96-97).  Outside the shapes above or 1 .. 8 states: MLHOT_ERR_UNSUPPORTED.  Whatever is
+ *   refused writes nothing.  GPU build only.  Added within ABI 7: bindings look the symbol up. */
+int mlhot_favor_summary_merge(const void* const* states /* host array of n device pointers */, int n,
+                              const float* m_floor /* one float, DEVICE memory, may be NULL */,
+                              int T, int H, int d, int m, void* out, size_t state_bytes, void* stream);
 
 /* ---- prefix sweep beyond 32 context shots: chunked running FAVOR+ prefixes (csrc/favor_prefix_long.h) -------------
  * mlhot_favor_prefix_long_fwd: q[T,Nq,H,d], k, v[T,Nc,H,d], proj[m,d] -> out[K,T,Nq,d*H] in mlhot_favor_fwd's merged order; out[i]

@@ -21,6 +21,8 @@
 //             [16 x mp] [mp x d] against A streamed from memory: wave w takes the 16-feature chunks w, w + 4, .. in ascending order
 //             for all d columns, the four partial tiles fold 0, 1, 2, 3 through LDS (F_q's space, dead by then); the row sums of
 //             F_q and of F_q a give the eps terms and the denominator.
+//   merge  grid (512 float4 slots of the state), ONE launch: n <= 8 states absorbed apart -> one, X' = sum_i exp(M_i - M') X_i
+//             (fsum::merge_kernel below)
 // No atomics; every sum has one order that depends on the dimensions alone.  ROW INVARIANCE of the query launch as in
 // favor_cached.h: a workgroup owns 16 rows and every feature of them, rows >= Nq are zeros and never stored, and every per-row sum
 // is laid out the same way at every row of a tile.
@@ -204,6 +206,81 @@ __global__ __launch_bounds__(256) void query_kernel(const QueryArgs a) {
   }
 }
 
+// ---- merge: n states that were absorbed apart -> the state of all their shots ---------------------------------------
+// The state is a sum over shots, so with M' = max_i M_i (and the caller's floor) it is  X' = sum_i exp(M_i - M') X_i  for A and a and
+// the plain sums for vs and cnt.  ONE launch, a stream: every region of the layout starts at a multiple of 4 floats (mp and d are
+// multiples of 16), so the whole state is one list of float4 slots and a lane owns MERGE_U of them, one grid stride apart; region, task,
+// head and feature row come from the flat slot index (pool_ingest.h's pool1_gather_kernel).  A lane issues its MERGE_U * N loads,
+// then folds the states 0, 1, .. N - 1 in ONE chain per element: no atomics, no split, the order a function of N alone.  Every
+// workgroup reads the N old stabilisers itself - out is none of the inputs (the entry refuses it), so nobody reads what another
+// workgroup writes.  s_i is exactly 1 where M_i == M' (so -inf - -inf never forms), features >= m are written as zeros by index.
+constexpr int MERGE_MAX = 8;              // states per launch
+constexpr int MERGE_U = 2;                // float4 slots per lane
+
+struct MergeArgs {
+  const float* in[MERGE_MAX];
+  const float* floor;                     // one float on the device, or nullptr
+  float* out;
+  long a_at, vs_at, m_at, cnt_at, n4;     // in float4 slots: where a, vs, M's block and cnt begin, and the whole state
+  int d4, mp, m, th;                      // d4: slots per row of A
+};
+
+template <int N>
+__global__ __launch_bounds__(256) void merge_kernel(const MergeArgs a) {
+  float s[N];
+  float M = a.floor ? a.floor[0] : -INFINITY;
+#pragma unroll
+  for (int i = 0; i < N; ++i) { s[i] = a.in[i][4 * a.m_at]; M = fmaxf(M, s[i]); }
+#pragma unroll
+  for (int i = 0; i < N; ++i) s[i] = s[i] == M ? 1.f : expf(s[i] - M);
+  const long stride = (long)gridDim.x * 256;
+  const long q0 = (long)blockIdx.x * 256 + threadIdx.x;
+  float4 x[MERGE_U][N];
+#pragma unroll
+  for (int u = 0; u < MERGE_U; ++u) {
+    const long q = q0 + u * stride;
+#pragma unroll
+    for (int i = 0; i < N; ++i) x[u][i] = q < a.n4 ? reinterpret_cast<const float4*>(a.in[i])[q] : float4{0.f, 0.f, 0.f, 0.f};
+  }
+#pragma unroll
+  for (int u = 0; u < MERGE_U; ++u) {
+    const long q = q0 + u * stride;
+    if (q >= a.n4) continue;
+    float4 o;
+    if (q < a.m_at) {                      // A, a (rescaled) and vs (plain): one chain, the states in order
+      const bool plain = q >= a.vs_at;
+      o = float4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const float si = plain ? 1.f : s[i];
+        if (i == 0) { o.x = si * x[u][0].x; o.y = si * x[u][0].y; o.z = si * x[u][0].z; o.w = si * x[u][0].w; }
+        else { o.x += si * x[u][i].x; o.y += si * x[u][i].y; o.z += si * x[u][i].z; o.w += si * x[u][i].w; }
+      }
+      if (q < a.a_at) {                    // a slot of A lies in one feature row: (task x head, row) = slot / d4
+        if ((int)((q / a.d4) % a.mp) >= a.m) o = float4{0.f, 0.f, 0.f, 0.f};
+      } else if (!plain) {                 // four features of a, never across a (task, head): mp % 4 == 0
+        const int j = (int)((4 * (q - a.a_at)) % a.mp);
+        if (j >= a.m) o.x = 0.f;
+        if (j + 1 >= a.m) o.y = 0.f;
+        if (j + 2 >= a.m) o.z = 0.f;
+        if (j + 3 >= a.m) o.w = 0.f;
+      }
+    } else if (q < a.cnt_at) {             // M's block of 16: M', then zeros as init leaves them
+      o = float4{q == a.m_at ? M : 0.f, 0.f, 0.f, 0.f};
+    } else {                               // cnt: int32 sums; the padding behind T H stays 0
+      const long e = 4 * (q - a.cnt_at);
+      int c[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        c[0] += __float_as_int(x[u][i].x); c[1] += __float_as_int(x[u][i].y); c[2] += __float_as_int(x[u][i].z); c[3] += __float_as_int(x[u][i].w);
+      }
+      o = float4{__int_as_float(e < a.th ? c[0] : 0), __int_as_float(e + 1 < a.th ? c[1] : 0), __int_as_float(e + 2 < a.th ? c[2] : 0),
+                 __int_as_float(e + 3 < a.th ? c[3] : 0)};
+    }
+    reinterpret_cast<float4*>(a.out)[q] = o;
+  }
+}
+
 }  // namespace fsum
 #endif
 
@@ -276,6 +353,50 @@ inline int favor_summary_absorb(const float* k, const float* v, const float* pro
     hipLaunchKernelGGL(fsum::absorb2_kernel, dim3(T * H, (a.mp + fsum::FC - 1) / fsum::FC), dim3(256), 0, s, a);
   }
   return check_launch("favor.sum_absorb2");
+#endif
+}
+
+// states: n device pointers in HOST memory; m_floor: one float in DEVICE memory or NULL ("the stabiliser is at least this")
+inline int favor_summary_merge(const void* const* states, int n, const float* m_floor, int T, int H, int d, int m, void* out, size_t state_bytes,
+                               hipStream_t s) {
+  if (T <= 0 || H <= 0 || d <= 0 || m <= 0 || n < 0 || !states || !out) { set_error("favor_summary_merge: bad argument"); return MLHOT_ERR_ARG; }
+  if (!favor_summary_ok(T, H, d, m)) return favor_summary_unsupported("favor_summary_merge", d, m);
+#ifdef MLHOT_HOSTSIM
+  (void)m_floor; (void)state_bytes; (void)s; return MLHOT_ERR_UNSUPPORTED;
+#else
+  if (n < 1 || n > fsum::MERGE_MAX) { set_error("favor_summary_merge takes 1 .. 8 states per call (got n=%d): fold more in groups", n); return MLHOT_ERR_UNSUPPORTED; }
+  const fsum::State st = fsum::carve_state(T, H, d, m, out);
+  const size_t need = st.floats * sizeof(float);
+  if (state_bytes != need) { set_error("favor_summary_merge: state_bytes must be mlhot_favor_summary_bytes' %zu (got %zu)", need, state_bytes); return MLHOT_ERR_WORKSPACE; }
+  if (!ft::aligned16(out) || (m_floor && (reinterpret_cast<uintptr_t>(m_floor) & 3))) { set_error("favor_summary_merge: out must be 16-byte aligned, m_floor 4-byte"); return MLHOT_ERR_ARG; }
+  fsum::MergeArgs a{};
+  const char* ob = (const char*)out;
+  for (int i = 0; i < n; ++i) {
+    const char* ib = (const char*)states[i];
+    if (!ib || !ft::aligned16(ib)) { set_error("favor_summary_merge: state %d is NULL or not 16-byte aligned", i); return MLHOT_ERR_ARG; }
+    if (ib < ob + need && ob < ib + need) {       // every workgroup reads every old M and one writes the new one: out is a buffer of its own
+      set_error("favor_summary_merge: out overlaps input state %d; the merged state needs its own buffer", i); return MLHOT_ERR_ARG;
+    }
+    a.in[i] = (const float*)states[i];
+  }
+  a.floor = m_floor; a.out = (float*)out;
+  a.a_at = (long)((st.a - st.A) / 4); a.vs_at = (long)((st.vs - st.A) / 4); a.m_at = (long)((st.M - st.A) / 4); a.cnt_at = a.m_at + 4;
+  a.n4 = (long)(st.floats / 4);
+  a.d4 = d / 4; a.mp = st.mp; a.m = m; a.th = T * H;
+  if ((a.n4 + 256 * fsum::MERGE_U - 1) / (256 * fsum::MERGE_U) >= (1l << 31)) { set_error("favor_summary_merge: the state is too large for one grid"); return MLHOT_ERR_ARG; }
+  ProfScope ps("favor.sum_merge", s);
+  const dim3 grid((unsigned)((a.n4 + 256 * fsum::MERGE_U - 1) / (256 * fsum::MERGE_U)));
+  switch (n) {
+    case 1: hipLaunchKernelGGL((fsum::merge_kernel<1>), grid, dim3(256), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((fsum::merge_kernel<2>), grid, dim3(256), 0, s, a); break;
+    case 3: hipLaunchKernelGGL((fsum::merge_kernel<3>), grid, dim3(256), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((fsum::merge_kernel<4>), grid, dim3(256), 0, s, a); break;
+    case 5: hipLaunchKernelGGL((fsum::merge_kernel<5>), grid, dim3(256), 0, s, a); break;
+    case 6: hipLaunchKernelGGL((fsum::merge_kernel<6>), grid, dim3(256), 0, s, a); break;
+    case 7: hipLaunchKernelGGL((fsum::merge_kernel<7>), grid, dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL((fsum::merge_kernel<8>), grid, dim3(256), 0, s, a); break;
+  }
+  return check_launch("favor.sum_merge");
 #endif
 }
 

@@ -362,6 +362,10 @@ int mlhot_favor_summary_query_fwd(const float* q, const void* state, const float
                                   void* ws, size_t ws_bytes, void* stream) {
   return favor_summary_query_forward(q, state, proj, T, H, Nq, d, m, out, ws, ws_bytes, (hipStream_t)stream);
 }
+int mlhot_favor_summary_merge(const void* const* states, int n, const float* m_floor, int T, int H, int d, int m, void* out, size_t state_bytes,
+                              void* stream) {
+  return favor_summary_merge(states, n, m_floor, T, H, d, m, out, state_bytes, (hipStream_t)stream);
+}
 // K context prefixes of any length: running sums over 32-shot chunks, three launches (csrc/favor_prefix_long.h)
 int mlhot_favor_prefix_long_supported(int T, int H, int Nq, int Nc, int d, int m, int K) { return favor_prefix_long_ok(T, H, Nq, Nc, d, m, K) ? 1 : 0; }
 size_t mlhot_favor_prefix_long_workspace_bytes(int T, int H, int Nq, int Nc, int d, int m, int K) { return favor_prefix_long_ws_need(T, H, Nq, Nc, d, m, K); }

@@ -282,6 +282,7 @@ SIGNATURES = {
     "mlhot_favor_summary_absorb": (i, [P, P, P, P, i, i, i, i, i, P, P, z, P, z, P]),
     "mlhot_favor_summary_query_ws_bytes": (z, [i] * 5),
     "mlhot_favor_summary_query_fwd": (i, [P, P, P, i, i, i, i, i, P, P, z, P]),
+    "mlhot_favor_summary_merge": (i, [P, i, P, i, i, i, i, P, z, P]),
     # prefix sweep beyond 32 context shots: chunked running FAVOR+ prefixes
     "mlhot_favor_prefix_long_supported": (i, [i] * 7),
     "mlhot_favor_prefix_long_workspace_bytes": (z, [i] * 7),
@@ -1193,6 +1194,32 @@ class MlhotLib:
         ws = self._bytes(self._fn("favor_summary_query_fwd", "mlhot_favor_summary_query_ws_bytes")(T, H, Nq, d, m), q)
         fn = self._fn("favor_summary_query_fwd", "mlhot_favor_summary_query_fwd")
         self._rc(fn(_ptr(q), _ptr(state), _ptr(proj), T, H, Nq, d, m, _ptr(out), _ptr(ws), ws.numel(), _stream(q)), "mlhot_favor_summary_query_fwd")
+        return out
+
+    MERGE_MAX = 8          # states per mlhot_favor_summary_merge call
+
+    def favor_summary_merge(self, bufs, T, H, d, m, floor=None, out=None):
+        """1 .. 8 summary states (uint8, favor_summary_bytes(T, H, d, m) bytes each) that were absorbed apart -> the state of all their
+        shots, in a buffer of its own (`out`, or a new one); the inputs are only read.  M' = max of the states' stabilisers and of
+        `floor` (None, or ONE fp32 value on the states' device: "the stabiliser is at least this"); A and a are rescaled by
+        exp(M_i - M') and added in the order of `bufs`, vs and cnt are added (include/mlhot.h).  One launch."""
+        fn = self._fn("favor_summary_merge", "mlhot_favor_summary_merge")
+        bufs = list(bufs)
+        nb = self.favor_summary_bytes(T, H, d, m)
+        if not nb:
+            raise MlhotError(f"favor_summary_merge serves d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536 (got d={d} m={m})")
+        if not 1 <= len(bufs) <= self.MERGE_MAX:
+            raise MlhotError(f"favor_summary_merge takes 1 .. {self.MERGE_MAX} states per call (got {len(bufs)}); mlhot.ops.favor_merge folds more in groups")
+        if out is None:
+            out = torch.empty(nb, dtype=torch.uint8, device=bufs[0].device)
+        for name, s in [(f"state {k}", b) for k, b in enumerate(bufs)] + [("out", out)]:
+            if not isinstance(s, torch.Tensor) or s.dtype != torch.uint8 or s.numel() < nb or s.device != bufs[0].device or not s.is_cuda:
+                raise MlhotError(f"favor_summary_merge: {name} is not a summary state for T={T} H={H} d={d} m={m} on one GPU ({nb} bytes needed)")
+        if floor is not None and (not isinstance(floor, torch.Tensor) or floor.dtype != torch.float32 or floor.numel() != 1 or floor.device != out.device):
+            raise MlhotError(f"favor_summary_merge: floor must be one fp32 value on {out.device}")
+        _chk(out, floor, *bufs)
+        table = (C.c_void_p * len(bufs))(*[b.data_ptr() for b in bufs])
+        self._rc(fn(table, len(bufs), _ptr(floor), T, H, d, m, _ptr(out), nb, _stream(out)), "mlhot_favor_summary_merge")
         return out
 
     # ---- prefix sweep beyond 32 context shots (csrc/favor_prefix_long.h) --------------------------

@@ -2,6 +2,7 @@
 
     state = mlhot.cached.condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys")     # "summary": beyond 32 shots (6c-4)
     state = mlhot.cached.extend(model, state, new_x, new_y, new_len=None)        # more context shots, only they are encoded (6c-3)
+    state = mlhot.cached.merge(model, [state_a, state_b, ..])       # summary states conditioned apart -> one, no image re-read (6c-6)
     mu = mlhot.cached.predict(model, state, qry_x, chunk=None)        # [T, Nq, y_dim]
     mu, attn = mlhot.cached.predict(model, state, qry_x, return_attention=True)      # attn [T, 8, Nq, Nc slots]: FAVOR+'s weight per context
                                                                                       # slot, head and target (attention models; 6c-5)
@@ -29,7 +30,7 @@ from mlhot.binding import HEADS
 from mlhot.context import ContextState as VanillaContextState          # noqa: F401  one class for both families; the name stays importable
 from mlhot.context import fingerprint as _fingerprint                  # noqa: F401
 from mlhot.ops import LinearFunction, _c, _need_gpu, agg_prefixes, favor_keys, favor_prefixes_long, favor_query, linear_rows
-from networks._resnet_np import ResNetNP
+from networks._resnet_np import ResNetNP, _CachedContext
 from networks._vanilla import VanillaNP
 from networks._vanilla_mr import VanillaMR
 
@@ -200,6 +201,17 @@ def extend(model, state, new_x, new_y, new_len=None):
     if isinstance(model, ResNetNP):
         return model.extend(state, new_x, new_y, new_len=new_len)
     return context.extend(_Vanilla(model), state, new_x, new_y, new_len)
+
+
+def merge(model, states):
+    """(summary states of this model, conditioned apart on the SAME T tasks) -> a NEW state holding all their context shots, as if
+    `condition(..., form="summary")` had seen them together: shards of one context, several sources or streams per
+    task, a stored library of per-object contexts.  FAVOR+'s summary is a sum over shots, so this is one launch per 8 states over
+    the states alone (mlhot.ops.favor_merge) - no image is encoded again - and it equals the joint state in exact arithmetic, with
+    one key stabiliser for the whole.  `lens` add up, `Nc` is their maximum; the inputs stay valid; `predict` and `extend` serve the
+    result like any summary state.  Both families; eval mode.  A latent state (it is stored behind its finishing Linear), a
+    form="keys" state (capped per-shot rows), a foreign or a stale state raise ValueError."""
+    return context.merge(_CachedContext(model) if isinstance(model, ResNetNP) else _Vanilla(model), states)
 
 
 def predict(model, state, qry_x, chunk=None, route=None, return_attention=False):

@@ -1,5 +1,5 @@
-"""Cached-context inference, the part both model families share (DESIGN.md 6c - 6c-4): the state `condition` leaves for `predict`, and
-the lifecycle condition -> extend -> predict with its entry checks, written once.  ResNetNP.condition / extend / predict
+"""Cached-context inference, the part both model families share (DESIGN.md 6c - 6c-6): the state `condition` leaves for `predict`, and
+the lifecycle condition -> extend / merge -> predict with its entry checks, written once.  ResNetNP.condition / extend / predict
 (networks/_resnet_np.py) and mlhot.cached.condition / extend / predict (the vanilla family) are thin callers of the functions here.
 
 What differs per family comes in as an adapter `ad`, a small object with
@@ -17,7 +17,7 @@ This module imports nothing from networks/: both families import it."""
 import torch
 
 from mlhot import lib, ragged
-from mlhot.ops import LinearFunction, favor_keys
+from mlhot.ops import LinearFunction, favor_keys, favor_merge
 
 
 class ContextState:
@@ -111,6 +111,39 @@ def extend(ad, state, new_x, new_y, new_len=None):
         if state.form == "summary":
             return _absorb(ad, state, new_x, new_y, add, state.wq)
         return _grow(ad, state, state.lens, state.capacity, new_x, new_y, add, state.wq)
+
+
+def merge(ad, states):
+    """Summary states of ONE model that were conditioned apart - shards of a context, several sources, stored per-object contexts -
+    -> a NEW state holding all their shots, as if condition(form="summary") had seen them together (DESIGN.md 6c-6:
+    mlhot.ops.favor_merge, one launch per 8 states, no image is encoded again).  The inputs stay valid.  `lens` add up, `Nc` is their
+    maximum; predict and extend serve the result like any summary state."""
+    what = "merge"
+    ad.refuse(what)
+    try:
+        states = list(states)
+    except TypeError:
+        raise ValueError(f"{what}: states must be a sequence of states of condition(form=\"summary\"), got {type(states).__name__}") from None
+    if not states:
+        raise ValueError(f"{what}: needs at least one state (got an empty sequence)")
+    for i, s in enumerate(states):
+        if not isinstance(s, ContextState) or s.owner is not ad.model:
+            raise ValueError(f"{what}: the state was not made by this model's condition() (states[{i}])")
+        if s.kind != "attention":
+            raise ValueError(f"{what}: states[{i}] is a {s.kind!r} state - it is stored behind its finishing Linear, which is not a sum over "
+                             "shots any more; only attention states of form=\"summary\" merge")
+        if s.form != "summary":
+            raise ValueError(f"{what}: states[{i}] has form {s.form!r} - it holds per-shot rows in at most {ragged.MAX_ATTENTION_CAPACITY} "
+                             "slots, not sums over shots; condition the parts with form=\"summary\"")
+        if s.T != states[0].T or s.T != ad.model.task_num:
+            raise ValueError(f"{what}: states[{i}] holds {s.T} tasks, states[0] {states[0].T}, the model {ad.model.task_num} (the key stabiliser "
+                             f"is the maximum over the conditioned batch: {what} serves the same tasks)")
+        if s.fingerprint != fingerprint(ad.model):
+            raise ValueError(f"{what}: the state is stale - a parameter of the model changed since condition() (states[{i}])")
+    with torch.no_grad():
+        keys = favor_merge([s.keys for s in states])
+    return ContextState(ad.model, states[0].T, max(keys.lens), states[0].fingerprint, "attention", keys=keys, wq=states[0].wq, lens=keys.lens,
+                        form="summary")
 
 
 def _absorb(ad, state, images, labels, add, wq):

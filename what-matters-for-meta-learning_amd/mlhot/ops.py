@@ -712,6 +712,53 @@ def favor_absorb(state, kh, vh, proj, lens=None):
     return FavorKeyState("summary", (T, max(total), H, d, m), buf=buf, lens=total)
 
 
+MERGE_GROUP = 8            # states per mlhot_favor_summary_merge call
+
+
+def favor_merge(states, floor=None):
+    """Summary states that were absorbed apart (several sources per task, several streams, a stored library of contexts) -> ONE new
+    FavorKeyState of route "summary" holding all their shots; the inputs stay valid and unchanged.  The summary is a sum over
+    shots, so with M' = max_i M_i:  A' = sum_i exp(M_i - M') A_i, a' likewise, vs' = sum_i vs_i, cnt' = sum_i cnt_i - in exact
+    arithmetic the state favor_absorb builds from all the shots, one stabiliser for the whole (csrc/favor_summary.h, DESIGN.md
+    6c-6).  `states`: a non-empty sequence of summary states of the same (T, H, d, m), device and dtype.  More than 8 are folded in
+    groups, left to right: the first 8 in one launch, then the result with the next 7, and so on - the order of every sum is a
+    function of len(states) alone.  lens add up and dims[1] is their maximum, as favor_absorb sets them.
+
+    `floor`: None, or ONE fp32 value on the states' device - "the stabiliser is at least this": M' = max(M_0, .., floor).  A floor
+    at or below every M_i changes nothing; a higher one scales A and a by one common factor exp(max_i M_i - floor).  favor_query's
+    quotient cancels that factor up to its eps terms: the key feature's +eps is relative to the stabiliser, so the result is the one
+    of a batch whose stabiliser IS the floor - what a caller needs who must agree on one stabiliser with states it does not hold.
+    Forward only."""
+    try:
+        states = list(states)
+    except TypeError:
+        raise MlhotError(f"favor_merge: states must be a sequence of summary states, got {type(states).__name__}") from None
+    if not states:
+        raise MlhotError("favor_merge: needs at least one summary state (got an empty sequence)")
+    for i, s in enumerate(states):
+        if not isinstance(s, FavorKeyState):
+            raise MlhotError(f"favor_merge: states[{i}] is a {type(s).__name__}, not a FavorKeyState of favor_absorb")
+        if s.route != "summary":
+            why = ("favor_keys' per-shot states hold rows, not sums: they do not merge (build the parts with favor_absorb)" if s.route == "cached"
+                   else "only favor_absorb's summary states are sums over shots")
+            raise MlhotError(f"favor_merge: states[{i}] has route {s.route!r}; {why}")
+    T, _, H, d, m = states[0].dims
+    for i, s in enumerate(states[1:], 1):
+        if (s.dims[0], *s.dims[2:]) != (T, H, d, m):
+            raise MlhotError(f"favor_merge: states[{i}] was built for T={s.dims[0]} H={s.dims[2]} d={s.dims[3]} m={s.dims[4]}, "
+                             f"states[0] for T={T} H={H} d={d} m={m}")
+        if s.buf.device != states[0].buf.device or s.buf.dtype != states[0].buf.dtype:
+            raise MlhotError(f"favor_merge: states[{i}] lies on {s.buf.device} as {s.buf.dtype}, states[0] on {states[0].buf.device} as {states[0].buf.dtype}")
+    if floor is not None and (not isinstance(floor, torch.Tensor) or floor.dtype != torch.float32 or floor.numel() != 1 or floor.device != states[0].buf.device):
+        raise MlhotError(f"favor_merge: floor must be None or one fp32 value on {states[0].buf.device} (the stabiliser is at least this)")
+    bufs = [s.buf for s in states]
+    buf = lib().favor_summary_merge(bufs[:MERGE_GROUP], T, H, d, m, floor=floor)
+    for at in range(MERGE_GROUP, len(bufs), MERGE_GROUP - 1):
+        buf = lib().favor_summary_merge([buf] + bufs[at:at + MERGE_GROUP - 1], T, H, d, m, floor=floor)
+    total = tuple(sum(s.lens[t] for s in states) for t in range(T))
+    return FavorKeyState("summary", (T, max(total), H, d, m), buf=buf, lens=total)
+
+
 def favor_query(qh, state, vh, proj, weights=False):
     """FAVOR+ attention of q [T, Nq, H, d] against a favor_keys state and v [T, Nc, H, d] -> merged [T, Nq, d*H], any Nq >= 1 in
     one launch.  On the "cached" route the bits of a row do not depend on the other rows of the call (csrc/favor_cached.h); the
