@@ -418,6 +418,32 @@ int mlhot_favor_prefix_long_fwd(const float* q, const float* k, const float* v, 
                                 int T, int H, int Nq, int Nc, int d, int m, float* out,
                                 void* ws, size_t ws_bytes, void* stream);
 
+/* ---- per-shot key states beyond 32 context slots: chunked keys and query with read-out (csrc/favor_long.h) ---------
+ * The split of mlhot_favor_keys_fwd / mlhot_favor_query_fwd with the context slots walked in chunks of 32, 1 <= Nc <= 256 slots per
+ * task.  The state keeps the finished key features of every slot, so the query can read out FAVOR+'s per-shot weights.
+ * mlhot_favor_keys_long_fwd: k[T,Nc,H,d], proj[m,d], lens[T] (int32, DEVICE memory, read on the device; NULL = Nc for every task;
+ *   1 <= lens[t] <= Nc is the caller's contract, a value outside is held to that range) -> state of mlhot_favor_keys_long_bytes bytes:
+ *   floats [0, T H Nc mp): F_k[T,H,Nc,mp] as mlhot_favor_keys_fwd lays it out, float T H Nc mp: M, the maximum of dd_k over the VALID
+ *   rows of all T tasks; the rest is the call's scratch.  Rows n >= lens[t] of k are never read and all mp features of such a row of
+ *   F_k are exactly 0.0f; every float of F_k and M is written, whatever the buffer held.  Two launches.
+ * mlhot_favor_query_long_fwd: q[T,Nq,H,d], that state, v[T,Nc,H,d], proj, the SAME lens (or NULL) -> out[T,Nq,d*H] in
+ *   mlhot_favor_fwd's merged order, ONE launch for any Nq >= 1; with w != NULL also w[T,H,Nq,Nc] = S / D as
+ *   mlhot_favor_query_weights_fwd defines it, columns n' >= lens[t] exactly 0.0f, and out BIT-EQUAL to the call with w == NULL.
+ *   Rows n >= lens[t] of v are never read.  ROW-INVARIANCE guarantee of mlhot_favor_query_fwd for out and w.  Every summation order
+ *   is a function of d, m and lens[t] alone (no atomics): the same shots kept at another capacity Nc give the same bits, and with
+ *   Nc <= 32 state, out and w are BIT-EQUAL to mlhot_favor_keys_fwd / mlhot_favor_query_weights_fwd on the same operands.
+ *   ws: at least 256 bytes (the kernel works in LDS alone).
+ * Served (mlhot_favor_long_supported): 1 <= Nc <= 256, d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536, T H < 2^20,
+ * T H ceil(Nq / 16) < 2^31, 16-byte aligned q, k, proj and state.  Otherwise mlhot_favor_keys_long_bytes returns 0 and the calls
+ * MLHOT_ERR_UNSUPPORTED, writing nothing.  Forward only; GPU build only.  Added within ABI 7: bindings look the symbols up. */
+int mlhot_favor_long_supported(int T, int H, int Nc, int d, int m);
+size_t mlhot_favor_keys_long_bytes(int T, int H, int Nc, int d, int m);
+int mlhot_favor_keys_long_fwd(const float* k, const float* proj, const int32_t* lens /* [T], device, or NULL */,
+                              int T, int H, int Nc, int d, int m, void* state, size_t state_bytes, void* stream);
+int mlhot_favor_query_long_fwd(const float* q, const void* state, const float* v, const float* proj,
+                               const int32_t* lens /* [T], device, or NULL */, int T, int H, int Nq, int Nc, int d, int m,
+                               float* out, float* w /* [T,H,Nq,Nc], or NULL */, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- strict sharded parity of the key stabiliser -------------------------
  * fast_attention.py:96-97 takes torch.max over the keys of the WHOLE batch.  When a caller shards the meta-batch over
  * ranks, each rank's launch sequence can be run in two halves around the caller's own collectives on `xchg`

@@ -1,5 +1,5 @@
 // The tile steps of the FAVOR+ inference kernels, each ONCE: favor_cached.h (keys, query), favor_summary.h (absorb, query),
-// favor_prefix_long.h (dd, sweep), favor_linear.h (apply), np_query.h and np_prefix.h (the attention part) are sequences of these
+// favor_prefix_long.h (dd, sweep), favor_linear.h (apply), favor_long.h (keys, query), np_query.h and np_prefix.h (the attention part) are sequences of these
 // calls plus what is their own.  The bits of one kernel are defined as equal to another's (tests compare them with torch.equal):
 // they are, because both run the same text here.  Every step keeps ONE order of its floating-point operations, a function of the
 // dimensions alone; the __shared__ arrays stay declared in the kernels and are passed in.
@@ -356,6 +356,49 @@ __device__ __forceinline__ void sv_tiles(const float* s_S, const float* s_D, con
     float bv[MAXNC / 4];
     load_v(bv, v0, vld, Nc, e, lq);
     const f32x4_t o = sv_chain(s_S, bv, Nc, lr, lq);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) store(4 * lq + r, e, o[r] / s_D[4 * lq + r]);
+  }
+}
+
+// ---- the same three steps over a WIDE S tile: more than 32 key slots, walked in chunks of 32 (favor_long.h) -----------------------------
+// s_S has row stride ld (odd, as LDS_S is).  Every sum keeps the order of its 32-slot twin above and carries on behind it: with at
+// most 32 slots these run the twin's operations exactly.
+// D = rowsum(S): the n columns in order; one barrier behind it
+__device__ __forceinline__ void s_rowsum_wide(const float* s_S, int ld, int n, float* s_D) {
+  const int tid = threadIdx.x;
+  if (tid < QT) {
+    float s = 0.f;
+    for (int np = 0; np < n; ++np) s += s_S[tid * ld + np];
+    s_D[tid] = s;
+  }
+  __syncthreads();
+}
+// load_v for the chunk of slots n0 .. n0 + 32 (zeros from n on)
+__device__ __forceinline__ void load_v_at(float (&bv)[MAXNC / 4], const float* v0, size_t vld, int n0, int n, int e, int lq) {
+#pragma unroll
+  for (int ks = 0; ks < MAXNC / 4; ++ks) { const int np = n0 + 4 * ks + lq; bv[ks] = np < n ? v0[np * vld + e] : 0.f; }
+}
+// sv_chain continued: o carries the chain over the slots < n0, this adds the slots n0 .. n0 + 32 in order (zeros from cut on, by index)
+__device__ __forceinline__ f32x4_t sv_chain_on(f32x4_t o, const float* s_S, int ld, const float (&bv)[MAXNC / 4], int n0, int cut, int lr, int lq) {
+#pragma unroll
+  for (int ks = 0; ks < MAXNC / 4; ++ks) {
+    const int np = n0 + 4 * ks + lq;
+    o = mfma4(np < cut ? s_S[lr * ld + np] : 0.f, bv[ks], o);
+  }
+  return o;
+}
+// sv_tiles over n slots: per element ONE chain over the slots in ascending order, the accumulator carried from chunk to chunk
+template <class Store>
+__device__ __forceinline__ void sv_tiles_wide(const float* s_S, int ld, const float* s_D, const float* v0, size_t vld, int n, int d, int wv, int lr, int lq, Store store) {
+  for (int et = wv; et * 16 < d; et += 4) {
+    const int e = 16 * et + lr;
+    f32x4_t o = {0.f, 0.f, 0.f, 0.f};
+    for (int n0 = 0; n0 < n; n0 += MAXNC) {
+      float bv[MAXNC / 4];
+      load_v_at(bv, v0, vld, n0, n, e, lq);
+      o = sv_chain_on(o, s_S, ld, bv, n0, n, lr, lq);
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) store(4 * lq + r, e, o[r] / s_D[4 * lq + r]);
   }

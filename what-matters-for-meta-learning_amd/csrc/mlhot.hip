@@ -31,6 +31,7 @@
 #include "np_prefix.h"
 #include "favor_summary.h"
 #include "favor_prefix_long.h"
+#include "favor_long.h"
 #include "resnet_trunk.h"
 #include "../../include/mlhot.h"
 
@@ -372,6 +373,17 @@ size_t mlhot_favor_prefix_long_workspace_bytes(int T, int H, int Nq, int Nc, int
 int mlhot_favor_prefix_long_fwd(const float* q, const float* k, const float* v, const float* proj, const int32_t* ks, int K, const int32_t* lens,
                                 int T, int H, int Nq, int Nc, int d, int m, float* out, void* ws, size_t ws_bytes, void* stream) {
   return favor_prefix_long_forward(q, k, v, proj, ks, K, lens, T, H, Nq, Nc, d, m, out, ws, ws_bytes, (hipStream_t)stream);
+}
+// per-shot key states of up to 256 slots: the cached split with the slots in chunks of 32, read-out included (csrc/favor_long.h)
+int mlhot_favor_long_supported(int T, int H, int Nc, int d, int m) { return favor_long_ok(T, H, Nc, d, m) ? 1 : 0; }
+size_t mlhot_favor_keys_long_bytes(int T, int H, int Nc, int d, int m) { return favor_keys_long_need(T, H, Nc, d, m); }
+int mlhot_favor_keys_long_fwd(const float* k, const float* proj, const int32_t* lens, int T, int H, int Nc, int d, int m, void* state,
+                              size_t state_bytes, void* stream) {
+  return favor_keys_long_forward(k, proj, lens, T, H, Nc, d, m, state, state_bytes, (hipStream_t)stream);
+}
+int mlhot_favor_query_long_fwd(const float* q, const void* state, const float* v, const float* proj, const int32_t* lens, int T, int H, int Nq,
+                               int Nc, int d, int m, float* out, float* w, void* ws, size_t ws_bytes, void* stream) {
+  return favor_query_long_forward(q, state, v, proj, lens, T, H, Nq, Nc, d, m, out, w, ws, ws_bytes, (hipStream_t)stream);
 }
 // Staged passes (strict sharded parity of the key stabiliser, csrc/stab_xchg.h): stage 0 runs up to the rank-local scalar and
 // publishes it in xchg, stage 1 takes the batch-wide scalar from xchg and runs the rest.

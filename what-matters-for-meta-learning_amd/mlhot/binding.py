@@ -287,6 +287,11 @@ SIGNATURES = {
     "mlhot_favor_prefix_long_supported": (i, [i] * 7),
     "mlhot_favor_prefix_long_workspace_bytes": (z, [i] * 7),
     "mlhot_favor_prefix_long_fwd": (i, [P, P, P, P, P, i, P, i, i, i, i, i, i, P, P, z, P]),
+    # per-shot key states beyond 32 context slots: chunked keys and query with read-out
+    "mlhot_favor_long_supported": (i, [i] * 5),
+    "mlhot_favor_keys_long_bytes": (z, [i] * 5),
+    "mlhot_favor_keys_long_fwd": (i, [P, P, P, i, i, i, i, i, P, z, P]),
+    "mlhot_favor_query_long_fwd": (i, [P, P, P, P, P, i, i, i, i, i, i, P, P, P, z, P]),
     # strict sharded parity of the key stabiliser
     "mlhot_favor_fwd_staged": (i, _qkvp + [P, P, z, i, P, P]),
     "mlhot_favor_bwd_staged": (i, _qkvp + [P, P, P, P, P, P, z, i, P, P]),
@@ -1122,6 +1127,70 @@ class MlhotLib:
         self._rc(fn(_ptr(q), _ptr(state), _ptr(v), _ptr(proj), T, H, Nq, Nc, d, m, _ptr(out), _ptr(w), _ptr(ws), ws.numel(), _stream(q)),
                  "mlhot_favor_query_weights_fwd")
         return out, w
+
+    # ---- per-shot key states of up to 256 slots (csrc/favor_long.h) -------------------------------
+    def favor_long_supported(self, T, H, Nc, d, m):
+        """Whether mlhot_favor_keys_long_fwd / mlhot_favor_query_long_fwd serve these dimensions."""
+        return bool(self._fn("favor_keys_long_fwd", "mlhot_favor_long_supported")(T, H, Nc, d, m))
+
+    def favor_keys_long_bytes(self, T, H, Nc, d, m):
+        """State bytes of mlhot_favor_keys_long_fwd; 0 for a shape the long kernels do not serve."""
+        return self._fn("favor_keys_long_fwd", "mlhot_favor_keys_long_bytes")(T, H, Nc, d, m)
+
+    @staticmethod
+    def _long_lens(what, lens, T, like):
+        if lens is not None and (lens.dtype != torch.int32 or tuple(lens.shape) != (T,) or lens.device != like.device):
+            raise MlhotError(f"{what}: lens must be int32 [{T}] on {like.device}, got {lens.dtype} {tuple(lens.shape)} on {lens.device}")
+
+    def favor_keys_long_fwd(self, k, proj, lens=None, out=None):
+        """k [T,Nc,H,d] with Nc <= 256, proj [m,d], lens [T] int32 on k's device or None (every task full) -> state (uint8): F_k
+        [T,H,Nc,mp] and M in favor_keys_fwd's layout (favor_state_views shows them), rows n >= lens[t] exact zeros and their k never
+        read (include/mlhot.h).  The values of lens are the caller's to check (1 .. Nc).  `out`: a buffer of
+        favor_keys_long_bytes bytes to fill.  Forward only."""
+        fn = self._fn("favor_keys_long_fwd", "mlhot_favor_keys_long_fwd")
+        if k.dtype != torch.float32 or k.dim() != 4 or proj.dtype != torch.float32 or proj.dim() != 2 or proj.shape[1] != k.shape[3] or proj.device != k.device:
+            raise MlhotError(f"favor_keys_long_fwd: k must be fp32 [T, Nc, H, d] and proj fp32 [m, d] on one device, got {tuple(k.shape)}, {tuple(proj.shape)}")
+        T, Nc, H, d = k.shape
+        self._long_lens("favor_keys_long_fwd", lens, T, k)
+        m = proj.shape[0]
+        nb = self.favor_keys_long_bytes(T, H, Nc, d, m)
+        if not nb:
+            raise MlhotError(f"favor_keys_long_fwd serves Nc <= 256, d % 16 == 0, d <= 256, 16 <= m <= 1536 (got Nc={Nc} d={d} m={m})")
+        _chk(k, proj, lens)
+        state = self._bytes(nb, k) if out is None else out
+        if state.dtype != torch.uint8 or state.numel() < nb or state.device != k.device or not state.is_contiguous():
+            raise MlhotError(f"favor_keys_long_fwd: out must be {nb} contiguous bytes (uint8) on {k.device}")
+        self._rc(fn(_ptr(k), _ptr(proj), _ptr(lens), T, H, Nc, d, m, _ptr(state), state.numel(), _stream(k)), "mlhot_favor_keys_long_fwd")
+        return state
+
+    def favor_query_long_fwd(self, q, state, v, proj, lens=None, weights=False):
+        """q [T,Nq,H,d], a favor_keys_long_fwd state, v [T,Nc,H,d], proj [m,d], the state's lens (or None) -> out [T,Nq,d*H] (merged
+        order), any Nq >= 1 in one launch, bits per row independent of the other rows; weights=True -> (out, w [T,H,Nq,Nc]), w = S / D
+        of the same launch with exact zeros behind lens[t], out bit-equal to the call without (csrc/favor_long.h).  Forward only."""
+        what = "favor_query_long_fwd"
+        fn = self._fn(what, "mlhot_favor_query_long_fwd")
+        for name, t in (("q", q), ("v", v)):
+            if t.dtype != torch.float32 or t.dim() != 4:
+                raise MlhotError(f"{what}: {name} must be fp32 [T, N, H, d], got {t.dtype} {tuple(t.shape)}")
+        T, Nq, H, d = q.shape
+        Nc = v.shape[1]
+        if tuple(v.shape) != (T, Nc, H, d) or proj.dtype != torch.float32 or proj.dim() != 2 or proj.shape[1] != d or Nq < 1:
+            raise MlhotError(f"{what}: q {tuple(q.shape)}, v {tuple(v.shape)}, proj {tuple(proj.shape)} do not fit together")
+        if any(t.device != q.device for t in (state, v, proj)):
+            raise MlhotError(f"{what}: q, state, v and proj must lie on one device")
+        self._long_lens(what, lens, T, q)
+        m = proj.shape[0]
+        nb = self.favor_keys_long_bytes(T, H, Nc, d, m)
+        if not nb or state.dtype != torch.uint8 or state.numel() < nb:
+            raise MlhotError(f"{what}: the state is not mlhot_favor_keys_long_fwd's for T={T} H={H} Nc={Nc} d={d} m={m} "
+                             f"({state.numel()} bytes, {nb} needed; 0 = shape not served)")
+        _chk(q, v, proj, state, lens)
+        out = torch.empty(T, Nq, d * H, device=q.device)
+        w = torch.empty(T, H, Nq, Nc, device=q.device) if weights else None
+        ws = self._bytes(256, q)
+        self._rc(fn(_ptr(q), _ptr(state), _ptr(v), _ptr(proj), _ptr(lens), T, H, Nq, Nc, d, m, _ptr(out), _ptr(w), _ptr(ws), ws.numel(), _stream(q)),
+                 "mlhot_favor_query_long_fwd")
+        return (out, w) if weights else out
 
     # ---- the fixed-size FAVOR+ summary state (csrc/favor_summary.h) ------------------------------
     def favor_summary_bytes(self, T, H, d, m):

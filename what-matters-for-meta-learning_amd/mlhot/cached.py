@@ -1,6 +1,7 @@
 """Cached-context inference as functions: `condition` once, `predict` for any targets.
 
     state = mlhot.cached.condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys")     # "summary": beyond 32 shots (6c-4)
+                                                                    # "long": per-shot rows for up to 256 shots, attention read-out (6c-7)
     state = mlhot.cached.extend(model, state, new_x, new_y, new_len=None)        # more context shots, only they are encoded (6c-3)
     state = mlhot.cached.merge(model, [state_a, state_b, ..])       # summary states conditioned apart -> one, no image re-read (6c-6)
     mu = mlhot.cached.predict(model, state, qry_x, chunk=None)        # [T, Nq, y_dim]
@@ -146,6 +147,11 @@ class _Vanilla:
                 raise ValueError('predict: route "fused" - mlhot_np_query_fwd reads per-shot key features; a summary state is served by '
                                  "the composed route (linear_rows and favor_query)")
             route = "composed"
+        if state.form == "long":
+            if route == "fused":
+                raise ValueError('predict: route "fused" - mlhot_np_query_fwd reads at most 32 context slots in one chunk; a long state is '
+                                 "served by the composed route (linear_rows and favor_query)")
+            route = "composed"
         _need_gpu(qry_x)
         self.dims = model._dims(state.Nc, 1)
         if route is None:
@@ -182,7 +188,11 @@ def condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys"):
 
     `form="summary"` (attention models): the state is FAVOR+'s fixed-size summary of the context - any number of
     shots, `ctx_len` honoured, no `capacity`, no per-shot rows kept; extend absorbs any number of further shots and predict runs
-    the composed route.  The default "keys" is every call as it was."""
+    the composed route.  The default "keys" is every call as it was.
+
+    `form="long"` (attention models): per-shot key features for up to 256 slots (`capacity` defaults to Nslots),
+    everything of "keys" - `ctx_len`, `capacity`, extend, `return_attention=True` - through the chunked kernels of
+    csrc/favor_long.h; predict runs the composed route.  It is the form that returns attention weights above 32 shots."""
     ragged.check_form("condition", form)
     if isinstance(model, ResNetNP):
         if form != "keys":
@@ -224,7 +234,7 @@ def predict(model, state, qry_x, chunk=None, route=None, return_attention=False)
     head and target (rows sum to 1; slots behind a task's ctx_len are exact zeros), concatenated over the chunks like mu.  The
     vanilla family runs the composed route for it - `route=None` picks it, a forced "fused" is a ValueError - and mu is bit-equal
     to `predict(..., route="composed")`; for a ResNetNP model mu is bit-equal to the call without the keyword.  A model without
-    attention and a summary state refuse with ValueError."""
+    attention and a summary state refuse with ValueError; a form="long" state serves it for up to 256 slots."""
     if isinstance(model, ResNetNP):
         if route is not None:
             raise ValueError("predict: route= belongs to the vanilla family")

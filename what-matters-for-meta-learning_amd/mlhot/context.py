@@ -1,4 +1,4 @@
-"""Cached-context inference, the part both model families share (DESIGN.md 6c - 6c-6): the state `condition` leaves for `predict`, and
+"""Cached-context inference, the part both model families share (DESIGN.md 6c - 6c-7): the state `condition` leaves for `predict`, and
 the lifecycle condition -> extend / merge -> predict with its entry checks, written once.  ResNetNP.condition / extend / predict
 (networks/_resnet_np.py) and mlhot.cached.condition / extend / predict (the vanilla family) are thin callers of the functions here.
 
@@ -33,13 +33,16 @@ class ContextState:
     (attention), `rs` - baco: the mean Linear's output - and `lv` (latent), with `r`, the aggregate before the finishing Linear.
 
     `form` "summary" (DESIGN.md 6c-4): `keys` is a fixed-size summary state (mlhot.ops.favor_absorb), `Nc` the largest of `lens`;
-    there is no capacity and there are no per-shot rows - `vh`, `kh` are None."""
+    there is no capacity and there are no per-shot rows - `vh`, `kh` are None.
+
+    `form` "long" (DESIGN.md 6c-7): everything of "keys" - `lens`, `capacity`, `kh` and `vh` in slot order - with up to 256 slots;
+    `keys` is mlhot.ops.favor_keys_long's state."""
 
     def __init__(self, owner, T, Nc, fingerprint, kind, keys=None, vh=None, z=None, lens=None, kh=None, rs=None, lv=None, r=None,
                  form="keys", wq=None):
         self.owner, self.T, self.Nc, self.fingerprint, self.kind = owner, T, Nc, fingerprint, kind
         self.keys, self.vh, self.z, self.wq, self.route = keys, vh, z, wq, None
-        self.lens, self.capacity, self.form = (Nc,) * T if lens is None else tuple(lens), Nc if form == "keys" else None, form
+        self.lens, self.capacity, self.form = (Nc,) * T if lens is None else tuple(lens), None if form == "summary" else Nc, form
         self.kh, self.rs, self.lv, self.r = kh, rs, lv, r
 
 
@@ -67,7 +70,7 @@ def _enter(ad, what, state, rows, noun):
 def condition(ad, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys"):
     """(ctx images [T, Nc, ...], ctx labels [T, Nc, L]) -> ContextState: the per-shot stage, then the FAVOR+ key features
     (attention) or the aggregation and the finishing Linear.  `ctx_len` / `capacity`: the masked path (_grow); `form="summary"`:
-    _absorb; neither: the call as it always was."""
+    _absorb; `form="long"`: always _grow, with mlhot.ops.favor_keys_long behind it; neither: the call as it always was."""
     model = ad.model
     ragged.check_form("condition", form)
     ad.refuse("condition")
@@ -76,6 +79,8 @@ def condition(ad, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys"):
         raise ValueError(f"condition: {T} tasks, the model was built for tasks_per_batch = {model.task_num}")
     if form == "summary":
         lens = ragged.summary_condition_args("condition", T, Nc, ctx_len, capacity, model.ATTENTION)
+    elif form == "long":
+        lens, capacity = ragged.long_condition_args("condition", T, Nc, ctx_len, capacity, model.ATTENTION)
     else:
         lens, capacity = ragged.condition_args("condition", T, Nc, ctx_len, capacity, model.ATTENTION)
     ad.prepare(ctx_x, ctx_y)
@@ -84,7 +89,7 @@ def condition(ad, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys"):
             return _absorb(ad, None, ctx_x, ctx_y, lens, ad.begin(True))
         wq = ad.begin(lens is not None or Nc > 0)
         if lens is not None:
-            return _grow(ad, None, (0,) * T, capacity, ctx_x, ctx_y, lens, wq)
+            return _grow(ad, None, (0,) * T, capacity, ctx_x, ctx_y, lens, wq, form)
         if Nc == 0:
             return ContextState(model, T, 0, fingerprint(model), "empty", z=ad.empty_z(ctx_x.device), wq=wq)
         a_rows, b_rows = ad.shot_rows(ctx_x.reshape(T * Nc, model.img_channels, model.img_size[0], model.img_size[1]), ctx_y.reshape(T * Nc, -1))
@@ -110,7 +115,7 @@ def extend(ad, state, new_x, new_y, new_len=None):
     with torch.no_grad():
         if state.form == "summary":
             return _absorb(ad, state, new_x, new_y, add, state.wq)
-        return _grow(ad, state, state.lens, state.capacity, new_x, new_y, add, state.wq)
+        return _grow(ad, state, state.lens, state.capacity, new_x, new_y, add, state.wq, state.form)
 
 
 def merge(ad, states):
@@ -133,7 +138,8 @@ def merge(ad, states):
             raise ValueError(f"{what}: states[{i}] is a {s.kind!r} state - it is stored behind its finishing Linear, which is not a sum over "
                              "shots any more; only attention states of form=\"summary\" merge")
         if s.form != "summary":
-            raise ValueError(f"{what}: states[{i}] has form {s.form!r} - it holds per-shot rows in at most {ragged.MAX_ATTENTION_CAPACITY} "
+            slots = ragged.MAX_LONG_CAPACITY if s.form == "long" else ragged.MAX_ATTENTION_CAPACITY
+            raise ValueError(f"{what}: states[{i}] has form {s.form!r} - it holds per-shot rows in at most {slots} "
                              "slots, not sums over shots; condition the parts with form=\"summary\"")
         if s.T != states[0].T or s.T != ad.model.task_num:
             raise ValueError(f"{what}: states[{i}] holds {s.T} tasks, states[0] {states[0].T}, the model {ad.model.task_num} (the key stabiliser "
@@ -159,7 +165,7 @@ def _absorb(ad, state, images, labels, add, wq):
     return ContextState(model, T, max(keys.lens), fingerprint(model), "attention", keys=keys, wq=wq, lens=keys.lens, form="summary")
 
 
-def _grow(ad, state, lens, capacity, images, labels, add, wq):
+def _grow(ad, state, lens, capacity, images, labels, add, wq, form="keys"):
     """`add[t]` of the slots of images / labels [T, n, ...] behind task t's lens[t] kept rows (state None: nothing kept yet), then the
     finishing step on the kept rows.  The valid shots travel as a packed list: a slot that is no shot is never read."""
     model = ad.model
@@ -176,8 +182,8 @@ def _grow(ad, state, lens, capacity, images, labels, add, wq):
         a_rows = ragged.scatter(a_rows, plan.dst, new_a)
         b_rows = ragged.scatter(b_rows, plan.dst, new_b) if new_b is not None else None
     if model.ATTENTION:
-        keys = ragged.masked_keys(a_rows, model.attn.projection_matrix, plan)
-        return ContextState(model, T, capacity, fingerprint(model), "attention", keys=keys, vh=b_rows, wq=wq, lens=plan.total, kh=a_rows)
+        keys = ragged.masked_keys(a_rows, model.attn.projection_matrix, plan, form)
+        return ContextState(model, T, capacity, fingerprint(model), "attention", keys=keys, vh=b_rows, wq=wq, lens=plan.total, kh=a_rows, form=form)
     return _latent(ad, capacity, a_rows, b_rows, ragged.gathered_aggregate(model.agg_mode, a_rows, b_rows, plan), plan.total)
 
 
@@ -194,8 +200,9 @@ def _refuse_attention(ad, state):
                          f"state is {state.kind!r}, the context enters the prediction as one aggregate")
     if state.form == "summary":
         raise ValueError("predict: return_attention=True - a summary state keeps no per-shot rows, so there is no weight per context shot to "
-                         'read out (condition with the default form="keys" for at most 32 shots)')
-    if state.keys.route != "cached":
+                         'read out (condition with the default form="keys" for at most 32 shots, or with form="long" for at most '
+                         f"{ragged.MAX_LONG_CAPACITY})")
+    if state.keys.route not in ("cached", "long"):
         raise ValueError("predict: return_attention=True needs the cached kernels' envelope (Nc <= 32, d % 16 == 0, d <= 256, "
                          f"16 <= m <= 1536); this state's keys are kept {state.keys.route!r} (T, Nc, H, d, m = {state.keys.dims})")
 

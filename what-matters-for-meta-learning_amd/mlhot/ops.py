@@ -591,17 +591,21 @@ class FavorKeyState:
     """What favor_keys / favor_absorb leave for favor_query.  `route` says what it holds: "cached" - `buf` is mlhot_favor_keys_fwd's
     state (the finished key features F_k and the batch-global stabiliser M; features() shows them) and favor_query is row-invariant;
     "plain" - a shape outside the cached kernels' envelope: `kh` itself, favor_query runs mlhot_favor_fwd, no invariance;
-    "summary" - favor_absorb's fixed-size state (csrc/favor_summary.h; summary() shows it), any number of shots, row-invariant.
+    "summary" - favor_absorb's fixed-size state (csrc/favor_summary.h; summary() shows it), any number of shots, row-invariant;
+    "long" - favor_keys_long's state (csrc/favor_long.h): F_k and M in the "cached" layout for up to 256 slots,
+    walked in chunks of 32; row-invariant, and like "cached" it reads out weights.  It carries `lens_dev`, the device copy of `lens`
+    that its query reads (None: every task full).
     `lens`: None, or the per-task context sizes (a tuple of T ints) of a masked state (mlhot_favor_keys_ragged_fwd): rows
     n >= lens[t] of F_k are exact zeros.  A summary state always carries `lens`, the shots each task has absorbed so far, and its
     dims[1] is the largest of them."""
 
-    def __init__(self, route, dims, buf=None, kh=None, lens=None):
+    def __init__(self, route, dims, buf=None, kh=None, lens=None, lens_dev=None):
         self.route, self.dims, self.buf, self.kh, self.lens = route, dims, buf, kh, lens      # dims = (T, Nc, H, d, m)
+        self.lens_dev = lens_dev
 
     def features(self):
-        """(F_k [T, H, Nc, mp], M [1]) of a "cached" state, as views."""
-        if self.route != "cached":
+        """(F_k [T, H, Nc, mp], M [1]) of a "cached" or a "long" state, as views."""
+        if self.route not in ("cached", "long"):
             raise MlhotError(f"FavorKeyState.features: this state holds no key features (route {self.route!r})")
         T, Nc, H, d, m = self.dims
         return lib().favor_state_views(self.buf, T, H, Nc, m)
@@ -668,6 +672,36 @@ def favor_keys(kh, proj, lens=None, lens_dev=None):
     if lib().favor_keys_bytes(T, H, Nc, d, proj.shape[0]):
         return FavorKeyState("cached", dims, buf=lib().favor_keys_fwd(kh, proj))
     return FavorKeyState("plain", dims, kh=kh)
+
+
+MAX_LONG_NC = 256          # context slots per task of the long per-shot state (csrc/favor_long.h)
+
+
+def favor_keys_long(kh, proj, lens=None, lens_dev=None):
+    """favor_keys for up to 256 context slots: k [T, Nc, H, d], proj [m, d] -> FavorKeyState of route "long", the
+    per-shot key features of every slot in favor_keys' layout (features() shows them), built 32 rows at a time in two launches
+    (csrc/favor_long.h).  favor_query walks the slots in chunks of 32 in ONE row-invariant launch and, unlike a summary state, can
+    read out the weights (weights=True).  `lens` / `lens_dev` as favor_keys takes them: row n of task t is a context shot iff
+    n < lens[t]; the other rows of kh are never read and are exact zeros in F_k.  The same shots give the same bits at any
+    capacity Nc, and with Nc <= 32 the state and favor_query's results have the bits of favor_keys' "cached" route.
+    Nc <= 256, d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536, else MlhotError - there is no other route.  Forward only."""
+    _forward_only("favor_keys_long", kh, proj)
+    _need_gpu(kh, proj)
+    kh, proj = _c(kh.detach()), _c(proj.detach())
+    if kh.dim() != 4 or proj.dim() != 2 or proj.shape[1] != kh.shape[3]:
+        raise MlhotError(f"favor_keys_long: k must be [T, Nc, H, d] and proj [m, d], got {tuple(kh.shape)}, {tuple(proj.shape)}")
+    T, Nc, H, d = kh.shape
+    m = proj.shape[0]
+    if lens is not None:
+        lens = host_lens(lens, T, 1, Nc, "favor_keys_long: lens")
+    if not lib().favor_long_supported(T, H, Nc, d, m):
+        bad = [f"{n}={v}" for n, v, ok in (("Nc", Nc, 1 <= Nc <= MAX_LONG_NC), ("d", d, d % 16 == 0 and 16 <= d <= 256),
+                                            ("m", m, 16 <= m <= 1536)) if not ok] or [f"T*H={T * H}"]
+        raise MlhotError(f"favor_keys_long serves Nc <= {MAX_LONG_NC}, d % 16 == 0, d <= 256, 16 <= m <= 1536, got {', '.join(bad)}")
+    dev = None
+    if lens is not None:
+        dev = torch.tensor(lens, dtype=torch.int32).to(kh.device) if lens_dev is None else _c(lens_dev)
+    return FavorKeyState("long", (T, Nc, H, d, m), buf=lib().favor_keys_long_fwd(kh, proj, dev), lens=lens, lens_dev=dev)
 
 
 ABSORB_CHUNK = 32          # new shots per task and mlhot_favor_summary_absorb call
@@ -761,7 +795,8 @@ def favor_merge(states, floor=None):
 
 def favor_query(qh, state, vh, proj, weights=False):
     """FAVOR+ attention of q [T, Nq, H, d] against a favor_keys state and v [T, Nc, H, d] -> merged [T, Nq, d*H], any Nq >= 1 in
-    one launch.  On the "cached" route the bits of a row do not depend on the other rows of the call (csrc/favor_cached.h); the
+    one launch.  On the "cached" route the bits of a row do not depend on the other rows of the call (csrc/favor_cached.h), nor on
+    the "long" route (favor_keys_long, csrc/favor_long.h: up to 256 slots in chunks of 32, weights=True included); the
     "plain" route is mlhot_favor_fwd on the kept keys.  Forward only.  Against a masked state (favor_keys with lens) the rows of v
     behind lens[t] must be finite - zero-fill them: their column of S is exactly 0, and 0 x NaN is not.  A "summary" state
     (favor_absorb) holds what it needs of v: `vh` may be None and is ignored; the call is row-invariant there too
@@ -769,9 +804,9 @@ def favor_query(qh, state, vh, proj, weights=False):
 
     `weights=True` -> (merged, w): w [T, H, Nq, Nc] = S / D of the same launch (mlhot_favor_query_weights_fwd),
     FAVOR+'s implied attention per head, query row and context slot - non-negative, rows summing to 1, exact zeros behind a masked
-    state's lens[t], row-invariant like merged; merged has the bits of the call without it.  "cached" states only: a "plain" or a
-    "summary" state raises MlhotError.  Without it the call launches what it always did."""
-    if weights and isinstance(state, FavorKeyState) and state.route != "cached":
+    state's lens[t], row-invariant like merged; merged has the bits of the call without it.  "cached" and "long" states only: a
+    "plain" or a "summary" state raises MlhotError.  Without it the call launches what it always did."""
+    if weights and isinstance(state, FavorKeyState) and state.route not in ("cached", "long"):
         if state.route == "summary":
             raise MlhotError("favor_query: weights=True - a summary state keeps no per-shot rows, so there is no weight per context shot to "
                              "read out (condition with the default form for at most 32 shots)")
@@ -801,6 +836,8 @@ def favor_query(qh, state, vh, proj, weights=False):
         if weights:
             return lib().favor_query_weights_fwd(qh, state.buf, vh, proj)
         return lib().favor_query_fwd(qh, state.buf, vh, proj)
+    if state.route == "long":
+        return lib().favor_query_long_fwd(qh, state.buf, vh, proj, lens=state.lens_dev, weights=weights)
     return lib().favor_fwd(qh, state.kh, vh, proj)[0]
 
 

@@ -6,10 +6,13 @@ import numbers
 
 import torch
 
-from mlhot.ops import agg_prefixes, favor_absorb, favor_keys, host_lens
+from mlhot.ops import agg_prefixes, favor_absorb, favor_keys, favor_keys_long, host_lens
 
 MAX_ATTENTION_CAPACITY = 32        # the cached FAVOR+ kernels' envelope on the context side (csrc/favor_cached.h)
-FORMS = ("keys", "summary")        # what an attention state holds: per-shot key features (<= 32 slots) or the fixed-size summary
+MAX_LONG_CAPACITY = 256            # the long per-shot kernels' (csrc/favor_long.h)
+# what an attention state holds: per-shot key features (<= 32 slots), the fixed-size summary, or per-shot key features in 32-slot
+# chunks (<= 256 slots)
+FORMS = ("keys", "summary", "long")
 
 
 def condition_args(what, T, Nslots, ctx_len, capacity, attention):
@@ -48,6 +51,27 @@ def summary_condition_args(what, T, Nslots, ctx_len, capacity, attention):
     if Nslots < 1:
         raise ValueError(f'{what}: form="summary" needs at least one context shot')
     return (Nslots,) * T if ctx_len is None else host_lens(ctx_len, T, 1, Nslots, f"{what}: ctx_len", ValueError)
+
+
+def long_condition_args(what, T, Nslots, ctx_len, capacity, attention):
+    """-> (lens, capacity) for condition(form="long"): always the masked path, lens defaults to every slot full."""
+    if not attention:
+        raise ValueError(f'{what}: form="long" serves the attention models; a latent state is one aggregate per task and is not '
+                         "capped at 32 shots - use the default form")
+    if Nslots < 1:
+        raise ValueError(f'{what}: form="long" needs at least one context shot')
+    lens = (Nslots,) * T if ctx_len is None else host_lens(ctx_len, T, 1, Nslots, f"{what}: ctx_len", ValueError)
+    if capacity is None:
+        capacity = Nslots
+    if isinstance(capacity, bool) or not isinstance(capacity, numbers.Integral):
+        raise ValueError(f"{what}: capacity must be an integer, got {capacity!r}")
+    capacity = int(capacity)
+    if capacity < Nslots:
+        raise ValueError(f"{what}: capacity = {capacity} is smaller than the {Nslots} context slots handed in")
+    if capacity > MAX_LONG_CAPACITY:
+        raise ValueError(f"{what}: capacity = {capacity} is outside the long attention kernels' envelope "
+                         f"(at most {MAX_LONG_CAPACITY} context slots per task)")
+    return lens, capacity
 
 
 def summary_extend_args(what, T, n, new_len):
@@ -119,8 +143,11 @@ def scatter(buf, idx, rows):
     return out
 
 
-def masked_keys(kh, proj, plan):
-    """The masked key state over the kept key rows kh [T, cap, H, d] (two launches, mlhot_favor_keys_ragged_fwd)."""
+def masked_keys(kh, proj, plan, form="keys"):
+    """The masked key state over the kept key rows kh [T, cap, H, d] (two launches): mlhot_favor_keys_ragged_fwd, or for form "long"
+    mlhot_favor_keys_long_fwd."""
+    if form == "long":
+        return favor_keys_long(kh, proj, lens=plan.total, lens_dev=plan.lens)
     return favor_keys(kh, proj, lens=plan.total, lens_dev=plan.lens)
 
 

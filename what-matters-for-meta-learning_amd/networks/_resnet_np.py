@@ -505,14 +505,19 @@ class ResNetNP(nn.Module):
         attention model takes at most 32).  Without either argument this is the call it always was.
 
         `form="summary"` (attention models): the state is FAVOR+'s fixed-size summary of the context - any number
-        of shots, `ctx_len` honoured, no `capacity`, no per-shot rows kept; extend absorbs any number of further shots."""
+        of shots, `ctx_len` honoured, no `capacity`, no per-shot rows kept; extend absorbs any number of further shots.
+
+        `form="long"` (attention models): per-shot key features for up to 256 slots (`capacity` defaults to
+        Nslots) through the chunked kernels of csrc/favor_long.h - `ctx_len`, `capacity`, extend and
+        `predict(..., return_attention=True)` all as for "keys"; the form that returns attention weights above 32 shots."""
         return context.condition(_CachedContext(self), batch_train_images, label_train, ctx_len, capacity, form)
 
     def extend(self, state, new_images, new_labels, new_len=None):
         """(ContextState, new ctx images [T, n, ...], their labels, new_len) -> a NEW ContextState whose task t holds new_len[t] more
         context shots (0 .. n each; default n), written behind its current ones; the old state stays valid.  Only the new shots
         run through the trunk, the task encoder and the head projections; then the masked key launches (attention) or the prefix
-        aggregate with its gather and `mu` (latent) run on the kept rows.  A state needs spare slots: condition with capacity=."""
+        aggregate with its gather and `mu` (latent) run on the kept rows.  A state needs spare slots: condition with capacity=.
+        A form="long" state grows the same way, its key features re-derived by mlhot.ops.favor_keys_long."""
         return context.extend(_CachedContext(self), state, new_images, new_labels, new_len)
 
     def _task_features(self, x_ctx, labels):
@@ -540,7 +545,7 @@ class ResNetNP(nn.Module):
         mlhot.ops.favor_query, so nothing behind the trunks depends on how many targets share the call.  `chunk` bounds the
         targets per launch sequence.  Against forward the result agrees to the kernels' tolerance, not to the bit.
 
-        `return_attention=True` (attention models, the default state form) -> (mu, attn): attn [T, heads, Nq, Nc
+        `return_attention=True` (attention models, state forms "keys" and "long") -> (mu, attn): attn [T, heads, Nq, Nc
         slots] is FAVOR+'s weight of every context slot for every head and target, read out of the same favor_query launch - rows
         sum to 1, slots behind a task's ctx_len are exact zeros, and mu has the bits of the call without the keyword.  A model
         without attention and a summary state refuse with ValueError."""
