@@ -393,6 +393,24 @@ int mlhot_favor_summary_query_fwd(const float* q, const void* state, const float
 int mlhot_favor_summary_merge(const void* const* states /* host array of n device pointers */, int n,
                               const float* m_floor /* one float, DEVICE memory, may be NULL */,
                               int T, int H, int d, int m, void* out, size_t state_bytes, void* stream);
+/* mlhot_favor_summary_gather: merge with a row per task.  n summary states of the same (H, d, m), 1 <= n <= 8, state i
+ *   with its own task count state_tasks[i] (both arrays in HOST memory) -> out, a state of T_out tasks.  parts: int32 [T_out][P][2] in
+ *   DEVICE memory, 1 <= P <= 8, 8-byte aligned; entry (i, u) of row t means "task u of state i is a part of output task t", i < 0 ends
+ *   the row.  The kernel reads the table itself - no host synchronisation, the call can be captured - and holds i to 0 .. n - 1 and u
+ *   to 0 .. state_tasks[i] - 1, so no table content reads out of bounds; whether the table means what the caller wants is the
+ *   caller's to check.  M' = max(M_0 .. M_{n-1}, *m_floor) over EVERY state passed, whether a part names it or not;  s_i as in merge
+ *   (1.0f exactly where M_i == M', also when both are -inf);  A'[t,h] = sum_p s_{i_p} A_{i_p}[u_p,h] and a' likewise, vs' and cnt'
+ *   plain sums, ONE chain per element over the row's parts in table order, through the fold step of merge: the same parts in the
+ *   same order give merge's bits.  A task without a part gets the rows of a fresh state (zeros, cnt 0).  EVERY float of out is
+ *   written (features >= m zeros by index, M's block M' and zeros, cnt's padding zeros), whatever out held; an input's paddings are
+ *   never trusted.  One launch over the slots of out.  MLHOT_ERR_ARG, nothing written: out overlaps an input, state_bytes is not
+ *   mlhot_favor_summary_bytes(T_out, H, d, m), n or P outside 1 .. 8.  Outside the shapes above for T_out or a state_tasks[i]:
+ *   MLHOT_ERR_UNSUPPORTED.  GPU build only.  Added within ABI 7: bindings look the symbol up. */
+int mlhot_favor_summary_gather(const void* const* states /* host array of n device pointers */,
+                               const int* state_tasks /* host array of n task counts */, int n,
+                               const int32_t* parts /* [T_out][P][2], DEVICE memory */, int P,
+                               const float* m_floor /* one float, DEVICE memory, may be NULL */,
+                               int T_out, int H, int d, int m, void* out, size_t state_bytes, void* stream);
 
 /* ---- prefix sweep beyond 32 context shots: chunked running FAVOR+ prefixes (csrc/favor_prefix_long.h) -------------
  * mlhot_favor_prefix_long_fwd: q[T,Nq,H,d], k, v[T,Nc,H,d], proj[m,d] -> out[K,T,Nq,d*H] in mlhot_favor_fwd's merged order; out[i]

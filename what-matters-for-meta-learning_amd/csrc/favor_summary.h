@@ -23,6 +23,8 @@
 //             F_q and of F_q a give the eps terms and the denominator.
 //   merge  grid (512 float4 slots of the state), ONE launch: n <= 8 states absorbed apart -> one, X' = sum_i exp(M_i - M') X_i
 //             (fsum::merge_kernel below)
+//   gather grid (512 float4 slots of the OUTPUT state), ONE launch: task t of the output = the sum of up to 8 (state, task) parts named
+//             by a table on the device - merge with a row per task (fsum::gather_kernel below)
 // No atomics; every sum has one order that depends on the dimensions alone.  ROW INVARIANCE of the query launch as in
 // favor_cached.h: a workgroup owns 16 rows and every feature of them, rows >= Nq are zeros and never stored, and every per-row sum
 // is laid out the same way at every row of a tile.
@@ -225,6 +227,26 @@ struct MergeArgs {
   int d4, mp, m, th;                      // d4: slots per row of A
 };
 
+// term p of an element's chain  s0 x0 + s1 x1 + s2 x2 + ..,  written with the roundings spelled out - they are the ones the
+// compiler's contraction of that sum has given merge_kernel since 6c-6 (of the first two products the SECOND is rounded and the first
+// fused onto it), so merge's bits stay where they were whatever a later compiler prefers:
+//   p == 0: o = rn(s0 x0)      p == 1: o = fma(s0, x0, rn(s1 x1))      p >= 2: o = fma(sp, xp, o)
+// merge_kernel and gather_kernel both fold through this step, so the same terms in the same order give the same bits in either.
+__device__ __forceinline__ void fold_step(float4& o, int p, float s0, const float4& x0, float sp, const float4& xp) {
+#pragma clang fp contract(off)
+  if (p == 0) { o.x = s0 * x0.x; o.y = s0 * x0.y; o.z = s0 * x0.z; o.w = s0 * x0.w; }
+  else if (p == 1) { o.x = fmaf(s0, x0.x, sp * xp.x); o.y = fmaf(s0, x0.y, sp * xp.y); o.z = fmaf(s0, x0.z, sp * xp.z); o.w = fmaf(s0, x0.w, sp * xp.w); }
+  else { o.x = fmaf(sp, xp.x, o.x); o.y = fmaf(sp, xp.y, o.y); o.z = fmaf(sp, xp.z, o.z); o.w = fmaf(sp, xp.w, o.w); }
+}
+// features >= m of a slot of A (one feature row `row`) or of a (the four features j .. j + 3) are zeros by index
+__device__ __forceinline__ void zero_row_behind_m(float4& o, int row, int m) { if (row >= m) o = float4{0.f, 0.f, 0.f, 0.f}; }
+__device__ __forceinline__ void zero_features_behind_m(float4& o, int j, int m) {
+  if (j >= m) o.x = 0.f;
+  if (j + 1 >= m) o.y = 0.f;
+  if (j + 2 >= m) o.z = 0.f;
+  if (j + 3 >= m) o.w = 0.f;
+}
+
 template <int N>
 __global__ __launch_bounds__(256) void merge_kernel(const MergeArgs a) {
   float s[N];
@@ -251,19 +273,11 @@ __global__ __launch_bounds__(256) void merge_kernel(const MergeArgs a) {
       const bool plain = q >= a.vs_at;
       o = float4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int i = 0; i < N; ++i) {
-        const float si = plain ? 1.f : s[i];
-        if (i == 0) { o.x = si * x[u][0].x; o.y = si * x[u][0].y; o.z = si * x[u][0].z; o.w = si * x[u][0].w; }
-        else { o.x += si * x[u][i].x; o.y += si * x[u][i].y; o.z += si * x[u][i].z; o.w += si * x[u][i].w; }
-      }
+      for (int i = 0; i < N; ++i) fold_step(o, i, plain ? 1.f : s[0], x[u][0], plain ? 1.f : s[i], x[u][i]);
       if (q < a.a_at) {                    // a slot of A lies in one feature row: (task x head, row) = slot / d4
-        if ((int)((q / a.d4) % a.mp) >= a.m) o = float4{0.f, 0.f, 0.f, 0.f};
+        zero_row_behind_m(o, (int)((q / a.d4) % a.mp), a.m);
       } else if (!plain) {                 // four features of a, never across a (task, head): mp % 4 == 0
-        const int j = (int)((4 * (q - a.a_at)) % a.mp);
-        if (j >= a.m) o.x = 0.f;
-        if (j + 1 >= a.m) o.y = 0.f;
-        if (j + 2 >= a.m) o.z = 0.f;
-        if (j + 3 >= a.m) o.w = 0.f;
+        zero_features_behind_m(o, (int)((4 * (q - a.a_at)) % a.mp), a.m);
       }
     } else if (q < a.cnt_at) {             // M's block of 16: M', then zeros as init leaves them
       o = float4{q == a.m_at ? M : 0.f, 0.f, 0.f, 0.f};
@@ -276,6 +290,136 @@ __global__ __launch_bounds__(256) void merge_kernel(const MergeArgs a) {
       }
       o = float4{__int_as_float(e < a.th ? c[0] : 0), __int_as_float(e + 1 < a.th ? c[1] : 0), __int_as_float(e + 2 < a.th ? c[2] : 0),
                  __int_as_float(e + 3 < a.th ? c[3] : 0)};
+    }
+    reinterpret_cast<float4*>(a.out)[q] = o;
+  }
+}
+
+// ---- gather: task t of the output = the sum of up to 8 (state, task) parts, named by a table on the device ---------
+// merge with a row per task.  The stream runs over the float4 slots of the OUTPUT state; region, (task, head) and the offset inside the
+// task come from the flat slot index as in merge_kernel.  Inside a region a task's rows lie at the same offsets in every state - only the
+// region's start depends on the state's own task count T_i - so part (i, u) of a slot is read at  T_i x (the floats per task of the regions
+// in front) + u x (the region's floats per task) + (the offset inside the task).  A lane owns MERGE_U slots one grid stride apart (they
+// may belong to different tasks); it reads their table rows, issues the MERGE_U * P loads, then folds every slot's parts in table order
+// through merge's fold_step in ONE chain.  M' is the maximum over all n states passed (and the floor), whether a part names them or not;
+// the n pointers, task counts and scales stand in LDS for the per-lane lookup - every workgroup fills its own copy from the kernel
+// arguments, nothing is exchanged between workgroups.  No atomics, no scratch.  Whatever the table holds, the state index is held to
+// 0 .. n - 1 and the task index to 0 .. T_i - 1 (ft::clamp_len's rule: the host checks the values, the clamp keeps every read in bounds).
+constexpr int GATHER_P = 8;               // parts per task and launch
+
+struct GatherArgs {
+  const float* in[MERGE_MAX];
+  int Ti[MERGE_MAX];                      // tasks of each source state
+  const int32_t* parts;                   // [T_out][P][2] on the device: (state, task); state < 0 ends a task's list
+  const float* floor;                     // one float on the device, or nullptr
+  float* out;
+  long a_at, vs_at, m_at, cnt_at, n4;     // of the OUTPUT, in float4 slots (MergeArgs)
+  long fA, fa, fv;                        // floats per task of A, a and vs
+  int d4, d, mp, m, th, H, n;             // th: T_out H
+};
+
+// part p of a task's table row -> (live, state, task), the indices held to their ranges; `on` stays false behind the first state < 0
+__device__ __forceinline__ void gather_part(const int32_t* row, int p, int n, const int* s_T, bool& on, int& i, int& u) {
+  const int2 e = reinterpret_cast<const int2*>(row)[p];
+  on = on && e.x >= 0;
+  i = on ? min(e.x, n - 1) : 0;
+  u = min(max(e.y, 0), s_T[i] - 1);
+}
+
+template <int P>
+__global__ __launch_bounds__(256) void gather_kernel(const GatherArgs a) {
+  __shared__ const float* s_in[MERGE_MAX];
+  __shared__ float s_s[MERGE_MAX];
+  __shared__ int s_T[MERGE_MAX];
+  const long fT = a.fA + a.fa + a.fv;     // floats per task in front of M's block
+  float M = a.floor ? a.floor[0] : -INFINITY;
+  {
+    float Mi[MERGE_MAX];
+#pragma unroll
+    for (int i = 0; i < MERGE_MAX; ++i) { Mi[i] = i < a.n ? a.in[i][(long)a.Ti[i] * fT] : -INFINITY; M = fmaxf(M, Mi[i]); }
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int i = 0; i < MERGE_MAX; ++i) {                  // slots >= n are never looked up: the state index is held below n
+        s_in[i] = a.in[i < a.n ? i : 0]; s_T[i] = a.Ti[i < a.n ? i : 0];
+        s_s[i] = Mi[i] == M ? 1.f : expf(Mi[i] - M);
+      }
+    }
+  }
+  __syncthreads();
+  const long stride = (long)gridDim.x * 256;
+  const long q0 = (long)blockIdx.x * 256 + threadIdx.x;
+  float4 x[MERGE_U][P];
+  float sc[MERGE_U][P];
+  bool live[MERGE_U][P];
+  int row_or_j[MERGE_U];                  // the feature row of a slot of A, the first of the four features of a slot of a
+#pragma unroll
+  for (int u = 0; u < MERGE_U; ++u) {
+    const long q = q0 + u * stride;
+    long w = 0, per = 0, pre = 0;         // the offset inside the task, the region's floats per task, the floats per task in front of it
+    int th = 0;
+    const bool sums = q < a.m_at;
+    const bool plain = q >= a.vs_at;
+    row_or_j[u] = 0;
+    if (q < a.a_at) {                      // A: slot / d4 is the feature row of all (task, head) rows, below 2^31 inside the envelope
+      const long R = q / a.d4;
+      const unsigned r = (unsigned)R;
+      th = (int)(r / (unsigned)a.mp);
+      row_or_j[u] = (int)(r - (unsigned)th * (unsigned)a.mp);
+      w = ((long)(th % a.H) * a.mp + row_or_j[u]) * a.d + 4 * (q - R * a.d4); per = a.fA;
+    } else if (!plain) {                   // a: four features of one (task, head)
+      const unsigned e = (unsigned)(4 * (q - a.a_at));
+      th = (int)(e / (unsigned)a.mp);
+      row_or_j[u] = (int)(e - (unsigned)th * (unsigned)a.mp);
+      w = (long)(th % a.H) * a.mp + row_or_j[u]; per = a.fa; pre = a.fA;
+    } else if (sums) {                     // vs: four columns of one (task, head)
+      const unsigned e = (unsigned)(4 * (q - a.vs_at));
+      th = (int)(e / (unsigned)a.d);
+      w = (long)(th % a.H) * a.d + (e - (unsigned)th * (unsigned)a.d); per = a.fv; pre = a.fA + a.fa;
+    }
+    const int32_t* row = a.parts + (long)(th / a.H) * (2 * P);
+    bool on = sums;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      int i = 0, t = 0;
+      if (sums) gather_part(row, p, a.n, s_T, on, i, t);
+      live[u][p] = on;
+      sc[u][p] = plain ? 1.f : s_s[i];
+      // the pointer comes out of LDS: gfptr says it is global memory (global_load, not flat_load)
+      typedef const __attribute__((address_space(1))) f32x4_t* g4ptr;
+      f32x4_t v = {0.f, 0.f, 0.f, 0.f};
+      if (on) v = *(g4ptr)((gfptr)s_in[i] + ((long)s_T[i] * pre + (long)t * per + w));
+      x[u][p] = float4{v[0], v[1], v[2], v[3]};
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < MERGE_U; ++u) {
+    const long q = q0 + u * stride;
+    if (q >= a.n4) continue;
+    float4 o = float4{0.f, 0.f, 0.f, 0.f};     // a task without a part: the rows of a fresh state
+    if (q < a.m_at) {                      // A, a (rescaled) and vs (plain): one chain, the parts in table order
+#pragma unroll
+      for (int p = 0; p < P; ++p)
+        if (live[u][p]) fold_step(o, p, sc[u][0], x[u][0], sc[u][p], x[u][p]);
+      if (q < a.a_at) zero_row_behind_m(o, row_or_j[u], a.m);
+      else if (q < a.vs_at) zero_features_behind_m(o, row_or_j[u], a.m);
+    } else if (q < a.cnt_at) {             // M's block of 16: M', then zeros as init leaves them
+      o.x = q == a.m_at ? M : 0.f;
+    } else {                               // cnt: int32 sums per (task, head); the padding behind T_out H stays 0
+      const long e = 4 * (q - a.cnt_at);
+      int c[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (e + k >= a.th) continue;
+        const int th = (int)(e + k);
+        const int32_t* row = a.parts + (long)(th / a.H) * (2 * P);
+        bool on = true;
+        for (int p = 0; p < P; ++p) {
+          int i, t;
+          gather_part(row, p, a.n, s_T, on, i, t);
+          if (on) c[k] += __float_as_int(((gfptr)s_in[i])[(long)s_T[i] * fT + 16 + (long)t * a.H + th % a.H]);
+        }
+      }
+      o = float4{__int_as_float(c[0]), __int_as_float(c[1]), __int_as_float(c[2]), __int_as_float(c[3])};
     }
     reinterpret_cast<float4*>(a.out)[q] = o;
   }
@@ -397,6 +541,60 @@ inline int favor_summary_merge(const void* const* states, int n, const float* m_
     default: hipLaunchKernelGGL((fsum::merge_kernel<8>), grid, dim3(256), 0, s, a); break;
   }
   return check_launch("favor.sum_merge");
+#endif
+}
+
+// states: n device pointers, tasks: their n task counts, both in HOST memory; parts: int32 [T_out][P][2] in DEVICE memory, read by the
+// kernel alone (no host synchronisation: the call can be captured); m_floor as in merge
+inline int favor_summary_gather(const void* const* states, const int* tasks, int n, const int32_t* parts, int P, const float* m_floor, int T_out, int H,
+                                int d, int m, void* out, size_t state_bytes, hipStream_t s) {
+  if (T_out <= 0 || H <= 0 || d <= 0 || m <= 0 || !states || !tasks || !parts || !out) { set_error("favor_summary_gather: bad argument"); return MLHOT_ERR_ARG; }
+  if (n < 1 || n > 8) { set_error("favor_summary_gather takes 1 .. 8 states per call (got n=%d): fold more in groups", n); return MLHOT_ERR_ARG; }
+  if (P < 1 || P > 8) { set_error("favor_summary_gather takes 1 .. 8 parts per task and call (got P=%d)", P); return MLHOT_ERR_ARG; }
+  for (int i = 0; i < n; ++i)
+    if (tasks[i] <= 0) { set_error("favor_summary_gather: state %d has %d tasks", i, tasks[i]); return MLHOT_ERR_ARG; }
+  for (int i = -1; i < n; ++i)
+    if (!favor_summary_ok(i < 0 ? T_out : tasks[i], H, d, m)) return favor_summary_unsupported("favor_summary_gather", d, m);
+#ifdef MLHOT_HOSTSIM
+  (void)m_floor; (void)state_bytes; (void)s; return MLHOT_ERR_UNSUPPORTED;
+#else
+  static_assert(fsum::GATHER_P == 8 && fsum::MERGE_MAX == 8, "the entry's checks and the launch table below are written for 8");
+  const fsum::State st = fsum::carve_state(T_out, H, d, m, out);
+  const size_t need = st.floats * sizeof(float);
+  if (state_bytes != need) { set_error("favor_summary_gather: state_bytes must be mlhot_favor_summary_bytes' %zu for T_out=%d (got %zu)", need, T_out, state_bytes); return MLHOT_ERR_ARG; }
+  if (!ft::aligned16(out) || (m_floor && (reinterpret_cast<uintptr_t>(m_floor) & 3)) || (reinterpret_cast<uintptr_t>(parts) & 7)) {
+    set_error("favor_summary_gather: out must be 16-byte aligned, parts 8-byte, m_floor 4-byte"); return MLHOT_ERR_ARG;
+  }
+  fsum::GatherArgs a{};
+  const char* ob = (const char*)out;
+  for (int i = 0; i < n; ++i) {
+    const char* ib = (const char*)states[i];
+    if (!ib || !ft::aligned16(ib)) { set_error("favor_summary_gather: state %d is NULL or not 16-byte aligned", i); return MLHOT_ERR_ARG; }
+    const size_t have = fsum::carve_state(tasks[i], H, d, m, nullptr).floats * sizeof(float);
+    if (ib < ob + need && ob < ib + have) {       // every workgroup reads every old M and one writes the new one: out is a buffer of its own
+      set_error("favor_summary_gather: out overlaps input state %d; the gathered state needs its own buffer", i); return MLHOT_ERR_ARG;
+    }
+    a.in[i] = (const float*)states[i]; a.Ti[i] = tasks[i];
+  }
+  a.parts = parts; a.floor = m_floor; a.out = (float*)out;
+  a.a_at = (long)((st.a - st.A) / 4); a.vs_at = (long)((st.vs - st.A) / 4); a.m_at = (long)((st.M - st.A) / 4); a.cnt_at = a.m_at + 4;
+  a.n4 = (long)(st.floats / 4);
+  a.fA = (long)H * st.mp * d; a.fa = (long)H * st.mp; a.fv = (long)H * d;
+  a.d4 = d / 4; a.d = d; a.mp = st.mp; a.m = m; a.th = T_out * H; a.H = H; a.n = n;
+  if ((a.n4 + 256 * fsum::MERGE_U - 1) / (256 * fsum::MERGE_U) >= (1l << 31)) { set_error("favor_summary_gather: the state is too large for one grid"); return MLHOT_ERR_ARG; }
+  ProfScope ps("favor.sum_gather", s);
+  const dim3 grid((unsigned)((a.n4 + 256 * fsum::MERGE_U - 1) / (256 * fsum::MERGE_U)));
+  switch (P) {
+    case 1: hipLaunchKernelGGL((fsum::gather_kernel<1>), grid, dim3(256), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((fsum::gather_kernel<2>), grid, dim3(256), 0, s, a); break;
+    case 3: hipLaunchKernelGGL((fsum::gather_kernel<3>), grid, dim3(256), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((fsum::gather_kernel<4>), grid, dim3(256), 0, s, a); break;
+    case 5: hipLaunchKernelGGL((fsum::gather_kernel<5>), grid, dim3(256), 0, s, a); break;
+    case 6: hipLaunchKernelGGL((fsum::gather_kernel<6>), grid, dim3(256), 0, s, a); break;
+    case 7: hipLaunchKernelGGL((fsum::gather_kernel<7>), grid, dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL((fsum::gather_kernel<8>), grid, dim3(256), 0, s, a); break;
+  }
+  return check_launch("favor.sum_gather");
 #endif
 }
 

@@ -367,6 +367,10 @@ int mlhot_favor_summary_merge(const void* const* states, int n, const float* m_f
                               void* stream) {
   return favor_summary_merge(states, n, m_floor, T, H, d, m, out, state_bytes, (hipStream_t)stream);
 }
+int mlhot_favor_summary_gather(const void* const* states, const int* state_tasks, int n, const int32_t* parts, int P, const float* m_floor, int T_out,
+                               int H, int d, int m, void* out, size_t state_bytes, void* stream) {
+  return favor_summary_gather(states, state_tasks, n, parts, P, m_floor, T_out, H, d, m, out, state_bytes, (hipStream_t)stream);
+}
 // K context prefixes of any length: running sums over 32-shot chunks, three launches (csrc/favor_prefix_long.h)
 int mlhot_favor_prefix_long_supported(int T, int H, int Nq, int Nc, int d, int m, int K) { return favor_prefix_long_ok(T, H, Nq, Nc, d, m, K) ? 1 : 0; }
 size_t mlhot_favor_prefix_long_workspace_bytes(int T, int H, int Nq, int Nc, int d, int m, int K) { return favor_prefix_long_ws_need(T, H, Nq, Nc, d, m, K); }

@@ -283,6 +283,7 @@ SIGNATURES = {
     "mlhot_favor_summary_query_ws_bytes": (z, [i] * 5),
     "mlhot_favor_summary_query_fwd": (i, [P, P, P, i, i, i, i, i, P, P, z, P]),
     "mlhot_favor_summary_merge": (i, [P, i, P, i, i, i, i, P, z, P]),
+    "mlhot_favor_summary_gather": (i, [P, P, i, P, i, P, i, i, i, i, P, z, P]),
     # prefix sweep beyond 32 context shots: chunked running FAVOR+ prefixes
     "mlhot_favor_prefix_long_supported": (i, [i] * 7),
     "mlhot_favor_prefix_long_workspace_bytes": (z, [i] * 7),
@@ -1289,6 +1290,44 @@ class MlhotLib:
         _chk(out, floor, *bufs)
         table = (C.c_void_p * len(bufs))(*[b.data_ptr() for b in bufs])
         self._rc(fn(table, len(bufs), _ptr(floor), T, H, d, m, _ptr(out), nb, _stream(out)), "mlhot_favor_summary_merge")
+        return out
+
+    GATHER_PARTS = 8       # parts per task and mlhot_favor_summary_gather call
+
+    def favor_summary_gather(self, bufs, tasks, parts, H, d, m, floor=None, out=None):
+        """1 .. 8 summary states of the same (H, d, m) - bufs[i] (uint8) holds tasks[i] tasks - and parts, an int32 [T_out, P, 2]
+        tensor on their device (1 <= P <= 8; entry (i, u): task u of state i, i < 0 ends a row) -> the state of T_out tasks whose
+        task t is the sum of its row's parts, in a buffer of its own (`out`, or a new one); the inputs are only read.  M' = max of
+        ALL the states' stabilisers and of `floor` (as in favor_summary_merge); the kernel reads the table and holds every index to
+        its range, whether the table means what the caller wants is the caller's to check (include/mlhot.h).
+        One launch."""
+        fn = self._fn("favor_summary_gather", "mlhot_favor_summary_gather")
+        bufs, tasks = list(bufs), [int(t) for t in tasks]
+        if not 1 <= len(bufs) <= self.MERGE_MAX or len(tasks) != len(bufs):
+            raise MlhotError(f"favor_summary_gather takes 1 .. {self.MERGE_MAX} states per call and one task count for each (got {len(bufs)} states, "
+                             f"{len(tasks)} counts); mlhot.ops.favor_gather folds more in groups")
+        if not isinstance(parts, torch.Tensor) or parts.dtype != torch.int32 or parts.dim() != 3 or parts.shape[0] < 1 or parts.shape[2] != 2 \
+                or not 1 <= parts.shape[1] <= self.GATHER_PARTS:
+            raise MlhotError(f"favor_summary_gather: parts must be an int32 [T_out, P, 2] tensor with 1 <= P <= {self.GATHER_PARTS}, got "
+                             f"{getattr(parts, 'dtype', type(parts).__name__)} {tuple(getattr(parts, 'shape', ()))}")
+        T_out, P = parts.shape[0], parts.shape[1]
+        need = [self.favor_summary_bytes(t, H, d, m) if t >= 1 else 0 for t in tasks]
+        nb = self.favor_summary_bytes(T_out, H, d, m)
+        if not nb or not all(need):
+            raise MlhotError(f"favor_summary_gather serves d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536 and at least one task per state "
+                             f"(got d={d} m={m}, tasks {tasks} -> {T_out})")
+        if out is None:
+            out = torch.empty(nb, dtype=torch.uint8, device=bufs[0].device)
+        for name, s, want in [(f"state {k}", b, n) for k, (b, n) in enumerate(zip(bufs, need))] + [("out", out, nb), ("parts", parts, 0)]:
+            if not isinstance(s, torch.Tensor) or s.device != bufs[0].device or not s.is_cuda or (want and (s.dtype != torch.uint8 or s.numel() < want)):
+                raise MlhotError(f"favor_summary_gather: {name} is not a summary state for H={H} d={d} m={m} on one GPU ({want} bytes needed)"
+                                 if want else f"favor_summary_gather: parts must lie on the states' GPU, {bufs[0].device}")
+        if floor is not None and (not isinstance(floor, torch.Tensor) or floor.dtype != torch.float32 or floor.numel() != 1 or floor.device != out.device):
+            raise MlhotError(f"favor_summary_gather: floor must be one fp32 value on {out.device}")
+        _chk(out, floor, parts, *bufs)
+        table = (C.c_void_p * len(bufs))(*[b.data_ptr() for b in bufs])
+        counts = (C.c_int * len(bufs))(*tasks)
+        self._rc(fn(table, counts, len(bufs), _ptr(parts), P, _ptr(floor), T_out, H, d, m, _ptr(out), nb, _stream(out)), "mlhot_favor_summary_gather")
         return out
 
     # ---- prefix sweep beyond 32 context shots (csrc/favor_prefix_long.h) --------------------------

@@ -4,6 +4,8 @@
                                                                     # "long": per-shot rows for up to 256 shots, attention read-out (6c-7)
     state = mlhot.cached.extend(model, state, new_x, new_y, new_len=None)        # more context shots, only they are encoded (6c-3)
     state = mlhot.cached.merge(model, [state_a, state_b, ..])       # summary states conditioned apart -> one, no image re-read (6c-6)
+    state = mlhot.cached.select(model, [state_a, state_b, ..], picks)      # a batch put together from the TASKS of summary states:
+                                                                    # picks[t] = (state, task) or a list of such pairs (6c-8)
     mu = mlhot.cached.predict(model, state, qry_x, chunk=None)        # [T, Nq, y_dim]
     mu, attn = mlhot.cached.predict(model, state, qry_x, return_attention=True)      # attn [T, 8, Nq, Nc slots]: FAVOR+'s weight per context
                                                                                       # slot, head and target (attention models; 6c-5)
@@ -222,6 +224,21 @@ def merge(model, states):
     result like any summary state.  Both families; eval mode.  A latent state (it is stored behind its finishing Linear), a
     form="keys" state (capped per-shot rows), a foreign or a stale state raise ValueError."""
     return context.merge(_CachedContext(model) if isinstance(model, ResNetNP) else _Vanilla(model), states)
+
+
+def select(model, states, picks):
+    """(summary states of this model, conditioned apart on ANY batches; picks) -> a NEW state for a batch put together from their
+    tasks: a stored library of per-object contexts served as whatever batch is asked for.  `picks` has
+    `tasks_per_batch` entries; entry t is one (state_index, task_index) pair - task t of the result is that task - or a list of
+    1 .. 8 pairs whose context shots add up, as `merge` adds whole states.  Objects conditioned in batches (a0, a1) and (b0, b1) are
+    queried as (a1, b0) with `select(model, [a, b], [(0, 1), (1, 0)])`; the same pair may stand in several tasks, tasks and states
+    that no pick names are left out.  One launch per 8 named states over the states alone (mlhot.ops.favor_gather) - no image is
+    encoded again.  The result is what `condition(..., form="summary")` builds from the chosen shots in a batch whose key stabiliser
+    is the maximum over the named states - the reference's forward on the UNION of the source batches, restricted to the picked
+    tasks; a batch of the picked tasks alone may have a lower stabiliser, which moves the result within the eps terms (6c-6).
+    `predict` and `extend` serve the result like any summary state.  Both families; eval mode.  A foreign, stale, latent, "keys" or
+    "long" state, an empty pick and the same pair twice inside one task raise ValueError."""
+    return context.select(_CachedContext(model) if isinstance(model, ResNetNP) else _Vanilla(model), states, picks)
 
 
 def predict(model, state, qry_x, chunk=None, route=None, return_attention=False):

@@ -1,5 +1,5 @@
-"""Cached-context inference, the part both model families share (DESIGN.md 6c - 6c-7): the state `condition` leaves for `predict`, and
-the lifecycle condition -> extend / merge -> predict with its entry checks, written once.  ResNetNP.condition / extend / predict
+"""Cached-context inference, the part both model families share (DESIGN.md 6c - 6c-8): the state `condition` leaves for `predict`, and
+the lifecycle condition -> extend / merge / select -> predict with its entry checks, written once.  ResNetNP.condition / extend / predict
 (networks/_resnet_np.py) and mlhot.cached.condition / extend / predict (the vanilla family) are thin callers of the functions here.
 
 What differs per family comes in as an adapter `ad`, a small object with
@@ -14,10 +14,12 @@ What differs per family comes in as an adapter `ad`, a small object with
     predict_targets(state, qry_x)       one launch sequence for the targets of one chunk -> mu [T, n, y_dim]; called with
                                         attention=True for predict(return_attention=True) -> (mu, attn [T, H, n, Nc])
 This module imports nothing from networks/: both families import it."""
+import numbers
+
 import torch
 
 from mlhot import lib, ragged
-from mlhot.ops import LinearFunction, favor_keys, favor_merge
+from mlhot.ops import GATHER_PARTS, LinearFunction, favor_gather, favor_keys, favor_merge
 
 
 class ContextState:
@@ -118,13 +120,9 @@ def extend(ad, state, new_x, new_y, new_len=None):
         return _grow(ad, state, state.lens, state.capacity, new_x, new_y, add, state.wq, state.form)
 
 
-def merge(ad, states):
-    """Summary states of ONE model that were conditioned apart - shards of a context, several sources, stored per-object contexts -
-    -> a NEW state holding all their shots, as if condition(form="summary") had seen them together (DESIGN.md 6c-6:
-    mlhot.ops.favor_merge, one launch per 8 states, no image is encoded again).  The inputs stay valid.  `lens` add up, `Nc` is their
-    maximum; predict and extend serve the result like any summary state."""
-    what = "merge"
-    ad.refuse(what)
+def _summary_states(ad, what, states, same_tasks=True):
+    """merge's and select's checks of their states: a non-empty sequence of this model's own, fresh attention states of
+    form="summary" -> the list."""
     try:
         states = list(states)
     except TypeError:
@@ -136,19 +134,69 @@ def merge(ad, states):
             raise ValueError(f"{what}: the state was not made by this model's condition() (states[{i}])")
         if s.kind != "attention":
             raise ValueError(f"{what}: states[{i}] is a {s.kind!r} state - it is stored behind its finishing Linear, which is not a sum over "
-                             "shots any more; only attention states of form=\"summary\" merge")
+                             f"shots any more; only attention states of form=\"summary\" {what}")
         if s.form != "summary":
             slots = ragged.MAX_LONG_CAPACITY if s.form == "long" else ragged.MAX_ATTENTION_CAPACITY
             raise ValueError(f"{what}: states[{i}] has form {s.form!r} - it holds per-shot rows in at most {slots} "
                              "slots, not sums over shots; condition the parts with form=\"summary\"")
-        if s.T != states[0].T or s.T != ad.model.task_num:
+        if same_tasks and (s.T != states[0].T or s.T != ad.model.task_num):
             raise ValueError(f"{what}: states[{i}] holds {s.T} tasks, states[0] {states[0].T}, the model {ad.model.task_num} (the key stabiliser "
                              f"is the maximum over the conditioned batch: {what} serves the same tasks)")
         if s.fingerprint != fingerprint(ad.model):
             raise ValueError(f"{what}: the state is stale - a parameter of the model changed since condition() (states[{i}])")
+    return states
+
+
+def merge(ad, states):
+    """Summary states of ONE model that were conditioned apart - shards of a context, several sources, stored per-object contexts -
+    -> a NEW state holding all their shots, as if condition(form="summary") had seen them together (DESIGN.md 6c-6:
+    mlhot.ops.favor_merge, one launch per 8 states, no image is encoded again).  The inputs stay valid.  `lens` add up, `Nc` is their
+    maximum; predict and extend serve the result like any summary state."""
+    what = "merge"
+    ad.refuse(what)
+    states = _summary_states(ad, what, states)
     with torch.no_grad():
         keys = favor_merge([s.keys for s in states])
     return ContextState(ad.model, states[0].T, max(keys.lens), states[0].fingerprint, "attention", keys=keys, wq=states[0].wq, lens=keys.lens,
+                        form="summary")
+
+
+def select(ad, states, picks):
+    """Pick and combine TASKS across summary states of ONE model (mlhot.ops.favor_gather, no image is encoded
+    again): `picks` has one entry per task of the model's batch, a (state_index, task_index) pair or a list of 1 .. 8 such pairs
+    whose shots add up -> a NEW summary state whose task t holds them.  Any task of any state can stand in any slot, also in
+    several; tasks that no pick names are left out, and so are states that no pick names (they do not enter the stabiliser).  The
+    inputs stay valid; predict and extend serve the result like any summary state.  It is the state condition(form="summary")
+    builds from the chosen shots in a batch whose stabiliser is the maximum over the named states."""
+    what = "select"
+    ad.refuse(what)
+    states = _summary_states(ad, what, states, same_tasks=False)
+    try:
+        picks = list(picks)
+    except TypeError:
+        raise ValueError(f"{what}: picks must be a sequence with one entry per task, got {type(picks).__name__}") from None
+    if len(picks) != ad.model.task_num:
+        raise ValueError(f"{what}: {len(picks)} picks, the model was built for tasks_per_batch = {ad.model.task_num}")
+    table = []
+    for t, pick in enumerate(picks):
+        if isinstance(pick, (tuple, list)) and len(pick) == 2 and all(isinstance(x, numbers.Integral) for x in pick):
+            pick = [pick]                               # one pair
+        try:
+            pick = [tuple(pair) for pair in pick]
+        except TypeError:
+            raise ValueError(f"{what}: picks[{t}] must be a (state_index, task_index) pair or a list of such pairs, got {pick!r}") from None
+        if not pick:
+            raise ValueError(f"{what}: picks[{t}] is empty - a task without a context shot has no attention (0 / 0)")
+        if len(pick) > GATHER_PARTS:
+            raise ValueError(f"{what}: picks[{t}] names {len(pick)} parts; a task takes at most {GATHER_PARTS}")
+        if len(set(pick)) != len(pick):
+            twice = next(pair for k, pair in enumerate(pick) if pair in pick[:k])
+            raise ValueError(f"{what}: picks[{t}] names {twice} twice - its shots would count double inside one task (the same pair may "
+                             "stand in different tasks)")
+        table.append(pick)
+    with torch.no_grad():
+        keys = favor_gather([s.keys for s in states], table)          # ValueError for a pair that is no pair or out of range
+    return ContextState(ad.model, len(table), max(keys.lens), states[0].fingerprint, "attention", keys=keys, wq=states[0].wq, lens=keys.lens,
                         form="summary")
 
 

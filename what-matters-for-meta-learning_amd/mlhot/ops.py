@@ -793,6 +793,101 @@ def favor_merge(states, floor=None):
     return FavorKeyState("summary", (T, max(total), H, d, m), buf=buf, lens=total)
 
 
+GATHER_PARTS = 8           # parts per output task of favor_gather
+
+
+def _gather_parts(parts, states):
+    """favor_gather's table on the host: parts[t] = a sequence of (state_index, task_index) pairs -> a list of lists of int pairs,
+    every index in range, at most 8 pairs per task; ValueError names what is wrong."""
+    try:
+        rows = [list(row) for row in parts]
+    except TypeError:
+        raise ValueError("favor_gather: parts must be a sequence with one sequence of (state_index, task_index) pairs per output task") from None
+    if not rows:
+        raise ValueError("favor_gather: parts is empty - the gathered state needs at least one task")
+    table = []
+    for t, row in enumerate(rows):
+        if len(row) > GATHER_PARTS:
+            raise ValueError(f"favor_gather: parts[{t}] names {len(row)} parts; a task takes at most {GATHER_PARTS}")
+        pairs = []
+        for p, pair in enumerate(row):
+            try:
+                i, u = pair
+            except (TypeError, ValueError):
+                raise ValueError(f"favor_gather: parts[{t}][{p}] must be a (state_index, task_index) pair, got {pair!r}") from None
+            if any(isinstance(x, bool) or not isinstance(x, numbers.Integral) for x in (i, u)):
+                raise ValueError(f"favor_gather: parts[{t}][{p}] must hold two integers, got {pair!r}")
+            if not 0 <= i < len(states):
+                raise ValueError(f"favor_gather: parts[{t}][{p}] names state {i}; there are {len(states)} states (0 .. {len(states) - 1})")
+            if not 0 <= u < states[i].dims[0]:
+                raise ValueError(f"favor_gather: parts[{t}][{p}] names task {u} of states[{i}], which holds {states[i].dims[0]} tasks "
+                                 f"(0 .. {states[i].dims[0] - 1})")
+            pairs.append((int(i), int(u)))
+        table.append(pairs)
+    return table
+
+
+def favor_gather(states, parts, floor=None):
+    """Pick and combine TASKS across summary states: output task t = the sum of the parts parts[t] = [(state_index,
+    task_index), ..] - merge with a row per task -> ONE new FavorKeyState of route "summary" with len(parts) tasks; the inputs stay
+    valid and unchanged.  Any task of any state can move into any slot, the same task may stand in several slots, tasks can be
+    dropped, and the states may hold different numbers of tasks.  With M' = the maximum of the stabilisers of the states that a
+    part names (and of `floor`): A'[t] = sum_p exp(M_i - M') A_i[u] over parts[t], a' likewise, vs' and cnt' plain sums, one chain
+    per element in the order of parts[t] (csrc/favor_summary.h) - in exact arithmetic the state favor_absorb builds from the chosen
+    shots in a batch whose stabiliser is M'.  A task without a part gets the rows of a fresh state (favor_query refuses it).
+
+    `states`: a non-empty sequence of summary states of the same (H, d, m), device and dtype; `parts`: a host sequence, at most 8
+    pairs per task, every index in range - else ValueError, before any launch.  States that no part names are dropped before the
+    call: they do not enter M'.  More than 8 named states are folded in groups like favor_merge's: the first 8 in one launch, then
+    the running result (as the first part of every task that has one) with the next 7, and so on - the order of every sum is a
+    function of the arguments alone.  lens[t] is the sum of the parts' lens, dims carries len(parts) and max(lens).  `floor` as in
+    favor_merge.  Forward only."""
+    try:
+        states = list(states)
+    except TypeError:
+        raise ValueError(f"favor_gather: states must be a sequence of summary states, got {type(states).__name__}") from None
+    if not states:
+        raise ValueError("favor_gather: needs at least one summary state (got an empty sequence)")
+    for i, s in enumerate(states):
+        if not isinstance(s, FavorKeyState):
+            raise ValueError(f"favor_gather: states[{i}] is a {type(s).__name__}, not a FavorKeyState of favor_absorb")
+        if s.route != "summary":
+            why = ("favor_keys' per-shot states hold rows, not sums: their tasks do not combine (build the parts with favor_absorb)"
+                   if s.route in ("cached", "long") else "only favor_absorb's summary states are sums over shots")
+            raise ValueError(f"favor_gather: states[{i}] has route {s.route!r}; {why}")
+    _, _, H, d, m = states[0].dims
+    for i, s in enumerate(states[1:], 1):
+        if tuple(s.dims[2:]) != (H, d, m):
+            raise ValueError(f"favor_gather: states[{i}] was built for H={s.dims[2]} d={s.dims[3]} m={s.dims[4]}, states[0] for H={H} d={d} m={m}")
+        if s.buf.device != states[0].buf.device or s.buf.dtype != states[0].buf.dtype:
+            raise ValueError(f"favor_gather: states[{i}] lies on {s.buf.device} as {s.buf.dtype}, states[0] on {states[0].buf.device} as {states[0].buf.dtype}")
+    dev = states[0].buf.device
+    if floor is not None and (not isinstance(floor, torch.Tensor) or floor.dtype != torch.float32 or floor.numel() != 1 or floor.device != dev):
+        raise ValueError(f"favor_gather: floor must be None or one fp32 value on {dev} (the stabiliser is at least this)")
+    table = _gather_parts(parts, states)
+    T_out = len(table)
+    named = sorted({i for row in table for i, _ in row})
+    if not named:                                       # no part at all: the fresh state, through the same launch (floor included)
+        fresh = lib().favor_summary_init(1, H, d, m, dev)
+        buf = lib().favor_summary_gather([fresh], [1], torch.full((T_out, 1, 2), -1, dtype=torch.int32).to(dev), H, d, m, floor=floor)
+        return FavorKeyState("summary", (T_out, 0, H, d, m), buf=buf, lens=(0,) * T_out)
+    # one launch per group of named states: 8 first, then the running result and the next 7
+    groups = [named[:MERGE_GROUP]] + [named[at:at + MERGE_GROUP - 1] for at in range(MERGE_GROUP, len(named), MERGE_GROUP - 1)]
+    buf, seen = None, [False] * T_out                   # seen[t]: the running result holds a part of task t
+    for g, group in enumerate(groups):
+        slot = {i: k + (g > 0) for k, i in enumerate(group)}
+        rows = [([(0, t)] if g > 0 and seen[t] else []) + [(slot[i], u) for i, u in row if i in slot] for t, row in enumerate(table)]
+        P = max(1, max(len(r) for r in rows))
+        dev_rows = torch.tensor([r + [(-1, 0)] * (P - len(r)) for r in rows], dtype=torch.int32).to(dev)
+        bufs, tasks = [states[i].buf for i in group], [states[i].dims[0] for i in group]
+        if g > 0:
+            bufs, tasks = [buf] + bufs, [T_out] + tasks
+        buf = lib().favor_summary_gather(bufs, tasks, dev_rows, H, d, m, floor=floor)
+        seen = [s or any(i in slot for i, _ in row) for s, row in zip(seen, table)]
+    total = tuple(sum(states[i].lens[u] for i, u in row) for row in table)
+    return FavorKeyState("summary", (T_out, max(total), H, d, m), buf=buf, lens=total)
+
+
 def favor_query(qh, state, vh, proj, weights=False):
     """FAVOR+ attention of q [T, Nq, H, d] against a favor_keys state and v [T, Nc, H, d] -> merged [T, Nq, d*H], any Nq >= 1 in
     one launch.  On the "cached" route the bits of a row do not depend on the other rows of the call (csrc/favor_cached.h), nor on

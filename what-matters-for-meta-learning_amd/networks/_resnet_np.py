@@ -112,7 +112,8 @@ class HeadStack:
 
 
 class _CachedContext:
-    """mlhot.context's adapter for ResNetNP: what its condition / extend / predict do differently from the vanilla family's."""
+    """mlhot.context's adapter for ResNetNP: what its condition / extend / predict do differently from the vanilla family's.
+    mlhot.cached.merge and mlhot.cached.select reach context.merge / context.select through it; the class gains no method for them."""
 
     def __init__(self, model):
         self.model, self.finish, self.refuse, self.shot_rows = model, model.mu, model._cached_refusals, model._shot_rows
