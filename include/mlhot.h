@@ -330,6 +330,23 @@ int mlhot_np_query_supported(const struct mlhot_np_dims* d);
 int mlhot_np_query_fwd(const struct mlhot_np_dims* d, const struct mlhot_np_params* p, const float* x_qry, int Nq,
                        const void* key_state, const float* vh, const float* z, float* mu, void* stream);
 
+/* ---- the same tail against a FAVOR+ summary state: any number of context shots, ONE launch (csrc/np_query_summary.h)
+ * mlhot_np_query_summary_fwd: x_qry[T*Nq,dim_w] -> mu[T*Nq,y_dim] for an attention model against summary_state, the state of
+ *   mlhot_favor_summary_bytes(T, 8, dim_w, m_feat) bytes exactly as mlhot_favor_summary_absorb, _merge and _gather leave it: per head
+ *   the query projection, the query features, (F_q A + eps vs sum F_q) / (F_q a + eps cnt sum F_q) with A streamed from memory into
+ *   the merged tile, then _W, r_to_z and decoder0.  Launch label np.query.summary.
+ * Grid task x 16-row target tile, no workspace, no atomics, with the ROW-INVARIANCE guarantee of mlhot_favor_query_fwd: the bits of
+ * mu[t,n,:] depend on x_qry[t,n], the state, the parameters and the dimensions only.  d->Nc and d->Nq are ignored; of p the
+ * query-side fields are read (wq_*, wo_*, r2z_*, dec_*, proj).  Served (mlhot_np_query_summary_supported): agg_mode attention and
+ * mlhot_np_query_supported's conditions without the Nc clause - dim_w % 16 == 0, dim_w <= 64, dim_z % 4 == 0, dim_z <= 64,
+ * dec_hidden % 4 == 0, dec_hidden <= 128, y_dim <= 16, dim_r == dim_w, 16 <= m_feat <= 272; 16-byte aligned pointers (mu included).
+ * Otherwise MLHOT_ERR_UNSUPPORTED, nothing written; a NULL pointer or Nq < 1: MLHOT_ERR_ARG, nothing written.  A task whose cnt is 0
+ * has no defined output (0 / 0), as for mlhot_favor_summary_query_fwd: the caller refuses it.  Forward only; GPU build only.  Added
+ * within ABI 7: bindings look the symbols up. */
+int mlhot_np_query_summary_supported(const struct mlhot_np_dims* d);
+int mlhot_np_query_summary_fwd(const struct mlhot_np_dims* d, const struct mlhot_np_params* p, const float* x_qry, int Nq,
+                               const void* summary_state, float* mu, void* stream);
+
 /* ---- prefix sweep of the vanilla family: the query tail for K context prefixes in one launch (csrc/np_prefix.h) ---
  * mlhot_np_prefix_fwd: x_qry[T*Nq,dim_w] -> mu[K,T,Nq,y_dim]; mu[i] is mlhot_np_query_fwd's result against the first ks[i] of the
  *   d->Nc context shots of every task.  ks: K ints in HOST memory, strictly increasing, 1 <= ks[i] <= d->Nc (else MLHOT_ERR_ARG).

@@ -30,6 +30,7 @@
 #include "np_query.h"
 #include "np_prefix.h"
 #include "favor_summary.h"
+#include "np_query_summary.h"
 #include "favor_prefix_long.h"
 #include "favor_long.h"
 #include "resnet_trunk.h"
@@ -339,6 +340,13 @@ int mlhot_np_query_fwd(const mlhot_np_dims* d, const mlhot_np_params* p, const f
                        const float* z, float* mu, void* stream) {
   if (!d || !p) { set_error("np_query_fwd: null dims/params"); return MLHOT_ERR_ARG; }
   return np_query_forward(*d, *p, x_qry, Nq, key_state, vh, z, mu, (hipStream_t)stream);
+}
+// the same tail against a FAVOR+ summary state: any number of context shots, one launch (csrc/np_query_summary.h)
+int mlhot_np_query_summary_supported(const mlhot_np_dims* d) { return d && np_query_summary_ok(*d) ? 1 : 0; }
+int mlhot_np_query_summary_fwd(const mlhot_np_dims* d, const mlhot_np_params* p, const float* x_qry, int Nq, const void* summary_state, float* mu,
+                               void* stream) {
+  if (!d || !p) { set_error("np_query_summary_fwd: null dims/params"); return MLHOT_ERR_ARG; }
+  return np_query_summary_forward(*d, *p, x_qry, Nq, summary_state, mu, (hipStream_t)stream);
 }
 // the same tail for K context prefixes of one batch, one sweep launch (csrc/np_prefix.h)
 int mlhot_np_prefix_supported(const mlhot_np_dims* d, int K) { return d && np_prefix_ok(*d, K) ? 1 : 0; }

@@ -71,6 +71,10 @@ struct Args {
   int T, Nq, Nc, ntile, dw, dz, dh, y, m, mp, out_act;
   ft::Scales sc;
 };
+// SUMMARY (np_query_summary.h) reads favor_summary.h's state through the three context pointers, so that the
+// argument block - and with it the per-shot kernels' code - stays what it was: fk = A [T][8][mp][d], v = a [T][8][mp],
+// z = vs [T][8][d]; cnt [T][8] (int32) lies 16 floats (M's block) behind vs in that state, which the entry checks.
+__device__ __forceinline__ const int32_t* summary_cnt(const Args& a) { return reinterpret_cast<const int32_t*>(a.z + (size_t)a.T * H * a.dw + 16); }
 
 // acc[j] += A[16][K] (LDS; arow = this lane's row + 4 lq) x B_j[16][K]^T (global; brow[j] = this lane's row + 4 lq, nullptr: zeros)
 // for the tiles with on[j]: per element one chain over k = 0, 16, 32, ..; the B loads of 64 k are in flight together.
@@ -125,14 +129,18 @@ __device__ __forceinline__ void tile_linear(const float* A, int lda, const float
   }
 }
 
-template <bool ATTN>
+// SUMMARY (with ATTN): the context is favor_summary.h's fixed-size state instead of per-shot key features - steps 4
+// and 5 of a head change, everything else is this text for both.
+template <bool ATTN, bool SUMMARY = false>
 __global__ __launch_bounds__(256) void query_kernel(const Args a) {
+  static_assert(ATTN || !SUMMARY, "a summary state belongs to the attention");
+  static_assert(4 * QT * ft::ldo(MAXD) <= QT * LDF, "the four partial tiles of F_q A fit into F_q's space");
   __shared__ __attribute__((aligned(16))) float s_xz[QT * LDXZ];
   __shared__ __attribute__((aligned(16))) float s_f[ATTN ? QT * LDF : 2 * QT * LDH];
   __shared__ __attribute__((aligned(16))) float s_q[ATTN ? QT * LDQ : 4];
   __shared__ __attribute__((aligned(16))) float s_mg[ATTN ? QT * LDM : 4];
-  __shared__ __attribute__((aligned(16))) float s_red[ATTN ? 4 * 2 * 64 * 4 : 4];
-  __shared__ float s_S[ATTN ? QT * LDS_S : 1], s_D[QT], s_diag[QT], s_pm[4][QT];
+  __shared__ __attribute__((aligned(16))) float s_red[ATTN && !SUMMARY ? 4 * 2 * 64 * 4 : 4];
+  __shared__ float s_S[ATTN && !SUMMARY ? QT * LDS_S : 1], s_D[QT], s_diag[QT], s_pm[4][QT], s_fs[SUMMARY ? QT : 1];
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, lq = lane >> 4;
   const int t = blockIdx.x / a.ntile, n0 = (blockIdx.x % a.ntile) * QT;
   const int Nq = a.Nq, dw = a.dw, dz = a.dz;
@@ -167,6 +175,28 @@ __global__ __launch_bounds__(256) void query_kernel(const Args a) {
       // 3. F_q = ratio exp(dd - diag - rowmax) + ratio 1e-4 in place, zeros at features >= m
       ft::features_inplace(s_f, LDF, m, mp, s_diag, s_pm, a.sc, tid);
       __syncthreads();
+      if constexpr (SUMMARY) {
+        const size_t th = (size_t)t * H + h;
+        // 4. per row: fs = sum_j F_q[j], and the denominator D = sum_j F_q[j] a[j] + eps cnt fs (fsum::query_kernel's step 4)
+        {
+          const int row = tid >> 4, p = tid & 15;
+          const float* av = a.v + th * mp;
+          float s[2];
+          ft::row_sums(mp, p, s, [&](int j, float (&u)[2]) { const float f = s_f[row * LDF + j]; u[0] += f; u[1] += f * av[j]; });
+          if (p == 0) { s_fs[row] = s[0]; s_D[row] = s[1] + (ft::EPS * (float)summary_cnt(a)[th]) * s[0]; }
+        }
+        // 5. F_q A[t, h], A streamed from memory: wave w takes the 16-feature chunks w, w + 4, .., the four partial tiles go where F_q
+        // was (two barriers inside) and fold 0, 1, 2, 3; merged[row][e H + h] = (F_q A + eps vs[e] fs) / D.  The next head writes
+        // s_f behind its first barrier.
+        ft::stream_product<1>(s_f, LDF, a.fk + th * mp * d, mp, d, wv, lr, lq);
+        const float* vs = a.z + th * d;
+        for (int idx = tid; idx < QT * d; idx += 256) {
+          const int row = idx / d, e = idx - row * d;
+          const float s = ft::fold_tiles(s_f, ft::ldo(d), row, e);
+          s_mg[row * LDM + e * H + h] = (s + (ft::EPS * vs[e]) * s_fs[row]) / s_D[row];
+        }
+        continue;
+      }
       // 4. S = F_q F_k^T (favor_cached.h's chunk order and fold), D = rowsum(S)
       const float* krow[2];
 #pragma unroll

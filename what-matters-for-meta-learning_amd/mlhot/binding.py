@@ -271,6 +271,9 @@ SIGNATURES = {
     # cached context of the vanilla family: the query tail in one launch
     "mlhot_np_query_supported": (i, [_p(NpDims)]),
     "mlhot_np_query_fwd": (i, [_p(NpDims), _p(NpParams), P, i, P, P, P, P, P]),
+    # the same tail against a FAVOR+ summary state
+    "mlhot_np_query_summary_supported": (i, [_p(NpDims)]),
+    "mlhot_np_query_summary_fwd": (i, [_p(NpDims), _p(NpParams), P, i, P, P, P]),
     # prefix sweep of the vanilla family: the query tail for K context prefixes in one launch
     "mlhot_np_prefix_supported": (i, [_p(NpDims), i]),
     "mlhot_np_prefix_ws_bytes": (z, [_p(NpDims), i]),
@@ -1705,6 +1708,49 @@ class MlhotLib:
         self._rc(fn(C.byref(dims), C.byref(ps), _ptr(x_qry), x_qry.shape[1], _ptr(key_state), _ptr(vh), _ptr(z), _ptr(mu), _stream(x_qry)),
                  "mlhot_np_query_fwd")
         return mu
+
+    # ---- the same tail against a FAVOR+ summary state (csrc/np_query_summary.h) -------------------------------
+    def np_query_summary_supported(self, dims):
+        """Whether mlhot_np_query_summary_fwd serves these dimensions (dims.Nc and dims.Nq are not looked at)."""
+        return bool(self._fn("np_query_summary_supported", "mlhot_np_query_summary_supported")(C.byref(dims)))
+
+    def np_query_summary_fwd(self, dims, params, x_qry, summary_state, proj, out=None):
+        """x_qry [T, Nq, dim_w] (the encoder's target rows) -> mu [T, Nq, y_dim] in ONE launch, any Nq >= 1, against summary_state:
+        favor_summary_absorb's / _merge's / _gather's state (uint8) for T tasks, 8 heads, dim_w and proj [m, dim_w], whatever number of
+        shots it holds (every task at least one: the caller's to check).  params: state_dict key -> tensor; the query-side ones are
+        read (_W_q, _W, r_to_z, decoder0).  `out`: a contiguous fp32 [T, Nq, y_dim] tensor to write into (default: a new one)."""
+        fn = self._fn("np_query_summary_fwd", "mlhot_np_query_summary_fwd")
+        if x_qry.dtype != torch.float32 or x_qry.dim() != 3 or x_qry.shape[0] != dims.T or x_qry.shape[1] < 1 or x_qry.shape[2] != dims.dim_w:
+            raise MlhotError(f"np_query_summary_fwd: x_qry must be fp32 [T = {dims.T}, Nq >= 1, dim_w = {dims.dim_w}], got {x_qry.dtype} {tuple(x_qry.shape)}")
+        if summary_state is None or proj is None or summary_state.dtype != torch.uint8 or proj.dtype != torch.float32 or \
+                tuple(proj.shape) != (dims.m_feat, dims.dim_w):
+            raise MlhotError(f"np_query_summary_fwd takes summary_state (uint8) and proj fp32 [{dims.m_feat}, {dims.dim_w}]")
+        if not self.np_query_summary_supported(dims):
+            raise MlhotError(f"np_query_summary_fwd serves attention models with dim_w % 16 == 0, dim_w <= 64, dim_z % 4 == 0, dim_z <= 64, dec_hidden % 4 == 0, "
+                             f"dec_hidden <= 128, y_dim <= 16, dim_r == dim_w, 16 <= m <= 272 (got dim_w={dims.dim_w} dim_r={dims.dim_r} dim_z={dims.dim_z} "
+                             f"dec_hidden={dims.dec_hidden} y_dim={dims.y_dim} m={dims.m_feat})")
+        nb = self.favor_summary_bytes(dims.T, HEADS, dims.dim_w, dims.m_feat)
+        if not nb or summary_state.numel() < nb:
+            raise MlhotError(f"np_query_summary_fwd: summary_state holds {summary_state.numel()} bytes, mlhot_favor_summary_bytes asks for {nb} "
+                             f"(T={dims.T}, 8 heads, d={dims.dim_w}, m={dims.m_feat})")
+        ps = NpParams()
+        used = []
+        for path, key in vanilla_param_map(dims.n_hidden, False, True):
+            if path[0] in ("dec_w", "dec_b", "r2z_w", "r2z_b", "wq_w", "wq_b", "wo_w", "wo_b"):
+                _set(ps, path, params[key].data_ptr())
+                used.append(params[key])
+        ps.proj = proj.data_ptr()
+        shape = (dims.T, x_qry.shape[1], dims.y_dim)
+        if out is None:
+            out = torch.empty(shape, device=x_qry.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != shape:
+            raise MlhotError(f"np_query_summary_fwd: out must be fp32 {shape}, got {out.dtype} {tuple(out.shape)}")
+        live = [x_qry, summary_state, proj, out, *used]
+        if any(t.device != x_qry.device for t in live):
+            raise MlhotError("np_query_summary_fwd: x_qry, the state, the parameters and out must lie on one device")
+        _chk(*live)
+        self._rc(fn(C.byref(dims), C.byref(ps), _ptr(x_qry), x_qry.shape[1], _ptr(summary_state), _ptr(out), _stream(x_qry)), "mlhot_np_query_summary_fwd")
+        return out
 
     # ---- prefix sweep of the vanilla family (csrc/np_prefix.h) -------------------------------------------------
     def np_prefix_supported(self, dims, K):

@@ -37,7 +37,8 @@ from networks._resnet_np import ResNetNP, _CachedContext
 from networks._vanilla import VanillaNP
 from networks._vanilla_mr import VanillaMR
 
-ROUTES = ("fused", "composed")
+ROUTES = ("fused", "composed", "fused_summary")      # predict's; "fused_summary" is opt-in, never picked by route=None
+SWEEP_ROUTES = ("fused", "composed")                  # sweep's own two
 _FRESH_WEIGHTS = ("Bayes-by-backprop draws fresh weights in every forward, so a cached context is not the reference's forward")
 # what serves a family (_family) at each entry point, or why nothing does
 _CACHED = {"resnet": "ResNetNP.condition / predict", "vanilla": "the vanilla family's query tail (mlhot_np_query_fwd)",
@@ -139,6 +140,9 @@ class _Vanilla:
         model, route = self.model, self.asked
         if route is not None and route not in ROUTES:
             raise ValueError(f"predict: route must be one of {ROUTES}, got {route!r}")
+        if route == "fused_summary":             # opt-in, an error where it cannot run - never another route
+            self._route_fused_summary(state, qry_x)
+            return
         if self.attention:           # the one-launch tail forms no weights to read out
             if route == "fused":
                 raise ValueError('predict: return_attention=True with route "fused" - mlhot_np_query_fwd keeps S and D inside its one launch '
@@ -147,7 +151,7 @@ class _Vanilla:
         if state.form == "summary":
             if route == "fused":
                 raise ValueError('predict: route "fused" - mlhot_np_query_fwd reads per-shot key features; a summary state is served by '
-                                 "the composed route (linear_rows and favor_query)")
+                                 'the composed route (linear_rows and favor_query) or, on request, by route "fused_summary"')
             route = "composed"
         if state.form == "long":
             if route == "fused":
@@ -164,6 +168,29 @@ class _Vanilla:
                                                  "runs composed from linear_rows / favor_query", type(model).__name__)
         state.route = route
 
+    def _route_fused_summary(self, state, qry_x):
+        """The checks of route "fused_summary" (mlhot_np_query_summary_fwd): every refusal is a ValueError before any launch."""
+        model = self.model
+        if self.attention:           # context.predict has refused a summary state already; this is the wording for every other form
+            raise ValueError('predict: return_attention=True with route "fused_summary" - a summary state keeps no per-shot rows, so there is '
+                             "no weight per context shot to read out")
+        if state.form != "summary":
+            what = {"empty": "empty", "latent": "latent"}.get(state.kind, state.form)
+            serves = {"keys": 'route "fused" (mlhot_np_query_fwd) or "composed"', "long": 'route "composed" (linear_rows and favor_query)',
+                      "latent": 'route "fused" (mlhot_np_query_fwd on z) or "composed"', "empty": 'route "fused" (mlhot_np_query_fwd on z) or "composed"'}[what]
+            raise ValueError(f'predict: route "fused_summary" reads a FAVOR+ summary state (condition(form="summary"), extend, merge, select); this state '
+                             f"is {what!r} and is served by {serves}")
+        if min(state.lens) < 1:
+            raise ValueError(f'predict: route "fused_summary" - a task of the summary state has absorbed no shot (shots per task: {list(state.lens)}): '
+                             "its attention is 0 / 0")
+        _need_gpu(qry_x)
+        self.dims = model._dims(state.Nc, 1)
+        if not lib().np_query_summary_supported(self.dims):
+            raise ValueError(f'predict: route "fused_summary" - {type(model).__name__}\'s dimensions are outside mlhot_np_query_summary_fwd\'s envelope '
+                             f"(dim_w={self.dims.dim_w} dim_r={self.dims.dim_r} dim_z={self.dims.dim_z} dec_hidden={self.dims.dec_hidden} "
+                             f"y_dim={self.dims.y_dim} m={self.dims.m_feat}); the composed route serves them")
+        state.route = "fused_summary"
+
     def predict_targets(self, state, qry_x, attention=False):
         model, T, Nq = self.model, qry_x.shape[0], qry_x.shape[1]
         x_qry = _encode(model, qry_x)
@@ -175,6 +202,8 @@ class _Vanilla:
             return composed_tail(params, x_qry, T, Nq, model.OUT_TANH, z=state.z)
         if state.route == "fused":
             return lib().np_query_fwd(self.dims, params, x_qry.view(T, Nq, -1), key_state=state.keys.buf, vh=state.vh, proj=proj)
+        if state.route == "fused_summary":
+            return lib().np_query_summary_fwd(self.dims, params, x_qry.view(T, Nq, -1), state.keys.buf, proj)
         return composed_tail(params, x_qry, T, Nq, model.OUT_TANH, keys=state.keys, vh=state.vh, proj=proj, wq=state.wq, weights=attention)
 
 
@@ -190,7 +219,8 @@ def condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys"):
 
     `form="summary"` (attention models): the state is FAVOR+'s fixed-size summary of the context - any number of
     shots, `ctx_len` honoured, no `capacity`, no per-shot rows kept; extend absorbs any number of further shots and predict runs
-    the composed route.  The default "keys" is every call as it was.
+    the composed route, or - on request, `predict(route="fused_summary")`, vanilla family - the one-launch tail on the summary
+    (mlhot_np_query_summary_fwd).  The default "keys" is every call as it was.
 
     `form="long"` (attention models): per-shot key features for up to 256 slots (`capacity` defaults to Nslots),
     everything of "keys" - `ctx_len`, `capacity`, extend, `return_attention=True` - through the chunked kernels of
@@ -245,7 +275,10 @@ def predict(model, state, qry_x, chunk=None, route=None, return_attention=False)
     """(state, target images [T, Nq, ...]) -> mu [T, Nq, y_dim] = `model(ctx, labels, targets, test=True)[0]` for the context the
     state was made from, any Nq >= 1.  `chunk` bounds the targets per launch sequence (and the encoder's activations with them).
     `route`: None picks "fused" where mlhot_np_query_supported says yes and "composed" otherwise; a test may force either.  The
-    state's `route` says which one ran.
+    state's `route` says which one ran.  "fused_summary"  is opt-in and never picked by None: on a form="summary"
+    state of the vanilla attention models it runs everything behind the encoder as ONE launch (mlhot_np_query_summary_fwd) for any
+    number of absorbed shots; another form, return_attention=True, dimensions outside that kernel's envelope and a task without a
+    shot are ValueErrors before any launch.
 
     `return_attention=True` -> (mu, attn): attn [T, 8, Nq, Nc slots] is FAVOR+'s weight of every context slot per
     head and target (rows sum to 1; slots behind a task's ctx_len are exact zeros), concatenated over the chunks like mu.  The
@@ -351,8 +384,8 @@ def sweep(model, ctx_x, ctx_y, qry_x, ks=None, route=None):
     if Nc < 1 or Nq < 1 or ctx_y.shape[1] != Nc:
         raise ValueError(f"sweep needs at least one context shot with its label and one target (got {Nc} shots, {ctx_y.shape[1]} labels, {Nq} targets)")
     ks = _sweep_ks(ks, Nc)
-    if route is not None and route not in ROUTES:
-        raise ValueError(f"sweep: route must be one of {ROUTES}, got {route!r}")
+    if route is not None and route not in SWEEP_ROUTES:
+        raise ValueError(f"sweep: route must be one of {SWEEP_ROUTES}, got {route!r}")
     model._check_agg()
     _need_gpu(ctx_x, ctx_y, qry_x, *model.parameters())
     K = len(ks)
