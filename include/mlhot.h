@@ -479,6 +479,35 @@ int mlhot_favor_query_long_fwd(const float* q, const void* state, const float* v
                                const int32_t* lens /* [T], device, or NULL */, int T, int H, int Nq, int Nc, int d, int m,
                                float* out, float* w /* [T,H,Nq,Nc], or NULL */, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- per-target context masks: one query pass, G masked read-outs (csrc/favor_cached.h, csrc/favor_long.h) -------
+ * mlhot_favor_query_masked_fwd serves a mlhot_favor_keys_fwd / _ragged_fwd state (Nc <= 32), mlhot_favor_query_long_masked_fwd a
+ * mlhot_favor_keys_long_fwd state (Nc <= 256, the SAME lens or NULL).  The arguments are the unmasked entry's plus
+ *   mask_words[T,G,Nq,W] (uint32, DEVICE memory, W = ceil(Nc / 32)): bit j of word c is context slot 32 c + j of that (task, group,
+ *   target row); all heads share it; bits at slots >= Nc are ignored; a slot counts iff its bit is set AND it is a valid shot of
+ *   the state (n' < lens[t]).  G >= 1 groups of masks over the same targets.
+ * -> out[T,G,Nq,d*H] in mlhot_favor_fwd's merged order, out_g = (S o mask_g) V / D_g with D_g = rowsum(S o mask_g); with w != NULL
+ *   also w[T,G,H,Nq,Nc] = (S o mask_g) / D_g, masked columns exactly 0.0f, and out BIT-EQUAL to the call with w == NULL.
+ *   ONE launch for any Nq and G: q's features and S are formed once per 16-row tile, whatever G; the G read-outs loop inside the
+ *   workgroup.  Every masked sum is the sum of the kept columns in the unmasked order (a dropped column adds +0.0f in its place) -
+ *   never "full minus masked" - so one dominant shot cancels nothing.  No atomics; every summation order is a function of the
+ *   dimensions (and of lens[t]) alone.  The mask does not move the key stabiliser: M stays the state's.
+ *   A (row, group) whose mask keeps no valid slot gets exact zeros in out and w, never NaN.
+ *   ROW and GROUP INVARIANCE: the bits of out[t,g,n,:] and w[t,g,:,n,:] depend on q[t,n], state, v, proj, the dimensions and the
+ *   mask words of (t,g,n) - not on Nq, G, n, g, the grid or other rows or groups.  With every bit set, out and w of every group
+ *   are BIT-EQUAL to mlhot_favor_query_weights_fwd / mlhot_favor_query_long_fwd on the same arguments.
+ * Envelope, alignment, workspace (mlhot_favor_query_ws_bytes; 256 bytes for the long entry - no LDS or workspace beyond the
+ * unmasked kernels') and error codes are the unmasked entry's; mask_words and w need 4-byte alignment; mask_words == NULL or G < 1
+ * is MLHOT_ERR_ARG; unsupported shapes write nothing.  Forward only; GPU build only.  Added within ABI 7: bindings look the symbols up. */
+int mlhot_favor_query_masked_fwd(const float* q, const void* state, const float* v, const float* proj,
+                                 const uint32_t* mask_words /* [T,G,Nq,1], device */, int G,
+                                 int T, int H, int Nq, int Nc, int d, int m, float* out /* [T,G,Nq,d*H] */,
+                                 float* w /* [T,G,H,Nq,Nc], or NULL */, void* ws, size_t ws_bytes, void* stream);
+int mlhot_favor_query_long_masked_fwd(const float* q, const void* state, const float* v, const float* proj,
+                                      const int32_t* lens /* [T], device, or NULL */,
+                                      const uint32_t* mask_words /* [T,G,Nq,ceil(Nc/32)], device */, int G,
+                                      int T, int H, int Nq, int Nc, int d, int m, float* out /* [T,G,Nq,d*H] */,
+                                      float* w /* [T,G,H,Nq,Nc], or NULL */, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- strict sharded parity of the key stabiliser -------------------------
  * fast_attention.py:96-97 takes torch.max over the keys of the WHOLE batch.  When a caller shards the meta-batch over
  * ranks, each rank's launch sequence can be run in two halves around the caller's own collectives on `xchg`

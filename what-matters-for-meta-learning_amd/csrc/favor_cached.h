@@ -157,6 +157,64 @@ __device__ __forceinline__ void query_body(const Args& a, float* w) {
 __global__ __launch_bounds__(256) void query_kernel(const Args a) { query_body<false>(a, nullptr); }
 __global__ __launch_bounds__(256) void query_weights_kernel(const Args a, float* w) { query_body<true>(a, w); }
 
+// ---- masked query (mlhot_favor_query_masked_fwd): G context masks per target row, ONE front half ----------------
+// Steps 1. - 4. are query_body's, once per tile: nothing in them sees the mask.  Then per group g: S with the dropped columns set
+// to +0 (ft::s_mask, into the space of the scaled query tile, which is dead behind step 2), D_g = its Nc columns in order,
+// w_g = that tile / D_g, out_g = the same 32-slot chain / D_g - query_body's steps on another tile, so with every bit set the
+// bits are query_weights_kernel's.  The value rows do not depend on g: a wave keeps those of its channel tiles in registers.
+// mask [T][G][Nq] words (Nc <= 32: one word per row), out [T][G][Nq][d H], w [T][G][H][Nq][Nc].  A row without a kept valid slot
+// has D_g == 0 and stores exact zeros.  Rows and groups share no sum: the bits of (t, g, n) depend on that row's words alone.
+template <bool WOUT>
+__device__ __forceinline__ void query_masked_body(const Args& a, const uint32_t* mask, int G, float* w) {
+  __shared__ __attribute__((aligned(16))) float s_f[QT * ft::ldf(ft::MAXM)];
+  __shared__ __attribute__((aligned(16))) float xs[QT * ft::LDX];
+  __shared__ __attribute__((aligned(16))) float red[4 * 2 * 64 * 4];
+  __shared__ float s_S[QT * ft::LDS_S], s_D[QT], s_diag[QT], s_pm[4][QT];
+  static_assert(QT * ft::LDS_S <= QT * ft::LDX, "the masked tile lives in xs");
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, lq = lane >> 4;
+  const int th = blockIdx.x / a.ntile, tile = blockIdx.x % a.ntile, t = th / a.H, h = th % a.H, n0 = tile * QT;
+  const int d = a.d, Nq = a.Nq, Nc = a.Nc, H = a.H, mp = a.mp;
+  ft::query_front([&](int r) { return n0 + r < Nq ? a.x + (((size_t)t * Nq + n0 + r) * H + h) * d : nullptr; }, a.proj, d, a.m, mp, a.sc, xs, s_f, s_diag, s_pm);
+  const float* krow[2];
+#pragma unroll
+  for (int jj = 0; jj < 2; ++jj) krow[jj] = 16 * jj + lr < Nc ? a.fk + ((size_t)th * Nc + 16 * jj + lr) * mp + 4 * lq : nullptr;
+  ft::s_tile(s_f, ft::ldf(mp), krow, (Nc + 15) / 16, mp / 16, Nc, ft::BPlain{}, red, s_S);
+  float* s_Sm = xs;
+  constexpr int ET = ft::MAXD / 64;                       // 16-channel tiles per wave
+  float bv[ET][ft::MAXNC / 4];
+#pragma unroll
+  for (int k = 0; k < ET; ++k) ft::load_v(bv[k], a.v + ((size_t)t * Nc * H + h) * d, (size_t)H * d, Nc, 16 * (wv + 4 * k) + lr, lq, 16 * (wv + 4 * k) < d);
+  const int rows = min(QT, Nq - n0);
+  for (int g = 0; g < G; ++g) {
+    const size_t tg = (size_t)t * G + g;
+    const uint32_t* mg = mask + tg * Nq + n0;
+    ft::s_mask(s_S, s_Sm, ft::LDS_S, Nc, [&](int row, int) { return row < rows ? mg[row] : 0u; });
+    ft::s_rowsum(s_Sm, Nc, s_D);
+    if constexpr (WOUT) {
+      float* wt = w + ((tg * H + h) * Nq + n0) * Nc;
+      for (int idx = tid; idx < rows * Nc; idx += 256) {
+        const int row = idx / Nc, np = idx - row * Nc;
+        wt[idx] = ft::div_kept(s_Sm[row * ft::LDS_S + np], s_D[row]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < ET; ++k) {
+      const int e = 16 * (wv + 4 * k) + lr;
+      if (16 * (wv + 4 * k) >= d) continue;
+      const ft::f32x4_t o = ft::sv_chain(s_Sm, bv[k], Nc, lr, lq);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 4 * lq + r;
+        if (row < rows) a.out[(tg * Nq + n0 + row) * ((size_t)d * H) + (size_t)e * H + h] = ft::div_kept(o[r], s_D[row]);
+      }
+    }
+    __syncthreads();                                      // s_Sm and s_D are the next group's
+  }
+}
+
+__global__ __launch_bounds__(256) void query_masked_kernel(const Args a, const uint32_t* mask, int G) { query_masked_body<false>(a, mask, G, nullptr); }
+__global__ __launch_bounds__(256) void query_masked_weights_kernel(const Args a, const uint32_t* mask, int G, float* w) { query_masked_body<true>(a, mask, G, w); }
+
 inline Args make_args(int T, int H, int Nq, int Nc, int d, int m, const State& st) {
   Args a{};
   a.T = T; a.H = H; a.Nq = Nq; a.Nc = Nc; a.d = d; a.m = m; a.mp = st.mp; a.nch = st.nch;
@@ -264,6 +322,35 @@ inline int favor_query_forward(const float* q, const void* state, const float* v
 inline int favor_query_weights_forward(const float* q, const void* state, const float* v, const float* proj, int T, int H, int Nq, int Nc, int d,
                                        int m, float* out, float* w, void* ws, size_t ws_bytes, hipStream_t s) {
   return favor_query_launch("favor_query_weights_fwd", q, state, v, proj, T, H, Nq, Nc, d, m, out, w, true, ws, ws_bytes, s);
+}
+
+// mlhot_favor_query_masked_fwd: G context masks per target row in one launch - mask [T][G][Nq] words on the
+// device, out [T][G][Nq][d H], w [T][G][H][Nq][Nc] or nullptr.  Envelope, workspace, alignment and codes are favor_query_launch's.
+inline int favor_query_masked_forward(const float* q, const void* state, const float* v, const float* proj, const uint32_t* mask, int G, int T, int H,
+                                      int Nq, int Nc, int d, int m, float* out, float* w, void* ws, size_t ws_bytes, hipStream_t s) {
+  const char* what = "favor_query_masked_fwd";
+  if (T <= 0 || H <= 0 || Nq <= 0 || Nc <= 0 || d <= 0 || m <= 0 || G < 1 || !q || !state || !v || !proj || !out || !mask) { set_error("%s: bad argument", what); return MLHOT_ERR_ARG; }
+  if (!favor_cached_ok(T, H, Nc, d, m)) {
+    set_error("%s serves Nc <= 32, d %% 16 == 0, d <= 256, 16 <= m <= 1536 on the GPU build (got Nc=%d d=%d m=%d)", what, Nc, d, m);
+    return MLHOT_ERR_UNSUPPORTED;
+  }
+#ifdef MLHOT_HOSTSIM
+  (void)w; (void)ws; (void)ws_bytes; (void)s; return MLHOT_ERR_UNSUPPORTED;
+#else
+  if (ws == nullptr || ws_bytes < favor_query_ws_need(T, H, Nq, Nc, d, m)) { set_error("%s: workspace too small", what); return MLHOT_ERR_WORKSPACE; }
+  const long long ntile = ((long long)Nq + fc::QT - 1) / fc::QT;
+  if (ntile * T * H >= (1ll << 31)) { set_error("%s: T H ceil(Nq / 16) must stay below 2^31 (chunk the query rows)", what); return MLHOT_ERR_ARG; }
+  if (!ft::aligned16(q) || !ft::aligned16(proj) || !ft::aligned16(state)) { set_error("%s: q, proj and state must be 16-byte aligned", what); return MLHOT_ERR_ARG; }
+  if ((reinterpret_cast<uintptr_t>(mask) & 3) != 0 || (w && (reinterpret_cast<uintptr_t>(w) & 3) != 0)) { set_error("%s: mask_words and w must be 4-byte aligned", what); return MLHOT_ERR_ARG; }
+  const fc::State st = fc::carve_state(T, H, Nc, m, const_cast<void*>(state));
+  fc::Args a = fc::make_args(T, H, Nq, Nc, d, m, st);
+  a.x = q; a.proj = proj; a.v = v; a.out = out; a.ntile = (int)ntile;
+  const char* label = w ? "favor.querymw" : "favor.querym";
+  ProfScope ps(label, s);
+  if (w) hipLaunchKernelGGL(fc::query_masked_weights_kernel, dim3((unsigned)(ntile * T * H)), dim3(256), 0, s, a, mask, G, w);
+  else hipLaunchKernelGGL(fc::query_masked_kernel, dim3((unsigned)(ntile * T * H)), dim3(256), 0, s, a, mask, G);
+  return check_launch(label);
+#endif
 }
 
 }  // namespace mlhot

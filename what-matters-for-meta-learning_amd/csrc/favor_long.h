@@ -158,6 +158,60 @@ __device__ __forceinline__ void query_body(const Args& a) {
 __global__ __launch_bounds__(256) void query_kernel(const Args a) { query_body<false>(a); }
 __global__ __launch_bounds__(256) void query_weights_kernel(const Args a) { query_body<true>(a); }
 
+// ---- masked query (mlhot_favor_query_long_masked_fwd): G context masks per target row, ONE front half -------------
+// Steps 1. - 4. are query_body's, once per tile.  Then per group g: the wide tile with the dropped columns set to +0 (ft::s_mask,
+// into the space of the scaled query tile, dead behind step 2), D_g over the task's need columns in order, w_g and out_g by
+// query_body's own steps on that tile - with every bit set, query_weights_kernel's bits.  A slot counts iff its bit is set AND it
+// is behind no lens[t]: the tile ends at need.  mask [T][G][Nq][W] words, W = ceil(Nc / 32); out [T][G][Nq][d H], w [T][G][H][Nq][Nc].
+template <bool WOUT>
+__device__ __forceinline__ void query_masked_body(const Args& a, const uint32_t* mask, int G) {
+  __shared__ __attribute__((aligned(16))) float s_f[QT * ft::ldf(ft::MAXM)];
+  __shared__ __attribute__((aligned(16))) float xs[QT * ft::LDX];
+  __shared__ __attribute__((aligned(16))) float red[4 * 2 * 64 * 4];
+  __shared__ float s_S[QT * ft::LDS_S], s_W[QT * LDW], s_D[QT], s_diag[QT], s_pm[4][QT];
+  static_assert(QT * LDW <= QT * ft::LDX, "the masked wide tile lives in xs");
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, lq = lane >> 4;
+  const int th = blockIdx.x / a.ntile, tile = blockIdx.x % a.ntile, t = th / a.H, h = th % a.H, n0 = tile * QT;
+  const int d = a.d, Nq = a.Nq, Nc = a.Nc, H = a.H, mp = a.mp;
+  const int need = ft::clamp_len(a.lens, t, 1, Nc);
+  ft::query_front([&](int r) { return n0 + r < Nq ? a.x + (((size_t)t * Nq + n0 + r) * H + h) * d : nullptr; }, a.proj, d, a.m, mp, a.sc, xs, s_f, s_diag, s_pm);
+  for (int c0 = 0; c0 < need; c0 += CH) {
+    const int ncol = min(CH, need - c0);
+    const float* krow[2];
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) krow[jj] = 16 * jj + lr < ncol ? a.fk + ((size_t)th * Nc + c0 + 16 * jj + lr) * mp + 4 * lq : nullptr;
+    ft::s_tile(s_f, ft::ldf(mp), krow, (ncol + 15) / 16, mp / 16, ncol, ft::BPlain{}, red, s_S);
+    for (int idx = tid; idx < QT * CH; idx += 256) {
+      const int row = idx / CH, np = idx - row * CH;
+      if (np < ncol) s_W[row * LDW + c0 + np] = s_S[row * ft::LDS_S + np];
+    }
+  }
+  __syncthreads();
+  float* s_Wm = xs;
+  const int rows = min(QT, Nq - n0), W = (Nc + 31) / 32;
+  for (int g = 0; g < G; ++g) {
+    const size_t tg = (size_t)t * G + g;
+    const uint32_t* mg = mask + (tg * Nq + n0) * W;
+    ft::s_mask(s_W, s_Wm, LDW, need, [&](int row, int c) { return row < rows ? mg[row * W + c] : 0u; });
+    ft::s_rowsum_wide(s_Wm, LDW, need, s_D);
+    if constexpr (WOUT) {
+      float* wt = a.w + ((tg * H + h) * Nq + n0) * Nc;
+      for (int idx = tid; idx < rows * Nc; idx += 256) {
+        const int row = idx / Nc, np = idx - row * Nc;
+        wt[idx] = np < need ? ft::div_kept(s_Wm[row * LDW + np], s_D[row]) : 0.f;
+      }
+    }
+    // sv_tiles_wide hands over o / D: a row that kept nothing (D == 0) is 0 / 0 there and stores exact zeros here
+    ft::sv_tiles_wide(s_Wm, LDW, s_D, a.v + ((size_t)t * Nc * H + h) * d, (size_t)H * d, need, d, wv, lr, lq, [&](int row, int e, float o) {
+      if (row < rows) a.out[(tg * Nq + n0 + row) * ((size_t)d * H) + (size_t)e * H + h] = s_D[row] > 0.f ? o : 0.f;
+    });
+    __syncthreads();                                                        // s_Wm and s_D are the next group's
+  }
+}
+
+__global__ __launch_bounds__(256) void query_masked_kernel(const Args a, const uint32_t* mask, int G) { query_masked_body<false>(a, mask, G); }
+__global__ __launch_bounds__(256) void query_masked_weights_kernel(const Args a, const uint32_t* mask, int G) { query_masked_body<true>(a, mask, G); }
+
 inline Args make_args(int T, int H, int Nq, int Nc, int d, int m, const State& st, const int32_t* lens) {
   Args a{};
   a.T = T; a.H = H; a.Nq = Nq; a.Nc = Nc; a.d = d; a.m = m; a.mp = st.mp; a.nch = st.nch; a.nrc = st.nrc;
@@ -232,6 +286,35 @@ inline int favor_query_long_forward(const float* q, const void* state, const flo
   ProfScope ps(label, s);
   if (w) hipLaunchKernelGGL(fl2::query_weights_kernel, dim3((unsigned)(ntile * T * H)), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(fl2::query_kernel, dim3((unsigned)(ntile * T * H)), dim3(256), 0, s, a);
+  return check_launch(label);
+#endif
+}
+
+// mlhot_favor_query_long_masked_fwd: G context masks per target row in one launch - mask [T][G][Nq][ceil(Nc / 32)]
+// words on the device, out [T][G][Nq][d H], w [T][G][H][Nq][Nc] or nullptr.  Everything else is favor_query_long_forward's.
+inline int favor_query_long_masked_forward(const float* q, const void* state, const float* v, const float* proj, const int32_t* lens, const uint32_t* mask,
+                                           int G, int T, int H, int Nq, int Nc, int d, int m, float* out, float* w, void* ws, size_t ws_bytes, hipStream_t s) {
+  const char* what = "favor_query_long_masked_fwd";
+  if (T <= 0 || H <= 0 || Nq <= 0 || Nc <= 0 || d <= 0 || m <= 0 || G < 1 || !q || !state || !v || !proj || !out || !mask) { set_error("%s: bad argument", what); return MLHOT_ERR_ARG; }
+  if (!favor_long_ok(T, H, Nc, d, m)) {
+    set_error("%s serves Nc <= 256, d %% 16 == 0, d <= 256, 16 <= m <= 1536 on the GPU build (got Nc=%d d=%d m=%d)", what, Nc, d, m);
+    return MLHOT_ERR_UNSUPPORTED;
+  }
+#ifdef MLHOT_HOSTSIM
+  (void)lens; (void)w; (void)ws; (void)ws_bytes; (void)s; return MLHOT_ERR_UNSUPPORTED;
+#else
+  if (ws == nullptr || ws_bytes < FAVOR_LONG_QUERY_WS) { set_error("%s: workspace too small", what); return MLHOT_ERR_WORKSPACE; }
+  const long long ntile = ((long long)Nq + fl2::QT - 1) / fl2::QT;
+  if (ntile * T * H >= (1ll << 31)) { set_error("%s: T H ceil(Nq / 16) must stay below 2^31 (chunk the query rows)", what); return MLHOT_ERR_UNSUPPORTED; }
+  if (!ft::aligned16(q) || !ft::aligned16(proj) || !ft::aligned16(state)) { set_error("%s: q, proj and state must be 16-byte aligned", what); return MLHOT_ERR_UNSUPPORTED; }
+  if ((reinterpret_cast<uintptr_t>(mask) & 3) != 0 || (w && (reinterpret_cast<uintptr_t>(w) & 3) != 0)) { set_error("%s: mask_words and w must be 4-byte aligned", what); return MLHOT_ERR_ARG; }
+  const fl2::State st = fl2::carve_state(T, H, Nc, m, const_cast<void*>(state));
+  fl2::Args a = fl2::make_args(T, H, Nq, Nc, d, m, st, lens);
+  a.x = q; a.proj = proj; a.v = v; a.out = out; a.w = w; a.ntile = (int)ntile;
+  const char* label = w ? "favor.lquerymw" : "favor.lquerym";
+  ProfScope ps(label, s);
+  if (w) hipLaunchKernelGGL(fl2::query_masked_weights_kernel, dim3((unsigned)(ntile * T * H)), dim3(256), 0, s, a, mask, G);
+  else hipLaunchKernelGGL(fl2::query_masked_kernel, dim3((unsigned)(ntile * T * H)), dim3(256), 0, s, a, mask, G);
   return check_launch(label);
 #endif
 }

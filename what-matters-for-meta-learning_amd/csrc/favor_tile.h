@@ -404,6 +404,23 @@ __device__ __forceinline__ void sv_tiles_wide(const float* s_S, int ld, const fl
   }
 }
 
+// ---- masked read-outs: G groups of per-row context masks over ONE S tile -------------------------------------------
+// s_Sm = S where the row's mask keeps the column, +0.0f elsewhere, over the first n columns (both tiles have row stride ld);
+// word(row, c) is the row's mask word c - bit j = column 32 c + j - and 0 for a row that is not stored.  One barrier behind it.
+// Every step above then runs on s_Sm unchanged: a masked sum IS the sum of the kept columns (a dropped one adds +0 in its place in
+// the same order), never a difference; with every bit set s_Sm has S's bits and so has everything formed from it.
+template <class Word>
+__device__ __forceinline__ void s_mask(const float* s_S, float* s_Sm, int ld, int n, Word word) {
+  const int nw = (n + 31) / 32 * 32;
+  for (int idx = threadIdx.x; idx < QT * nw; idx += 256) {
+    const int row = idx / nw, np = idx - row * nw;
+    if (np < n) s_Sm[row * ld + np] = (word(row, np >> 5) >> (np & 31)) & 1u ? s_S[row * ld + np] : 0.f;
+  }
+  __syncthreads();
+}
+// x / D, and exact zero for a row whose mask kept no valid column (D == 0: every kept column of S is positive)
+__device__ __forceinline__ float div_kept(float x, float D) { return D > 0.f ? x / D : 0.f; }
+
 // ---- [16 x mp] [mp x d]: F in LDS against C streamed from memory -----------------------------------------------------------------------
 // NG: 64-column groups of d.  A lane's float4 of C[j][64 g + 4 lr ..] serves four MFMAs whose 16 output columns are 64 g + 4 lr' + y.
 // Wave w takes the 16-feature chunks w, w + 4, .. in ascending order for every column group; the next chunk's rows of C are in flight

@@ -397,6 +397,15 @@ int mlhot_favor_query_long_fwd(const float* q, const void* state, const float* v
                                int Nc, int d, int m, float* out, float* w, void* ws, size_t ws_bytes, void* stream) {
   return favor_query_long_forward(q, state, v, proj, lens, T, H, Nq, Nc, d, m, out, w, ws, ws_bytes, (hipStream_t)stream);
 }
+// per-target context masks: one query pass, G masked read-outs (csrc/favor_cached.h, csrc/favor_long.h)
+int mlhot_favor_query_masked_fwd(const float* q, const void* state, const float* v, const float* proj, const uint32_t* mask_words, int G, int T, int H,
+                                 int Nq, int Nc, int d, int m, float* out, float* w, void* ws, size_t ws_bytes, void* stream) {
+  return favor_query_masked_forward(q, state, v, proj, mask_words, G, T, H, Nq, Nc, d, m, out, w, ws, ws_bytes, (hipStream_t)stream);
+}
+int mlhot_favor_query_long_masked_fwd(const float* q, const void* state, const float* v, const float* proj, const int32_t* lens, const uint32_t* mask_words,
+                                      int G, int T, int H, int Nq, int Nc, int d, int m, float* out, float* w, void* ws, size_t ws_bytes, void* stream) {
+  return favor_query_long_masked_forward(q, state, v, proj, lens, mask_words, G, T, H, Nq, Nc, d, m, out, w, ws, ws_bytes, (hipStream_t)stream);
+}
 // Staged passes (strict sharded parity of the key stabiliser, csrc/stab_xchg.h): stage 0 runs up to the rank-local scalar and
 // publishes it in xchg, stage 1 takes the batch-wide scalar from xchg and runs the rest.
 static int staged_args(int stage, float* xchg, const char* what) {

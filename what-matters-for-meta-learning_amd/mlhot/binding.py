@@ -296,6 +296,9 @@ SIGNATURES = {
     "mlhot_favor_keys_long_bytes": (z, [i] * 5),
     "mlhot_favor_keys_long_fwd": (i, [P, P, P, i, i, i, i, i, P, z, P]),
     "mlhot_favor_query_long_fwd": (i, [P, P, P, P, P, i, i, i, i, i, i, P, P, P, z, P]),
+    # per-target context masks: one query pass, G masked read-outs
+    "mlhot_favor_query_masked_fwd": (i, [P, P, P, P, P, i, i, i, i, i, i, i, P, P, P, z, P]),
+    "mlhot_favor_query_long_masked_fwd": (i, [P, P, P, P, P, P, i, i, i, i, i, i, i, P, P, P, z, P]),
     # strict sharded parity of the key stabiliser
     "mlhot_favor_fwd_staged": (i, _qkvp + [P, P, z, i, P, P]),
     "mlhot_favor_bwd_staged": (i, _qkvp + [P, P, P, P, P, P, z, i, P, P]),
@@ -1194,6 +1197,52 @@ class MlhotLib:
         ws = self._bytes(256, q)
         self._rc(fn(_ptr(q), _ptr(state), _ptr(v), _ptr(proj), _ptr(lens), T, H, Nq, Nc, d, m, _ptr(out), _ptr(w), _ptr(ws), ws.numel(), _stream(q)),
                  "mlhot_favor_query_long_fwd")
+        return (out, w) if weights else out
+
+    # ---- per-target context masks: one query pass, G masked read-outs -----------
+    def favor_query_masked_fwd(self, q, state, v, proj, mask_words, lens=None, long=False, weights=False):
+        """q [T,Nq,H,d], a favor_keys_fwd state (long=True: a favor_keys_long_fwd state and its lens), v [T,Nc,H,d], proj [m,d],
+        mask_words [T,G,Nq,ceil(Nc/32)] int32 on q's device (bit j of word c = slot 32 c + j, mlhot.ragged.pack_mask) ->
+        out [T,G,Nq,d*H]; weights=True -> (out, w [T,G,H,Nq,Nc]).  ONE launch: the query features and S once per 16 rows, the G
+        masked read-outs behind them; a row that keeps no valid slot gets exact zeros (include/mlhot.h).  Forward only."""
+        what = "favor_query_long_masked_fwd" if long else "favor_query_masked_fwd"
+        fn = self._fn(what, "mlhot_" + what)
+        if long:
+            for name, t in (("q", q), ("v", v)):
+                if t.dtype != torch.float32 or t.dim() != 4:
+                    raise MlhotError(f"{what}: {name} must be fp32 [T, N, H, d], got {t.dtype} {tuple(t.shape)}")
+            T, Nq, H, d = q.shape
+            Nc = v.shape[1]
+            if tuple(v.shape) != (T, Nc, H, d) or proj.dtype != torch.float32 or proj.dim() != 2 or proj.shape[1] != d or Nq < 1:
+                raise MlhotError(f"{what}: q {tuple(q.shape)}, v {tuple(v.shape)}, proj {tuple(proj.shape)} do not fit together")
+            if any(t.device != q.device for t in (state, v, proj)):
+                raise MlhotError(f"{what}: q, state, v and proj must lie on one device")
+            self._long_lens(what, lens, T, q)
+            m = proj.shape[0]
+            nb = self.favor_keys_long_bytes(T, H, Nc, d, m)
+            if not nb or state.dtype != torch.uint8 or state.numel() < nb:
+                raise MlhotError(f"{what}: the state is not mlhot_favor_keys_long_fwd's for T={T} H={H} Nc={Nc} d={d} m={m} "
+                                 f"({state.numel()} bytes, {nb} needed; 0 = shape not served)")
+            _chk(q, v, proj, state, lens)
+            ws = self._bytes(256, q)
+        else:
+            T, H, Nq, Nc, d, m = self._favor_query_dims(what, q, state, v, proj)
+            ws = self._bytes(self._fn(what, "mlhot_favor_query_ws_bytes")(T, H, Nq, Nc, d, m), q)
+        W = (Nc + 31) // 32
+        if (not isinstance(mask_words, torch.Tensor) or mask_words.dtype != torch.int32 or mask_words.dim() != 4 or mask_words.shape[1] < 1
+                or (mask_words.shape[0], mask_words.shape[2], mask_words.shape[3]) != (T, Nq, W) or mask_words.device != q.device):
+            got = f"{mask_words.dtype} {tuple(mask_words.shape)} on {mask_words.device}" if isinstance(mask_words, torch.Tensor) else type(mask_words).__name__
+            raise MlhotError(f"{what}: mask_words must be int32 [T={T}, G, Nq={Nq}, {W}] on {q.device}, got {got}")
+        _chk(mask_words)
+        G = mask_words.shape[1]
+        out = torch.empty(T, G, Nq, d * H, device=q.device)
+        w = torch.empty(T, G, H, Nq, Nc, device=q.device) if weights else None
+        if long:
+            rc = fn(_ptr(q), _ptr(state), _ptr(v), _ptr(proj), _ptr(lens), _ptr(mask_words), G, T, H, Nq, Nc, d, m, _ptr(out), _ptr(w), _ptr(ws),
+                    ws.numel(), _stream(q))
+        else:
+            rc = fn(_ptr(q), _ptr(state), _ptr(v), _ptr(proj), _ptr(mask_words), G, T, H, Nq, Nc, d, m, _ptr(out), _ptr(w), _ptr(ws), ws.numel(), _stream(q))
+        self._rc(rc, "mlhot_" + what)
         return (out, w) if weights else out
 
     # ---- the fixed-size FAVOR+ summary state (csrc/favor_summary.h) ------------------------------

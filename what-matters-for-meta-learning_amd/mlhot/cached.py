@@ -9,6 +9,10 @@
     mu = mlhot.cached.predict(model, state, qry_x, chunk=None)        # [T, Nq, y_dim]
     mu, attn = mlhot.cached.predict(model, state, qry_x, return_attention=True)      # attn [T, 8, Nq, Nc slots]: FAVOR+'s weight per context
                                                                                       # slot, head and target (attention models; 6c-5)
+    mu = mlhot.cached.predict(model, state, qry_x, context_mask=mask)     # mask bool [T, Nq, Nc slots]: every target attends to its own
+                                                                    # subset of the context; [T, G, Nq, Nc] -> mu [T, G, Nq, y_dim], G masks
+                                                                    # of the same targets from one encoder pass and one query launch (6c-10)
+    mu = mlhot.cached.leave_one_out(model, state, qry_x)            # [T, Nc slots, Nq, y_dim]: group c predicts without context slot c
     ok, reason = mlhot.cached.supports(model)
     mu = mlhot.cached.sweep(model, ctx_x, ctx_y, qry_x, ks=None, route=None)      # [len(ks), T, Nq, y_dim]: every context prefix (6b-2)
     ok, reason = mlhot.cached.supports_sweep(model)
@@ -116,6 +120,7 @@ class _Vanilla:
 
     def __init__(self, model, route=None, attention=False):
         self.model, self.asked, self.dims, self.attention = model, route, None, attention
+        self.masked = False          # context.predict sets it for predict(context_mask=)
 
     finish = property(lambda self: self.model.r_to_z)
 
@@ -140,6 +145,11 @@ class _Vanilla:
         model, route = self.model, self.asked
         if route is not None and route not in ROUTES:
             raise ValueError(f"predict: route must be one of {ROUTES}, got {route!r}")
+        if self.masked:              # the one-launch tails take no mask
+            if route in ("fused", "fused_summary"):
+                raise ValueError(f'predict: context_mask= with route "{route}" - the one-launch tails keep S inside their launch and stay as '
+                                 "they are; per-target context masks run the composed route (linear_rows and favor_query)")
+            route = "composed"
         if route == "fused_summary":             # opt-in, an error where it cannot run - never another route
             self._route_fused_summary(state, qry_x)
             return
@@ -191,11 +201,22 @@ class _Vanilla:
                              f"y_dim={self.dims.y_dim} m={self.dims.m_feat}); the composed route serves them")
         state.route = "fused_summary"
 
-    def predict_targets(self, state, qry_x, attention=False):
+    def predict_targets(self, state, qry_x, attention=False, mask_words=None):
         model, T, Nq = self.model, qry_x.shape[0], qry_x.shape[1]
         x_qry = _encode(model, qry_x)
         proj = _c(model.attn.projection_matrix) if model.ATTENTION else None
         params = {k: _c(p.detach()) for k, p in model.named_parameters()}
+        if mask_words is not None:   # G masked read-outs of one query pass, then the tail over the G * T * Nq rows
+            G, att = mask_words.shape[1], []
+
+            def favor(qh):
+                res = favor_query(qh, state.keys, state.vh, proj, weights=attention, mask=mask_words)
+                if attention:
+                    att.append(res[1])
+                    res = res[0]
+                return res.transpose(0, 1).contiguous()               # [G, T, Nq, d*H]: the target rows wrap every T * Nq, as for prefixes
+            mu = composed_tail(params, x_qry, T, Nq, model.OUT_TANH, wq=state.wq, favor=favor, prefixes=G).transpose(0, 1).contiguous()
+            return (mu, att[0]) if attention else mu
         if state.kind != "attention":
             if state.route == "fused":
                 return lib().np_query_fwd(self.dims, params, x_qry.view(T, Nq, -1), z=state.z)
@@ -271,7 +292,7 @@ def select(model, states, picks):
     return context.select(_CachedContext(model) if isinstance(model, ResNetNP) else _Vanilla(model), states, picks)
 
 
-def predict(model, state, qry_x, chunk=None, route=None, return_attention=False):
+def predict(model, state, qry_x, chunk=None, route=None, return_attention=False, context_mask=None):
     """(state, target images [T, Nq, ...]) -> mu [T, Nq, y_dim] = `model(ctx, labels, targets, test=True)[0]` for the context the
     state was made from, any Nq >= 1.  `chunk` bounds the targets per launch sequence (and the encoder's activations with them).
     `route`: None picks "fused" where mlhot_np_query_supported says yes and "composed" otherwise; a test may force either.  The
@@ -284,14 +305,44 @@ def predict(model, state, qry_x, chunk=None, route=None, return_attention=False)
     head and target (rows sum to 1; slots behind a task's ctx_len are exact zeros), concatenated over the chunks like mu.  The
     vanilla family runs the composed route for it - `route=None` picks it, a forced "fused" is a ValueError - and mu is bit-equal
     to `predict(..., route="composed")`; for a ResNetNP model mu is bit-equal to the call without the keyword.  A model without
-    attention and a summary state refuse with ValueError; a form="long" state serves it for up to 256 slots."""
+    attention and a summary state refuse with ValueError; a form="long" state serves it for up to 256 slots.
+
+    `context_mask`: a bool tensor [T, Nq, Nc slots] - target n of task t attends only to the slots that are True
+    (and valid: behind no ctx_len) - -> mu [T, Nq, y_dim]; or [T, G, Nq, Nc slots], G masks of the same targets (leave-one-out,
+    k-fold over the context, a causal stream) -> mu [T, G, Nq, y_dim] and, with return_attention=True, attn [T, G, 8, Nq, Nc] with
+    exact zeros in the masked columns.  The targets go through the encoder ONCE and the query features are formed once per target;
+    the G masked read-outs are one launch (mlhot_favor_query_masked_fwd / _long_masked_fwd), the Linears behind them run over the
+    T * G * Nq rows through linear_rows.  The key stabiliser stays the state's (the maximum over all conditioned shots, the masked
+    ones included), so against a forward on the sub-context the result moves within the eps terms when a mask drops the shot
+    that holds it (6c-6).  An all-True mask gives the bits of `predict(..., route="composed")` (ResNetNP: of plain predict); a 4-D
+    mask gives the bits of its G 3-D calls; chunked equals unchunked.  The vanilla family runs the composed route for it: a forced
+    "fused" or "fused_summary" is a ValueError.  Also refused, before any launch: a summary, latent or empty state, keys kept on
+    another route than "cached" / "long", a mask of the wrong shape or dtype, and a mask that leaves a (task, group, target)
+    without any of the task's valid shots - that check reads ONE reduced bool back from the mask's device."""
     if isinstance(model, ResNetNP):
         if route is not None:
             raise ValueError("predict: route= belongs to the vanilla family")
+        if context_mask is not None:
+            return model.predict(state, qry_x, chunk=chunk, return_attention=return_attention, context_mask=context_mask)
         if return_attention:
             return model.predict(state, qry_x, chunk=chunk, return_attention=True)
         return model.predict(state, qry_x, chunk=chunk)
-    return context.predict(_Vanilla(model, route, return_attention), state, qry_x, chunk, return_attention)
+    return context.predict(_Vanilla(model, route, return_attention), state, qry_x, chunk, return_attention, context_mask)
+
+
+def leave_one_out(model, state, qry_x, chunk=None):
+    """(state, target images [T, Nq, ...]) -> mu [T, Nc slots, Nq, y_dim]: group c is the prediction WITHOUT context slot c - the
+    influence of every shot on the prediction itself, not only on the attention weight; with the context's own images as targets,
+    outlier detection among the context labels.  It is `predict(context_mask=)` with the G = Nc masks
+    ~eye(Nc) built on the device: one encoder pass over the targets, one masked query launch per chunk.  Groups c >= lens[t] drop
+    a slot that holds no shot and equal the unmasked prediction.  A task with a single shot is refused (nothing would be left),
+    and so is everything predict(context_mask=) refuses."""
+    Nc, lens = getattr(state, "Nc", 0), getattr(state, "lens", ())
+    if getattr(state, "kind", None) == "attention" and lens and min(lens) < 2:
+        raise ValueError(f"leave_one_out: a task of the state holds a single context shot (shots per task: {list(lens)}): without it "
+                         "nothing is left to attend to")
+    mask = ~torch.eye(max(Nc, 1), dtype=torch.bool, device=qry_x.device)[None, :, None, :].expand(qry_x.shape[0], -1, qry_x.shape[1], -1)
+    return predict(model, state, qry_x, chunk=chunk, context_mask=mask)
 
 
 def _rows(sources, lin_w, lin_b, act):

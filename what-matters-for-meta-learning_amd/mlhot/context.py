@@ -255,11 +255,46 @@ def _refuse_attention(ad, state):
                          f"16 <= m <= 1536); this state's keys are kept {state.keys.route!r} (T, Nc, H, d, m = {state.keys.dims})")
 
 
-def predict(ad, state, qry_x, chunk=None, return_attention=False):
+def _refuse_mask(ad, state, mask, Nq):
+    """predict(context_mask=): what has no per-shot column to mask, a mask of the wrong shape or dtype, and a (task, group, target)
+    left without a valid shot.  Host checks only, in that order; the last costs ONE host read of a reduced mask
+    (a bool per task), whichever device the mask lies on.  -> the mask as [T, G, Nq, Nc slots]."""
+    if state.kind != "attention":
+        raise ValueError(f"predict: context_mask= - {type(ad.model).__name__} (agg_mode {ad.model.agg_mode!r}) has no attention: its "
+                         f"state is {state.kind!r}, the context enters the prediction as one aggregate with no per-shot column to mask")
+    if state.form == "summary":
+        raise ValueError("predict: context_mask= - a summary state keeps no per-shot rows, so there is no column per context shot to "
+                         'mask (condition with the default form="keys" for at most 32 shots, or with form="long" for at most '
+                         f"{ragged.MAX_LONG_CAPACITY})")
+    if state.keys.route not in ("cached", "long"):
+        raise ValueError("predict: context_mask= needs the cached kernels' envelope (Nc <= 32, d % 16 == 0, d <= 256, "
+                         f"16 <= m <= 1536); this state's keys are kept {state.keys.route!r} (T, Nc, H, d, m = {state.keys.dims})")
+    T, Nc = state.T, state.Nc
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool:
+        got = str(mask.dtype) if isinstance(mask, torch.Tensor) else type(mask).__name__
+        raise ValueError(f"predict: context_mask must be a bool tensor (True = the target sees the slot), got {got}")
+    if mask.dim() not in (3, 4) or (mask.shape[0], mask.shape[-2], mask.shape[-1]) != (T, Nq, Nc) or mask.shape[1] < 1:
+        raise ValueError(f"predict: context_mask must be [T={T}, Nq={Nq}, Nc={Nc} slots] or [T, G, Nq, Nc], got {tuple(mask.shape)}")
+    mask4 = mask if mask.dim() == 4 else mask[:, None]
+    valid = torch.arange(Nc)[None, :] < torch.tensor(state.lens)[:, None]                          # [T, Nc]
+    kept = (mask4 & valid.to(mask.device)[:, None, None, :]).any(dim=-1)                            # [T, G, Nq]
+    if not bool(kept.all()):                                                                        # the one host read
+        t, g, n = (int(x) for x in (~kept).nonzero()[0])
+        raise ValueError(f"predict: context_mask keeps none of the {state.lens[t]} valid context shots of task {t} for target {n}"
+                         f"{f' in group {g}' if mask.dim() == 4 else ''}: its attention is 0 / 0")
+    return mask4
+
+
+def predict(ad, state, qry_x, chunk=None, return_attention=False, context_mask=None):
     """(state, target images [T, Nq, ...]) -> mu [T, Nq, y_dim] for the context the state was made from, any Nq >= 1.  `chunk` bounds
     the targets per launch sequence.  `return_attention`: -> (mu, attn), attn [T, H, Nq, Nc slots] FAVOR+'s weight of
     every context slot per head and target (mlhot.ops.favor_query(weights=True)), exact zeros at the slots behind a task's ctx_len,
-    concatenated over the chunks like mu; mu has the bits of the call without it on the same route."""
+    concatenated over the chunks like mu; mu has the bits of the call without it on the same route.
+
+    `context_mask`: bool [T, Nq, Nc slots] - target n of task t attends only to the slots whose entry is True -
+    -> mu [T, Nq, y_dim]; or [T, G, Nq, Nc] for G masks of the same targets -> mu [T, G, Nq, y_dim] and attn [T, G, H, Nq, Nc], from
+    ONE encoder pass over the targets and one masked query launch per chunk (mlhot.ops.favor_query(mask=)).  The key stabiliser
+    stays the state's.  Refusals: _refuse_mask."""
     _enter(ad, "predict", state, qry_x, "targets")
     Nq = qry_x.shape[1]
     if Nq < 1:
@@ -268,6 +303,22 @@ def predict(ad, state, qry_x, chunk=None, return_attention=False):
         raise ValueError(f"predict: chunk must be a positive number of targets, got {chunk}")
     if return_attention:
         _refuse_attention(ad, state)
+    if context_mask is not None:
+        mask4 = _refuse_mask(ad, state, context_mask, Nq)
+        ad.masked = True
+        ad.route(state, qry_x)
+        step = Nq if chunk is None else min(int(chunk), Nq)
+        with torch.no_grad():
+            words = ragged.pack_mask(mask4.to(qry_x.device), state.Nc)                              # [T, G, Nq, W]
+            res = [ad.predict_targets(state, qry_x[:, i:i + step], attention=return_attention, mask_words=words[:, :, i:i + step].contiguous())
+                   for i in range(0, Nq, step)]
+        if return_attention:
+            mu, att = (r[0] if len(res) == 1 else torch.cat(r, dim=k) for r, k in zip(zip(*res), (2, 3)))
+        else:
+            mu, att = res[0] if len(res) == 1 else torch.cat(res, dim=2), None
+        if context_mask.dim() == 3:
+            mu, att = mu[:, 0], None if att is None else att[:, 0]
+        return (mu, att) if return_attention else mu
     ad.route(state, qry_x)
     step = Nq if chunk is None else min(int(chunk), Nq)
     with torch.no_grad():

@@ -888,7 +888,25 @@ def favor_gather(states, parts, floor=None):
     return FavorKeyState("summary", (T_out, max(total), H, d, m), buf=buf, lens=total)
 
 
-def favor_query(qh, state, vh, proj, weights=False):
+def _mask_words(mask, T, Nq, Nc, device):
+    """favor_query's `mask`: a bool tensor [T, Nq, Nc] / [T, G, Nq, Nc] or packed words [T, G, Nq, ceil(Nc / 32)] (int32 or uint32)
+    -> int32 words on `device`."""
+    from mlhot.ragged import pack_mask                   # ragged imports this module
+    W = (Nc + 31) // 32
+    if not isinstance(mask, torch.Tensor):
+        raise MlhotError(f"favor_query: mask must be a bool tensor or packed int32 words, got {type(mask).__name__}")
+    if mask.dtype == torch.bool:
+        if mask.dim() not in (3, 4) or (mask.shape[0], mask.shape[-2], mask.shape[-1]) != (T, Nq, Nc):
+            raise MlhotError(f"favor_query: a bool mask must be [T={T}, Nq={Nq}, Nc={Nc}] or [T, G, Nq, Nc], got {tuple(mask.shape)}")
+        return pack_mask(mask.to(device), Nc)
+    if mask.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+        raise MlhotError(f"favor_query: mask must be bool or packed int32 / uint32 words, got {mask.dtype}")
+    if mask.dim() != 4 or mask.shape[1] < 1 or (mask.shape[0], mask.shape[2], mask.shape[3]) != (T, Nq, W):
+        raise MlhotError(f"favor_query: packed mask words must be [T={T}, G, Nq={Nq}, {W}], got {tuple(mask.shape)}")
+    return _c(mask.view(torch.int32).to(device))
+
+
+def favor_query(qh, state, vh, proj, weights=False, mask=None):
     """FAVOR+ attention of q [T, Nq, H, d] against a favor_keys state and v [T, Nc, H, d] -> merged [T, Nq, d*H], any Nq >= 1 in
     one launch.  On the "cached" route the bits of a row do not depend on the other rows of the call (csrc/favor_cached.h), nor on
     the "long" route (favor_keys_long, csrc/favor_long.h: up to 256 slots in chunks of 32, weights=True included); the
@@ -900,7 +918,21 @@ def favor_query(qh, state, vh, proj, weights=False):
     `weights=True` -> (merged, w): w [T, H, Nq, Nc] = S / D of the same launch (mlhot_favor_query_weights_fwd),
     FAVOR+'s implied attention per head, query row and context slot - non-negative, rows summing to 1, exact zeros behind a masked
     state's lens[t], row-invariant like merged; merged has the bits of the call without it.  "cached" and "long" states only: a
-    "plain" or a "summary" state raises MlhotError.  Without it the call launches what it always did."""
+    "plain" or a "summary" state raises MlhotError.  Without it the call launches what it always did.
+
+    `mask`: per-target context masks, bool [T, Nq, Nc] / [T, G, Nq, Nc] (True = the target sees the slot) or the
+    packed words of mlhot.ragged.pack_mask -> merged [T, G, Nq, d*H] (and w [T, G, H, Nq, Nc]): G masked read-outs of ONE query
+    pass (mlhot_favor_query_masked_fwd / _long_masked_fwd) - the masked sums are sums of the kept columns, the stabiliser stays the
+    state's, rows and groups are independent bit for bit, all-ones reproduces the unmasked call's bits, and a row that keeps no
+    valid slot comes back as exact zeros (callers that cannot have that check first, as predict does).  "cached" and "long"
+    states only.  Without `mask` the call is the one it always was."""
+    if mask is not None and isinstance(state, FavorKeyState) and state.route not in ("cached", "long"):
+        if state.route == "summary":
+            raise MlhotError("favor_query: mask= - a summary state keeps no per-shot rows, so there is no column of S to mask "
+                             '(condition with the default form for at most 32 shots, or with form="long")')
+        T, Nc, H, d, m = state.dims
+        raise MlhotError(f"favor_query: mask= needs the cached kernels' envelope (Nc <= 32, d % 16 == 0, d <= 256, 16 <= m <= 1536), "
+                         f"got Nc={Nc} d={d} m={m}: mlhot_favor_fwd on the kept keys takes no mask")
     if weights and isinstance(state, FavorKeyState) and state.route not in ("cached", "long"):
         if state.route == "summary":
             raise MlhotError("favor_query: weights=True - a summary state keeps no per-shot rows, so there is no weight per context shot to "
@@ -927,6 +959,11 @@ def favor_query(qh, state, vh, proj, weights=False):
     T, Nc, H, d, m = state.dims
     if tuple(vh.shape) != (T, Nc, H, d) or qh.dim() != 4 or (qh.shape[0], qh.shape[2], qh.shape[3]) != (T, H, d) or tuple(proj.shape) != (m, d):
         raise MlhotError(f"favor_query: the state was built for T={T} Nc={Nc} H={H} d={d} m={m}; got q {tuple(qh.shape)}, v {tuple(vh.shape)}, proj {tuple(proj.shape)}")
+    if mask is not None:
+        words = _mask_words(mask, T, qh.shape[1], Nc, qh.device)
+        if state.route == "long":
+            return lib().favor_query_masked_fwd(qh, state.buf, vh, proj, words, lens=state.lens_dev, long=True, weights=weights)
+        return lib().favor_query_masked_fwd(qh, state.buf, vh, proj, words, weights=weights)
     if state.route == "cached":
         if weights:
             return lib().favor_query_weights_fwd(qh, state.buf, vh, proj)

@@ -105,6 +105,23 @@ def extend_args(what, state, T, n, new_len):
     return add
 
 
+def pack_mask(mask, Nc):
+    """A per-target context mask as the words the masked query kernels read: bool [T, Nq, Nc] (one group) or
+    [T, G, Nq, Nc] -> int32 [T, G, Nq, ceil(Nc / 32)], bit j of word c = slot 32 c + j (the bit pattern of the kernels' uint32; the
+    bits at slots >= Nc are 0).  Pure torch on the mask's device - a CPU tensor packs on the CPU."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.dim() not in (3, 4):
+        got = f"{mask.dtype} {tuple(mask.shape)}" if isinstance(mask, torch.Tensor) else type(mask).__name__
+        raise ValueError(f"pack_mask: mask must be a bool tensor [T, Nq, Nc] or [T, G, Nq, Nc], got {got}")
+    if isinstance(Nc, bool) or not isinstance(Nc, numbers.Integral) or Nc < 1 or mask.shape[-1] != Nc:
+        raise ValueError(f"pack_mask: the mask's last axis has {mask.shape[-1]} slots, Nc = {Nc!r} (at least 1)")
+    if mask.dim() == 3:
+        mask = mask[:, None]
+    W = (Nc + 31) // 32
+    bits = torch.nn.functional.pad(mask, (0, 32 * W - Nc)).reshape(*mask.shape[:-1], W, 32).to(torch.int64)
+    words = (bits << torch.arange(32, dtype=torch.int64, device=mask.device)).sum(dim=-1)            # 0 .. 2^32 - 1
+    return torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32).contiguous()
+
+
 class Plan:
     """Every index a growth step needs, on the device after ONE upload made before the first launch (an upload from pageable host
     memory waits for the stream: made later it would hold the host until the encoder is done).  `src` / `dst`: flat indices of the

@@ -132,7 +132,9 @@ class _CachedContext:
     def route(self, state, qry_x):
         pass
 
-    def predict_targets(self, state, qry_x, attention=False):
+    def predict_targets(self, state, qry_x, attention=False, mask_words=None):
+        if mask_words is not None:
+            return self.model._predict_targets(state, qry_x.contiguous(), return_attention=attention, mask_words=mask_words)
         if attention:
             return self.model._predict_targets(state, qry_x.contiguous(), return_attention=True)
         return self.model._predict_targets(state, qry_x.contiguous())
@@ -539,7 +541,7 @@ class ResNetNP(nn.Module):
             return self._heads(x_ctx[None], self._W_k)[0], self._heads(feats[None], self._W_v)[0]
         return self._latent_rows(feats)
 
-    def predict(self, state, batch_test_images, chunk=None, return_attention=False):
+    def predict(self, state, batch_test_images, chunk=None, return_attention=False, context_mask=None):
         """(ContextState, target images [T, Nq, ...]) -> mu [T, Nq, out] = `forward(ctx, labels, targets, test=True)[0]` for the
         context the state was made from, any Nq >= 1.  One run_trunks call does the target (attention models) and decoder passes;
         the query head projection, `_W`, `mu` and the decoder head go through mlhot.ops.linear_rows and the attention through
@@ -549,10 +551,15 @@ class ResNetNP(nn.Module):
         `return_attention=True` (attention models, state forms "keys" and "long") -> (mu, attn): attn [T, heads, Nq, Nc
         slots] is FAVOR+'s weight of every context slot for every head and target, read out of the same favor_query launch - rows
         sum to 1, slots behind a task's ctx_len are exact zeros, and mu has the bits of the call without the keyword.  A model
-        without attention and a summary state refuse with ValueError."""
-        return context.predict(_CachedContext(self), state, batch_test_images, chunk, return_attention)
+        without attention and a summary state refuse with ValueError.
 
-    def _predict_targets(self, state, batch_test_images, return_attention=False):
+        `context_mask`: bool [T, Nq, Nc slots] -> mu [T, Nq, out], every target attending only to the slots that
+        are True; [T, G, Nq, Nc slots] -> mu [T, G, Nq, out] and attn [T, G, heads, Nq, Nc]: G masks of the same targets from ONE
+        pass through the trunks and one masked favor_query launch, the Linears behind it over the T * G * Nq rows.  An all-True
+        mask gives plain predict's bits.  mlhot.cached.predict states the refusals."""
+        return context.predict(_CachedContext(self), state, batch_test_images, chunk, return_attention, context_mask)
+
+    def _predict_targets(self, state, batch_test_images, return_attention=False, mask_words=None):
         self._refresh_arena()
         with torch.no_grad():
             T, Nq = self.task_num, batch_test_images.shape[1]
@@ -572,6 +579,14 @@ class ResNetNP(nn.Module):
                 w, b = self._stack(self._W_q).tensors()
                 qh = _fold_linear([(x_tgt.reshape(T * Nq, -1), 1, 0)], _Stacked(w, b), "none", 1).view(T, Nq, self.N_HEADS, -1)
                 attn = None
+                if mask_words is not None:       # G masked read-outs; rows [G, T, Nq] so the decoder features wrap every T * Nq
+                    G = mask_words.shape[1]
+                    res = favor_query(qh, state.keys, state.vh, self.attn.projection_matrix, weights=return_attention, mask=mask_words)
+                    merged, attn = res if return_attention else (res, None)
+                    sample = _fold_linear([(merged.transpose(0, 1).reshape(G * T * Nq, -1), 1, 0)], self._W.linear, "none", G)
+                    sample = _fold_linear([(sample, 1, 0)], self.mu, "none", G)
+                    mu = self._fold_head(x_dec, sample, 1, G, Nq).transpose(0, 1).contiguous()
+                    return (mu, attn) if return_attention else mu
                 if return_attention:
                     merged, attn = favor_query(qh, state.keys, state.vh, self.attn.projection_matrix, weights=True)
                 else:
