@@ -508,6 +508,44 @@ int mlhot_favor_query_long_masked_fwd(const float* q, const void* state, const f
                                       int T, int H, int Nq, int Nc, int d, int m, float* out /* [T,G,Nq,d*H] */,
                                       float* w /* [T,G,H,Nq,Nc], or NULL */, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- per-shot key states beyond 256 context slots: the query walks PAGES of 256 slots (csrc/favor_paged.h) ---------
+ * A form of its own beside the long entries, which keep their envelope: 1 <= Nc <= 4096 (csrc's FAVOR_PAGED_MAXNC - an envelope decision,
+ * F_k and w grow linearly with Nc) slots per task.
+ * mlhot_favor_keys_paged_fwd: arguments, state layout (mlhot_favor_keys_paged_bytes bytes), lens and contract are
+ *   mlhot_favor_keys_long_fwd's - rows n >= lens[t] of k are never read and are exact zeros in F_k, every float of F_k and M is
+ *   written, M is the maximum over the valid rows of all tasks.  The same two launches.
+ * mlhot_favor_query_paged_fwd: mlhot_favor_query_long_fwd's arguments and contract - out[T,Nq,d*H], ONE launch for any Nq >= 1;
+ *   with w != NULL also w[T,H,Nq,Nc] = S / D, columns n' >= lens[t] exactly 0.0f, out BIT-EQUAL to the call with w == NULL.  D and
+ *   the chains of out run on over the pages, each ONE chain over the slots in ascending order (never a sum of page sums).
+ * mlhot_favor_query_paged_masked_fwd: mlhot_favor_query_long_masked_fwd's arguments and contract - mask_words[T,G,Nq,ceil(Nc/32)],
+ *   out[T,G,Nq,d*H], w[T,G,H,Nq,Nc]; D_g is the sum of the kept columns in the unmasked order (+0.0f in a dropped column's place);
+ *   a (row, group) that keeps no valid slot gets exact zeros; with every bit set the result is BIT-EQUAL to the unmasked entry's.
+ * ws: mlhot_favor_query_paged_bytes(T, H, Nq, Nc, d, m, G) bytes, G = 0 for the unmasked entry (256: the kernel works in LDS
+ *   alone), G >= 1 for the masked one (D_g between the pages: T H ceil(Nq / 16) G 16 floats); 4-byte aligned; its contents are the
+ *   call's scratch.  Between the pages the masked entry also keeps the unnormalised out_g in out and both entries the
+ *   unnormalised S in w: both buffers hold their results when the call is done.
+ * BITS: every summation order is a function of d, m and lens[t] alone (no atomics).  The bits of out[t,n] and w[t,:,n] (masked:
+ *   of [t,g,n]) depend on q[t,n], the state, v, proj, the dimensions, lens[t] and that row's mask words - not on Nq, G, the other
+ *   rows or groups, the grid or the capacity Nc the same shots are kept in.  With Nc <= 256 state, out and w are BIT-EQUAL to the
+ *   long entries' on the same operands.
+ * Served (mlhot_favor_paged_supported): 1 <= Nc <= 4096, d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536, T H < 2^20, T Nc < 2^31,
+ * T H ceil(Nq / 16) < 2^31, 16-byte aligned q, k, proj and state.  Otherwise the _bytes entries return 0 and the calls
+ * MLHOT_ERR_UNSUPPORTED, writing nothing; mask_words == NULL or G < 1 is MLHOT_ERR_ARG.  Forward only; GPU build only.  Added
+ * within ABI 7: bindings look the symbols up. */
+int mlhot_favor_paged_supported(int T, int H, int Nc, int d, int m);
+size_t mlhot_favor_keys_paged_bytes(int T, int H, int Nc, int d, int m);
+size_t mlhot_favor_query_paged_bytes(int T, int H, int Nq, int Nc, int d, int m, int G /* 0: the unmasked entry */);
+int mlhot_favor_keys_paged_fwd(const float* k, const float* proj, const int32_t* lens /* [T], device, or NULL */,
+                               int T, int H, int Nc, int d, int m, void* state, size_t state_bytes, void* stream);
+int mlhot_favor_query_paged_fwd(const float* q, const void* state, const float* v, const float* proj,
+                                const int32_t* lens /* [T], device, or NULL */, int T, int H, int Nq, int Nc, int d, int m,
+                                float* out, float* w /* [T,H,Nq,Nc], or NULL */, void* ws, size_t ws_bytes, void* stream);
+int mlhot_favor_query_paged_masked_fwd(const float* q, const void* state, const float* v, const float* proj,
+                                       const int32_t* lens /* [T], device, or NULL */,
+                                       const uint32_t* mask_words /* [T,G,Nq,ceil(Nc/32)], device */, int G,
+                                       int T, int H, int Nq, int Nc, int d, int m, float* out /* [T,G,Nq,d*H] */,
+                                       float* w /* [T,G,H,Nq,Nc], or NULL */, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- strict sharded parity of the key stabiliser -------------------------
  * fast_attention.py:96-97 takes torch.max over the keys of the WHOLE batch.  When a caller shards the meta-batch over
  * ranks, each rank's launch sequence can be run in two halves around the caller's own collectives on `xchg`

@@ -404,6 +404,38 @@ __device__ __forceinline__ void sv_tiles_wide(const float* s_S, int ld, const fl
   }
 }
 
+// ---- the wide steps continued across PAGES of the wide tile (favor_paged.h) --------------------------------------------
+// The wide tile holds one page of the slots at a time, its column 0 being slot p0.  D and the out chains carry on from page to page:
+// each is still ONE chain over the slots in ascending order, so with a single page these run the wide steps' operations exactly.
+// s_rowsum_wide continued: D = carry (nullptr: 0) + the page's n columns in order; carry may be s_D itself.  One barrier behind it
+__device__ __forceinline__ void s_rowsum_page(const float* s_S, int ld, int n, float* s_D, const float* carry) {
+  const int tid = threadIdx.x;
+  if (tid < QT) {
+    float s = carry ? carry[tid] : 0.f;
+    for (int np = 0; np < n; ++np) s += s_S[tid * ld + np];
+    s_D[tid] = s;
+  }
+  __syncthreads();
+}
+// sv_chain_on against a page: slot np is column np - p0 of s_S (zeros from cut on, by index)
+__device__ __forceinline__ f32x4_t sv_chain_page(f32x4_t o, const float* s_S, int ld, const float (&bv)[MAXNC / 4], int n0, int p0, int cut, int lr, int lq) {
+#pragma unroll
+  for (int ks = 0; ks < MAXNC / 4; ++ks) {
+    const int np = n0 + 4 * ks + lq;
+    o = mfma4(np < cut ? s_S[lr * ld + np - p0] : 0.f, bv[ks], o);
+  }
+  return o;
+}
+// one channel tile's chain over the page's slots p0 .. pend (pend <= n, the task's slots): sv_tiles_wide's inner loop, o carried in
+__device__ __forceinline__ f32x4_t sv_page(f32x4_t o, const float* s_S, int ld, const float* v0, size_t vld, int p0, int pend, int n, int e, int lr, int lq) {
+  for (int n0 = p0; n0 < pend; n0 += MAXNC) {
+    float bv[MAXNC / 4];
+    load_v_at(bv, v0, vld, n0, n, e, lq);
+    o = sv_chain_page(o, s_S, ld, bv, n0, p0, n, lr, lq);
+  }
+  return o;
+}
+
 // ---- masked read-outs: G groups of per-row context masks over ONE S tile -------------------------------------------
 // s_Sm = S where the row's mask keeps the column, +0.0f elsewhere, over the first n columns (both tiles have row stride ld);
 // word(row, c) is the row's mask word c - bit j = column 32 c + j - and 0 for a row that is not stored.  One barrier behind it.

@@ -33,6 +33,7 @@
 #include "np_query_summary.h"
 #include "favor_prefix_long.h"
 #include "favor_long.h"
+#include "favor_paged.h"
 #include "resnet_trunk.h"
 #include "../../include/mlhot.h"
 
@@ -405,6 +406,23 @@ int mlhot_favor_query_masked_fwd(const float* q, const void* state, const float*
 int mlhot_favor_query_long_masked_fwd(const float* q, const void* state, const float* v, const float* proj, const int32_t* lens, const uint32_t* mask_words,
                                       int G, int T, int H, int Nq, int Nc, int d, int m, float* out, float* w, void* ws, size_t ws_bytes, void* stream) {
   return favor_query_long_masked_forward(q, state, v, proj, lens, mask_words, G, T, H, Nq, Nc, d, m, out, w, ws, ws_bytes, (hipStream_t)stream);
+}
+// per-shot key states of up to 4096 slots: the long split with the query's wide tile walked in pages of 256 (csrc/favor_paged.h)
+int mlhot_favor_paged_supported(int T, int H, int Nc, int d, int m) { return favor_paged_ok(T, H, Nc, d, m) ? 1 : 0; }
+size_t mlhot_favor_keys_paged_bytes(int T, int H, int Nc, int d, int m) { return favor_keys_paged_need(T, H, Nc, d, m); }
+size_t mlhot_favor_query_paged_bytes(int T, int H, int Nq, int Nc, int d, int m, int G) { return favor_query_paged_ws_need(T, H, Nq, Nc, d, m, G); }
+int mlhot_favor_keys_paged_fwd(const float* k, const float* proj, const int32_t* lens, int T, int H, int Nc, int d, int m, void* state,
+                               size_t state_bytes, void* stream) {
+  return favor_keys_paged_forward(k, proj, lens, T, H, Nc, d, m, state, state_bytes, (hipStream_t)stream);
+}
+int mlhot_favor_query_paged_fwd(const float* q, const void* state, const float* v, const float* proj, const int32_t* lens, int T, int H, int Nq,
+                                int Nc, int d, int m, float* out, float* w, void* ws, size_t ws_bytes, void* stream) {
+  return favor_query_paged_launch("favor_query_paged_fwd", false, q, state, v, proj, lens, nullptr, 0, T, H, Nq, Nc, d, m, out, w, ws, ws_bytes, (hipStream_t)stream);
+}
+int mlhot_favor_query_paged_masked_fwd(const float* q, const void* state, const float* v, const float* proj, const int32_t* lens, const uint32_t* mask_words,
+                                       int G, int T, int H, int Nq, int Nc, int d, int m, float* out, float* w, void* ws, size_t ws_bytes, void* stream) {
+  return favor_query_paged_launch("favor_query_paged_masked_fwd", true, q, state, v, proj, lens, mask_words, G, T, H, Nq, Nc, d, m, out, w, ws, ws_bytes,
+                                  (hipStream_t)stream);
 }
 // Staged passes (strict sharded parity of the key stabiliser, csrc/stab_xchg.h): stage 0 runs up to the rank-local scalar and
 // publishes it in xchg, stage 1 takes the batch-wide scalar from xchg and runs the rest.

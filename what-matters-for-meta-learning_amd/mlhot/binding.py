@@ -299,6 +299,13 @@ SIGNATURES = {
     # per-target context masks: one query pass, G masked read-outs
     "mlhot_favor_query_masked_fwd": (i, [P, P, P, P, P, i, i, i, i, i, i, i, P, P, P, z, P]),
     "mlhot_favor_query_long_masked_fwd": (i, [P, P, P, P, P, P, i, i, i, i, i, i, i, P, P, P, z, P]),
+    # per-shot key states beyond 256 context slots: the query walks pages of 256 slots
+    "mlhot_favor_paged_supported": (i, [i] * 5),
+    "mlhot_favor_keys_paged_bytes": (z, [i] * 5),
+    "mlhot_favor_query_paged_bytes": (z, [i] * 7),
+    "mlhot_favor_keys_paged_fwd": (i, [P, P, P, i, i, i, i, i, P, z, P]),
+    "mlhot_favor_query_paged_fwd": (i, [P, P, P, P, P, i, i, i, i, i, i, P, P, P, z, P]),
+    "mlhot_favor_query_paged_masked_fwd": (i, [P, P, P, P, P, P, i, i, i, i, i, i, i, P, P, P, z, P]),
     # strict sharded parity of the key stabiliser
     "mlhot_favor_fwd_staged": (i, _qkvp + [P, P, z, i, P, P]),
     "mlhot_favor_bwd_staged": (i, _qkvp + [P, P, P, P, P, P, z, i, P, P]),
@@ -1242,6 +1249,79 @@ class MlhotLib:
                     ws.numel(), _stream(q))
         else:
             rc = fn(_ptr(q), _ptr(state), _ptr(v), _ptr(proj), _ptr(mask_words), G, T, H, Nq, Nc, d, m, _ptr(out), _ptr(w), _ptr(ws), ws.numel(), _stream(q))
+        self._rc(rc, "mlhot_" + what)
+        return (out, w) if weights else out
+
+    # ---- per-shot key states of up to 4096 slots, the query in pages of 256 (csrc/favor_paged.h) -----
+    def favor_paged_supported(self, T, H, Nc, d, m):
+        """Whether mlhot_favor_keys_paged_fwd / mlhot_favor_query_paged_fwd serve these dimensions."""
+        return bool(self._fn("favor_keys_paged_fwd", "mlhot_favor_paged_supported")(T, H, Nc, d, m))
+
+    def favor_keys_paged_bytes(self, T, H, Nc, d, m):
+        """State bytes of mlhot_favor_keys_paged_fwd; 0 for a shape the paged kernels do not serve."""
+        return self._fn("favor_keys_paged_fwd", "mlhot_favor_keys_paged_bytes")(T, H, Nc, d, m)
+
+    def favor_keys_paged_fwd(self, k, proj, lens=None, out=None):
+        """k [T,Nc,H,d] with Nc <= 4096, proj [m,d], lens [T] int32 on k's device or None (every task full) -> state (uint8) in
+        favor_keys_long_fwd's layout and under its contract (include/mlhot.h).  Forward only."""
+        what = "favor_keys_paged_fwd"
+        fn = self._fn(what, "mlhot_favor_keys_paged_fwd")
+        if k.dtype != torch.float32 or k.dim() != 4 or proj.dtype != torch.float32 or proj.dim() != 2 or proj.shape[1] != k.shape[3] or proj.device != k.device:
+            raise MlhotError(f"{what}: k must be fp32 [T, Nc, H, d] and proj fp32 [m, d] on one device, got {tuple(k.shape)}, {tuple(proj.shape)}")
+        T, Nc, H, d = k.shape
+        self._long_lens(what, lens, T, k)
+        m = proj.shape[0]
+        nb = self.favor_keys_paged_bytes(T, H, Nc, d, m)
+        if not nb:
+            raise MlhotError(f"{what} serves Nc <= 4096, d % 16 == 0, d <= 256, 16 <= m <= 1536 (got Nc={Nc} d={d} m={m})")
+        _chk(k, proj, lens)
+        state = self._bytes(nb, k) if out is None else out
+        if state.dtype != torch.uint8 or state.numel() < nb or state.device != k.device or not state.is_contiguous():
+            raise MlhotError(f"{what}: out must be {nb} contiguous bytes (uint8) on {k.device}")
+        self._rc(fn(_ptr(k), _ptr(proj), _ptr(lens), T, H, Nc, d, m, _ptr(state), state.numel(), _stream(k)), "mlhot_favor_keys_paged_fwd")
+        return state
+
+    def favor_query_paged_fwd(self, q, state, v, proj, lens=None, weights=False, mask_words=None):
+        """q [T,Nq,H,d], a favor_keys_paged_fwd state, v [T,Nc,H,d], proj [m,d], the state's lens (or None) -> out [T,Nq,d*H];
+        weights=True -> (out, w [T,H,Nq,Nc]).  mask_words [T,G,Nq,ceil(Nc/32)] int32 (mlhot.ragged.pack_mask): the masked entry,
+        out [T,G,Nq,d*H] and w [T,G,H,Nq,Nc].  ONE launch either way (csrc/favor_paged.h).  Forward only."""
+        what = "favor_query_paged_fwd" if mask_words is None else "favor_query_paged_masked_fwd"
+        fn = self._fn(what, "mlhot_" + what)
+        for name, t in (("q", q), ("v", v)):
+            if t.dtype != torch.float32 or t.dim() != 4:
+                raise MlhotError(f"{what}: {name} must be fp32 [T, N, H, d], got {t.dtype} {tuple(t.shape)}")
+        T, Nq, H, d = q.shape
+        Nc = v.shape[1]
+        if tuple(v.shape) != (T, Nc, H, d) or proj.dtype != torch.float32 or proj.dim() != 2 or proj.shape[1] != d or Nq < 1:
+            raise MlhotError(f"{what}: q {tuple(q.shape)}, v {tuple(v.shape)}, proj {tuple(proj.shape)} do not fit together")
+        if any(t.device != q.device for t in (state, v, proj)):
+            raise MlhotError(f"{what}: q, state, v and proj must lie on one device")
+        self._long_lens(what, lens, T, q)
+        m = proj.shape[0]
+        nb = self.favor_keys_paged_bytes(T, H, Nc, d, m)
+        if not nb or state.dtype != torch.uint8 or state.numel() < nb:
+            raise MlhotError(f"{what}: the state is not mlhot_favor_keys_paged_fwd's for T={T} H={H} Nc={Nc} d={d} m={m} "
+                             f"({state.numel()} bytes, {nb} needed; 0 = shape not served)")
+        _chk(q, v, proj, state, lens)
+        G = 0
+        if mask_words is not None:
+            W = (Nc + 31) // 32
+            if (not isinstance(mask_words, torch.Tensor) or mask_words.dtype != torch.int32 or mask_words.dim() != 4 or mask_words.shape[1] < 1
+                    or (mask_words.shape[0], mask_words.shape[2], mask_words.shape[3]) != (T, Nq, W) or mask_words.device != q.device):
+                got = f"{mask_words.dtype} {tuple(mask_words.shape)} on {mask_words.device}" if isinstance(mask_words, torch.Tensor) else type(mask_words).__name__
+                raise MlhotError(f"{what}: mask_words must be int32 [T={T}, G, Nq={Nq}, {W}] on {q.device}, got {got}")
+            _chk(mask_words)
+            G = mask_words.shape[1]
+        ws = self._bytes(self._fn(what, "mlhot_favor_query_paged_bytes")(T, H, Nq, Nc, d, m, G), q)
+        if G:
+            out = torch.empty(T, G, Nq, d * H, device=q.device)
+            w = torch.empty(T, G, H, Nq, Nc, device=q.device) if weights else None
+            rc = fn(_ptr(q), _ptr(state), _ptr(v), _ptr(proj), _ptr(lens), _ptr(mask_words), G, T, H, Nq, Nc, d, m, _ptr(out), _ptr(w), _ptr(ws),
+                    ws.numel(), _stream(q))
+        else:
+            out = torch.empty(T, Nq, d * H, device=q.device)
+            w = torch.empty(T, H, Nq, Nc, device=q.device) if weights else None
+            rc = fn(_ptr(q), _ptr(state), _ptr(v), _ptr(proj), _ptr(lens), T, H, Nq, Nc, d, m, _ptr(out), _ptr(w), _ptr(ws), ws.numel(), _stream(q))
         self._rc(rc, "mlhot_" + what)
         return (out, w) if weights else out
 

@@ -2,6 +2,7 @@
 
     state = mlhot.cached.condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys")     # "summary": beyond 32 shots (6c-4)
                                                                     # "long": per-shot rows for up to 256 shots, attention read-out (6c-7)
+                                                                    # "paged": the same for up to 4096 shots (6c-11)
     state = mlhot.cached.extend(model, state, new_x, new_y, new_len=None)        # more context shots, only they are encoded (6c-3)
     state = mlhot.cached.merge(model, [state_a, state_b, ..])       # summary states conditioned apart -> one, no image re-read (6c-6)
     state = mlhot.cached.select(model, [state_a, state_b, ..], picks)      # a batch put together from the TASKS of summary states:
@@ -36,7 +37,7 @@ from mlhot import context, lib, ragged
 from mlhot.binding import HEADS
 from mlhot.context import ContextState as VanillaContextState          # noqa: F401  one class for both families; the name stays importable
 from mlhot.context import fingerprint as _fingerprint                  # noqa: F401
-from mlhot.ops import LinearFunction, _c, _need_gpu, agg_prefixes, favor_keys, favor_prefixes_long, favor_query, linear_rows
+from mlhot.ops import LinearFunction, _c, _need_gpu, agg_prefixes, favor_keys, favor_prefixes_long, favor_query, linear_rows, linear_rows_any
 from networks._resnet_np import ResNetNP, _CachedContext
 from networks._vanilla import VanillaNP
 from networks._vanilla_mr import VanillaMR
@@ -96,9 +97,17 @@ def _stacked(mods):
     return (torch.cat([m.linear.weight.detach() for m in mods], dim=0), torch.cat([m.linear.bias.detach() for m in mods], dim=0))
 
 
-def _encoded_rows(model, x_ctx, labels):
+def _encoded_rows(model, x_ctx, labels, invariant=False):
     """The per-shot stage behind the encoder: its rows x_ctx [P, dim_w], labels [P, L] -> (kh, vh) [P, 8, dim_w] for the attention
     models, (rs, lv) [P, R] for the others (baco: rs_to_mu's and rs_to_var's outputs, rs_to_var first; else lv None)."""
+    if invariant:                    # form "paged" (DESIGN.md 6c-11): every Linear row-invariant, attention models
+        ly = linear_rows_any([(labels, 1, 0)], model.transform_y.weight, model.transform_y.bias)
+        lins = model.encoder_r.linears()
+        rs = linear_rows_any([(x_ctx, 1, 0), (ly, 1, 0)], lins[0].weight, lins[0].bias, "relu" if len(lins) > 1 else "none")
+        for i, lin in enumerate(lins[1:], 1):
+            rs = linear_rows_any([(rs, 1, 0)], lin.weight, lin.bias, "relu" if i < len(lins) - 1 else "none")
+        return (linear_rows_any([(x_ctx, 1, 0)], *_stacked(model._W_k)).view(-1, HEADS, model.dim_w),
+                linear_rows_any([(rs, 1, 0)], *_stacked(model._W_v)).view(-1, HEADS, model.dim_w))
     ly = LinearFunction.apply(labels, model.transform_y.weight, model.transform_y.bias, "none")
     rs = model.encoder_r(torch.cat([x_ctx, ly], dim=1))
     if model.ATTENTION:
@@ -110,9 +119,9 @@ def _encoded_rows(model, x_ctx, labels):
     return rs, None
 
 
-def _shot_rows(model, imgs, labels):
+def _shot_rows(model, imgs, labels, invariant=False):
     """The per-shot part of condition for a packed list of P shots: images [P, 1, 128, 128], labels [P, L] -> _encoded_rows."""
-    return _encoded_rows(model, _encode(model, imgs), labels)
+    return _encoded_rows(model, _encode(model, imgs), labels, invariant)
 
 
 class _Vanilla:
@@ -135,8 +144,8 @@ class _Vanilla:
             self.model._check_agg()
         return _stacked(self.model._W_q) if self.model.ATTENTION else None
 
-    def shot_rows(self, imgs, labels):
-        return _shot_rows(self.model, imgs, labels)
+    def shot_rows(self, imgs, labels, invariant=False):
+        return _shot_rows(self.model, imgs, labels, invariant)
 
     def empty_z(self, device):
         return torch.zeros(self.model.task_num, self.model.dim_z, device=device)
@@ -168,6 +177,11 @@ class _Vanilla:
                 raise ValueError('predict: route "fused" - mlhot_np_query_fwd reads at most 32 context slots in one chunk; a long state is '
                                  "served by the composed route (linear_rows and favor_query)")
             route = "composed"
+        if state.form == "paged":
+            if route == "fused":
+                raise ValueError('predict: route "fused" - mlhot_np_query_fwd reads at most 32 context slots in one chunk; a paged state is '
+                                 "served by the composed route (linear_rows and favor_query)")
+            route = "composed"
         _need_gpu(qry_x)
         self.dims = model._dims(state.Nc, 1)
         if route is None:
@@ -187,6 +201,7 @@ class _Vanilla:
         if state.form != "summary":
             what = {"empty": "empty", "latent": "latent"}.get(state.kind, state.form)
             serves = {"keys": 'route "fused" (mlhot_np_query_fwd) or "composed"', "long": 'route "composed" (linear_rows and favor_query)',
+                      "paged": 'route "composed" (linear_rows and favor_query)',
                       "latent": 'route "fused" (mlhot_np_query_fwd on z) or "composed"', "empty": 'route "fused" (mlhot_np_query_fwd on z) or "composed"'}[what]
             raise ValueError(f'predict: route "fused_summary" reads a FAVOR+ summary state (condition(form="summary"), extend, merge, select); this state '
                              f"is {what!r} and is served by {serves}")
@@ -245,7 +260,11 @@ def condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys"):
 
     `form="long"` (attention models): per-shot key features for up to 256 slots (`capacity` defaults to Nslots),
     everything of "keys" - `ctx_len`, `capacity`, extend, `return_attention=True` - through the chunked kernels of
-    csrc/favor_long.h; predict runs the composed route.  It is the form that returns attention weights above 32 shots."""
+    csrc/favor_long.h; predict runs the composed route.  It is the form that returns attention weights above 32 shots.
+
+    `form="paged"` (attention models): everything of "long" for up to 4096 slots - `ctx_len`, `capacity`, extend,
+    `return_attention=True`, `context_mask=` and leave_one_out - the query walking the slots in pages of 256 (csrc/favor_paged.h);
+    predict runs the composed route, a forced "fused" or "fused_summary" is a ValueError.  Never a default: ask for it."""
     ragged.check_form("condition", form)
     if isinstance(model, ResNetNP):
         if form != "keys":
@@ -305,7 +324,8 @@ def predict(model, state, qry_x, chunk=None, route=None, return_attention=False,
     head and target (rows sum to 1; slots behind a task's ctx_len are exact zeros), concatenated over the chunks like mu.  The
     vanilla family runs the composed route for it - `route=None` picks it, a forced "fused" is a ValueError - and mu is bit-equal
     to `predict(..., route="composed")`; for a ResNetNP model mu is bit-equal to the call without the keyword.  A model without
-    attention and a summary state refuse with ValueError; a form="long" state serves it for up to 256 slots.
+    attention and a summary state refuse with ValueError; a form="long" state serves it for up to 256 slots, a
+    form="paged" state for up to 4096 (6c-11).
 
     `context_mask`: a bool tensor [T, Nq, Nc slots] - target n of task t attends only to the slots that are True
     (and valid: behind no ctx_len) - -> mu [T, Nq, y_dim]; or [T, G, Nq, Nc slots], G masks of the same targets (leave-one-out,
@@ -317,7 +337,7 @@ def predict(model, state, qry_x, chunk=None, route=None, return_attention=False,
     that holds it (6c-6).  An all-True mask gives the bits of `predict(..., route="composed")` (ResNetNP: of plain predict); a 4-D
     mask gives the bits of its G 3-D calls; chunked equals unchunked.  The vanilla family runs the composed route for it: a forced
     "fused" or "fused_summary" is a ValueError.  Also refused, before any launch: a summary, latent or empty state, keys kept on
-    another route than "cached" / "long", a mask of the wrong shape or dtype, and a mask that leaves a (task, group, target)
+    another route than "cached" / "long" / "paged", a mask of the wrong shape or dtype, and a mask that leaves a (task, group, target)
     without any of the task's valid shots - that check reads ONE reduced bool back from the mask's device."""
     if isinstance(model, ResNetNP):
         if route is not None:

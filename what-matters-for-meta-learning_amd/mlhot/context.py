@@ -7,7 +7,8 @@ What differs per family comes in as an adapter `ad`, a small object with
     refuse(what)                        raises, in the family's own words, for a model or a mode the path does not serve
     prepare(*tensors)                   host work before the first launch (the gradient arena / the device check)
     begin(launches)                     inside no_grad, before condition's launches -> what the state carries as `wq`
-    shot_rows(imgs [P, C, H, W], labels [P, L])     the per-shot stage -> (kh, vh) [P, H, d] or (rs, lv) [P, R], lv None but for baco
+    shot_rows(imgs [P, C, H, W], labels [P, L])     the per-shot stage -> (kh, vh) [P, H, d] or (rs, lv) [P, R], lv None but for baco;
+                                        invariant=True (form "paged", attention): its Linears through mlhot.ops.linear_rows_any
     finish                              the Linear behind the aggregate (`mu` / `r_to_z`)
     empty_z(device)                     `z` of the state without a context shot
     route(state, qry_x)                 predict's own checks and choices, behind the shared ones
@@ -19,7 +20,7 @@ import numbers
 import torch
 
 from mlhot import lib, ragged
-from mlhot.ops import GATHER_PARTS, LinearFunction, favor_gather, favor_keys, favor_merge
+from mlhot.ops import GATHER_PARTS, PER_SHOT_ROUTES, LinearFunction, favor_gather, favor_keys, favor_merge
 
 
 class ContextState:
@@ -38,7 +39,9 @@ class ContextState:
     there is no capacity and there are no per-shot rows - `vh`, `kh` are None.
 
     `form` "long" (DESIGN.md 6c-7): everything of "keys" - `lens`, `capacity`, `kh` and `vh` in slot order - with up to 256 slots;
-    `keys` is mlhot.ops.favor_keys_long's state."""
+    `keys` is mlhot.ops.favor_keys_long's state.
+
+    `form` "paged" (DESIGN.md 6c-11): the same with up to 4096 slots; `keys` is mlhot.ops.favor_keys_paged's state."""
 
     def __init__(self, owner, T, Nc, fingerprint, kind, keys=None, vh=None, z=None, lens=None, kh=None, rs=None, lv=None, r=None,
                  form="keys", wq=None):
@@ -72,7 +75,8 @@ def _enter(ad, what, state, rows, noun):
 def condition(ad, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys"):
     """(ctx images [T, Nc, ...], ctx labels [T, Nc, L]) -> ContextState: the per-shot stage, then the FAVOR+ key features
     (attention) or the aggregation and the finishing Linear.  `ctx_len` / `capacity`: the masked path (_grow); `form="summary"`:
-    _absorb; `form="long"`: always _grow, with mlhot.ops.favor_keys_long behind it; neither: the call as it always was."""
+    _absorb; `form="long"` / `"paged"`: always _grow, with mlhot.ops.favor_keys_long / favor_keys_paged behind it; neither: the call
+    as it always was."""
     model = ad.model
     ragged.check_form("condition", form)
     ad.refuse("condition")
@@ -81,8 +85,8 @@ def condition(ad, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys"):
         raise ValueError(f"condition: {T} tasks, the model was built for tasks_per_batch = {model.task_num}")
     if form == "summary":
         lens = ragged.summary_condition_args("condition", T, Nc, ctx_len, capacity, model.ATTENTION)
-    elif form == "long":
-        lens, capacity = ragged.long_condition_args("condition", T, Nc, ctx_len, capacity, model.ATTENTION)
+    elif form in ragged.PER_SHOT_CAPACITY:
+        lens, capacity = ragged.long_condition_args("condition", T, Nc, ctx_len, capacity, model.ATTENTION, form)
     else:
         lens, capacity = ragged.condition_args("condition", T, Nc, ctx_len, capacity, model.ATTENTION)
     ad.prepare(ctx_x, ctx_y)
@@ -136,7 +140,7 @@ def _summary_states(ad, what, states, same_tasks=True):
             raise ValueError(f"{what}: states[{i}] is a {s.kind!r} state - it is stored behind its finishing Linear, which is not a sum over "
                              f"shots any more; only attention states of form=\"summary\" {what}")
         if s.form != "summary":
-            slots = ragged.MAX_LONG_CAPACITY if s.form == "long" else ragged.MAX_ATTENTION_CAPACITY
+            slots = ragged.PER_SHOT_CAPACITY.get(s.form, ragged.MAX_ATTENTION_CAPACITY)
             raise ValueError(f"{what}: states[{i}] has form {s.form!r} - it holds per-shot rows in at most {slots} "
                              "slots, not sums over shots; condition the parts with form=\"summary\"")
         if same_tasks and (s.T != states[0].T or s.T != ad.model.task_num):
@@ -223,7 +227,10 @@ def _grow(ad, state, lens, capacity, images, labels, add, wq, form="keys"):
     if state is not None and a_rows is None:
         raise ValueError("extend: the state carries no per-shot rows (it was not made by condition())")
     if plan.n:
-        new_a, new_b = ad.shot_rows(ragged.pack(_images(model, images), plan.src), ragged.pack(labels.reshape(T, n, -1), plan.src))
+        shots = (ragged.pack(_images(model, images), plan.src), ragged.pack(labels.reshape(T, n, -1), plan.src))
+        # "paged" (DESIGN.md 6c-11): the Linears of the per-shot stage through the row-invariant kernel - a shot's rows have the
+        # same bits whatever shares the call, so a state grown by extend IS the state conditioned on all its shots
+        new_a, new_b = ad.shot_rows(*shots, invariant=True) if form == "paged" else ad.shot_rows(*shots)
         if state is None:
             a_rows = torch.zeros(T, capacity, *new_a.shape[1:], device=dev)
             b_rows = torch.zeros_like(a_rows) if new_b is not None else None
@@ -250,7 +257,7 @@ def _refuse_attention(ad, state):
         raise ValueError("predict: return_attention=True - a summary state keeps no per-shot rows, so there is no weight per context shot to "
                          'read out (condition with the default form="keys" for at most 32 shots, or with form="long" for at most '
                          f"{ragged.MAX_LONG_CAPACITY})")
-    if state.keys.route not in ("cached", "long"):
+    if state.keys.route not in PER_SHOT_ROUTES:
         raise ValueError("predict: return_attention=True needs the cached kernels' envelope (Nc <= 32, d % 16 == 0, d <= 256, "
                          f"16 <= m <= 1536); this state's keys are kept {state.keys.route!r} (T, Nc, H, d, m = {state.keys.dims})")
 
@@ -266,7 +273,7 @@ def _refuse_mask(ad, state, mask, Nq):
         raise ValueError("predict: context_mask= - a summary state keeps no per-shot rows, so there is no column per context shot to "
                          'mask (condition with the default form="keys" for at most 32 shots, or with form="long" for at most '
                          f"{ragged.MAX_LONG_CAPACITY})")
-    if state.keys.route not in ("cached", "long"):
+    if state.keys.route not in PER_SHOT_ROUTES:
         raise ValueError("predict: context_mask= needs the cached kernels' envelope (Nc <= 32, d % 16 == 0, d <= 256, "
                          f"16 <= m <= 1536); this state's keys are kept {state.keys.route!r} (T, Nc, H, d, m = {state.keys.dims})")
     T, Nc = state.T, state.Nc

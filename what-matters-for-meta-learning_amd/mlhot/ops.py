@@ -587,6 +587,9 @@ def favor_prefixes_long(qh, kh, vh, proj, ks=None, lens=None):
     return out
 
 
+PER_SHOT_ROUTES = ("cached", "long", "paged")      # the states that keep F_k per slot: weights and masks can be read out of them
+
+
 class FavorKeyState:
     """What favor_keys / favor_absorb leave for favor_query.  `route` says what it holds: "cached" - `buf` is mlhot_favor_keys_fwd's
     state (the finished key features F_k and the batch-global stabiliser M; features() shows them) and favor_query is row-invariant;
@@ -595,6 +598,8 @@ class FavorKeyState:
     "long" - favor_keys_long's state (csrc/favor_long.h): F_k and M in the "cached" layout for up to 256 slots,
     walked in chunks of 32; row-invariant, and like "cached" it reads out weights.  It carries `lens_dev`, the device copy of `lens`
     that its query reads (None: every task full).
+    "paged" - favor_keys_paged's state (csrc/favor_paged.h): the "long" layout for up to 4096 slots, the query
+    walking pages of 256 slots; row-invariant, reads out weights and takes masks like "long".
     `lens`: None, or the per-task context sizes (a tuple of T ints) of a masked state (mlhot_favor_keys_ragged_fwd): rows
     n >= lens[t] of F_k are exact zeros.  A summary state always carries `lens`, the shots each task has absorbed so far, and its
     dims[1] is the largest of them."""
@@ -604,8 +609,8 @@ class FavorKeyState:
         self.lens_dev = lens_dev
 
     def features(self):
-        """(F_k [T, H, Nc, mp], M [1]) of a "cached" or a "long" state, as views."""
-        if self.route not in ("cached", "long"):
+        """(F_k [T, H, Nc, mp], M [1]) of a "cached", a "long" or a "paged" state, as views."""
+        if self.route not in PER_SHOT_ROUTES:
             raise MlhotError(f"FavorKeyState.features: this state holds no key features (route {self.route!r})")
         T, Nc, H, d, m = self.dims
         return lib().favor_state_views(self.buf, T, H, Nc, m)
@@ -702,6 +707,35 @@ def favor_keys_long(kh, proj, lens=None, lens_dev=None):
     if lens is not None:
         dev = torch.tensor(lens, dtype=torch.int32).to(kh.device) if lens_dev is None else _c(lens_dev)
     return FavorKeyState("long", (T, Nc, H, d, m), buf=lib().favor_keys_long_fwd(kh, proj, dev), lens=lens, lens_dev=dev)
+
+
+MAX_PAGED_NC = 4096        # context slots per task of the paged per-shot state (csrc/favor_paged.h: FAVOR_PAGED_MAXNC)
+
+
+def favor_keys_paged(kh, proj, lens=None, lens_dev=None):
+    """favor_keys_long beyond 256 context slots: k [T, Nc, H, d], proj [m, d] -> FavorKeyState of route "paged",
+    the per-shot key features of every slot in favor_keys' layout (features() shows them) from favor_keys_long's own two launches.
+    favor_query walks the slots in pages of 256 in ONE row-invariant launch, D and the chains of out carried from page to page, and
+    serves weights=True and mask= like a "long" state.  `lens` / `lens_dev` as favor_keys_long takes them.  The same shots give the
+    same bits at any capacity Nc, and with Nc <= 256 the state and favor_query's results have the bits of the "long" route.
+    Nc <= 4096, d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536, else MlhotError - there is no other route.  Forward only."""
+    _forward_only("favor_keys_paged", kh, proj)
+    _need_gpu(kh, proj)
+    kh, proj = _c(kh.detach()), _c(proj.detach())
+    if kh.dim() != 4 or proj.dim() != 2 or proj.shape[1] != kh.shape[3]:
+        raise MlhotError(f"favor_keys_paged: k must be [T, Nc, H, d] and proj [m, d], got {tuple(kh.shape)}, {tuple(proj.shape)}")
+    T, Nc, H, d = kh.shape
+    m = proj.shape[0]
+    if lens is not None:
+        lens = host_lens(lens, T, 1, Nc, "favor_keys_paged: lens")
+    if not lib().favor_paged_supported(T, H, Nc, d, m):
+        bad = [f"{n}={v}" for n, v, ok in (("Nc", Nc, 1 <= Nc <= MAX_PAGED_NC), ("d", d, d % 16 == 0 and 16 <= d <= 256),
+                                            ("m", m, 16 <= m <= 1536)) if not ok] or [f"T*H={T * H}, T*Nc={T * Nc}"]
+        raise MlhotError(f"favor_keys_paged serves Nc <= {MAX_PAGED_NC}, d % 16 == 0, d <= 256, 16 <= m <= 1536, got {', '.join(bad)}")
+    dev = None
+    if lens is not None:
+        dev = torch.tensor(lens, dtype=torch.int32).to(kh.device) if lens_dev is None else _c(lens_dev)
+    return FavorKeyState("paged", (T, Nc, H, d, m), buf=lib().favor_keys_paged_fwd(kh, proj, dev), lens=lens, lens_dev=dev)
 
 
 ABSORB_CHUNK = 32          # new shots per task and mlhot_favor_summary_absorb call
@@ -853,7 +887,7 @@ def favor_gather(states, parts, floor=None):
             raise ValueError(f"favor_gather: states[{i}] is a {type(s).__name__}, not a FavorKeyState of favor_absorb")
         if s.route != "summary":
             why = ("favor_keys' per-shot states hold rows, not sums: their tasks do not combine (build the parts with favor_absorb)"
-                   if s.route in ("cached", "long") else "only favor_absorb's summary states are sums over shots")
+                   if s.route in PER_SHOT_ROUTES else "only favor_absorb's summary states are sums over shots")
             raise ValueError(f"favor_gather: states[{i}] has route {s.route!r}; {why}")
     _, _, H, d, m = states[0].dims
     for i, s in enumerate(states[1:], 1):
@@ -886,6 +920,23 @@ def favor_gather(states, parts, floor=None):
         seen = [s or any(i in slot for i, _ in row) for s, row in zip(seen, table)]
     total = tuple(sum(states[i].lens[u] for i, u in row) for row in table)
     return FavorKeyState("summary", (T_out, max(total), H, d, m), buf=buf, lens=total)
+
+
+def linear_rows_any(sources, weight, bias, act="none"):
+    """linear_rows for sources [(x [R, k], 1, 0), ..] whose LAST width need not be a multiple of 4 (the kernel's k granule): that
+    source and the weight's trailing columns are padded with zero columns, which add exact zeros to every chain.  The per-shot
+    stage of condition(form="paged") runs its Linears through this: the bits of a shot's rows then do not depend
+    on how many shots share the call, so extend equals conditioning on all shots to the bit.  A shape linear_rows still does not
+    serve raises MlhotError - there is no other row-invariant route.  Forward only."""
+    srcs = [tuple(s) for s in sources]
+    pad = -srcs[-1][0].shape[1] % 4
+    if pad:
+        srcs[-1] = (torch.nn.functional.pad(srcs[-1][0], (0, pad)),) + srcs[-1][1:]
+        weight = torch.nn.functional.pad(weight.detach(), (0, pad))
+    k0, k1 = srcs[0][0].shape[1], srcs[1][0].shape[1] if len(srcs) > 1 else 0
+    if not lib().linear_rows_supported(k0, k1, weight.shape[0]):
+        raise MlhotError(f"linear_rows_any: no row-invariant kernel for a Linear [{k0} | {k1}] -> {weight.shape[0]}")
+    return linear_rows(srcs, weight, bias, act)
 
 
 def _mask_words(mask, T, Nq, Nc, device):
@@ -925,15 +976,18 @@ def favor_query(qh, state, vh, proj, weights=False, mask=None):
     pass (mlhot_favor_query_masked_fwd / _long_masked_fwd) - the masked sums are sums of the kept columns, the stabiliser stays the
     state's, rows and groups are independent bit for bit, all-ones reproduces the unmasked call's bits, and a row that keeps no
     valid slot comes back as exact zeros (callers that cannot have that check first, as predict does).  "cached" and "long"
-    states only.  Without `mask` the call is the one it always was."""
-    if mask is not None and isinstance(state, FavorKeyState) and state.route not in ("cached", "long"):
+    states only.  Without `mask` the call is the one it always was.
+
+    A "paged" state (favor_keys_paged, csrc/favor_paged.h, DESIGN.md 6c-11: up to 4096 slots in pages of 256) is served like a
+    "long" one throughout - row-invariant, `weights=True` and `mask=` included (mlhot_favor_query_paged_fwd / _paged_masked_fwd)."""
+    if mask is not None and isinstance(state, FavorKeyState) and state.route not in PER_SHOT_ROUTES:
         if state.route == "summary":
             raise MlhotError("favor_query: mask= - a summary state keeps no per-shot rows, so there is no column of S to mask "
                              '(condition with the default form for at most 32 shots, or with form="long")')
         T, Nc, H, d, m = state.dims
         raise MlhotError(f"favor_query: mask= needs the cached kernels' envelope (Nc <= 32, d % 16 == 0, d <= 256, 16 <= m <= 1536), "
                          f"got Nc={Nc} d={d} m={m}: mlhot_favor_fwd on the kept keys takes no mask")
-    if weights and isinstance(state, FavorKeyState) and state.route not in ("cached", "long"):
+    if weights and isinstance(state, FavorKeyState) and state.route not in PER_SHOT_ROUTES:
         if state.route == "summary":
             raise MlhotError("favor_query: weights=True - a summary state keeps no per-shot rows, so there is no weight per context shot to "
                              "read out (condition with the default form for at most 32 shots)")
@@ -961,6 +1015,8 @@ def favor_query(qh, state, vh, proj, weights=False, mask=None):
         raise MlhotError(f"favor_query: the state was built for T={T} Nc={Nc} H={H} d={d} m={m}; got q {tuple(qh.shape)}, v {tuple(vh.shape)}, proj {tuple(proj.shape)}")
     if mask is not None:
         words = _mask_words(mask, T, qh.shape[1], Nc, qh.device)
+        if state.route == "paged":
+            return lib().favor_query_paged_fwd(qh, state.buf, vh, proj, lens=state.lens_dev, weights=weights, mask_words=words)
         if state.route == "long":
             return lib().favor_query_masked_fwd(qh, state.buf, vh, proj, words, lens=state.lens_dev, long=True, weights=weights)
         return lib().favor_query_masked_fwd(qh, state.buf, vh, proj, words, weights=weights)
@@ -970,6 +1026,8 @@ def favor_query(qh, state, vh, proj, weights=False, mask=None):
         return lib().favor_query_fwd(qh, state.buf, vh, proj)
     if state.route == "long":
         return lib().favor_query_long_fwd(qh, state.buf, vh, proj, lens=state.lens_dev, weights=weights)
+    if state.route == "paged":
+        return lib().favor_query_paged_fwd(qh, state.buf, vh, proj, lens=state.lens_dev, weights=weights)
     return lib().favor_fwd(qh, state.kh, vh, proj)[0]
 
 

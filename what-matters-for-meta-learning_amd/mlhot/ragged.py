@@ -6,13 +6,16 @@ import numbers
 
 import torch
 
-from mlhot.ops import agg_prefixes, favor_absorb, favor_keys, favor_keys_long, host_lens
+from mlhot.ops import agg_prefixes, favor_absorb, favor_keys, favor_keys_long, favor_keys_paged, host_lens
 
 MAX_ATTENTION_CAPACITY = 32        # the cached FAVOR+ kernels' envelope on the context side (csrc/favor_cached.h)
 MAX_LONG_CAPACITY = 256            # the long per-shot kernels' (csrc/favor_long.h)
-# what an attention state holds: per-shot key features (<= 32 slots), the fixed-size summary, or per-shot key features in 32-slot
-# chunks (<= 256 slots)
-FORMS = ("keys", "summary", "long")
+MAX_PAGED_CAPACITY = 4096          # the paged per-shot kernels' (csrc/favor_paged.h)
+# what an attention state holds: per-shot key features (<= 32 slots), the fixed-size summary, per-shot key features in 32-slot
+# chunks (<= 256 slots), or the same with the query in 256-slot pages (<= 4096 slots)
+FORMS = ("keys", "summary", "long", "paged")
+# the forms with per-shot rows beyond "keys": the masked path always, one capacity each
+PER_SHOT_CAPACITY = {"long": MAX_LONG_CAPACITY, "paged": MAX_PAGED_CAPACITY}
 
 
 def condition_args(what, T, Nslots, ctx_len, capacity, attention):
@@ -53,13 +56,14 @@ def summary_condition_args(what, T, Nslots, ctx_len, capacity, attention):
     return (Nslots,) * T if ctx_len is None else host_lens(ctx_len, T, 1, Nslots, f"{what}: ctx_len", ValueError)
 
 
-def long_condition_args(what, T, Nslots, ctx_len, capacity, attention):
-    """-> (lens, capacity) for condition(form="long"): always the masked path, lens defaults to every slot full."""
+def long_condition_args(what, T, Nslots, ctx_len, capacity, attention, form="long"):
+    """-> (lens, capacity) for condition(form="long" | "paged"): always the masked path, lens defaults to every slot full
+    (DESIGN.md 6c-7, 6c-11)."""
     if not attention:
-        raise ValueError(f'{what}: form="long" serves the attention models; a latent state is one aggregate per task and is not '
+        raise ValueError(f'{what}: form="{form}" serves the attention models; a latent state is one aggregate per task and is not '
                          "capped at 32 shots - use the default form")
     if Nslots < 1:
-        raise ValueError(f'{what}: form="long" needs at least one context shot')
+        raise ValueError(f'{what}: form="{form}" needs at least one context shot')
     lens = (Nslots,) * T if ctx_len is None else host_lens(ctx_len, T, 1, Nslots, f"{what}: ctx_len", ValueError)
     if capacity is None:
         capacity = Nslots
@@ -68,9 +72,9 @@ def long_condition_args(what, T, Nslots, ctx_len, capacity, attention):
     capacity = int(capacity)
     if capacity < Nslots:
         raise ValueError(f"{what}: capacity = {capacity} is smaller than the {Nslots} context slots handed in")
-    if capacity > MAX_LONG_CAPACITY:
-        raise ValueError(f"{what}: capacity = {capacity} is outside the long attention kernels' envelope "
-                         f"(at most {MAX_LONG_CAPACITY} context slots per task)")
+    if capacity > PER_SHOT_CAPACITY[form]:
+        raise ValueError(f"{what}: capacity = {capacity} is outside the {form} attention kernels' envelope "
+                         f"(at most {PER_SHOT_CAPACITY[form]} context slots per task)")
     return lens, capacity
 
 
@@ -161,8 +165,10 @@ def scatter(buf, idx, rows):
 
 
 def masked_keys(kh, proj, plan, form="keys"):
-    """The masked key state over the kept key rows kh [T, cap, H, d] (two launches): mlhot_favor_keys_ragged_fwd, or for form "long"
-    mlhot_favor_keys_long_fwd."""
+    """The masked key state over the kept key rows kh [T, cap, H, d] (two launches): mlhot_favor_keys_ragged_fwd, for form "long"
+    mlhot_favor_keys_long_fwd, for form "paged" mlhot_favor_keys_paged_fwd."""
+    if form == "paged":
+        return favor_keys_paged(kh, proj, lens=plan.total, lens_dev=plan.lens)
     if form == "long":
         return favor_keys_long(kh, proj, lens=plan.total, lens_dev=plan.lens)
     return favor_keys(kh, proj, lens=plan.total, lens_dev=plan.lens)

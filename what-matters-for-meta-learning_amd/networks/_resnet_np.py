@@ -12,7 +12,7 @@ import logging
 from mlhot import context, lib, ragged
 from mlhot.context import ContextState         # noqa: F401  one class for both families; the name stays importable from here
 from mlhot.ops import (AggFunction, FavorFunction, HeadStacksFunction, LinearFunction, StackedLinearFunction, agg_prefixes,
-                       favor_prefixes, favor_prefixes_long, favor_query, linear_rows)
+                       favor_prefixes, favor_prefixes_long, favor_query, linear_rows, linear_rows_any)
 from networks.ResNet import run_conv
 from networks.fast_attention import FastAttention
 from networks.models import AttnLinear, ImageEncoder, NPDecoder, _aggregate_feature_map, _mlp3, run_trunks
@@ -512,7 +512,10 @@ class ResNetNP(nn.Module):
 
         `form="long"` (attention models): per-shot key features for up to 256 slots (`capacity` defaults to
         Nslots) through the chunked kernels of csrc/favor_long.h - `ctx_len`, `capacity`, extend and
-        `predict(..., return_attention=True)` all as for "keys"; the form that returns attention weights above 32 shots."""
+        `predict(..., return_attention=True)` all as for "keys"; the form that returns attention weights above 32 shots.
+
+        `form="paged"` (attention models): the same for up to 4096 slots, the query walking pages of 256 slots
+        (csrc/favor_paged.h) - read-out, `context_mask=` and extend included.  Never a default."""
         return context.condition(_CachedContext(self), batch_train_images, label_train, ctx_len, capacity, form)
 
     def extend(self, state, new_images, new_labels, new_len=None):
@@ -523,19 +526,32 @@ class ResNetNP(nn.Module):
         A form="long" state grows the same way, its key features re-derived by mlhot.ops.favor_keys_long."""
         return context.extend(_CachedContext(self), state, new_images, new_labels, new_len)
 
-    def _task_features(self, x_ctx, labels):
-        """transform_y (the *Distractor classes) and the task encoder over [x_ctx | labels], per shot."""
+    def _task_features(self, x_ctx, labels, invariant=False):
+        """transform_y (the *Distractor classes) and the task encoder over [x_ctx | labels], per shot.  `invariant` (form "paged",
+        DESIGN.md 6c-11): every Linear through the row-invariant kernel (mlhot.ops.linear_rows_any)."""
+        if invariant:
+            if self.TRANSFORM_Y:
+                labels = linear_rows_any([(labels, 1, 0)], self.transform_y.weight, self.transform_y.bias)
+            lins = [m for m in self.task_encoder if isinstance(m, nn.Linear)]
+            h = linear_rows_any([(x_ctx, 1, 0), (labels, 1, 0)], lins[0].weight, lins[0].bias, "relu")
+            for lin in lins[1:]:
+                h = linear_rows_any([(h, 1, 0)], lin.weight, lin.bias, "relu")
+            return h
         if self.TRANSFORM_Y:
             labels = LinearFunction.apply(labels, self.transform_y.weight, self.transform_y.bias, "none")
         return _mlp3(x_ctx, self.task_encoder, last_relu=True, side=labels)
 
-    def _shot_rows(self, imgs, labels):
+    def _shot_rows(self, imgs, labels, invariant=False):
         """The per-shot part of condition for a packed list of P shots: images [P, C, H, W], labels [P, L] -> (kh, vh) [P, heads, 256]
         for the attention models, (rs, lv) [P, 256] for the others (baco: latent_mu's and latent_var's outputs; else lv None)."""
         maps = run_trunks([self.img_encoder.trunk_job(imgs)])
         enc = self.img_encoder
         fmap = maps[0] if maps is not None else enc.resnet.trunk(run_conv(enc.conv1, imgs, relu=True), enc._taps())
         x_ctx = _aggregate_feature_map(fmap, enc.aggregate)
+        if invariant:                # form "paged": attention models only (mlhot.ragged.long_condition_args)
+            feats = self._task_features(x_ctx, labels, invariant=True)
+            return tuple(linear_rows_any([(x, 1, 0)], *self._stack(mods).tensors()).view(x.shape[0], self.N_HEADS, -1)
+                         for x, mods in ((x_ctx, self._W_k), (feats, self._W_v)))
         feats = self._task_features(x_ctx, labels)
         if self.ATTENTION:
             return self._heads(x_ctx[None], self._W_k)[0], self._heads(feats[None], self._W_v)[0]
@@ -548,7 +564,7 @@ class ResNetNP(nn.Module):
         mlhot.ops.favor_query, so nothing behind the trunks depends on how many targets share the call.  `chunk` bounds the
         targets per launch sequence.  Against forward the result agrees to the kernels' tolerance, not to the bit.
 
-        `return_attention=True` (attention models, state forms "keys" and "long") -> (mu, attn): attn [T, heads, Nq, Nc
+        `return_attention=True` (attention models, state forms "keys", "long" and "paged") -> (mu, attn): attn [T, heads, Nq, Nc
         slots] is FAVOR+'s weight of every context slot for every head and target, read out of the same favor_query launch - rows
         sum to 1, slots behind a task's ctx_len are exact zeros, and mu has the bits of the call without the keyword.  A model
         without attention and a summary state refuse with ValueError.
