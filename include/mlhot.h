@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define MLHOT_ABI_VERSION 7
+#define MLHOT_ABI_VERSION 8
 
 enum { MLHOT_ACT_NONE = 0, MLHOT_ACT_RELU = 1, MLHOT_ACT_TANH = 2 };
 enum { MLHOT_AGG_MEAN = 0, MLHOT_AGG_MAX = 1, MLHOT_AGG_BACO = 2, MLHOT_AGG_ATTENTION = 3 };
@@ -827,14 +827,16 @@ int mlhot_pool1_augment_ingest_u8_img(const uint8_t* pool, long n_pool, const in
 /* ---- optimizer: torch.optim.Adam (train.py:52-56) as ONE launch over flat buffers -------------------
  * param / grad / exp_avg / exp_avg_sq: n floats each, laid out alike (e.g. mlhot_np_grads_flat_layout).
  * step >= 1 is the 1-based update count (bias correction); grad_scale multiplies the gradient first
- * (1/world after a sum all-reduce); weight_decay is torch's L2 form (added to the gradient); amsgrad off. */
-int mlhot_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
+ * (1/world after a sum all-reduce); weight_decay is torch's L2 form (added to the gradient); amsgrad off.
+ * beta1 / beta2 are doubles: 1 - beta and the bias corrections 1 - beta^step are formed in double from the caller's values and
+ * rounded once (formed from a float beta2 = 0.999f, 1 - beta2 is off by 1.3e-5 of itself, and exp_avg_sq with it). */
+int mlhot_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, double beta1, double beta2,
                     float eps, float weight_decay, float grad_scale, int step, void* stream);
 
 /* The same update with the 1-based step count kept in device memory: *step_counter is incremented on the device first, then
  * used for the bias corrections.  Capture-safe - a replayed hipGraph of a whole training step advances the count by itself. */
-int mlhot_adam_step_counter(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1,
-                            float beta2, float eps, float weight_decay, float grad_scale, int* step_counter, void* stream);
+int mlhot_adam_step_counter(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, double beta1,
+                            double beta2, float eps, float weight_decay, float grad_scale, int* step_counter, void* stream);
 
 /* ---- X1: ConvEmbeddingModel building blocks (networks/conv_embedding_model.py:99-184) -------------
  * Train-mode batch norm over the shots of ONE task, fused with the ReLU that follows it:

@@ -24,7 +24,7 @@ STRUCTS = {"mlhot_enc_params": B.EncParams, "mlhot_enc_grads": B.EncGrads, "mlho
 # the records mlhot/augment.py builds as int32 / uint8 tensors: the binding knows their size only
 BYTES = {"mlhot_aug_record": B.AUG_RECORD_BYTES, "mlhot_aug_record_img": B.AUG_IMG_RECORD_BYTES, "mlhot_colour_tabs": B.COLOUR_TABS_BYTES}
 CONSTANTS = {"MLHOT_ABI_VERSION": B.ABI_VERSION, "MLHOT_HEADS": B.HEADS, "MLHOT_MAX_HIDDEN": B.MAX_HIDDEN}
-SCALARS = {"int": C.c_int, "float": C.c_float, "size_t": C.c_size_t, "long": C.c_long, "int64_t": C.c_int64, "uint64_t": C.c_uint64}
+SCALARS = {"int": C.c_int, "float": C.c_float, "size_t": C.c_size_t, "long": C.c_long, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "double": C.c_double}
 
 
 def _header():

@@ -1476,13 +1476,21 @@ def test_nt_xent_kernel_vs_definition(gpulib, N, d, div, mod):
 
 def test_flat_adam_matches_torch_adam(gpulib):
     """mlhot.optim.FlatAdam (parameters re-pointed into ONE flat buffer laid out like the library's
-    flat gradient buffer; one mlhot_adam_step launch) against torch.optim.Adam on an identically seeded model, 3 steps."""
+    flat gradient buffer; one mlhot_adam_step launch) against torch.optim.Adam on an identically seeded model, 3 steps.
+    On the parameter (of order 0.1, lr 1e-3) 1e-5 passes an update that is wrong by percents, so the MOVEMENT is held as well, by
+    tests/flat_adam_cases.py's rule: a float64 torch.optim.Adam on CPU copies takes the same gradients, e32 is the error of the fp32
+    torch.optim.Adam's movement against it (relative to the largest entry of the movement, over all parameters), and FlatAdam's may be
+    4 x e32."""
     from mlhot.optim import FlatAdam
+    from tests.flat_adam_cases import MARGIN
     from trainer.losses import LossFunc
     fx, meta = U.load_case("s_anp_shapenet1d_ragged")
     cx, qx, cy, qy = (t.to(DEV) for t in U.case_inputs(meta))
     models = [U.build_model(meta, DEV, fx=fx).to(DEV) for _ in range(2)]
     ref_opt = torch.optim.Adam(models[0].parameters(), lr=1e-3)
+    first = [p.detach().double().cpu().clone() for p in models[0].parameters()]
+    p64 = [torch.nn.Parameter(p.clone()) for p in first]
+    opt64 = torch.optim.Adam(p64, lr=1e-3)
     flat_opt = FlatAdam(models[1], lr=1e-3, ctx_num=meta["Nc"], test_num=meta["Nq"])
     storages = {p.untyped_storage().data_ptr() for p in models[1].parameters()}
     assert len(storages) == 1                                  # every parameter is a view of the one flat tensor
@@ -1499,10 +1507,18 @@ def test_flat_adam_matches_torch_adam(gpulib):
         with torch.no_grad():
             for p0, p1 in zip(models[0].parameters(), models[1].parameters()):
                 p1.grad.copy_(p0.grad)
+        for q, p0 in zip(p64, models[0].parameters()):
+            q.grad = p0.grad.detach().double().cpu()
         ref_opt.step()
         flat_opt.step()
+        opt64.step()
     for (k, a), (_, b) in zip(models[0].named_parameters(), models[1].named_parameters()):
         assert U.rel_err(b, a) <= 1e-5, k
+    moved = [torch.cat([(p.detach().double().cpu() - f).reshape(-1) for p, f in zip(ps, first)])
+             for ps in (p64, models[0].parameters(), models[1].parameters())]
+    e32, got = U.rel_err(moved[1], moved[0]), U.rel_err(moved[2], moved[0])
+    print(f"[flat_adam] parity model, 3 steps, movement: e32 {e32:.3e} got {got:.3e} ({got / e32:.2f}x)")
+    assert moved[0].abs().max() > 1e-3 and got <= MARGIN * e32
     assert set(models[1].state_dict().keys()) == set(models[0].state_dict().keys())
 
 

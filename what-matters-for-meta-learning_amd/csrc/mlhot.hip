@@ -841,20 +841,21 @@ int mlhot_pool1_augment_ingest_u8_img(const uint8_t* pool, long n_pool, const in
 }
 
 // ---- fused Adam over a flat parameter / gradient buffer ------------------------------------------------
-int mlhot_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
+int mlhot_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, double beta1, double beta2,
                     float eps, float weight_decay, float grad_scale, int step, void* stream) {
   if (!param || !grad || !exp_avg || !exp_avg_sq || step < 1) { set_error("adam_step: bad argument"); return MLHOT_ERR_ARG; }
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  return run_foreach(AdamStep{param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, grad_scale, (float)(lr / bc1),
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  return run_foreach(AdamStep{param, grad, exp_avg, exp_avg_sq, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, grad_scale, (float)(lr / bc1),
                               (float)(1.0 / sqrt(bc2))}, n, (hipStream_t)stream, "adam.step");
 }
 
-int mlhot_adam_step_counter(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
+int mlhot_adam_step_counter(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, double beta1, double beta2,
                             float eps, float weight_decay, float grad_scale, int* step_counter, void* stream) {
   if (!param || !grad || !exp_avg || !exp_avg_sq || !step_counter) { set_error("adam_step_counter: bad argument"); return MLHOT_ERR_ARG; }
   hipStream_t s = (hipStream_t)stream;
   MLHOT_TRY(run_foreach(CounterInc{step_counter}, 1, s, "adam.count"));
-  return run_foreach(AdamStepCounter{param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, grad_scale, lr, step_counter}, n, s,
+  return run_foreach(AdamStepCounter{param, grad, exp_avg, exp_avg_sq, beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay,
+                                     grad_scale, lr, step_counter}, n, s,
                      "adam.step");
 }
 

@@ -125,14 +125,15 @@ struct BbbSampleBwd {   // dmu = dw + dkl * mu/sigma^2 ; drho = (dw*eps + dkl * 
 // (amsgrad off, L2 weight decay added to the gradient): step t >= 1,
 //   g = grad_scale * grad + wd * p;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;
 //   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// 1 - b1 and 1 - b2 arrive rounded from the caller's doubles (omb1, omb2), like torch's scalar arguments: 1.f - 0.999f is 0.99998713e-3.
 // ------------------------------------------------------------------------------------------
 struct AdamStep {
   float* p; const float* g; float* m; float* v;
-  float b1, b2, eps, wd, grad_scale, step_size, inv_sqrt_bc2;
+  float b1, b2, omb1, omb2, eps, wd, grad_scale, step_size, inv_sqrt_bc2;
   MLHOT_HD void operator()(size_t i) const {
     const float gi = grad_scale * g[i] + wd * p[i];
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    const float mi = b1 * m[i] + omb1 * gi;
+    const float vi = b2 * v[i] + omb2 * gi * gi;
     m[i] = mi; v[i] = vi;
     p[i] -= step_size * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
   }
@@ -144,14 +145,14 @@ struct AdamStep {
 struct CounterInc { int* c; MLHOT_HD void operator()(size_t) const { c[0] += 1; } };
 struct AdamStepCounter {
   float* p; const float* g; float* m; float* v;
-  float b1, b2, eps, wd, grad_scale, lr; const int* step;
+  double b1d, b2d; float b1, b2, omb1, omb2, eps, wd, grad_scale, lr; const int* step;
   MLHOT_HD void operator()(size_t i) const {
     const int t = step[0];
-    const float step_size = (float)((double)lr / (1.0 - pow((double)b1, (double)t)));
-    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, (double)t)));
+    const float step_size = (float)((double)lr / (1.0 - pow(b1d, (double)t)));
+    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow(b2d, (double)t)));
     const float gi = grad_scale * g[i] + wd * p[i];
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    const float mi = b1 * m[i] + omb1 * gi;
+    const float vi = b2 * v[i] + omb2 * gi * gi;
     m[i] = mi; v[i] = vi;
     p[i] -= step_size * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
   }

@@ -23,7 +23,7 @@ LOSS = {"azimuth": 0, "mse": 1, "quaternion": 2, "degree": 3, "distractor": 4}
 
 _f = C.c_void_p  # every device pointer travels as void*
 
-ABI_VERSION = 7     # include/mlhot.h MLHOT_ABI_VERSION (2: + nt_xent, mt19937_normal, the *_staged entries, trunk / skinny flat gradients; 3: + conv12_fwd / _bwd; 4: + np_vanilla_bwd_loss; 5: + mt19937_advance; 6: + host_f32_to_u8_exact; 7: + loss_plus_fwd / _bwd)
+ABI_VERSION = 8     # include/mlhot.h MLHOT_ABI_VERSION (2: + nt_xent, mt19937_normal, the *_staged entries, trunk / skinny flat gradients; 3: + conv12_fwd / _bwd; 4: + np_vanilla_bwd_loss; 5: + mt19937_advance; 6: + host_f32_to_u8_exact; 7: + loss_plus_fwd / _bwd; 8: adam_step / adam_step_counter take beta1, beta2 as doubles)
 
 
 # sizeof of the records the augmenting ingests read (tensors built by mlhot/augment.py), checked against the library's *_bytes() at load
@@ -209,6 +209,7 @@ def _nhwc(wrapper, src):
 # ---- the C ABI, once: name -> (restype, argtypes), one line per prototype of include/mlhot.h in the header's order
 # (tests/test_binding_abi.py holds this table to the header).  MlhotLib applies it when it loads a library.
 i, z, P, f32, i64, u64, L, s, _p = C.c_int, C.c_size_t, C.c_void_p, C.c_float, C.c_int64, C.c_uint64, C.c_long, C.c_char_p, C.POINTER
+f64 = C.c_double
 _qkvp = [P, P, P, P, i, i, i, i, i, i]                # q, k, v, proj, T, H, Nq, Nc, d, m
 _model = [_p(NpDims), _p(NpParams), P, P, P]          # dims, params, ctx_x, ctx_y, qry_x
 _trunk = [_p(TrunkPass), i, _p(TrunkWset), i, i, i]   # passes, n_pass, wsets, n_wset, C, H
@@ -347,8 +348,8 @@ SIGNATURES = {
     "mlhot_pool1_augment_ingest_u8": (i, [P, L, P, P, L, i, i, f32, P, P, i, P]),
     "mlhot_pool1_augment_ingest_u8_img": (i, [P, L, P, P, L, i, i, i, f32, f32, P, P, i, P, P]),
     # optimizer
-    "mlhot_adam_step": (i, [P, P, P, P, z] + [f32] * 6 + [i, P]),
-    "mlhot_adam_step_counter": (i, [P, P, P, P, z] + [f32] * 6 + [P, P]),
+    "mlhot_adam_step": (i, [P, P, P, P, z, f32, f64, f64, f32, f32, f32, i, P]),
+    "mlhot_adam_step_counter": (i, [P, P, P, P, z, f32, f64, f64, f32, f32, f32, P, P]),
     # X1: ConvEmbeddingModel building blocks
     "mlhot_bn_relu_fwd": (i, [P, P, P, P, P, f32, f32, i, i, i, P, P, P, P]),
     "mlhot_bn_relu_bwd": (i, [P, P, P, P, P, P, f32, i, i, i, P, P, P, P]),

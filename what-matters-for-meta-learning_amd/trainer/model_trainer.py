@@ -343,8 +343,10 @@ class ModelTrainer(BaseTrainer):
             shot = int(getattr(config, "max_ctx_num", 15) or 15)
             flat = FlatAdam.from_torch_adam(self.optimizer, model, ctx_num=min(shot, 15), test_num=min(shot, 15))
             if flat is not None:
-                # From here on `trainer.optimizer` IS the optimizer: checkpoint its state_dict() (torch.optim.Adam's layout), point an LR
-                # scheduler at its param_groups[0]["lr"].  The caller's torch object is left as it was - it no longer steps anything.
+                # From here on `trainer.optimizer` IS the optimizer: checkpoint its state_dict() (torch.optim.Adam's layout); a learning-rate
+                # schedule WRITES trainer.optimizer.param_groups[0]["lr"] (the torch.optim.lr_scheduler classes take a torch.optim.Optimizer
+                # only and refuse it).  The caller's torch object is left as it was - it no longer steps anything, so a scheduler built on
+                # it has no effect (_announce says so when it finds one).
                 self.replaced_optimizer, self.optimizer = self.optimizer, flat
                 if hasattr(model, "enable_flat_grads") and model.__dict__.get("_arena") is None:
                     model.enable_flat_grads()      # ResNet / BBB family: the gradients as the mirror of the flat parameter buffer
@@ -371,7 +373,13 @@ class ModelTrainer(BaseTrainer):
         """Once, at the start of train(): what the constructor promoted (nothing here is silent)."""
         if self.replaced_optimizer is not None:
             self._log("mlhot: torch.optim.Adam continued by mlhot.optim.FlatAdam (one launch over the flat parameter buffer; same hyper-parameters, "
-                      "moments and step count).  Checkpoint / schedule `trainer.optimizer`; the optimizer object passed in no longer steps.")
+                      "moments and step count).  Checkpoint `trainer.optimizer`; a learning-rate schedule must write "
+                      'trainer.optimizer.param_groups[0]["lr"] (a torch.optim.lr_scheduler does not accept it); the optimizer object passed in no '
+                      "longer steps.")
+            # a torch scheduler's constructor leaves `initial_lr` in the groups of the optimizer it was built on
+            if any("initial_lr" in g for g in self.replaced_optimizer.param_groups):
+                self._log("mlhot: a torch.optim.lr_scheduler was built on the optimizer passed in: it keeps writing to an optimizer that no longer "
+                          'steps, so it has no effect.  Copy its value per iteration into trainer.optimizer.param_groups[0]["lr"] instead.')
         if self._graph_default:
             self._log("mlhot: training iterations are replayed from hipGraphs (one per batch shape); a change of trainer.optimizer.param_groups[0] "
                       "(lr, betas, eps, weight_decay) is picked up by re-capturing.")
