@@ -428,6 +428,20 @@ int mlhot_favor_summary_gather(const void* const* states /* host array of n devi
                                const int32_t* parts /* [T_out][P][2], DEVICE memory */, int P,
                                const float* m_floor /* one float, DEVICE memory, may be NULL */,
                                int T_out, int H, int d, int m, void* out, size_t state_bytes, void* stream);
+/* mlhot_favor_summary_retract: mlhot_favor_summary_absorb's argument list with the sign turned - k, v [T,n,H,d] are
+ *   shots that were absorbed into state_in EARLIER (n <= 32 per task and call; lens as for absorb, 0 .. n) and are taken out again.
+ *   M stays as it is (no rescale; the stabiliser of a summary never falls);  e[n,j] = exp(min(dd[n,j] - M, 0) - diag[n]) - for a shot
+ *   that was absorbed dd <= M holds and the min does nothing;  A <- A - sum_n e v,  a <- max(a - sum_n e, 0),  vs -= sum_n v,
+ *   cnt -= lens.  In exact arithmetic the result is the state absorbed from the remaining shots with the M of the larger set; in
+ *   fp32 the subtraction rounds at the scale of the state BEFORE the retraction.  A shot that was never absorbed gives a result
+ *   that is undefined in value but finite (e <= 1).  That cnt stays >= 0 is the caller's to see to.  state_in and state_out may be the
+ *   same pointer (in place, bit-equal to the call with a buffer of its own; otherwise state_in is left as it is, and a partial
+ *   overlap is MLHOT_ERR_ARG).  ws: mlhot_favor_summary_ws_bytes(T, H, n, d, m) bytes.  Two launches (labels favor.sum_retract1 - absorb's
+ *   first launch as it is - and favor.sum_retract2), no atomics, every summation order a function of the dimensions alone.  Shapes and
+ *   error codes as for absorb; whatever is refused writes nothing.  GPU build only.  Added within ABI 8: bindings look the symbol up. */
+int mlhot_favor_summary_retract(const float* k, const float* v, const float* proj, const int32_t* lens /* [T], device, or NULL */,
+                                int T, int H, int n, int d, int m, const void* state_in, void* state_out, size_t state_bytes,
+                                void* ws, size_t ws_bytes, void* stream);
 
 /* ---- prefix sweep beyond 32 context shots: chunked running FAVOR+ prefixes (csrc/favor_prefix_long.h) -------------
  * mlhot_favor_prefix_long_fwd: q[T,Nq,H,d], k, v[T,Nc,H,d], proj[m,d] -> out[K,T,Nq,d*H] in mlhot_favor_fwd's merged order; out[i]
@@ -545,6 +559,20 @@ int mlhot_favor_query_paged_masked_fwd(const float* q, const void* state, const 
                                        const uint32_t* mask_words /* [T,G,Nq,ceil(Nc/32)], device */, int G,
                                        int T, int H, int Nq, int Nc, int d, int m, float* out /* [T,G,Nq,d*H] */,
                                        float* w /* [T,G,H,Nq,Nc], or NULL */, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- cached contexts that let shots go: the per-shot rows moved by a plan (csrc/rows_compact.h) ------------------
+ * mlhot_rows_compact: `sets` row sets, 1 <= sets <= 4, that share one plan.  Row set i is (src[i], dst[i], W[i]): fp32 rows of W[i]
+ *   floats in [T][cap][W[i]]; src, dst and W are arrays of `sets` entries in HOST memory.  plan[T][cap] (int32, DEVICE memory, read by
+ *   the kernel alone - no host synchronisation):  dst_i[t][s][:] = src_i[t][plan[t][s]][:],  and a row of exact zeros - src is not
+ *   read - where plan[t][s] is -1.  A plan value outside -1 .. cap - 1 is held to -1, so no plan content reads or writes out of
+ *   bounds.  Rows are selected by index, never by a product with a mask: a NaN or Inf in a row that no plan entry names does not reach
+ *   dst.  EVERY row of every dst is written, whatever it held.  ONE launch (label rows.compact), float4 loads and stores, no atomics.
+ *   Served: W[i] % 4 == 0, 16-byte aligned src and dst, 1 <= cap <= 4096 (and fewer than 2^31 float4 per task over all sets);
+ *   otherwise MLHOT_ERR_UNSUPPORTED.  A dst that overlaps any src, or another dst: MLHOT_ERR_ARG.  Whatever is refused writes nothing.
+ *   GPU build only (the host build returns MLHOT_ERR_UNSUPPORTED).  Added within ABI 8: bindings look the symbol up. */
+int mlhot_rows_compact(const float* const* src /* host array of `sets` device pointers */,
+                       float* const* dst /* host array of `sets` device pointers */, const int* W /* host array */, int sets,
+                       const int32_t* plan /* [T][cap], DEVICE memory */, int T, int cap, void* stream);
 
 /* ---- strict sharded parity of the key stabiliser -------------------------
  * fast_attention.py:96-97 takes torch.max over the keys of the WHOLE batch.  When a caller shards the meta-batch over

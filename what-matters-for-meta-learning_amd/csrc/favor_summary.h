@@ -17,6 +17,8 @@
 //             -inf - -inf never forms), e[n, j] = exp(dd - diag - M') in LDS (0 behind lens[t] and at features >= m - selected by
 //             index, never by a product), then A <- s A + e^T v on the matrix core (K = the 32 shot slots), a <- s a + the row sums of
 //             e^T; chunk 0 of a (task, head) adds vs and cnt, chunk 0 of (0, 0) writes M'
+//   retract R1 = A1 as it is, R2 grid as A2: M stays, e = exp(min(dd - M, 0) - diag), A <- A - e^T v, a <- max(a - rowsum e, 0), vs and
+//             cnt go down (fsum::retract2_kernel below)
 //   query  grid (task x head x 16-row query tile), ONE launch for any Nq: F_q in LDS (ft::query_front), then
 //             [16 x mp] [mp x d] against A streamed from memory: wave w takes the 16-feature chunks w, w + 4, .. in ascending order
 //             for all d columns, the four partial tiles fold 0, 1, 2, 3 through LDS (F_q's space, dead by then); the row sums of
@@ -162,6 +164,76 @@ __global__ __launch_bounds__(256) void absorb2_kernel(const AbsorbArgs a) {
     }
     if (tid == 0) a.out.cnt[th] = a.in.cnt[th] + len;
     if (th == 0 && tid == 0) a.out.M[0] = M;
+  }
+}
+
+// ---- retract, launch 2: shots that were absorbed earlier are taken out again ------------------------------------
+// absorb2_kernel's grid and layout with the sign turned: M stays the state's (no rescale; absorb1's maxima in the workspace are not
+// read), e[n, j] = exp(min(dd - M, 0) - diag) - for a shot that WAS absorbed dd <= M holds and the min does nothing; for one that never
+// was, it keeps e <= 1, so the result is undefined in value but finite - then A <- A - e^T v on the matrix core, a <- max(a - the row
+// sums of e^T, 0), vs -= sum v, cnt -= len.  A kernel of its own: absorb2_kernel keeps its code, its bits and its resources.  In place
+// (in == out) no workgroup writes M; out of place one workgroup copies M's block and cnt's padding, which nobody reads.
+__global__ __launch_bounds__(256) void retract2_kernel(const AbsorbArgs a) {
+  __shared__ float es[MAXN * LDE];
+  __shared__ float s_diag[MAXN];
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, lq = lane >> 4;
+  const int th = blockIdx.x, t = th / a.H, h = th % a.H, chunk = blockIdx.y;
+  const int d = a.d, n = a.n, m = a.m, mp = a.mp, H = a.H;
+  const int len = new_len(a.lens, t, n);
+  {
+    const int r = tid >> 3;
+    const float dg = ft::key_diag(r < len ? a.k + ((size_t)(t * n + r) * H + h) * d : nullptr, d, a.c, tid);
+    if ((tid & 7) == 0) s_diag[r] = dg;
+  }
+  __syncthreads();
+  const float M = a.ws.Mold[0];
+  const int j0 = chunk * FC;
+  const float* ddb = a.ws.dd + (size_t)th * n * mp;
+  for (int idx = tid; idx < MAXN * FC; idx += 256) {
+    const int row = idx / FC, jj = idx - row * FC, j = j0 + jj;
+    es[row * LDE + jj] = (row < len && j < m) ? expf(fminf(ddb[(size_t)row * mp + j] - M, 0.f) - s_diag[row]) : 0.f;
+  }
+  __syncthreads();
+  const int jw = j0 + 16 * wv;
+  if (jw < mp) {
+    const int nks = (len + 3) / 4;
+    float ea[MAXN / 4];
+#pragma unroll
+    for (int ks = 0; ks < MAXN / 4; ++ks) ea[ks] = es[(4 * ks + lq) * LDE + 16 * wv + lr];
+    const float* Ain = a.in.A + ((size_t)th * mp + jw) * d;
+    float* Aout = a.out.A + ((size_t)th * mp + jw) * d;
+    for (int et = 0; 16 * et < d; ++et) {
+      const int e = 16 * et + lr;
+      float bv[MAXN / 4], old[4];
+#pragma unroll
+      for (int ks = 0; ks < MAXN / 4; ++ks) { const int np = 4 * ks + lq; bv[ks] = np < len ? a.v[((size_t)(t * n + np) * H + h) * d + e] : 0.f; }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) old[r] = Ain[(size_t)(4 * lq + r) * d + e];
+      f32x4_t o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < MAXN / 4; ++ks)
+        if (ks < nks) o = mfma4(ea[ks], bv[ks], o);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Aout[(size_t)(4 * lq + r) * d + e] = old[r] - o[r];
+    }
+  }
+  if (tid < FC && j0 + tid < mp) {
+    float s = 0.f;
+    for (int row = 0; row < len; ++row) s += es[row * LDE + tid];
+    a.out.a[(size_t)th * mp + j0 + tid] = fmaxf(a.in.a[(size_t)th * mp + j0 + tid] - s, 0.f);
+  }
+  if (chunk == 0) {
+    if (tid < d) {
+      float s = 0.f;
+      for (int row = 0; row < len; ++row) s += a.v[((size_t)(t * n + row) * H + h) * d + tid];
+      a.out.vs[(size_t)th * d + tid] = a.in.vs[(size_t)th * d + tid] - s;
+    }
+    if (tid == 0) a.out.cnt[th] = a.in.cnt[th] - len;
+    if (th == 0 && a.out.M != a.in.M) {                          // a buffer of its own: M's block, and cnt's padding as init leaves it
+      if (tid < 16) a.out.M[tid] = tid == 0 ? M : 0.f;
+      const int thn = a.T * H;
+      if (tid >= 64 && tid < 80 && thn + tid - 64 < (thn + 15) / 16 * 16) a.out.cnt[thn + tid - 64] = 0;
+    }
   }
 }
 
@@ -497,6 +569,49 @@ inline int favor_summary_absorb(const float* k, const float* v, const float* pro
     hipLaunchKernelGGL(fsum::absorb2_kernel, dim3(T * H, (a.mp + fsum::FC - 1) / fsum::FC), dim3(256), 0, s, a);
   }
   return check_launch("favor.sum_absorb2");
+#endif
+}
+
+// the shots k, v - absorbed into state_in earlier - taken out again: absorb's argument list, absorb's first launch, fsum::retract2_kernel
+inline int favor_summary_retract(const float* k, const float* v, const float* proj, const int32_t* lens, int T, int H, int n, int d, int m,
+                                 const void* state_in, void* state_out, size_t state_bytes, void* ws, size_t ws_bytes, hipStream_t s) {
+  if (T <= 0 || H <= 0 || n <= 0 || d <= 0 || m <= 0 || !k || !v || !proj || !state_in || !state_out) { set_error("favor_summary_retract: bad argument"); return MLHOT_ERR_ARG; }
+  if (!favor_summary_ok(T, H, d, m)) return favor_summary_unsupported("favor_summary_retract", d, m);
+#ifdef MLHOT_HOSTSIM
+  (void)lens; (void)state_bytes; (void)ws; (void)ws_bytes; (void)s; return MLHOT_ERR_UNSUPPORTED;
+#else
+  if (n > fsum::MAXN) { set_error("favor_summary_retract takes at most 32 shots per task and call (got n=%d): retract in chunks", n); return MLHOT_ERR_UNSUPPORTED; }
+  fsum::AbsorbArgs a{};
+  a.in = fsum::carve_state(T, H, d, m, const_cast<void*>(state_in));
+  a.out = fsum::carve_state(T, H, d, m, state_out);
+  a.ws = fsum::carve_ws(T, H, n, a.in.mp, ws);
+  const size_t need = a.in.floats * sizeof(float);
+  if (state_bytes < need) { set_error("favor_summary_retract: state too small (%zu < %zu)", state_bytes, need); return MLHOT_ERR_WORKSPACE; }
+  if (!ws || ws_bytes < a.ws.floats * sizeof(float)) { set_error("favor_summary_retract: workspace too small"); return MLHOT_ERR_WORKSPACE; }
+  if (!ft::aligned16(k) || !ft::aligned16(v) || !ft::aligned16(proj) || !ft::aligned16(state_in) || !ft::aligned16(state_out) || !ft::aligned16(ws)) {
+    set_error("favor_summary_retract: k, v, proj, the states and ws must be 16-byte aligned"); return MLHOT_ERR_ARG;
+  }
+  {
+    const char* ib = (const char*)state_in;
+    const char* ob = (const char*)state_out;
+    if (ib != ob && ib < ob + need && ob < ib + need) {           // the same buffer (in place) or two apart, nothing in between
+      set_error("favor_summary_retract: state_out overlaps state_in without being it"); return MLHOT_ERR_ARG;
+    }
+  }
+  a.k = k; a.v = v; a.proj = proj; a.lens = lens;
+  a.T = T; a.H = H; a.n = n; a.d = d; a.m = m; a.mp = a.in.mp;
+  a.c = ft::Scales(d, m).c;
+  {
+    ProfScope ps("favor.sum_retract1", s);
+    if (n <= 16) hipLaunchKernelGGL((fsum::absorb1_kernel<1>), dim3(T * H, a.ws.nch), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((fsum::absorb1_kernel<2>), dim3(T * H, a.ws.nch), dim3(256), 0, s, a);
+  }
+  MLHOT_TRY(check_launch("favor.sum_retract1"));
+  {
+    ProfScope ps("favor.sum_retract2", s);
+    hipLaunchKernelGGL(fsum::retract2_kernel, dim3(T * H, (a.mp + fsum::FC - 1) / fsum::FC), dim3(256), 0, s, a);
+  }
+  return check_launch("favor.sum_retract2");
 #endif
 }
 

@@ -34,6 +34,7 @@
 #include "favor_prefix_long.h"
 #include "favor_long.h"
 #include "favor_paged.h"
+#include "rows_compact.h"
 #include "resnet_trunk.h"
 #include "../../include/mlhot.h"
 
@@ -380,6 +381,10 @@ int mlhot_favor_summary_gather(const void* const* states, const int* state_tasks
                                int H, int d, int m, void* out, size_t state_bytes, void* stream) {
   return favor_summary_gather(states, state_tasks, n, parts, P, m_floor, T_out, H, d, m, out, state_bytes, (hipStream_t)stream);
 }
+int mlhot_favor_summary_retract(const float* k, const float* v, const float* proj, const int32_t* lens, int T, int H, int n, int d, int m,
+                                const void* state_in, void* state_out, size_t state_bytes, void* ws, size_t ws_bytes, void* stream) {
+  return favor_summary_retract(k, v, proj, lens, T, H, n, d, m, state_in, state_out, state_bytes, ws, ws_bytes, (hipStream_t)stream);
+}
 // K context prefixes of any length: running sums over 32-shot chunks, three launches (csrc/favor_prefix_long.h)
 int mlhot_favor_prefix_long_supported(int T, int H, int Nq, int Nc, int d, int m, int K) { return favor_prefix_long_ok(T, H, Nq, Nc, d, m, K) ? 1 : 0; }
 size_t mlhot_favor_prefix_long_workspace_bytes(int T, int H, int Nq, int Nc, int d, int m, int K) { return favor_prefix_long_ws_need(T, H, Nq, Nc, d, m, K); }
@@ -423,6 +428,10 @@ int mlhot_favor_query_paged_masked_fwd(const float* q, const void* state, const 
                                        int G, int T, int H, int Nq, int Nc, int d, int m, float* out, float* w, void* ws, size_t ws_bytes, void* stream) {
   return favor_query_paged_launch("favor_query_paged_masked_fwd", true, q, state, v, proj, lens, mask_words, G, T, H, Nq, Nc, d, m, out, w, ws, ws_bytes,
                                   (hipStream_t)stream);
+}
+// cached contexts that let shots go: the per-shot rows of up to 4 row sets moved by one plan, one launch (csrc/rows_compact.h)
+int mlhot_rows_compact(const float* const* src, float* const* dst, const int* W, int sets, const int32_t* plan, int T, int cap, void* stream) {
+  return rows_compact(src, dst, W, sets, plan, T, cap, (hipStream_t)stream);
 }
 // Staged passes (strict sharded parity of the key stabiliser, csrc/stab_xchg.h): stage 0 runs up to the rank-local scalar and
 // publishes it in xchg, stage 1 takes the batch-wide scalar from xchg and runs the rest.

@@ -288,6 +288,7 @@ SIGNATURES = {
     "mlhot_favor_summary_query_fwd": (i, [P, P, P, i, i, i, i, i, P, P, z, P]),
     "mlhot_favor_summary_merge": (i, [P, i, P, i, i, i, i, P, z, P]),
     "mlhot_favor_summary_gather": (i, [P, P, i, P, i, P, i, i, i, i, P, z, P]),
+    "mlhot_favor_summary_retract": (i, [P, P, P, P, i, i, i, i, i, P, P, z, P, z, P]),
     # prefix sweep beyond 32 context shots: chunked running FAVOR+ prefixes
     "mlhot_favor_prefix_long_supported": (i, [i] * 7),
     "mlhot_favor_prefix_long_workspace_bytes": (z, [i] * 7),
@@ -307,6 +308,8 @@ SIGNATURES = {
     "mlhot_favor_keys_paged_fwd": (i, [P, P, P, i, i, i, i, i, P, z, P]),
     "mlhot_favor_query_paged_fwd": (i, [P, P, P, P, P, i, i, i, i, i, i, P, P, P, z, P]),
     "mlhot_favor_query_paged_masked_fwd": (i, [P, P, P, P, P, P, i, i, i, i, i, i, i, P, P, P, z, P]),
+    # cached contexts that let shots go: the per-shot rows moved by a plan
+    "mlhot_rows_compact": (i, [P, P, P, i, P, i, i, P]),
     # strict sharded parity of the key stabiliser
     "mlhot_favor_fwd_staged": (i, _qkvp + [P, P, z, i, P, P]),
     "mlhot_favor_bwd_staged": (i, _qkvp + [P, P, P, P, P, P, z, i, P, P]),
@@ -1344,29 +1347,39 @@ class MlhotLib:
         """k, v [T,n,H,d] (n <= 32 new shots per task), proj [m,d], a summary state, lens [T] int32 on k's device or None -> the
         state with the valid new shots absorbed: `out` (may be `state` itself: in place) or a new buffer; `state` is then left as it
         is.  Rows at or behind lens[t] of k and v are never read.  The values of lens are the caller's to check (0 .. n)."""
-        fn = self._fn("favor_summary_absorb", "mlhot_favor_summary_absorb")
+        return self._favor_summary_step("favor_summary_absorb", k, v, proj, state, lens, out)
+
+    def favor_summary_retract(self, k, v, proj, state, lens=None, out=None):
+        """favor_summary_absorb's arguments with the sign turned: k, v [T,n,H,d] are shots that WERE absorbed into
+        `state` and are taken out again -> `out` (may be `state` itself: in place, the same bits) or a new buffer.  The stabiliser
+        stays the state's.  That the shots were absorbed, and that no task goes below zero shots, is the caller's to see to."""
+        return self._favor_summary_step("favor_summary_retract", k, v, proj, state, lens, out)
+
+    def _favor_summary_step(self, what, k, v, proj, state, lens, out):
+        """mlhot_favor_summary_absorb / _retract: one argument list, one set of checks."""
+        fn = self._fn(what, "mlhot_" + what)
         if k.dtype != torch.float32 or k.dim() != 4 or v.dtype != torch.float32 or v.shape != k.shape or proj.dtype != torch.float32 or proj.dim() != 2 \
                 or proj.shape[1] != k.shape[3] or any(t.device != k.device for t in (v, proj, state)):
-            raise MlhotError(f"favor_summary_absorb: k and v must be fp32 [T, n, H, d] and proj fp32 [m, d] on the state's device, got "
+            raise MlhotError(f"{what}: k and v must be fp32 [T, n, H, d] and proj fp32 [m, d] on the state's device, got "
                              f"{tuple(k.shape)}, {tuple(v.shape)}, {tuple(proj.shape)}")
         T, n, H, d = k.shape
         m = proj.shape[0]
         if lens is not None and (lens.dtype != torch.int32 or tuple(lens.shape) != (T,) or lens.device != k.device):
-            raise MlhotError(f"favor_summary_absorb: lens must be int32 [{T}] on {k.device}, got {lens.dtype} {tuple(lens.shape)} on {lens.device}")
+            raise MlhotError(f"{what}: lens must be int32 [{T}] on {k.device}, got {lens.dtype} {tuple(lens.shape)} on {lens.device}")
         nb = self.favor_summary_bytes(T, H, d, m)
-        wb = self._fn("favor_summary_absorb", "mlhot_favor_summary_ws_bytes")(T, H, n, d, m)
+        wb = self._fn(what, "mlhot_favor_summary_ws_bytes")(T, H, n, d, m)
         if not nb or not wb:
-            raise MlhotError(f"favor_summary_absorb serves 1 <= n <= 32 new shots per call, d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536 "
+            raise MlhotError(f"{what} serves 1 <= n <= 32 new shots per call, d % 16 == 0, 16 <= d <= 256, 16 <= m <= 1536 "
                              f"(got n={n} d={d} m={m}); mlhot.ops.favor_absorb chunks longer inputs")
         if out is None:
             out = torch.empty(nb, dtype=torch.uint8, device=k.device)
         for name, s in (("state", state), ("out", out)):
             if s.dtype != torch.uint8 or s.numel() < nb or s.device != k.device:
-                raise MlhotError(f"favor_summary_absorb: {name} is not a summary state for T={T} H={H} d={d} m={m} ({s.numel()} bytes, {nb} needed)")
+                raise MlhotError(f"{what}: {name} is not a summary state for T={T} H={H} d={d} m={m} ({s.numel()} bytes, {nb} needed)")
         _chk(k, v, proj, state, out, *([lens] if lens is not None else []))
         ws = self._bytes(wb, k)
         self._rc(fn(_ptr(k), _ptr(v), _ptr(proj), _ptr(lens) if lens is not None else None, T, H, n, d, m, _ptr(state), _ptr(out), nb,
-                    _ptr(ws), ws.numel(), _stream(k)), "mlhot_favor_summary_absorb")
+                    _ptr(ws), ws.numel(), _stream(k)), "mlhot_" + what)
         return out
 
     @staticmethod
@@ -1462,6 +1475,31 @@ class MlhotLib:
         counts = (C.c_int * len(bufs))(*tasks)
         self._rc(fn(table, counts, len(bufs), _ptr(parts), P, _ptr(floor), T_out, H, d, m, _ptr(out), nb, _stream(out)), "mlhot_favor_summary_gather")
         return out
+
+    # ---- per-shot rows moved by a plan (csrc/rows_compact.h) --------------------------------------
+    ROWS_COMPACT_SETS = 4  # row sets per mlhot_rows_compact call
+
+    def rows_compact(self, srcs, plan):
+        """1 .. 4 row sets srcs[i] fp32 [T, cap, ...] that share plan, int32 [T, cap] on their device -> new tensors of the same
+        shapes: row s of task t is row plan[t, s] of the source, a row of exact zeros where plan[t, s] is -1 (or out of range).
+        ONE launch (rows.compact); the sources are only read.  cap <= 4096 and row widths that are multiples of 4 floats, else
+        MlhotError."""
+        fn = self._fn("rows_compact", "mlhot_rows_compact")
+        srcs = list(srcs)
+        if not 1 <= len(srcs) <= self.ROWS_COMPACT_SETS:
+            raise MlhotError(f"rows_compact takes 1 .. {self.ROWS_COMPACT_SETS} row sets per call (got {len(srcs)})")
+        if not isinstance(plan, torch.Tensor) or plan.dtype != torch.int32 or plan.dim() != 2 or not plan.is_cuda:
+            raise MlhotError("rows_compact: plan must be an int32 [T, cap] tensor on the GPU")
+        T, cap = plan.shape
+        for k, x in enumerate(srcs):
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() < 3 or tuple(x.shape[:2]) != (T, cap) or x.device != plan.device:
+                raise MlhotError(f"rows_compact: row set {k} must be fp32 [T={T}, cap={cap}, ...] on {plan.device}")
+        _chk(plan, *srcs)
+        outs = [torch.empty_like(x) for x in srcs]
+        n = len(srcs)
+        self._rc(fn((C.c_void_p * n)(*[x.data_ptr() for x in srcs]), (C.c_void_p * n)(*[o.data_ptr() for o in outs]),
+                    (C.c_int * n)(*[x[0, 0].numel() for x in srcs]), n, _ptr(plan), T, cap, _stream(plan)), "mlhot_rows_compact")
+        return outs
 
     # ---- prefix sweep beyond 32 context shots (csrc/favor_prefix_long.h) --------------------------
     def favor_prefix_long_supported(self, T, H, Nq, Nc, d, m, K):

@@ -4,6 +4,9 @@
                                                                     # "long": per-shot rows for up to 256 shots, attention read-out (6c-7)
                                                                     # "paged": the same for up to 4096 shots (6c-11)
     state = mlhot.cached.extend(model, state, new_x, new_y, new_len=None)        # more context shots, only they are encoded (6c-3)
+    state = mlhot.cached.evict(model, state, drop)                  # drop[t]: the slots task t lets go; no image is encoded (6c-12)
+    state = mlhot.cached.retract(model, state, old_x, old_y, old_len=None)       # the same for a summary: the old shots are handed in
+    state = mlhot.cached.slide(model, state, new_x, new_y, new_len=None)         # a window: the oldest shots go, the new ones come
     state = mlhot.cached.merge(model, [state_a, state_b, ..])       # summary states conditioned apart -> one, no image re-read (6c-6)
     state = mlhot.cached.select(model, [state_a, state_b, ..], picks)      # a batch put together from the TASKS of summary states:
                                                                     # picks[t] = (state, task) or a list of such pairs (6c-8)
@@ -283,6 +286,47 @@ def extend(model, state, new_x, new_y, new_len=None):
     if isinstance(model, ResNetNP):
         return model.extend(state, new_x, new_y, new_len=new_len)
     return context.extend(_Vanilla(model), state, new_x, new_y, new_len)
+
+
+def _adapter(model):
+    return _CachedContext(model) if isinstance(model, ResNetNP) else _Vanilla(model)
+
+
+def evict(model, state, drop):
+    """(per-shot or latent state, drop) -> a NEW state without the context shots in the slots `drop[t]` of task t.
+    `drop` is a sequence of T sequences of host ints: distinct slot indices below `state.lens[t]`, possibly none.  Capacity, form and
+    kind stay; `lens[t]` shrinks by `len(drop[t])`; the kept shots move to the front in their order and the freed slots behind them
+    are zero rows, exactly as `condition(ctx_len=, capacity=)` leaves spare slots, so `extend`, `predict`, `return_attention=True`,
+    `context_mask=` and `leave_one_out` serve the result like any state of its form.  The old state stays valid.  No image is
+    encoded again: ONE launch (mlhot_rows_compact) moves the kept rows of both row sets, then the state's own key launches run with
+    the new lens - the key stabiliser is the maximum over the shots that remain, exactly what a fresh `condition` computes
+    (attention) - or extend's finishing steps, the prefix aggregate with its gather and r_to_z (latent).  Both families; eval
+    mode.  Refused with ValueError before anything touches the GPU: a foreign or stale state or one of another T, a summary or
+    empty state, an index out of range or named twice, a `drop` that leaves a task without a shot.  ResNetNP: model.evict."""
+    if isinstance(model, ResNetNP):
+        return model.evict(state, drop)
+    return context.evict(_Vanilla(model), state, drop)
+
+
+def retract(model, state, old_x, old_y, old_len=None):
+    """(summary state, ctx images [T, n, ...] it holds, their labels [T, n, L], old_len) -> a NEW summary state without the first
+    `old_len[t]` (0 .. n; default n) of them per task; the old state stays valid.  A summary keeps no per-shot rows,
+    so the caller hands in the shots to take out; they are encoded like extend's new shots and subtracted
+    (mlhot.ops.favor_retract).  The key stabiliser stays the state's: in exact arithmetic the result is
+    `condition(form="summary")` on the remaining shots with the stabiliser of the larger set - merge's and select's caveat (6c-6):
+    the result moves within the eps terms - and in fp32 it carries the rounding of a subtraction at the scale of the state before
+    the retraction.  Shots that the state never absorbed give a finite but meaningless state.  Both families; eval mode.  Refused
+    with ValueError before anything touches the GPU: everything extend refuses on a summary state, a state that is no summary, and
+    `old_len[t] >= state.lens[t]` - a task keeps at least one shot."""
+    return context.retract(_adapter(model), state, old_x, old_y, old_len)
+
+
+def slide(model, state, new_x, new_y, new_len=None):
+    """(per-shot or latent state, new ctx images [T, n, ...], labels, new_len) -> a NEW state holding the new shots like extend's,
+    every task having given up its OLDEST slots first, only as many as `new_len[t]` needs beyond the spare capacity (DESIGN.md
+    6c-12): a window over the last `capacity` shots of a stream in which only the new shots are ever encoded.  evict, then extend.
+    `new_len[t]` above the capacity, a summary or empty state and whatever extend refuses raise ValueError."""
+    return context.slide(_adapter(model), state, new_x, new_y, new_len)
 
 
 def merge(model, states):

@@ -20,7 +20,7 @@ import numbers
 import torch
 
 from mlhot import lib, ragged
-from mlhot.ops import GATHER_PARTS, PER_SHOT_ROUTES, LinearFunction, favor_gather, favor_keys, favor_merge
+from mlhot.ops import GATHER_PARTS, PER_SHOT_ROUTES, LinearFunction, _c, favor_gather, favor_keys, favor_merge
 
 
 class ContextState:
@@ -122,6 +122,101 @@ def extend(ad, state, new_x, new_y, new_len=None):
         if state.form == "summary":
             return _absorb(ad, state, new_x, new_y, add, state.wq)
         return _grow(ad, state, state.lens, state.capacity, new_x, new_y, add, state.wq, state.form)
+
+
+def _own(ad, what, state):
+    """_enter's checks for a call that brings no rows of its own (evict)."""
+    ad.refuse(what)
+    if not isinstance(state, ContextState) or state.owner is not ad.model:
+        raise ValueError(f"{what}: the state was not made by this model's condition()")
+    if state.T != ad.model.task_num:
+        raise ValueError(f"{what}: the state holds {state.T} tasks, the model was built for tasks_per_batch = {ad.model.task_num}")
+    if state.fingerprint != fingerprint(ad.model):
+        raise ValueError(f"{what}: the state is stale - a parameter of the model changed since condition()")
+
+
+def _refuse_rowless(what, state, instead):
+    """evict's and slide's: a state without per-shot rows has no slot to free."""
+    if state.kind == "empty":
+        raise ValueError(f"{what}: the state holds no context shot")
+    if state.form == "summary":
+        raise ValueError(f"{what}: a summary state keeps no per-shot rows, so there is no slot to free; {instead}")
+
+
+def _compact(state, plan):
+    """The per-shot rows of `state` moved by plan.rows: ONE mlhot_rows_compact launch for both row sets -> (kh, vh) / (rs, lv)."""
+    a_rows, b_rows = (state.kh, state.vh) if state.kind == "attention" else (state.rs, state.lv)
+    if a_rows is None:
+        raise ValueError("evict: the state carries no per-shot rows (it was not made by condition())")
+    out = lib().rows_compact([_c(x) for x in (a_rows, b_rows) if x is not None], plan.rows)
+    return out[0], out[1] if b_rows is not None else None
+
+
+def evict(ad, state, drop):
+    """(state, drop) -> a NEW state without the context shots in the slots drop[t] of task t: the kept shots move to
+    the front in their order, the freed slots behind them are zero rows as condition(ctx_len=, capacity=) leaves spare slots;
+    capacity, form and kind stay, the old state stays valid.  No image is encoded: one mlhot_rows_compact launch moves the kept rows,
+    then the finishing step of extend runs on them - the key launches of the state's form with the new lens, so the key stabiliser
+    is the maximum over the shots that remain, exactly condition's on them (attention), or the prefix aggregate with its gather
+    and the finishing Linear (latent)."""
+    what = "evict"
+    _own(ad, what, state)
+    _refuse_rowless(what, state, "mlhot.cached.retract takes shots out of a summary")
+    drop = ragged.evict_args(what, state, drop)
+    ad.prepare()
+    model = ad.model
+    with torch.no_grad():
+        plan = ragged.KeepPlan(state.lens, drop, state.capacity, (state.kh if state.kind == "attention" else state.rs).device)
+        a_rows, b_rows = _compact(state, plan)
+        if state.kind == "attention":
+            keys = ragged.masked_keys(a_rows, model.attn.projection_matrix, plan, state.form)
+            return ContextState(model, state.T, state.capacity, fingerprint(model), "attention", keys=keys, vh=b_rows, wq=state.wq, lens=plan.total,
+                                kh=a_rows, form=state.form)
+        return _latent(ad, state.capacity, a_rows, b_rows, ragged.gathered_aggregate(model.agg_mode, a_rows, b_rows, plan), plan.total)
+
+
+def retract(ad, state, old_x, old_y, old_len=None):
+    """(summary state, ctx images [T, n, ...] that were conditioned or extended into it, their labels [T, n, L], old_len) -> a NEW
+    summary state without the first old_len[t] (0 .. n; default n) of them per task; the old state stays valid.  A
+    summary keeps no per-shot rows, so the shots to take out are handed in again: they go through the per-shot stage like extend's
+    new shots and are subtracted (mlhot.ops.favor_retract).  The key stabiliser stays the state's."""
+    what = "retract"
+    _enter(ad, what, state, old_x, "old shots")
+    if state.form != "summary":
+        raise ValueError(f"{what}: the state is no summary ({state.kind!r}, form {state.form!r}) - a state with per-shot rows lets shots go by "
+                         "their slots: mlhot.cached.evict")
+    T, n = old_x.shape[0], old_x.shape[1]
+    sub = ragged.retract_args(what, state, T, n, old_len)
+    ad.prepare(old_x, old_y)
+    model = ad.model
+    with torch.no_grad():
+        plan = ragged.Plan((0,) * T, sub, n, n, old_x.device)
+        keys = state.keys
+        if plan.n:
+            old_k, old_v = ad.shot_rows(ragged.pack(_images(model, old_x), plan.src), ragged.pack(old_y.reshape(T, n, -1), plan.src))
+            keys = ragged.summary_retract(keys, old_k, old_v, plan, T, n, model.attn.projection_matrix, sub)
+        return ContextState(model, T, max(keys.lens), fingerprint(model), "attention", keys=keys, wq=state.wq, lens=keys.lens, form="summary")
+
+
+def slide(ad, state, new_x, new_y, new_len=None):
+    """(per-shot or latent state, new ctx images [T, n, ...], labels, new_len) -> a NEW state that holds the new shots like extend's,
+    every task having given up its OLDEST slots first - only as many as new_len[t] needs beyond the spare capacity:
+    the window of the last `capacity` shots of a stream.  evict, then extend; of evict only the row compaction runs, its finishing
+    step would be overwritten by extend's on the same rows."""
+    what = "slide"
+    _enter(ad, what, state, new_x, "new shots")
+    _refuse_rowless(what, state, "a summary follows a stream with mlhot.cached.retract and extend")
+    T, n = new_x.shape[0], new_x.shape[1]
+    add, drop = ragged.slide_args(what, state, T, n, new_len)
+    ad.prepare(new_x, new_y)
+    with torch.no_grad():
+        kept = state
+        if any(drop):
+            plan = ragged.KeepPlan(state.lens, drop, state.capacity, new_x.device)
+            a_rows, b_rows = _compact(state, plan)
+            rows = dict(kh=a_rows, vh=b_rows) if state.kind == "attention" else dict(rs=a_rows, lv=b_rows)
+            kept = ContextState(state.owner, T, state.capacity, state.fingerprint, state.kind, lens=plan.total, form=state.form, **rows)
+        return _grow(ad, kept, kept.lens, state.capacity, new_x, new_y, add, state.wq, state.form)
 
 
 def _summary_states(ad, what, states, same_tasks=True):

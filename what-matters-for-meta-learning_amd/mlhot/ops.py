@@ -780,6 +780,49 @@ def favor_absorb(state, kh, vh, proj, lens=None):
     return FavorKeyState("summary", (T, max(total), H, d, m), buf=buf, lens=total)
 
 
+def favor_retract(state, kh, vh, proj, lens=None):
+    """Context shots out of a FAVOR+ summary again: `state` a summary state, k, v [T, n, H, d] (any n >= 1) the head
+    rows of shots that were absorbed into it earlier, proj [m, d] -> a NEW FavorKeyState of route "summary"; `state` stays valid.
+    `lens` (a host int sequence or CPU integer tensor of T values in 0..n): task t gives up its first lens[t] rows, the others are
+    never read; every task must keep at least one shot.  The stabiliser M stays the state's: in exact arithmetic the result is the
+    state absorbed from the remaining shots at the M of the larger set (the caveat of favor_merge and favor_gather), in fp32 the
+    subtraction rounds at the scale of the state before the retraction.  A shot that was never absorbed gives values that are
+    undefined but finite.  Longer inputs go in calls of 32 shots (mlhot_favor_summary_retract).  Forward only."""
+    _forward_only("favor_retract", kh, vh, proj)
+    _need_gpu(kh, vh, proj)
+    kh, vh, proj = _c(kh.detach()), _c(vh.detach()), _c(proj.detach())
+    if kh.dim() != 4 or vh.shape != kh.shape or kh.shape[1] < 1 or proj.dim() != 2 or proj.shape[1] != kh.shape[3]:
+        raise MlhotError(f"favor_retract: k and v must be [T, n >= 1, H, d] and proj [m, d], got {tuple(kh.shape)}, {tuple(vh.shape)}, {tuple(proj.shape)}")
+    T, n, H, d = kh.shape
+    m = proj.shape[0]
+    if not isinstance(state, FavorKeyState) or state.route != "summary":
+        raise MlhotError("favor_retract: state must be a summary state (favor_absorb's; a per-shot state lets shots go by compacting its rows)")
+    if (state.dims[0], *state.dims[2:]) != (T, H, d, m):
+        raise MlhotError(f"favor_retract: the state was built for T={state.dims[0]} H={state.dims[2]} d={state.dims[3]} m={state.dims[4]}; "
+                         f"got k {tuple(kh.shape)}, proj {tuple(proj.shape)}")
+    sub = (n,) * T if lens is None else host_lens(lens, T, 0, n, "favor_retract: lens")
+    short = [(t, s, l) for t, (s, l) in enumerate(zip(sub, state.lens)) if s >= l]
+    if short:
+        t, s, l = short[0]
+        raise MlhotError(f"favor_retract: task {t} holds {l} shots and would give up {s}; a task keeps at least one (its attention is 0 / 0 otherwise)")
+    starts = range(0, n, ABSORB_CHUNK)
+    dev = None            # one upload for every chunk's lens, before the first launch
+    if lens is not None:
+        dev = torch.tensor([[min(max(a - s, 0), ABSORB_CHUNK) for a in sub] for s in starts], dtype=torch.int32).to(kh.device)
+    buf = None
+    for i, s in enumerate(starts):
+        if lens is not None and max(sub) <= s:
+            break                                      # nothing valid from here on
+        e = min(s + ABSORB_CHUNK, n)
+        # the first call writes a buffer of this call's own, the later ones update it in place; the caller's state is only read
+        buf = lib().favor_summary_retract(_c(kh[:, s:e]), _c(vh[:, s:e]), proj, state.buf if buf is None else buf,
+                                          lens=None if dev is None else dev[i], out=buf)
+    if buf is None:                                    # no valid shot at all: still a state of its own
+        buf = state.buf.clone()
+    total = tuple(l - s for l, s in zip(state.lens, sub))
+    return FavorKeyState("summary", (T, max(total), H, d, m), buf=buf, lens=total)
+
+
 MERGE_GROUP = 8            # states per mlhot_favor_summary_merge call
 
 

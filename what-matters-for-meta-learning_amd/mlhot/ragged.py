@@ -6,7 +6,7 @@ import numbers
 
 import torch
 
-from mlhot.ops import agg_prefixes, favor_absorb, favor_keys, favor_keys_long, favor_keys_paged, host_lens
+from mlhot.ops import agg_prefixes, favor_absorb, favor_keys, favor_keys_long, favor_keys_paged, favor_retract, host_lens
 
 MAX_ATTENTION_CAPACITY = 32        # the cached FAVOR+ kernels' envelope on the context side (csrc/favor_cached.h)
 MAX_LONG_CAPACITY = 256            # the long per-shot kernels' (csrc/favor_long.h)
@@ -95,6 +95,16 @@ def summary_absorb(keys, new_k, new_v, plan, T, n, proj, add):
     return favor_absorb(keys, kh.view(T, n, *new_k.shape[1:]), vh.view(T, n, *new_k.shape[1:]), proj, lens=add)
 
 
+def summary_retract(keys, old_k, old_v, plan, T, n, proj, sub):
+    """summary_absorb with the sign turned: the packed head rows old_k, old_v [P, H, d] of the shots to take out (plan.dst: their flat
+    slots t * n + j) out of the summary state `keys` -> the new summary state (mlhot.ops.favor_retract; the old one stays valid)."""
+    kh = torch.zeros(T * n, *old_k.shape[1:], device=old_k.device)
+    vh = torch.zeros_like(kh)
+    kh.index_copy_(0, plan.dst, old_k)
+    vh.index_copy_(0, plan.dst, old_v)
+    return favor_retract(keys, kh.view(T, n, *old_k.shape[1:]), vh.view(T, n, *old_k.shape[1:]), proj, lens=sub)
+
+
 def extend_args(what, state, T, n, new_len):
     """-> the new shots per task; the state's own lens / capacity are checked against them."""
     lens, capacity = getattr(state, "lens", None), getattr(state, "capacity", None)
@@ -107,6 +117,87 @@ def extend_args(what, state, T, n, new_len):
         raise ValueError(f"{what}: task {t} would hold {total} context shots, the state's capacity is {capacity} - condition with "
                          "capacity= to reserve room for later shots")
     return add
+
+
+def _slots(what, state):
+    lens, capacity = getattr(state, "lens", None), getattr(state, "capacity", None)
+    if lens is None or capacity is None or getattr(state, "kind", None) not in ("attention", "latent"):
+        raise ValueError(f"{what}: the state carries no per-shot rows (it was not made by condition())")
+    return lens, capacity
+
+
+def evict_args(what, state, drop):
+    """-> drop as T sorted tuples of slot indices: distinct host ints below lens[t], and every task keeps a shot."""
+    lens, _ = _slots(what, state)
+    if isinstance(drop, torch.Tensor):
+        raise ValueError(f"{what}: drop must be a host sequence with one sequence of slot indices per task, got a tensor")
+    try:
+        drop = list(drop)
+        if any(isinstance(d, torch.Tensor) and d.is_cuda for d in drop):
+            raise ValueError(f"{what}: drop must hold host values (they are checked on the host), got a tensor on the GPU")
+        drop = [list(d.tolist() if isinstance(d, torch.Tensor) else d) for d in drop]
+    except TypeError:
+        raise ValueError(f"{what}: drop must be a sequence with one sequence of slot indices per task, got {drop!r}") from None
+    if len(drop) != len(lens):
+        raise ValueError(f"{what}: drop has {len(drop)} entries, the state holds {len(lens)} tasks")
+    out = []
+    for t, (d, l) in enumerate(zip(drop, lens)):
+        if any(isinstance(x, bool) or not isinstance(x, numbers.Integral) for x in d):
+            raise ValueError(f"{what}: drop[{t}] must hold integers (host values: they are checked on the host), got {d!r}")
+        d = [int(x) for x in d]
+        if d and (min(d) < 0 or max(d) >= l):
+            raise ValueError(f"{what}: drop[{t}] = {d} names a slot outside 0..{l - 1}, the {l} context shots task {t} holds")
+        if len(set(d)) != len(d):
+            raise ValueError(f"{what}: drop[{t}] = {d} names a slot twice")
+        if len(d) >= l:
+            raise ValueError(f"{what}: drop[{t}] would leave task {t} without a context shot (it holds {l}); a task keeps at least one")
+        out.append(tuple(sorted(d)))
+    return out
+
+
+def keep_rows(lens, drop, capacity):
+    """The plan of an eviction on the host: per task the source slot of every destination slot - the kept shots in their order,
+    then -1 ("a row of zeros") up to the capacity - and the new lens."""
+    rows, total = [], []
+    for l, d in zip(lens, drop):
+        gone = set(d)
+        keep = [s for s in range(l) if s not in gone]
+        rows.append(keep + [-1] * (capacity - len(keep)))
+        total.append(len(keep))
+    return rows, tuple(total)
+
+
+class KeepPlan:
+    """An eviction's indices on the device after ONE upload made before the first launch (Plan's rule): `rows` int32 [T, capacity]
+    is what mlhot_rows_compact reads (keep_rows); `total`, `lens` and `last` are Plan's, for the finishing steps on the kept rows."""
+
+    def __init__(self, lens, drop, capacity, device):
+        T = len(lens)
+        rows, self.total = keep_rows(lens, drop, capacity)
+        last = [(l - 1) * T + t for t, l in enumerate(self.total)]
+        buf = torch.tensor([s for r in rows for s in r] + last + list(self.total), dtype=torch.int32).to(device)
+        self.rows, self.last, self.lens = buf[:T * capacity].view(T, capacity), buf[T * capacity:T * capacity + T].long(), buf[T * capacity + T:]
+
+
+def retract_args(what, state, T, n, old_len):
+    """-> the shots per task a summary state gives up: 0 .. n each, and fewer than the task holds."""
+    sub = summary_extend_args(what, T, n, old_len)
+    for t, (s, l) in enumerate(zip(sub, state.lens)):
+        if s >= l:
+            raise ValueError(f"{what}: task {t} holds {l} context shots and would give up {s}; a task keeps at least one")
+    return sub
+
+
+def slide_args(what, state, T, n, new_len):
+    """-> (the new shots per task, the oldest slots every task gives up for them): only as many as do not fit into the spare slots."""
+    lens, capacity = _slots(what, state)
+    if n < 1:
+        raise ValueError(f"{what}: no new context slot handed in")
+    add = (n,) * T if new_len is None else host_lens(new_len, T, 0, n, f"{what}: new_len", ValueError)
+    for t, a in enumerate(add):
+        if a > capacity:
+            raise ValueError(f"{what}: task {t} takes {a} new context shots, the state's capacity is {capacity}")
+    return add, [tuple(range(max(0, l + a - capacity))) for l, a in zip(lens, add)]
 
 
 def pack_mask(mask, Nc):

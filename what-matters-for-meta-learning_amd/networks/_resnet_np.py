@@ -526,6 +526,13 @@ class ResNetNP(nn.Module):
         A form="long" state grows the same way, its key features re-derived by mlhot.ops.favor_keys_long."""
         return context.extend(_CachedContext(self), state, new_images, new_labels, new_len)
 
+    def evict(self, state, drop):
+        """(ContextState with per-shot rows, drop) -> a NEW ContextState without the context shots in the slots drop[t] of task t
+        (T sequences of distinct host ints below state.lens[t]); the kept shots move to the front, the freed slots are spare again
+        and the old state stays valid.  No image runs through the trunk: one row-compaction launch, then extend's finishing step
+        on the kept rows (mlhot.cached.evict states the refusals)."""
+        return context.evict(_CachedContext(self), state, drop)
+
     def _task_features(self, x_ctx, labels, invariant=False):
         """transform_y (the *Distractor classes) and the task encoder over [x_ctx | labels], per shot.  `invariant` (form "paged",
         DESIGN.md 6c-11): every Linear through the row-invariant kernel (mlhot.ops.linear_rows_any)."""
