@@ -574,6 +574,25 @@ int mlhot_rows_compact(const float* const* src /* host array of `sets` device po
                        float* const* dst /* host array of `sets` device pointers */, const int* W /* host array */, int sets,
                        const int32_t* plan /* [T][cap], DEVICE memory */, int T, int cap, void* stream);
 
+/* ---- cached contexts joined or regrouped across states: per-shot rows gathered from several sources (csrc/rows_gather.h)
+ * mlhot_rows_gather: `sets` row sets, 1 <= sets <= 2, filled from `nsrc` sources, 1 <= nsrc <= 8, by one plan.  Row set i holds fp32
+ *   rows of W[i] floats.  Source j is a flat list of rows[j] rows per set (a state's [T_j][cap_j] slots; the sources may differ in
+ *   both): src[i * nsrc + j] is set i of source j.  dst[i] is [T][cap][W[i]].  src, rows, dst and W are arrays in HOST memory.
+ *   plan[T][cap][2] (int32, DEVICE memory, read by the kernel alone - no host synchronisation) = (source, flat row in it):
+ *       dst_i[t][s][:] = src_{ps,i}[pr][:]  with (ps, pr) = plan[t][s],
+ *   and a row of exact zeros - no source is read - where ps is outside 0 .. nsrc - 1 or pr outside 0 .. rows[ps] - 1; (-1, -1) is
+ *   the fill.  No plan content reads or writes out of bounds.  Rows are selected by index, never by a product with a mask: a NaN
+ *   or Inf in a row that no plan entry names does not reach dst.  One source row may be named by several destination rows.  EVERY
+ *   row of every dst is written, whatever it held.  ONE launch (label rows.gather), float4 loads and stores, no atomics.
+ *   Served: W[i] % 4 == 0, 16-byte aligned src and dst, 8-byte aligned plan, sets, nsrc as above, 1 <= cap <= 4096, fewer than
+ *   2^31 float4 per task over all sets and rows[j] < 2^31; otherwise MLHOT_ERR_UNSUPPORTED.  A NULL pointer, rows[j] < 1, or a dst
+ *   that overlaps any src or another dst: MLHOT_ERR_ARG.  Whatever is refused writes nothing.  GPU build only (the host build
+ *   returns MLHOT_ERR_UNSUPPORTED).  Added within ABI 8: bindings look the symbol up. */
+int mlhot_rows_gather(const float* const* src /* host array of sets * nsrc device pointers */,
+                      const int64_t* rows /* host array of nsrc row counts */, int nsrc,
+                      float* const* dst /* host array of `sets` device pointers */, const int* W /* host array */, int sets,
+                      const int32_t* plan /* [T][cap][2], DEVICE memory */, int T, int cap, void* stream);
+
 /* ---- strict sharded parity of the key stabiliser -------------------------
  * fast_attention.py:96-97 takes torch.max over the keys of the WHOLE batch.  When a caller shards the meta-batch over
  * ranks, each rank's launch sequence can be run in two halves around the caller's own collectives on `xchg`

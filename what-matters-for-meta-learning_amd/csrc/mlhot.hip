@@ -35,6 +35,7 @@
 #include "favor_long.h"
 #include "favor_paged.h"
 #include "rows_compact.h"
+#include "rows_gather.h"
 #include "resnet_trunk.h"
 #include "../../include/mlhot.h"
 
@@ -432,6 +433,12 @@ int mlhot_favor_query_paged_masked_fwd(const float* q, const void* state, const 
 // cached contexts that let shots go: the per-shot rows of up to 4 row sets moved by one plan, one launch (csrc/rows_compact.h)
 int mlhot_rows_compact(const float* const* src, float* const* dst, const int* W, int sets, const int32_t* plan, int T, int cap, void* stream) {
   return rows_compact(src, dst, W, sets, plan, T, cap, (hipStream_t)stream);
+}
+// cached contexts joined or regrouped across states: up to 2 row sets gathered from up to 8 sources by one plan, one launch
+// (csrc/rows_gather.h)
+int mlhot_rows_gather(const float* const* src, const int64_t* rows, int nsrc, float* const* dst, const int* W, int sets, const int32_t* plan,
+                      int T, int cap, void* stream) {
+  return rows_gather(src, rows, nsrc, dst, W, sets, plan, T, cap, (hipStream_t)stream);
 }
 // Staged passes (strict sharded parity of the key stabiliser, csrc/stab_xchg.h): stage 0 runs up to the rank-local scalar and
 // publishes it in xchg, stage 1 takes the batch-wide scalar from xchg and runs the rest.

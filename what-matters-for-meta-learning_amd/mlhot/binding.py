@@ -310,6 +310,8 @@ SIGNATURES = {
     "mlhot_favor_query_paged_masked_fwd": (i, [P, P, P, P, P, P, i, i, i, i, i, i, i, P, P, P, z, P]),
     # cached contexts that let shots go: the per-shot rows moved by a plan
     "mlhot_rows_compact": (i, [P, P, P, i, P, i, i, P]),
+    # cached contexts joined or regrouped across states: per-shot rows gathered from several sources
+    "mlhot_rows_gather": (i, [P, P, i, P, P, i, P, i, i, P]),
     # strict sharded parity of the key stabiliser
     "mlhot_favor_fwd_staged": (i, _qkvp + [P, P, z, i, P, P]),
     "mlhot_favor_bwd_staged": (i, _qkvp + [P, P, P, P, P, P, z, i, P, P]),
@@ -1499,6 +1501,39 @@ class MlhotLib:
         n = len(srcs)
         self._rc(fn((C.c_void_p * n)(*[x.data_ptr() for x in srcs]), (C.c_void_p * n)(*[o.data_ptr() for o in outs]),
                     (C.c_int * n)(*[x[0, 0].numel() for x in srcs]), n, _ptr(plan), T, cap, _stream(plan)), "mlhot_rows_compact")
+        return outs
+
+    # ---- per-shot rows gathered from several sources (csrc/rows_gather.h) ---------------------------
+    ROWS_GATHER_SETS = 2     # row sets per mlhot_rows_gather call
+    ROWS_GATHER_SOURCES = 8  # sources per call
+
+    def rows_gather(self, sources, plan, T, cap):
+        """sources[j]: the 1 .. 2 row sets of source j, fp32 [T_j, cap_j, ...] each (the same trailing shape per set in every source;
+        T_j and cap_j are the source's own), 1 .. 8 sources; plan int32 [T, cap, 2] on their device = (source, flat row t_j * cap_j +
+        s_j in it) -> new tensors [T, cap, ...], one per row set: row s of task t is the named row, a row of exact zeros where the
+        source or the row is out of range ((-1, -1) is the fill).  ONE launch (rows.gather); the sources are only read.  cap <= 4096
+        and row widths that are multiples of 4 floats, else MlhotError."""
+        fn = self._fn("rows_gather", "mlhot_rows_gather")
+        sources = [list(src) for src in sources]
+        if not 1 <= len(sources) <= self.ROWS_GATHER_SOURCES:
+            raise MlhotError(f"rows_gather takes 1 .. {self.ROWS_GATHER_SOURCES} sources per call (got {len(sources)})")
+        n = len(sources[0])
+        if not 1 <= n <= self.ROWS_GATHER_SETS or any(len(src) != n for src in sources):
+            raise MlhotError(f"rows_gather takes 1 .. {self.ROWS_GATHER_SETS} row sets, the same number from every source (got {[len(src) for src in sources]})")
+        if not isinstance(plan, torch.Tensor) or plan.dtype != torch.int32 or tuple(plan.shape) != (T, cap, 2) or not plan.is_cuda:
+            raise MlhotError(f"rows_gather: plan must be an int32 [T={T}, cap={cap}, 2] tensor on the GPU")
+        for j, src in enumerate(sources):
+            for k, x in enumerate(src):
+                if (not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() < 3 or x.device != plan.device
+                        or x.shape[:2] != src[0].shape[:2] or x.shape[2:] != sources[0][k].shape[2:]):
+                    raise MlhotError(f"rows_gather: row set {k} of source {j} must be fp32 [T_j, cap_j, {', '.join(map(str, sources[0][k].shape[2:]))}] "
+                                     f"on {plan.device}")
+        _chk(plan, *[x for src in sources for x in src])
+        outs = [torch.empty(T, cap, *x.shape[2:], dtype=torch.float32, device=plan.device) for x in sources[0]]
+        ns = len(sources)
+        self._rc(fn((C.c_void_p * (n * ns))(*[sources[j][k].data_ptr() for k in range(n) for j in range(ns)]),
+                    (C.c_int64 * ns)(*[src[0].shape[0] * src[0].shape[1] for src in sources]), ns, (C.c_void_p * n)(*[o.data_ptr() for o in outs]),
+                    (C.c_int * n)(*[x[0, 0].numel() for x in sources[0]]), n, _ptr(plan), T, cap, _stream(plan)), "mlhot_rows_gather")
         return outs
 
     # ---- prefix sweep beyond 32 context shots (csrc/favor_prefix_long.h) --------------------------

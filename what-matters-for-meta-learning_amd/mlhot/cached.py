@@ -10,6 +10,10 @@
     state = mlhot.cached.merge(model, [state_a, state_b, ..])       # summary states conditioned apart -> one, no image re-read (6c-6)
     state = mlhot.cached.select(model, [state_a, state_b, ..], picks)      # a batch put together from the TASKS of summary states:
                                                                     # picks[t] = (state, task) or a list of such pairs (6c-8)
+    state = mlhot.cached.concat(model, [state_a, state_b, ..], form=None, capacity=None)      # per-shot or latent states conditioned apart
+                                                                    # -> one: rows are copied by one launch, none recomputed (6c-13)
+    state = mlhot.cached.regroup(model, [state_a, state_b, ..], picks, form=None, capacity=None)     # select's picks for those states
+    state = mlhot.cached.summarize(model, state)                    # a per-shot attention state -> form="summary", for merge / select
     mu = mlhot.cached.predict(model, state, qry_x, chunk=None)        # [T, Nq, y_dim]
     mu, attn = mlhot.cached.predict(model, state, qry_x, return_attention=True)      # attn [T, 8, Nq, Nc slots]: FAVOR+'s weight per context
                                                                                       # slot, head and target (attention models; 6c-5)
@@ -327,6 +331,44 @@ def slide(model, state, new_x, new_y, new_len=None):
     6c-12): a window over the last `capacity` shots of a stream in which only the new shots are ever encoded.  evict, then extend.
     `new_len[t]` above the capacity, a summary or empty state and whatever extend refuses raise ValueError."""
     return context.slide(_adapter(model), state, new_x, new_y, new_len)
+
+
+def concat(model, states, form=None, capacity=None):
+    """(1 .. 8 states of this model that keep per-shot rows, conditioned apart on the SAME T tasks) -> a NEW state whose task t holds
+    the shots of states[0] task t, then states[1] task t, and so on: context shards, several sources for one task,
+    stored per-object contexts - with everything only per-shot states offer (`return_attention=True`, `context_mask=`,
+    `leave_one_out`, `evict`, `slide`).  All states are per-shot attention states - "keys", "long", "paged", mixed freely - or all are
+    latent (CNP) states.  `lens` add up; the inputs stay valid.  No image is encoded and no row is recomputed: one plan upload, ONE
+    launch (mlhot_rows_gather) copies the rows of both row sets into a new buffer, then evict's finishing step runs on them - the
+    key launches of the result's form with the new lens, so the key stabiliser is the maximum over all shots of the result, which
+    is what a fresh `condition` computes (attention), or the prefix aggregate with its gather and the finishing Linear (latent).
+    `capacity` defaults to the largest total of a task (spare slots beyond it serve `extend`); `form` (attention only) defaults to
+    the smallest form that holds the capacity - "keys" up to 32, "long" up to 256, "paged" up to 4096 - and an explicit one must hold
+    it.  When every source and the result are "paged" the result is, bit for bit, `condition(form="paged", capacity=)` on the
+    concatenated shots; for the other forms it agrees with a fresh condition to the kernels' tolerance (the per-shot Linears of the
+    sources picked their kernel by row count).  More than 8 states: calls nest.  Both families; eval mode.  Refused with ValueError
+    before anything touches the GPU: a foreign or stale state or one of another T, a summary state (merge / select combine those;
+    `summarize` maps a per-shot state to one), an empty state, attention and latent states mixed, more than 8 states, a total above
+    the capacity, a capacity above the form's, `form=` on latent states."""
+    return context.concat(_adapter(model), states, form, capacity)
+
+
+def regroup(model, states, picks, form=None, capacity=None):
+    """`select`'s picks for states that keep per-shot rows: `states` as `concat` takes them, conditioned on ANY
+    batches; `picks` has `tasks_per_batch` entries, entry t one (state_index, task_index) pair - task t of the result is that task -
+    or a list of 1 .. 8 pairs whose shots stand behind one another in task t.  Any task of any state may stand in any slot, also in
+    several; tasks and states that no pick names are left out.  The launches, `form`, `capacity` and the bit statements are
+    concat's: `concat(model, states)` is `regroup(model, states, [[(0, t), (1, t), ..] for t in range(T)])`.  Also refused: an empty
+    `picks[t]`, the same pair twice inside one task, a pair out of range, more than 8 parts in a task."""
+    return context.regroup(_adapter(model), states, picks, form, capacity)
+
+
+def summarize(model, state):
+    """(per-shot attention state: "keys", "long" or "paged") -> a NEW form="summary" state of the same shots, the
+    bridge to `merge` / `select`: the kept key and value rows go through mlhot.ops.favor_absorb as extend's new shots do on a
+    summary, no image is encoded, the old state stays valid.  `merge`, `select`, `extend`, `retract` and `predict` serve the result
+    like any summary state.  A latent, empty or summary state raises ValueError."""
+    return context.summarize(_adapter(model), state)
 
 
 def merge(model, states):

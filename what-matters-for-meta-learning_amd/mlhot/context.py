@@ -299,6 +299,115 @@ def select(ad, states, picks):
                         form="summary")
 
 
+def _row_states(ad, what, states, same_tasks):
+    """concat's and regroup's checks of their states: 1 .. 8 of this model's own, fresh states that keep per-shot
+    rows, all attention ("keys", "long", "paged", mixed freely) or all latent -> (the list, the model's fingerprint)."""
+    try:
+        states = list(states)
+    except TypeError:
+        raise ValueError(f"{what}: states must be a sequence of per-shot or latent states of condition(), got {type(states).__name__}") from None
+    if not states:
+        raise ValueError(f"{what}: needs at least one state (got an empty sequence)")
+    if len(states) > ragged.JOIN_PARTS:
+        raise ValueError(f"{what}: {len(states)} states; a call takes at most {ragged.JOIN_PARTS} - calls nest: {what} the states in groups, "
+                         "then the results")
+    fresh = fingerprint(ad.model)                      # once: it walks every parameter and buffer
+    for i, s in enumerate(states):
+        if not isinstance(s, ContextState) or s.owner is not ad.model:
+            raise ValueError(f"{what}: the state was not made by this model's condition() (states[{i}])")
+        if s.kind == "empty":
+            raise ValueError(f"{what}: states[{i}] holds no context shot - there is no row to take from it")
+        if s.form == "summary":
+            raise ValueError(f"{what}: states[{i}] is a summary state - it keeps sums over shots, no per-shot rows; mlhot.cached.merge and "
+                             "mlhot.cached.select combine summary states, and mlhot.cached.summarize maps a per-shot state to a summary "
+                             "to mix the two")
+        if s.kind != states[0].kind:
+            raise ValueError(f"{what}: states[{i}] is a {s.kind!r} state, states[0] a {states[0].kind!r} one - attention and latent states "
+                             "do not mix")
+        if same_tasks and (s.T != states[0].T or s.T != ad.model.task_num):
+            raise ValueError(f"{what}: states[{i}] holds {s.T} tasks, states[0] {states[0].T}, the model {ad.model.task_num} (task t of the "
+                             f"result is task t of every state: {what} serves the same tasks)")
+        if s.fingerprint != fresh:
+            raise ValueError(f"{what}: the state is stale - a parameter of the model changed since condition() (states[{i}])")
+        if (s.kh if s.kind == "attention" else s.rs) is None or s.capacity is None:
+            raise ValueError(f"{what}: states[{i}] carries no per-shot rows (it was not made by condition())")
+        for x in ((s.kh, s.vh) if s.kind == "attention" else (s.rs, s.lv)):
+            if x is not None and x[0, 0].numel() % 4:
+                raise ValueError(f"{what}: states[{i}] keeps per-shot rows of {x[0, 0].numel()} floats; mlhot_rows_gather moves rows whose "
+                                 "width is a multiple of 4 floats")
+    return states, fresh
+
+
+def _join(ad, what, states, parts, total, form, capacity, fresh):
+    """regroup's and concat's launches: one plan upload, ONE mlhot_rows_gather launch for both row sets, then evict's finishing step
+    on the gathered rows."""
+    model, kind = ad.model, states[0].kind
+    ad.prepare()
+    with torch.no_grad():
+        sources = [[_c(x) for x in ((s.kh, s.vh) if kind == "attention" else (s.rs, s.lv)) if x is not None] for s in states]
+        plan = ragged.GatherPlan(parts, [s.lens for s in states], [s.capacity for s in states], capacity, sources[0][0].device)
+        out = lib().rows_gather(sources, plan.rows, len(parts), capacity)
+        a_rows, b_rows = out[0], out[1] if len(out) > 1 else None
+        if kind == "attention":
+            keys = ragged.masked_keys(a_rows, model.attn.projection_matrix, plan, form)
+            return ContextState(model, len(parts), capacity, fresh, "attention", keys=keys, vh=b_rows, wq=states[0].wq, lens=plan.total,
+                                kh=a_rows, form=form)
+        return _latent(ad, capacity, a_rows, b_rows, ragged.gathered_aggregate(model.agg_mode, a_rows, b_rows, plan), plan.total)
+
+
+def regroup(ad, states, picks, form=None, capacity=None):
+    """select's picks for states that keep per-shot rows: `states` 1 .. 8 per-shot attention states ("keys", "long",
+    "paged", mixed freely) or latent states of ONE model; `picks` has one entry per task of the model's batch, a (state_index,
+    task_index) pair or a list of 1 .. 8 such pairs whose shots stand behind one another in task t -> a NEW state.  Any task of any
+    state may stand in any slot, also in several; the inputs stay valid and no image is encoded: one plan upload, ONE
+    mlhot_rows_gather launch for both row sets, then evict's finishing step - the key launches of the result's form with the new
+    lens, so the key stabiliser is the maximum over the shots of the result, exactly condition's on them (attention), or the
+    prefix aggregate with its gather and the finishing Linear (latent).  `capacity` defaults to the largest total, `form`
+    (attention only) to the smallest form that holds the capacity; `wq` is states[0]'s."""
+    what = "regroup"
+    ad.refuse(what)
+    states, fresh = _row_states(ad, what, states, same_tasks=False)
+    attention = states[0].kind == "attention"
+    parts, total, form, capacity = ragged.regroup_args(what, [(s.lens, s.capacity) for s in states], picks, ad.model.task_num, attention, form, capacity)
+    return _join(ad, what, states, parts, total, form, capacity, fresh)
+
+
+def concat(ad, states, form=None, capacity=None):
+    """Per-shot attention states or latent states of ONE model that were conditioned apart on the SAME T tasks -> a NEW state whose
+    task t holds the shots of states[0] task t, then states[1] task t, and so on: regroup with picks[t] =
+    [(0, t), (1, t), ..].  `lens` add up; the inputs stay valid."""
+    what = "concat"
+    ad.refuse(what)
+    states, fresh = _row_states(ad, what, states, same_tasks=True)
+    attention = states[0].kind == "attention"
+    parts, total, form, capacity = ragged.join_args(what, [(s.lens, s.capacity) for s in states], ad.model.task_num, attention, form, capacity)
+    return _join(ad, what, states, parts, total, form, capacity, fresh)
+
+
+def summarize(ad, state):
+    """A per-shot attention state ("keys", "long", "paged") -> a NEW form="summary" state of the same shots: the
+    kept kh / vh rows, packed, go through ragged.summary_absorb as _absorb's new shots do (mlhot.ops.favor_absorb, chunks of 32); no
+    image is encoded and the old state stays valid.  merge, select, extend, retract and predict serve the result like any summary."""
+    what = "summarize"
+    _own(ad, what, state)
+    if state.kind == "empty":
+        raise ValueError(f"{what}: the state holds no context shot")
+    if state.kind != "attention":
+        raise ValueError(f"{what}: the state is a {state.kind!r} state - it is one aggregate per task behind its finishing Linear; only "
+                         'attention states have a form="summary"')
+    if state.form == "summary":
+        raise ValueError(f"{what}: the state is a summary already")
+    if state.kh is None or state.vh is None:
+        raise ValueError(f"{what}: the state carries no per-shot rows (it was not made by condition())")
+    ad.prepare()
+    model, T, cap = ad.model, state.T, state.capacity
+    with torch.no_grad():
+        plan = ragged.Plan((0,) * T, state.lens, cap, cap, state.kh.device)
+        keys = ragged.summary_absorb(None, ragged.pack(state.kh, plan.src), ragged.pack(state.vh, plan.src), plan, T, cap,
+                                     model.attn.projection_matrix, state.lens)
+    return ContextState(model, T, max(keys.lens), fingerprint(model), "attention", keys=keys, wq=state.wq, lens=keys.lens, form="summary")
+
+
 def _absorb(ad, state, images, labels, add, wq):
     """`add[t]` of the slots of images / labels [T, n, ...] into the summary state (state None: a fresh one): only those shots go
     through the per-shot stage, as a packed list, and nothing absorbed earlier is read again."""

@@ -179,6 +179,117 @@ class KeepPlan:
         self.rows, self.last, self.lens = buf[:T * capacity].view(T, capacity), buf[T * capacity:T * capacity + T].long(), buf[T * capacity + T:]
 
 
+JOIN_PARTS = 8                     # states per concat / regroup call and parts per task (csrc/rows_gather.h: ROWS_GATHER_MAX_SRC)
+
+
+def smallest_form(capacity):
+    """The smallest per-shot form that holds `capacity` slots: "keys" up to 32, "long" up to 256, "paged" up to 4096."""
+    return "keys" if capacity <= MAX_ATTENTION_CAPACITY else "long" if capacity <= MAX_LONG_CAPACITY else "paged"
+
+
+def regroup_args(what, metas, picks, T, attention, form=None, capacity=None, name="picks"):
+    """The host checks of mlhot.cached.regroup behind those of its states (DESIGN.md 6c-13).  metas: (lens, capacity) per state;
+    picks: one entry per task of the model's batch, a (state_index, task_index) pair or a list of 1 .. 8 such pairs
+    -> (parts, the new lens, form, capacity): parts[t] the list of pairs of task t; `capacity` defaults to the largest total, `form`
+    (attention only) to the smallest that holds the capacity.  `name`: what a message calls an entry ("picks", or concat's
+    "states" - its parts are [(0, t), (1, t), ..])."""
+    try:
+        picks = list(picks)
+    except TypeError:
+        raise ValueError(f"{what}: picks must be a sequence with one entry per task, got {type(picks).__name__}") from None
+    if len(picks) != T:
+        raise ValueError(f"{what}: {len(picks)} picks, the model was built for tasks_per_batch = {T}")
+    parts, total = [], []
+    for t, pick in enumerate(picks):
+        if isinstance(pick, (tuple, list)) and len(pick) == 2 and all(isinstance(x, numbers.Integral) and not isinstance(x, bool) for x in pick):
+            pick = [pick]                               # one pair
+        try:
+            pick = [tuple(pair) for pair in pick]
+        except TypeError:
+            raise ValueError(f"{what}: picks[{t}] must be a (state_index, task_index) pair or a list of such pairs, got {pick!r}") from None
+        if not pick:
+            raise ValueError(f"{what}: picks[{t}] is empty - a task without a context shot has no attention (0 / 0) and no aggregate")
+        if len(pick) > JOIN_PARTS:
+            raise ValueError(f"{what}: picks[{t}] names {len(pick)} parts; a task takes at most {JOIN_PARTS} per call - calls nest: "
+                             f"{what} the parts in groups, then the results")
+        for pair in pick:
+            if len(pair) != 2 or any(isinstance(x, bool) or not isinstance(x, numbers.Integral) for x in pair):
+                raise ValueError(f"{what}: picks[{t}] holds {pair!r}, which is no (state_index, task_index) pair of integers")
+            si, ti = pair
+            if not 0 <= si < len(metas) or not 0 <= ti < len(metas[si][0]):
+                tasks = f"states[{si}] holds {len(metas[si][0])} tasks" if 0 <= si < len(metas) else f"there are {len(metas)} states"
+                raise ValueError(f"{what}: picks[{t}] names {pair}, which is out of range - {tasks}")
+        if len(set(pick)) != len(pick):
+            twice = next(pair for k, pair in enumerate(pick) if pair in pick[:k])
+            raise ValueError(f"{what}: picks[{t}] names {twice} twice - its shots would count double inside one task (the same pair may "
+                             "stand in different tasks)")
+        parts.append([(int(si), int(ti)) for si, ti in pick])
+        total.append(sum(metas[si][0][ti] for si, ti in pick))
+    if capacity is None:
+        capacity = max(max(total), 1)
+    if isinstance(capacity, bool) or not isinstance(capacity, numbers.Integral):
+        raise ValueError(f"{what}: capacity must be an integer, got {capacity!r}")
+    capacity = int(capacity)
+    if not attention and form is not None:
+        raise ValueError(f"{what}: form= belongs to the attention models - a latent state keeps its per-shot rows in one layout at any "
+                         f"capacity (got form={form!r})")
+    if attention:
+        if form is not None and form not in PER_SHOT_CAPACITY and form != "keys":
+            hint = '; mlhot.cached.summarize maps the result to form="summary"' if form == "summary" else ""
+            raise ValueError(f'{what}: form must be one of ("keys", "long", "paged") or None, got {form!r}{hint}')
+        if capacity > MAX_PAGED_CAPACITY:
+            raise ValueError(f"{what}: capacity = {capacity} is above the {MAX_PAGED_CAPACITY} slots of the largest per-shot form (\"paged\"); "
+                             f'beyond it a context is held as form="summary": mlhot.cached.summarize the parts, then merge / select them')
+        if form is None:
+            form = smallest_form(capacity)
+        cap = MAX_ATTENTION_CAPACITY if form == "keys" else PER_SHOT_CAPACITY[form]
+        if capacity > cap:
+            raise ValueError(f"{what}: capacity = {capacity} is outside the {form} attention kernels' envelope (at most {cap} context slots "
+                             f'per task); form="{smallest_form(capacity)}" holds it')
+    elif capacity > MAX_PAGED_CAPACITY:
+        raise ValueError(f"{what}: capacity = {capacity} is above the {MAX_PAGED_CAPACITY} slots mlhot_rows_gather serves")
+    for t, n in enumerate(total):
+        if n > capacity:
+            who = f"picks[{t}]" if name == "picks" else f"task {t} over all states"
+            raise ValueError(f"{what}: {who} holds {n} context shots in all, the capacity is {capacity}")
+        if n < 1:
+            who = f"picks[{t}]" if name == "picks" else f"task {t} of the states"
+            raise ValueError(f"{what}: {who} holds no context shot - a task without one has no attention (0 / 0) and no aggregate")
+    return parts, tuple(total), form, capacity
+
+
+def join_args(what, metas, T, attention, form=None, capacity=None):
+    """regroup_args for mlhot.cached.concat: task t is task t of every state, in the states' order."""
+    return regroup_args(what, metas, [[(i, t) for i in range(len(metas))] for t in range(T)], T, attention, form, capacity, name="states")
+
+
+def gather_rows(parts, lens, caps, capacity):
+    """The plan of a join on the host: parts[t] = [(state_index, task_index), ..]; lens[i] the shots per task of
+    state i, caps[i] its capacity -> (table [T][capacity][2], the new lens).  Per task the lens[i][j] valid shots of every part
+    (i, j) stand in the order given, as (i, flat row j * caps[i] + s); then (-1, -1) - "a row of zeros" - up to the capacity."""
+    table, total = [], []
+    for task in parts:
+        rows = [(i, j * caps[i] + s) for i, j in task for s in range(lens[i][j])]
+        total.append(len(rows))
+        table.append(rows + [(-1, -1)] * (capacity - len(rows)))
+    return table, tuple(total)
+
+
+class GatherPlan:
+    """A join's indices on the device after ONE upload made before the first launch (Plan's rule): `rows` int32 [T, capacity, 2] is
+    what mlhot_rows_gather reads (gather_rows); `total`, `lens` and `last` are Plan's, for the finishing steps on the gathered rows."""
+
+    def __init__(self, parts, lens, caps, capacity, device):
+        T = len(parts)
+        rows, self.total = gather_rows(parts, lens, caps, capacity)
+        last = [(l - 1) * T + t for t, l in enumerate(self.total)]
+        # lens in front, padded to 16 bytes: both it and rows start aligned, so no entry copies them on the way in (mlhot.ops._c)
+        pad = -T % 4
+        buf = torch.tensor(list(self.total) + [0] * pad + [x for r in rows for pair in r for x in pair] + last, dtype=torch.int32).to(device)
+        a, n = T + pad, 2 * T * capacity
+        self.rows, self.last, self.lens = buf[a:a + n].view(T, capacity, 2), buf[a + n:].long(), buf[:T]
+
+
 def retract_args(what, state, T, n, old_len):
     """-> the shots per task a summary state gives up: 0 .. n each, and fewer than the task holds."""
     sub = summary_extend_args(what, T, n, old_len)
