@@ -560,6 +560,49 @@ int mlhot_favor_query_paged_masked_fwd(const float* q, const void* state, const 
                                        int T, int H, int Nq, int Nc, int d, int m, float* out /* [T,G,Nq,d*H] */,
                                        float* w /* [T,G,H,Nq,Nc], or NULL */, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- attention mass per context slot: the read-out reduced over the targets inside the query launch (csrc/favor_mass.h)
+ *     mass[t,h,c] = sum over targets n of  tw[t,n] * w[t,h,n,c],   w = S / D exactly as mlhot_favor_query_weights_fwd defines it,
+ * without w[T,H,Nq,Nc] being allocated or written in any form.  mlhot_favor_query_mass_fwd serves a mlhot_favor_keys_fwd / _ragged_fwd
+ * state (Nc <= 32), mlhot_favor_query_long_mass_fwd a mlhot_favor_keys_long_fwd state (Nc <= 256), mlhot_favor_query_paged_mass_fwd a
+ * mlhot_favor_keys_paged_fwd state (Nc <= 4096).  The arguments are the unmasked entry's (mlhot_favor_query_fwd / _long_fwd /
+ * _paged_fwd without w) plus
+ *   tw[T,Nq] (fp32, DEVICE memory, finite and >= 0 - the caller's to check) or NULL: the plain column sum;
+ *   mass and fold: fold != 0 -> mass[T,H,Nc], and ws (mlhot_favor_query_mass_bytes bytes) holds the tile partials;
+ *                  fold == 0 -> mass IS the tile partials part[T,H,ceil(Nq/16),Nc], nothing is folded and ws is the 256-byte token
+ *                  block: a caller that splits the targets at multiples of 16 concatenates the pieces' partials along the tile
+ *                  axis and folds ONCE with mlhot_favor_mass_fold(part, T*H, tiles, Nc, mass) - the single call's bits.
+ * out is BIT-EQUAL to the entry without mass on the same arguments: the mass is one more store behind D, as w is.
+ * SUMMATION ORDER (no atomics): every (task, head, 16-row tile) workgroup adds its rows' terms per column in ascending row order from
+ *   +0.0f into its tile partial; the fold adds the tile partials per column in ascending tile order from +0.0f.  A term is the
+ *   read-out's own single IEEE divide S / D; with tw it is ONE rounded multiply tw * w, then ONE rounded add - no FMA contraction
+ *   is used (the functions that add are compiled with `#pragma clang fp contract(off)`).  So with tw == NULL
+ *   mass is the fp32 fold, in that order, of the bits the read-out entry stores into w on the same arguments.
+ * Columns c >= lens[t] are exactly 0.0f; rows n >= lens[t] of v are never read by the long and paged entries (the keys entry reads
+ *   v as mlhot_favor_query_fwd does: zero-fill them).  The bits do not depend on the capacity Nc the same shots are kept in
+ *   (long, paged); a paged state of at most 256 slots gives the long entry's bits, a long state of at most 32 the keys entry's.
+ * The paged entry walks the pages twice: D is final behind the last page only, so S of every page but the last is formed again
+ *   and reduced with the final D (the last page is reduced from LDS).
+ * MEMORY: mlhot_favor_query_mass_bytes(T, H, Nq, Nc, d, m) = T H ceil(Nq/16) Nc floats (in blocks of 256 bytes), 1/16 of w - everything this
+ *   path writes beside out and mass.  0 for a shape none of the three serves.
+ * Envelope, alignment and error codes are those of the entry each one extends; tw, mass and ws need 4-byte alignment; mass == NULL is
+ * MLHOT_ERR_ARG; unsupported shapes write nothing.  Forward only; GPU build only.  Added within ABI 8: bindings look the symbols up. */
+size_t mlhot_favor_query_mass_bytes(int T, int H, int Nq, int Nc, int d, int m);
+int mlhot_favor_query_mass_fwd(const float* q, const void* state, const float* v, const float* proj,
+                               const float* tw /* [T,Nq], device, or NULL */, int T, int H, int Nq, int Nc, int d, int m,
+                               float* out, float* mass /* [T,H,Nc]; fold == 0: [T,H,ceil(Nq/16),Nc] */, int fold,
+                               void* ws, size_t ws_bytes, void* stream);
+int mlhot_favor_query_long_mass_fwd(const float* q, const void* state, const float* v, const float* proj,
+                                    const int32_t* lens /* [T], device, or NULL */, const float* tw /* [T,Nq], device, or NULL */,
+                                    int T, int H, int Nq, int Nc, int d, int m, float* out,
+                                    float* mass /* [T,H,Nc]; fold == 0: [T,H,ceil(Nq/16),Nc] */, int fold,
+                                    void* ws, size_t ws_bytes, void* stream);
+int mlhot_favor_query_paged_mass_fwd(const float* q, const void* state, const float* v, const float* proj,
+                                     const int32_t* lens /* [T], device, or NULL */, const float* tw /* [T,Nq], device, or NULL */,
+                                     int T, int H, int Nq, int Nc, int d, int m, float* out,
+                                     float* mass /* [T,H,Nc]; fold == 0: [T,H,ceil(Nq/16),Nc] */, int fold,
+                                     void* ws, size_t ws_bytes, void* stream);
+int mlhot_favor_mass_fold(const float* part /* [TH,ntile,Nc] */, int TH, int ntile, int Nc, float* mass /* [TH,Nc] */, void* stream);
+
 /* ---- cached contexts that let shots go: the per-shot rows moved by a plan (csrc/rows_compact.h) ------------------
  * mlhot_rows_compact: `sets` row sets, 1 <= sets <= 4, that share one plan.  Row set i is (src[i], dst[i], W[i]): fp32 rows of W[i]
  *   floats in [T][cap][W[i]]; src, dst and W are arrays of `sets` entries in HOST memory.  plan[T][cap] (int32, DEVICE memory, read by

@@ -34,6 +34,7 @@
 #include "favor_prefix_long.h"
 #include "favor_long.h"
 #include "favor_paged.h"
+#include "favor_mass.h"
 #include "rows_compact.h"
 #include "rows_gather.h"
 #include "resnet_trunk.h"
@@ -429,6 +430,23 @@ int mlhot_favor_query_paged_masked_fwd(const float* q, const void* state, const 
                                        int G, int T, int H, int Nq, int Nc, int d, int m, float* out, float* w, void* ws, size_t ws_bytes, void* stream) {
   return favor_query_paged_launch("favor_query_paged_masked_fwd", true, q, state, v, proj, lens, mask_words, G, T, H, Nq, Nc, d, m, out, w, ws, ws_bytes,
                                   (hipStream_t)stream);
+}
+// attention mass per context slot: the read-out reduced over the targets inside the query launch (csrc/favor_mass.h)
+size_t mlhot_favor_query_mass_bytes(int T, int H, int Nq, int Nc, int d, int m) { return favor_query_mass_ws_need(T, H, Nq, Nc, d, m); }
+int mlhot_favor_query_mass_fwd(const float* q, const void* state, const float* v, const float* proj, const float* tw, int T, int H, int Nq, int Nc,
+                               int d, int m, float* out, float* mass, int fold, void* ws, size_t ws_bytes, void* stream) {
+  return favor_query_mass_launch("favor_query_mass_fwd", 0, q, state, v, proj, nullptr, tw, T, H, Nq, Nc, d, m, out, mass, fold, ws, ws_bytes, (hipStream_t)stream);
+}
+int mlhot_favor_query_long_mass_fwd(const float* q, const void* state, const float* v, const float* proj, const int32_t* lens, const float* tw, int T, int H,
+                                    int Nq, int Nc, int d, int m, float* out, float* mass, int fold, void* ws, size_t ws_bytes, void* stream) {
+  return favor_query_mass_launch("favor_query_long_mass_fwd", 1, q, state, v, proj, lens, tw, T, H, Nq, Nc, d, m, out, mass, fold, ws, ws_bytes, (hipStream_t)stream);
+}
+int mlhot_favor_query_paged_mass_fwd(const float* q, const void* state, const float* v, const float* proj, const int32_t* lens, const float* tw, int T, int H,
+                                     int Nq, int Nc, int d, int m, float* out, float* mass, int fold, void* ws, size_t ws_bytes, void* stream) {
+  return favor_query_mass_launch("favor_query_paged_mass_fwd", 2, q, state, v, proj, lens, tw, T, H, Nq, Nc, d, m, out, mass, fold, ws, ws_bytes, (hipStream_t)stream);
+}
+int mlhot_favor_mass_fold(const float* part, int TH, int ntile, int Nc, float* mass, void* stream) {
+  return favor_mass_fold(part, TH, ntile, Nc, mass, (hipStream_t)stream);
 }
 // cached contexts that let shots go: the per-shot rows of up to 4 row sets moved by one plan, one launch (csrc/rows_compact.h)
 int mlhot_rows_compact(const float* const* src, float* const* dst, const int* W, int sets, const int32_t* plan, int T, int cap, void* stream) {

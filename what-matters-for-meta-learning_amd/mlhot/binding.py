@@ -308,6 +308,12 @@ SIGNATURES = {
     "mlhot_favor_keys_paged_fwd": (i, [P, P, P, i, i, i, i, i, P, z, P]),
     "mlhot_favor_query_paged_fwd": (i, [P, P, P, P, P, i, i, i, i, i, i, P, P, P, z, P]),
     "mlhot_favor_query_paged_masked_fwd": (i, [P, P, P, P, P, P, i, i, i, i, i, i, i, P, P, P, z, P]),
+    # attention mass per context slot: the read-out reduced over the targets inside the query launch
+    "mlhot_favor_query_mass_bytes": (z, [i] * 6),
+    "mlhot_favor_query_mass_fwd": (i, [P, P, P, P, P, i, i, i, i, i, i, P, P, i, P, z, P]),
+    "mlhot_favor_query_long_mass_fwd": (i, [P, P, P, P, P, P, i, i, i, i, i, i, P, P, i, P, z, P]),
+    "mlhot_favor_query_paged_mass_fwd": (i, [P, P, P, P, P, P, i, i, i, i, i, i, P, P, i, P, z, P]),
+    "mlhot_favor_mass_fold": (i, [P, i, i, i, P, P]),
     # cached contexts that let shots go: the per-shot rows moved by a plan
     "mlhot_rows_compact": (i, [P, P, P, i, P, i, i, P]),
     # cached contexts joined or regrouped across states: per-shot rows gathered from several sources
@@ -1330,6 +1336,60 @@ class MlhotLib:
             rc = fn(_ptr(q), _ptr(state), _ptr(v), _ptr(proj), _ptr(lens), T, H, Nq, Nc, d, m, _ptr(out), _ptr(w), _ptr(ws), ws.numel(), _stream(q))
         self._rc(rc, "mlhot_" + what)
         return (out, w) if weights else out
+
+    # ---- attention mass per context slot (csrc/favor_mass.h) ----------------------
+    def favor_query_mass_bytes(self, T, H, Nq, Nc, d, m):
+        """Workspace bytes of the mass entries - the tile partials, T H ceil(Nq/16) Nc floats: the path's whole footprint beside out
+        and mass; 0 for a shape none of them serves."""
+        return self._fn("favor_query_mass_fwd", "mlhot_favor_query_mass_bytes")(T, H, Nq, Nc, d, m)
+
+    def favor_query_mass_fwd(self, q, state, v, proj, form, lens=None, tw=None, fold=True):
+        """q [T,Nq,H,d], a per-shot key state of `form` ("cached" | "long" | "paged") with its lens, v [T,Nc,H,d], proj [m,d], tw
+        [T,Nq] fp32 on q's device or None -> (out [T,Nq,d*H], mass [T,H,Nc]): mass[t,h,c] = sum_n tw[t,n] w[t,h,n,c] of the read-out
+        w = S / D, reduced inside the query launch in a fixed order - w itself is never stored; out has the plain entry's bits
+        (include/mlhot.h).  fold=False -> (out, part [T,H,ceil(Nq/16),Nc]), the tile partials for favor_mass_fold.  Forward only."""
+        what = {"cached": "favor_query_mass_fwd", "long": "favor_query_long_mass_fwd", "paged": "favor_query_paged_mass_fwd"}[form]
+        fn = self._fn(what, "mlhot_" + what)
+        for name, t in (("q", q), ("v", v)):
+            if t.dtype != torch.float32 or t.dim() != 4:
+                raise MlhotError(f"{what}: {name} must be fp32 [T, N, H, d], got {t.dtype} {tuple(t.shape)}")
+        T, Nq, H, d = q.shape
+        Nc = v.shape[1]
+        if tuple(v.shape) != (T, Nc, H, d) or proj.dtype != torch.float32 or proj.dim() != 2 or proj.shape[1] != d or Nq < 1:
+            raise MlhotError(f"{what}: q {tuple(q.shape)}, v {tuple(v.shape)}, proj {tuple(proj.shape)} do not fit together")
+        if any(t.device != q.device for t in (state, v, proj)):
+            raise MlhotError(f"{what}: q, state, v and proj must lie on one device")
+        self._long_lens(what, lens, T, q)
+        if form == "cached" and lens is not None:
+            raise MlhotError(f"{what}: a keys state carries its lens as zero rows of F_k; the entry takes none")
+        m = proj.shape[0]
+        nb = {"cached": self.favor_keys_bytes, "long": self.favor_keys_long_bytes, "paged": self.favor_keys_paged_bytes}[form](T, H, Nc, d, m)
+        if not nb or state.dtype != torch.uint8 or state.numel() < nb:
+            raise MlhotError(f"{what}: the state is not this form's for T={T} H={H} Nc={Nc} d={d} m={m} "
+                             f"({state.numel()} bytes, {nb} needed; 0 = shape not served)")
+        if tw is not None and (not isinstance(tw, torch.Tensor) or tw.dtype != torch.float32 or tuple(tw.shape) != (T, Nq) or tw.device != q.device):
+            got = f"{tw.dtype} {tuple(tw.shape)} on {tw.device}" if isinstance(tw, torch.Tensor) else type(tw).__name__
+            raise MlhotError(f"{what}: tw must be fp32 [T={T}, Nq={Nq}] on {q.device}, got {got}")
+        _chk(q, v, proj, state, lens, tw)
+        out = torch.empty(T, Nq, d * H, device=q.device)
+        ntile = (Nq + 15) // 16
+        mass = torch.empty((T, H, Nc) if fold else (T, H, ntile, Nc), device=q.device)
+        ws = self._bytes(self.favor_query_mass_bytes(T, H, Nq, Nc, d, m) if fold else 256, q)
+        head = (_ptr(q), _ptr(state), _ptr(v), _ptr(proj)) + (() if form == "cached" else (_ptr(lens),))
+        self._rc(fn(*head, _ptr(tw), T, H, Nq, Nc, d, m, _ptr(out), _ptr(mass), int(bool(fold)), _ptr(ws), ws.numel(), _stream(q)), "mlhot_" + what)
+        return out, mass
+
+    def favor_mass_fold(self, part):
+        """part [T,H,tiles,Nc] (the tile partials of favor_query_mass_fwd(fold=False), concatenated along the tile axis in target
+        order) -> mass [T,H,Nc]: the tiles added per column in ascending order, one rounded add each."""
+        fn = self._fn("favor_mass_fold", "mlhot_favor_mass_fold")
+        if part.dtype != torch.float32 or part.dim() != 4 or part.shape[2] < 1:
+            raise MlhotError(f"favor_mass_fold: part must be fp32 [T, H, tiles, Nc], got {part.dtype} {tuple(part.shape)}")
+        _chk(part)
+        T, H, ntile, Nc = part.shape
+        mass = torch.empty(T, H, Nc, device=part.device)
+        self._rc(fn(_ptr(part), T * H, ntile, Nc, _ptr(mass), _stream(part)), "mlhot_favor_mass_fold")
+        return mass
 
     # ---- the fixed-size FAVOR+ summary state (csrc/favor_summary.h) ------------------------------
     def favor_summary_bytes(self, T, H, d, m):

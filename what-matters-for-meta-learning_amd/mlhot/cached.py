@@ -21,6 +21,9 @@
                                                                     # subset of the context; [T, G, Nq, Nc] -> mu [T, G, Nq, y_dim], G masks
                                                                     # of the same targets from one encoder pass and one query launch (6c-10)
     mu = mlhot.cached.leave_one_out(model, state, qry_x)            # [T, Nc slots, Nq, y_dim]: group c predicts without context slot c
+    mu, mass = mlhot.cached.predict(model, state, qry_x, attention_mass=True, target_weight=None)     # mass [T, 8, Nc slots]: attn summed over
+                                                                    # the targets inside the query launch, attn never stored (6c-14)
+    state, drop = mlhot.cached.prune(model, state, qry_x, keep)     # keep[t] slots with the largest mass stay, the rest go through evict
     ok, reason = mlhot.cached.supports(model)
     mu = mlhot.cached.sweep(model, ctx_x, ctx_y, qry_x, ks=None, route=None)      # [len(ks), T, Nq, y_dim]: every context prefix (6b-2)
     ok, reason = mlhot.cached.supports_sweep(model)
@@ -135,7 +138,8 @@ class _Vanilla:
     """mlhot.context's adapter for the vanilla family; `route` is what predict's caller asked for."""
 
     def __init__(self, model, route=None, attention=False):
-        self.model, self.asked, self.dims, self.attention = model, route, None, attention
+        # attention: False, or the keyword that asks for per-shot weights, as the refusals name it
+        self.model, self.asked, self.dims, self.attention = model, route, None, "return_attention=True" if attention is True else attention
         self.masked = False          # context.predict sets it for predict(context_mask=) (DESIGN.md 6c-10)
 
     finish = property(lambda self: self.model.r_to_z)
@@ -171,7 +175,7 @@ class _Vanilla:
             return
         if self.attention:           # the one-launch tail forms no weights to read out
             if route == "fused":
-                raise ValueError('predict: return_attention=True with route "fused" - mlhot_np_query_fwd keeps S and D inside its one launch '
+                raise ValueError(f'predict: {self.attention} with route "fused" - mlhot_np_query_fwd keeps S and D inside its one launch '
                                  "and stays as it is; the attention read-out runs the composed route (linear_rows and favor_query)")
             route = "composed"
         if state.form == "summary":
@@ -203,7 +207,7 @@ class _Vanilla:
         """The checks of route "fused_summary" (mlhot_np_query_summary_fwd): every refusal is a ValueError before any launch."""
         model = self.model
         if self.attention:           # context.predict has refused a summary state already; this is the wording for every other form
-            raise ValueError('predict: return_attention=True with route "fused_summary" - a summary state keeps no per-shot rows, so there is '
+            raise ValueError(f'predict: {self.attention} with route "fused_summary" - a summary state keeps no per-shot rows, so there is '
                              "no weight per context shot to read out")
         if state.form != "summary":
             what = {"empty": "empty", "latent": "latent"}.get(state.kind, state.form)
@@ -223,7 +227,7 @@ class _Vanilla:
                              f"y_dim={self.dims.y_dim} m={self.dims.m_feat}); the composed route serves them")
         state.route = "fused_summary"
 
-    def predict_targets(self, state, qry_x, attention=False, mask_words=None):
+    def predict_targets(self, state, qry_x, attention=False, mask_words=None, target_weight=None):
         model, T, Nq = self.model, qry_x.shape[0], qry_x.shape[1]
         x_qry = _encode(model, qry_x)
         proj = _c(model.attn.projection_matrix) if model.ATTENTION else None
@@ -247,7 +251,8 @@ class _Vanilla:
             return lib().np_query_fwd(self.dims, params, x_qry.view(T, Nq, -1), key_state=state.keys.buf, vh=state.vh, proj=proj)
         if state.route == "fused_summary":
             return lib().np_query_summary_fwd(self.dims, params, x_qry.view(T, Nq, -1), state.keys.buf, proj)
-        return composed_tail(params, x_qry, T, Nq, model.OUT_TANH, keys=state.keys, vh=state.vh, proj=proj, wq=state.wq, weights=attention)
+        return composed_tail(params, x_qry, T, Nq, model.OUT_TANH, keys=state.keys, vh=state.vh, proj=proj, wq=state.wq, weights=attention,
+                             target_weight=target_weight)
 
 
 def condition(model, ctx_x, ctx_y, ctx_len=None, capacity=None, form="keys"):
@@ -397,7 +402,7 @@ def select(model, states, picks):
     return context.select(_CachedContext(model) if isinstance(model, ResNetNP) else _Vanilla(model), states, picks)
 
 
-def predict(model, state, qry_x, chunk=None, route=None, return_attention=False, context_mask=None):
+def predict(model, state, qry_x, chunk=None, route=None, return_attention=False, context_mask=None, attention_mass=False, target_weight=None):
     """(state, target images [T, Nq, ...]) -> mu [T, Nq, y_dim] = `model(ctx, labels, targets, test=True)[0]` for the context the
     state was made from, any Nq >= 1.  `chunk` bounds the targets per launch sequence (and the encoder's activations with them).
     `route`: None picks "fused" where mlhot_np_query_supported says yes and "composed" otherwise; a test may force either.  The
@@ -424,16 +429,43 @@ def predict(model, state, qry_x, chunk=None, route=None, return_attention=False,
     mask gives the bits of its G 3-D calls; chunked equals unchunked.  The vanilla family runs the composed route for it: a forced
     "fused" or "fused_summary" is a ValueError.  Also refused, before any launch: a summary, latent or empty state, keys kept on
     another route than "cached" / "long" / "paged", a mask of the wrong shape or dtype, and a mask that leaves a (task, group, target)
-    without any of the task's valid shots - that check reads ONE reduced bool back from the mask's device."""
+    without any of the task's valid shots - that check reads ONE reduced bool back from the mask's device.
+
+    `attention_mass=True` -> (mu, mass): mass [T, 8, Nc slots] = attn summed over the targets, each weighed by
+    `target_weight` [T, Nq] (finite and >= 0; None: 1) - how much this batch of targets attended to each stored shot, per head -
+    reduced inside the query launch in a fixed order, so attn [T, 8, Nq, Nc] is never stored (the call holds 1/16 of it): the
+    read-out that still fits at 4096 slots.  With target_weight None, mass is bit-equal to `fold32` of return_attention=True's attn
+    (16-row tiles in ascending row order, then the tiles in order); slots behind a task's ctx_len are exact zeros; mu has the bits
+    return_attention=True's mu has.  `chunk` must be a multiple of 16: the chunks' tile partials are folded once behind the last
+    chunk, so every such chunk size gives the same bits as chunk=None.  Served and routed exactly where return_attention=True is;
+    summary, latent and empty states refuse in its words; return_attention=True and context_mask= do not combine with it.
+    `prune` chooses the slots to keep by this quantity."""
     if isinstance(model, ResNetNP):
         if route is not None:
             raise ValueError("predict: route= belongs to the vanilla family")
+        if attention_mass or target_weight is not None:
+            return model.predict(state, qry_x, chunk=chunk, return_attention=return_attention, context_mask=context_mask,
+                                 attention_mass=attention_mass, target_weight=target_weight)
         if context_mask is not None:
             return model.predict(state, qry_x, chunk=chunk, return_attention=return_attention, context_mask=context_mask)
         if return_attention:
             return model.predict(state, qry_x, chunk=chunk, return_attention=True)
         return model.predict(state, qry_x, chunk=chunk)
-    return context.predict(_Vanilla(model, route, return_attention), state, qry_x, chunk, return_attention, context_mask)
+    return context.predict(_Vanilla(model, route, "attention_mass=True" if attention_mass else return_attention), state, qry_x, chunk,
+                           return_attention, context_mask, attention_mass, target_weight)
+
+
+def prune(model, state, qry_x, keep, target_weight=None, chunk=None):
+    """(per-shot attention state, target images [T, Nq, ...], keep) -> (a NEW state, drop): relevance-based forgetting for a bounded
+    stream.  Per task the `keep[t]` valid slots (`keep`: an int or T ints, each >= 1) with the largest attention
+    mass of these targets - `predict(attention_mass=True, target_weight=)` summed over the heads - stay, in their order; the others
+    are let go through `evict`, with everything evict states: one row-compaction launch, no image encoded, the key stabiliser
+    re-derived as the maximum over the shots that remain, the old state still valid.  Ties go to the lower slot index; a task with
+    `lens[t] <= keep[t]` is untouched.  `drop`, T ascending lists of slot indices, is what evict was given - log it.  The choice
+    costs ONE device-to-host copy of [T, Nc] floats.  `chunk` as predict(attention_mass=True) takes it (a multiple of 16).  Refused
+    with ValueError: `keep[t] < 1`, and whatever predict(attention_mass=True) and evict refuse."""
+    ad = _CachedContext(model) if isinstance(model, ResNetNP) else _Vanilla(model, None, "attention_mass=True")
+    return context.prune(ad, state, qry_x, keep, target_weight, chunk)
 
 
 def leave_one_out(model, state, qry_x, chunk=None):
@@ -463,7 +495,8 @@ def _rows(sources, lin_w, lin_b, act):
     return LinearFunction.apply(x, lin_w, lin_b, act)
 
 
-def composed_tail(params, x_qry, T, Nq, tanh, keys=None, vh=None, proj=None, z=None, wq=None, favor=None, prefixes=None, weights=False):
+def composed_tail(params, x_qry, T, Nq, tanh, keys=None, vh=None, proj=None, z=None, wq=None, favor=None, prefixes=None, weights=False,
+                  target_weight=None):
     """The query tail from the existing row-invariant operators - the yardstick of the fused launch and the route for dimensions
     it does not serve.  params: state_dict key -> tensor; x_qry [T * Nq, dim_w]; attention: keys (FavorKeyState), vh, proj (wq: the
     stacked _W_q weight and bias, else stacked here); otherwise z [T, dim_z].  -> mu [T, Nq, y_dim].
@@ -472,7 +505,9 @@ def composed_tail(params, x_qry, T, Nq, tanh, keys=None, vh=None, proj=None, z=N
     = K it answers for K context prefixes at once (favor_prefixes_long) and every Linear behind it runs once over the K * T * Nq
     rows, x_qry wrapping every T * Nq - row-invariant, so a row has the single tail's bits.  -> mu [K, T, Nq, y_dim].
 
-    `weights` (with `keys`, the default FAVOR+ stage): -> (mu, w), w [T, 8, Nq, Nc] from favor_query(weights=True); mu's bits stay."""
+    `weights` (with `keys`, the default FAVOR+ stage): -> (mu, w), w [T, 8, Nq, Nc] from favor_query(weights=True); mu's bits stay.
+    `weights="mass"`: -> (mu, part), the tile partials [T, 8, ceil(Nq / 16), Nc] of favor_query(mass="tiles",
+    target_weight=); mu's bits stay."""
     def lin(sources, name, act="none"):
         return _rows(sources, params[name + ".weight"], params[name + ".bias"], act)
     K = 1 if prefixes is None else prefixes
@@ -482,7 +517,8 @@ def composed_tail(params, x_qry, T, Nq, tanh, keys=None, vh=None, proj=None, z=N
         qh = _rows([(x_qry, 1, 0)], w, b, "none").view(T, Nq, HEADS, -1)
         att = None
         if weights:
-            merged, att = favor_query(qh, keys, vh, proj, weights=True)
+            merged, att = (favor_query(qh, keys, vh, proj, mass="tiles", target_weight=target_weight) if weights == "mass"
+                           else favor_query(qh, keys, vh, proj, weights=True))
             merged = merged.view(K * T * Nq, -1)
         else:
             merged = (favor_query(qh, keys, vh, proj) if favor is None else favor(qh)).view(K * T * Nq, -1)

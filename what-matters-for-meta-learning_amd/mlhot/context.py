@@ -20,7 +20,7 @@ import numbers
 import torch
 
 from mlhot import lib, ragged
-from mlhot.ops import GATHER_PARTS, PER_SHOT_ROUTES, LinearFunction, _c, favor_gather, favor_keys, favor_merge
+from mlhot.ops import GATHER_PARTS, PER_SHOT_ROUTES, LinearFunction, _c, favor_gather, favor_keys, favor_merge, target_weight_arg
 
 
 class ContextState:
@@ -496,7 +496,74 @@ def _refuse_mask(ad, state, mask, Nq):
     return mask4
 
 
-def predict(ad, state, qry_x, chunk=None, return_attention=False, context_mask=None):
+def prune_choice(score, lens, keep):
+    """prune's slot choice, host work only: score [T][Nc] (numbers; any nested sequence, array or CPU tensor), lens the valid slots
+    per task, keep an int or T ints >= 1 -> drop, T ascending lists of slot indices: per task the valid slots that are NOT among the
+    keep[t] with the largest score.  Ties go to the lower slot index; a task with lens[t] <= keep[t] drops nothing."""
+    T = len(lens)
+    if isinstance(keep, bool) or (isinstance(keep, numbers.Integral) and not isinstance(keep, bool)):
+        keep = [keep] * T
+    elif isinstance(keep, torch.Tensor):
+        keep = keep.tolist()
+    try:
+        keep = list(keep)
+    except TypeError:
+        raise ValueError(f"prune: keep must be an int or a sequence of {T} ints, got {type(keep).__name__}") from None
+    if len(keep) != T:
+        raise ValueError(f"prune: keep has {len(keep)} entries for {T} tasks")
+    for k in keep:
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+            raise ValueError(f"prune: keep must hold integers, got {k!r}")
+    if min(keep) < 1:
+        raise ValueError(f"prune: keep must be at least 1 for every task (a task without a context shot has no attention), got {[int(k) for k in keep]}")
+    drop = []
+    for t in range(T):
+        if score is None or lens[t] <= keep[t]:
+            drop.append([])
+            continue
+        row = [float(x) for x in score[t][:lens[t]]]
+        order = sorted(range(lens[t]), key=lambda c: (-row[c], c))
+        drop.append(sorted(order[int(keep[t]):]))
+    return drop
+
+
+def prune(ad, state, qry_x, keep, target_weight=None, chunk=None):
+    """(per-shot attention state, target images [T, Nq, ...], keep) -> (a NEW state, drop): per task the keep[t] valid slots with the
+    largest attention mass of these targets, summed over the heads (predict(attention_mass=True, target_weight=)),
+    stay - in their order - and the rest go through evict, whose statement about the key stabiliser holds: it becomes the maximum
+    over the shots that remain.  `drop` is what evict was given, T ascending slot lists, for a caller's log.  Ties go to the lower
+    slot index; a task with lens[t] <= keep[t] is untouched.  One device-to-host copy of [T, Nc] floats."""
+    what = "prune"
+    _enter(ad, what, state, qry_x, "targets")
+    _refuse_rowless(what, state, "a summary has no per-shot weights to prune by")
+    prune_choice(None, state.lens, keep)                                   # keep's own refusals, before any launch
+    _, mass = predict(ad, state, qry_x, chunk, attention_mass=True, target_weight=target_weight)
+    score = mass[:, 0]
+    for h in range(1, mass.shape[1]):                                      # the heads in ascending order: one order, whatever torch.sum's
+        score = score + mass[:, h]
+    drop = prune_choice(score.cpu(), state.lens, keep)                     # the one device-to-host copy
+    return evict(ad, state, drop), drop
+
+
+def _refuse_mass(ad, state, chunk, return_attention, context_mask):
+    """predict(attention_mass=True): what it does not combine with, the states without per-shot weights - in the read-out's words -
+    and a chunk that would split a 16-row tile.  Host checks only."""
+    if return_attention:
+        raise ValueError("predict: attention_mass=True with return_attention=True - the mass exists so that attn [T, H, Nq, Nc] is never "
+                         "stored; ask for one of the two (the mass is attn summed over the targets)")
+    if context_mask is not None:
+        raise ValueError("predict: attention_mass=True with context_mask= - the masked read-outs have no reduced form; ask for "
+                         "return_attention=True with the mask and sum over the targets")
+    try:
+        _refuse_attention(ad, state)
+    except ValueError as e:
+        raise ValueError(str(e).replace("return_attention=True", "attention_mass=True")) from None
+    if chunk is not None and int(chunk) % 16:
+        raise ValueError(f"predict: attention_mass=True sums the targets in tiles of 16 rows; chunk must be a multiple of 16 so that "
+                         f"every chunk starts on a tile and the mass is the same bits for every chunk size, got {chunk}")
+
+
+def predict(ad, state, qry_x, chunk=None, return_attention=False, context_mask=None, attention_mass=False, target_weight=None):
     """(state, target images [T, Nq, ...]) -> mu [T, Nq, y_dim] for the context the state was made from, any Nq >= 1.  `chunk` bounds
     the targets per launch sequence.  `return_attention`: -> (mu, attn), attn [T, H, Nq, Nc slots] FAVOR+'s weight of
     every context slot per head and target (mlhot.ops.favor_query(weights=True)), exact zeros at the slots behind a task's ctx_len,
@@ -505,13 +572,32 @@ def predict(ad, state, qry_x, chunk=None, return_attention=False, context_mask=N
     `context_mask`: bool [T, Nq, Nc slots] - target n of task t attends only to the slots whose entry is True -
     -> mu [T, Nq, y_dim]; or [T, G, Nq, Nc] for G masks of the same targets -> mu [T, G, Nq, y_dim] and attn [T, G, H, Nq, Nc], from
     ONE encoder pass over the targets and one masked query launch per chunk (mlhot.ops.favor_query(mask=)).  The key stabiliser
-    stays the state's.  Refusals: _refuse_mask."""
+    stays the state's.  Refusals: _refuse_mask.
+
+    `attention_mass`: -> (mu, mass), mass [T, H, Nc slots] = sum over the targets n of target_weight[t, n] *
+    attn[t, :, n, :] (`target_weight` [T, Nq] finite and >= 0; None: the plain sum), reduced inside the query launch
+    (mlhot.ops.favor_query(mass=)) - attn itself is never stored.  The chunks hand back their 16-row tile partials and ONE fold
+    runs behind the last chunk, so the mass has the same bits for every chunk (a multiple of 16) and for chunk=None.  mu has the
+    bits of the call without it on the same route.  Refusals: _refuse_mass."""
     _enter(ad, "predict", state, qry_x, "targets")
     Nq = qry_x.shape[1]
     if Nq < 1:
         raise ValueError("predict needs at least one target")
     if chunk is not None and int(chunk) < 1:
         raise ValueError(f"predict: chunk must be a positive number of targets, got {chunk}")
+    if target_weight is not None and not attention_mass:
+        raise ValueError("predict: target_weight= weighs the targets of attention_mass=True; without it there is nothing to weigh")
+    if attention_mass:
+        _refuse_mass(ad, state, chunk, return_attention, context_mask)
+        tw = target_weight_arg("predict", target_weight, state.T, Nq, qry_x.device, ValueError)
+        ad.route(state, qry_x)
+        step = Nq if chunk is None else min(int(chunk), Nq)
+        with torch.no_grad():
+            out, part = zip(*[ad.predict_targets(state, qry_x[:, i:i + step], attention="mass",
+                                                 target_weight=None if tw is None else tw[:, i:i + step].contiguous())
+                              for i in range(0, Nq, step)])
+            mass = lib().favor_mass_fold(part[0] if len(part) == 1 else torch.cat(part, dim=2))
+        return (out[0] if len(out) == 1 else torch.cat(out, dim=1)), mass
     if return_attention:
         _refuse_attention(ad, state)
     if context_mask is not None:

@@ -1000,7 +1000,23 @@ def _mask_words(mask, T, Nq, Nc, device):
     return _c(mask.view(torch.int32).to(device))
 
 
-def favor_query(qh, state, vh, proj, weights=False, mask=None):
+def target_weight_arg(what, tw, T, Nq, device, exc=MlhotError):
+    """`target_weight` of the attention mass: None, or a real tensor [T, Nq], finite and >= 0 -> fp32 on `device`.
+    The values are checked where the tensor lies (a device tensor costs ONE reduced bool read back), before any launch."""
+    if tw is None:
+        return None
+    if not isinstance(tw, torch.Tensor) or not tw.is_floating_point():
+        got = str(tw.dtype) if isinstance(tw, torch.Tensor) else type(tw).__name__
+        raise exc(f"{what}: target_weight must be a floating-point tensor [T={T}, Nq={Nq}], got {got}")
+    if tuple(tw.shape) != (T, Nq):
+        raise exc(f"{what}: target_weight must be [T={T}, Nq={Nq}], one weight per target, got {tuple(tw.shape)}")
+    tw = tw.detach()
+    if not bool((torch.isfinite(tw) & (tw >= 0)).all()):
+        raise exc(f"{what}: target_weight must be finite and >= 0 (the mass is a sum of non-negative terms)")
+    return _c(tw.to(device=device, dtype=torch.float32))
+
+
+def favor_query(qh, state, vh, proj, weights=False, mask=None, mass=False, target_weight=None):
     """FAVOR+ attention of q [T, Nq, H, d] against a favor_keys state and v [T, Nc, H, d] -> merged [T, Nq, d*H], any Nq >= 1 in
     one launch.  On the "cached" route the bits of a row do not depend on the other rows of the call (csrc/favor_cached.h), nor on
     the "long" route (favor_keys_long, csrc/favor_long.h: up to 256 slots in chunks of 32, weights=True included); the
@@ -1022,7 +1038,31 @@ def favor_query(qh, state, vh, proj, weights=False, mask=None):
     states only.  Without `mask` the call is the one it always was.
 
     A "paged" state (favor_keys_paged, csrc/favor_paged.h, DESIGN.md 6c-11: up to 4096 slots in pages of 256) is served like a
-    "long" one throughout - row-invariant, `weights=True` and `mask=` included (mlhot_favor_query_paged_fwd / _paged_masked_fwd)."""
+    "long" one throughout - row-invariant, `weights=True` and `mask=` included (mlhot_favor_query_paged_fwd / _paged_masked_fwd).
+
+    `mass=True` -> (merged, mass): mass [T, H, Nc] = sum over the targets n of target_weight[t, n] * w[t, h, n, :]
+    (`target_weight` [T, Nq] finite and >= 0, or None: the plain column sum), reduced INSIDE the query launch in a fixed order -
+    16-row tiles in ascending row order, then the tiles in ascending order - so w [T, H, Nq, Nc] is never stored: the call holds
+    1/16 of it.  With target_weight None the result is bit-equal to that fold of `weights=True`'s w; merged has the plain call's
+    bits.  "cached", "long" and "paged" states, refused where `weights=True` is; exclusive with `weights=True` and `mask=`.
+    `mass="tiles"` -> (merged, part [T, H, ceil(Nq / 16), Nc]): the tile partials, unfolded, for a caller that splits the targets at
+    multiples of 16 and folds once (mlhot.lib().favor_mass_fold)."""
+    if mass:
+        if weights:
+            raise ValueError("favor_query: mass=True with weights=True - the mass exists so that w [T, H, Nq, Nc] is never stored; ask for one "
+                             "of the two (the mass is the fold of w over the targets)")
+        if mask is not None:
+            raise ValueError("favor_query: mass=True with mask= - the masked read-outs have no reduced form; ask for weights=True with the mask "
+                             "and sum over the targets")
+    elif target_weight is not None:
+        raise ValueError("favor_query: target_weight= weighs the targets of mass=True; without it there is nothing to weigh")
+    if mass and isinstance(state, FavorKeyState) and state.route not in PER_SHOT_ROUTES:
+        if state.route == "summary":
+            raise MlhotError("favor_query: mass=True - a summary state keeps no per-shot rows, so there is no weight per context shot to "
+                             "read out (condition with the default form for at most 32 shots)")
+        T, Nc, H, d, m = state.dims
+        raise MlhotError(f"favor_query: mass=True needs the cached kernels' envelope (Nc <= 32, d % 16 == 0, d <= 256, 16 <= m <= 1536), "
+                         f"got Nc={Nc} d={d} m={m}: mlhot_favor_fwd on the kept keys forms no per-shot weights")
     if mask is not None and isinstance(state, FavorKeyState) and state.route not in PER_SHOT_ROUTES:
         if state.route == "summary":
             raise MlhotError("favor_query: mask= - a summary state keeps no per-shot rows, so there is no column of S to mask "
@@ -1056,6 +1096,9 @@ def favor_query(qh, state, vh, proj, weights=False, mask=None):
     T, Nc, H, d, m = state.dims
     if tuple(vh.shape) != (T, Nc, H, d) or qh.dim() != 4 or (qh.shape[0], qh.shape[2], qh.shape[3]) != (T, H, d) or tuple(proj.shape) != (m, d):
         raise MlhotError(f"favor_query: the state was built for T={T} Nc={Nc} H={H} d={d} m={m}; got q {tuple(qh.shape)}, v {tuple(vh.shape)}, proj {tuple(proj.shape)}")
+    if mass:
+        tw = target_weight_arg("favor_query", target_weight, T, qh.shape[1], qh.device)
+        return lib().favor_query_mass_fwd(qh, state.buf, vh, proj, state.route, lens=state.lens_dev, tw=tw, fold=mass != "tiles")
     if mask is not None:
         words = _mask_words(mask, T, qh.shape[1], Nc, qh.device)
         if state.route == "paged":

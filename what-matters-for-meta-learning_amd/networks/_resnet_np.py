@@ -132,7 +132,9 @@ class _CachedContext:
     def route(self, state, qry_x):
         pass
 
-    def predict_targets(self, state, qry_x, attention=False, mask_words=None):
+    def predict_targets(self, state, qry_x, attention=False, mask_words=None, target_weight=None):
+        if attention == "mass":      # -> (mu, the tile partials of the attention mass)
+            return self.model._predict_targets(state, qry_x.contiguous(), return_attention="mass", target_weight=target_weight)
         if mask_words is not None:
             return self.model._predict_targets(state, qry_x.contiguous(), return_attention=attention, mask_words=mask_words)
         if attention:
@@ -564,7 +566,7 @@ class ResNetNP(nn.Module):
             return self._heads(x_ctx[None], self._W_k)[0], self._heads(feats[None], self._W_v)[0]
         return self._latent_rows(feats)
 
-    def predict(self, state, batch_test_images, chunk=None, return_attention=False, context_mask=None):
+    def predict(self, state, batch_test_images, chunk=None, return_attention=False, context_mask=None, attention_mass=False, target_weight=None):
         """(ContextState, target images [T, Nq, ...]) -> mu [T, Nq, out] = `forward(ctx, labels, targets, test=True)[0]` for the
         context the state was made from, any Nq >= 1.  One run_trunks call does the target (attention models) and decoder passes;
         the query head projection, `_W`, `mu` and the decoder head go through mlhot.ops.linear_rows and the attention through
@@ -579,10 +581,15 @@ class ResNetNP(nn.Module):
         `context_mask`: bool [T, Nq, Nc slots] -> mu [T, Nq, out], every target attending only to the slots that
         are True; [T, G, Nq, Nc slots] -> mu [T, G, Nq, out] and attn [T, G, heads, Nq, Nc]: G masks of the same targets from ONE
         pass through the trunks and one masked favor_query launch, the Linears behind it over the T * G * Nq rows.  An all-True
-        mask gives plain predict's bits.  mlhot.cached.predict states the refusals."""
-        return context.predict(_CachedContext(self), state, batch_test_images, chunk, return_attention, context_mask)
+        mask gives plain predict's bits.  mlhot.cached.predict states the refusals.
 
-    def _predict_targets(self, state, batch_test_images, return_attention=False, mask_words=None):
+        `attention_mass=True` -> (mu, mass): mass [T, heads, Nc slots] = attn summed over the targets, weighed by
+        `target_weight` [T, Nq] (None: 1), reduced inside the favor_query launch so that attn is never stored; bit-equal to the
+        documented fp32 fold of return_attention=True's attn, the same for every chunk that is a multiple of 16; mu has plain
+        predict's bits.  mlhot.cached.predict states the rest."""
+        return context.predict(_CachedContext(self), state, batch_test_images, chunk, return_attention, context_mask, attention_mass, target_weight)
+
+    def _predict_targets(self, state, batch_test_images, return_attention=False, mask_words=None, target_weight=None):
         self._refresh_arena()
         with torch.no_grad():
             T, Nq = self.task_num, batch_test_images.shape[1]
@@ -610,7 +617,9 @@ class ResNetNP(nn.Module):
                     sample = _fold_linear([(sample, 1, 0)], self.mu, "none", G)
                     mu = self._fold_head(x_dec, sample, 1, G, Nq).transpose(0, 1).contiguous()
                     return (mu, attn) if return_attention else mu
-                if return_attention:
+                if return_attention == "mass":
+                    merged, attn = favor_query(qh, state.keys, state.vh, self.attn.projection_matrix, mass="tiles", target_weight=target_weight)
+                elif return_attention:
                     merged, attn = favor_query(qh, state.keys, state.vh, self.attn.projection_matrix, weights=True)
                 else:
                     merged = favor_query(qh, state.keys, state.vh, self.attn.projection_matrix)
