@@ -603,6 +603,41 @@ int mlhot_favor_query_paged_mass_fwd(const float* q, const void* state, const fl
                                      void* ws, size_t ws_bytes, void* stream);
 int mlhot_favor_mass_fold(const float* part /* [TH,ntile,Nc] */, int TH, int ntile, int Nc, float* mass /* [TH,Nc] */, void* stream);
 
+/* ---- top-k attention read-out: the k heaviest context slots per target row inside the query launch (csrc/favor_topk.h)
+ * Per (task, head, target row n) the valid slots are ranked by the UN-NORMALISED score S[n,c] - the bits the read-out divides - in
+ * descending order, ties to the lower slot index:
+ *     idx[t,h,n,j] = the j-th slot of that ranking,     wk[t,h,n,j] = S[n,idx] / D[n],
+ * the read-out's own single IEEE divide with the row's final D: the bits mlhot_favor_query_weights_fwd (or its long / paged sibling)
+ * stores into w[t,h,n,idx].  D > 0 is one number per row and IEEE division is monotone, so the order of S is an order of w; where
+ * two different S round to one w the VALUES agree with a top-k over w, the indices need not.  w[T,H,Nq,Nc] is never allocated or
+ * written.  mlhot_favor_query_topk_fwd serves a mlhot_favor_keys_fwd / _ragged_fwd state (Nc <= 32), mlhot_favor_query_long_topk_fwd a
+ * mlhot_favor_keys_long_fwd state (Nc <= 256), mlhot_favor_query_paged_topk_fwd a mlhot_favor_keys_paged_fwd state (Nc <= 4096).  The
+ * arguments are the unmasked entry's (mlhot_favor_query_fwd / _long_fwd / _paged_fwd without w; ws is the 256-byte token block) plus
+ *   k, 1 <= k <= 16; idx[T,H,Nq,k] int32 and wk[T,H,Nq,k] fp32, DEVICE memory, 4-byte aligned.
+ * Valid slots: c < lens[t] (long, paged; lens NULL: all Nc).  The keys entry takes no lens, like the entry it extends: a column whose
+ *   S is exactly +0 is a zero row of F_k and counts as absent.  Entries j >= the number of valid slots are idx = -1, wk = +0.0f.
+ * out is BIT-EQUAL to the entry without top-k on the same arguments.  Rows n >= lens[t] of v are never read by the long and paged
+ *   entries (the keys entry reads v as mlhot_favor_query_fwd does).  The bits of a row depend neither on the other rows of the call
+ *   nor on the capacity Nc the same shots are kept in; a paged state of at most 256 slots gives the long entry's bits, a long state
+ *   of at most 32 the keys entry's.
+ * The paged entry walks the pages ONCE: the order of S needs no D, so each page joins the running k best (kept in registers) while
+ *   its S lies in LDS, and k numbers per row are divided behind the last page.  (S descending, slot ascending) is a total order: the
+ *   result does not depend on how the slots fall into pages.  No atomics, no workspace beyond the token block.
+ * Envelope, alignment and error codes are those of the entry each one extends; idx == NULL, wk == NULL or k outside 1 .. 16 is
+ * MLHOT_ERR_ARG; unsupported shapes write nothing.  Forward only; GPU build only.  Added within ABI 8: bindings look the symbols up. */
+int mlhot_favor_query_topk_fwd(const float* q, const void* state, const float* v, const float* proj,
+                               int T, int H, int Nq, int Nc, int d, int m, float* out,
+                               int k, int32_t* idx /* [T,H,Nq,k] */, float* wk /* [T,H,Nq,k] */,
+                               void* ws, size_t ws_bytes, void* stream);
+int mlhot_favor_query_long_topk_fwd(const float* q, const void* state, const float* v, const float* proj,
+                                    const int32_t* lens /* [T], device, or NULL */, int T, int H, int Nq, int Nc, int d, int m,
+                                    float* out, int k, int32_t* idx /* [T,H,Nq,k] */, float* wk /* [T,H,Nq,k] */,
+                                    void* ws, size_t ws_bytes, void* stream);
+int mlhot_favor_query_paged_topk_fwd(const float* q, const void* state, const float* v, const float* proj,
+                                     const int32_t* lens /* [T], device, or NULL */, int T, int H, int Nq, int Nc, int d, int m,
+                                     float* out, int k, int32_t* idx /* [T,H,Nq,k] */, float* wk /* [T,H,Nq,k] */,
+                                     void* ws, size_t ws_bytes, void* stream);
+
 /* ---- cached contexts that let shots go: the per-shot rows moved by a plan (csrc/rows_compact.h) ------------------
  * mlhot_rows_compact: `sets` row sets, 1 <= sets <= 4, that share one plan.  Row set i is (src[i], dst[i], W[i]): fp32 rows of W[i]
  *   floats in [T][cap][W[i]]; src, dst and W are arrays of `sets` entries in HOST memory.  plan[T][cap] (int32, DEVICE memory, read by

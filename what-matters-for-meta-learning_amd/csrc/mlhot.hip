@@ -35,6 +35,7 @@
 #include "favor_long.h"
 #include "favor_paged.h"
 #include "favor_mass.h"
+#include "favor_topk.h"
 #include "rows_compact.h"
 #include "rows_gather.h"
 #include "resnet_trunk.h"
@@ -447,6 +448,19 @@ int mlhot_favor_query_paged_mass_fwd(const float* q, const void* state, const fl
 }
 int mlhot_favor_mass_fold(const float* part, int TH, int ntile, int Nc, float* mass, void* stream) {
   return favor_mass_fold(part, TH, ntile, Nc, mass, (hipStream_t)stream);
+}
+// top-k attention read-out: the k heaviest context slots per target row, selected inside the query launch (csrc/favor_topk.h)
+int mlhot_favor_query_topk_fwd(const float* q, const void* state, const float* v, const float* proj, int T, int H, int Nq, int Nc, int d, int m,
+                               float* out, int k, int32_t* idx, float* wk, void* ws, size_t ws_bytes, void* stream) {
+  return favor_query_topk_launch("favor_query_topk_fwd", 0, q, state, v, proj, nullptr, T, H, Nq, Nc, d, m, out, k, idx, wk, ws, ws_bytes, (hipStream_t)stream);
+}
+int mlhot_favor_query_long_topk_fwd(const float* q, const void* state, const float* v, const float* proj, const int32_t* lens, int T, int H, int Nq,
+                                    int Nc, int d, int m, float* out, int k, int32_t* idx, float* wk, void* ws, size_t ws_bytes, void* stream) {
+  return favor_query_topk_launch("favor_query_long_topk_fwd", 1, q, state, v, proj, lens, T, H, Nq, Nc, d, m, out, k, idx, wk, ws, ws_bytes, (hipStream_t)stream);
+}
+int mlhot_favor_query_paged_topk_fwd(const float* q, const void* state, const float* v, const float* proj, const int32_t* lens, int T, int H, int Nq,
+                                     int Nc, int d, int m, float* out, int k, int32_t* idx, float* wk, void* ws, size_t ws_bytes, void* stream) {
+  return favor_query_topk_launch("favor_query_paged_topk_fwd", 2, q, state, v, proj, lens, T, H, Nq, Nc, d, m, out, k, idx, wk, ws, ws_bytes, (hipStream_t)stream);
 }
 // cached contexts that let shots go: the per-shot rows of up to 4 row sets moved by one plan, one launch (csrc/rows_compact.h)
 int mlhot_rows_compact(const float* const* src, float* const* dst, const int* W, int sets, const int32_t* plan, int T, int cap, void* stream) {

@@ -314,6 +314,10 @@ SIGNATURES = {
     "mlhot_favor_query_long_mass_fwd": (i, [P, P, P, P, P, P, i, i, i, i, i, i, P, P, i, P, z, P]),
     "mlhot_favor_query_paged_mass_fwd": (i, [P, P, P, P, P, P, i, i, i, i, i, i, P, P, i, P, z, P]),
     "mlhot_favor_mass_fold": (i, [P, i, i, i, P, P]),
+    # top-k attention read-out: the k heaviest context slots per target row inside the query launch
+    "mlhot_favor_query_topk_fwd": (i, [P, P, P, P, i, i, i, i, i, i, P, i, P, P, P, z, P]),
+    "mlhot_favor_query_long_topk_fwd": (i, [P, P, P, P, P, i, i, i, i, i, i, P, i, P, P, P, z, P]),
+    "mlhot_favor_query_paged_topk_fwd": (i, [P, P, P, P, P, i, i, i, i, i, i, P, i, P, P, P, z, P]),
     # cached contexts that let shots go: the per-shot rows moved by a plan
     "mlhot_rows_compact": (i, [P, P, P, i, P, i, i, P]),
     # cached contexts joined or regrouped across states: per-shot rows gathered from several sources
@@ -1378,6 +1382,42 @@ class MlhotLib:
         head = (_ptr(q), _ptr(state), _ptr(v), _ptr(proj)) + (() if form == "cached" else (_ptr(lens),))
         self._rc(fn(*head, _ptr(tw), T, H, Nq, Nc, d, m, _ptr(out), _ptr(mass), int(bool(fold)), _ptr(ws), ws.numel(), _stream(q)), "mlhot_" + what)
         return out, mass
+
+    # ---- top-k attention read-out (csrc/favor_topk.h) ---------------------------
+    def favor_query_topk_fwd(self, q, state, v, proj, form, k, lens=None):
+        """q [T,Nq,H,d], a per-shot key state of `form` ("cached" | "long" | "paged") with its lens, v [T,Nc,H,d], proj [m,d], 1 <= k
+        <= 16 -> (out [T,Nq,d*H], idx int32 [T,H,Nq,k], wk fp32 [T,H,Nq,k]): per row the k valid slots of largest S, descending, ties to
+        the lower slot, and wk = S / D with the bits the read-out stores into w[t,h,n,idx]; -1 / +0 behind the valid slots; selected
+        inside the query launch - w itself is never stored; out has the plain entry's bits (include/mlhot.h).  Forward only."""
+        what = {"cached": "favor_query_topk_fwd", "long": "favor_query_long_topk_fwd", "paged": "favor_query_paged_topk_fwd"}[form]
+        fn = self._fn(what, "mlhot_" + what)
+        for name, t in (("q", q), ("v", v)):
+            if t.dtype != torch.float32 or t.dim() != 4:
+                raise MlhotError(f"{what}: {name} must be fp32 [T, N, H, d], got {t.dtype} {tuple(t.shape)}")
+        T, Nq, H, d = q.shape
+        Nc = v.shape[1]
+        if tuple(v.shape) != (T, Nc, H, d) or proj.dtype != torch.float32 or proj.dim() != 2 or proj.shape[1] != d or Nq < 1:
+            raise MlhotError(f"{what}: q {tuple(q.shape)}, v {tuple(v.shape)}, proj {tuple(proj.shape)} do not fit together")
+        if any(t.device != q.device for t in (state, v, proj)):
+            raise MlhotError(f"{what}: q, state, v and proj must lie on one device")
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 16:
+            raise MlhotError(f"{what}: k must be an integer in 1 .. 16, got {k!r}")
+        self._long_lens(what, lens, T, q)
+        if form == "cached" and lens is not None:
+            raise MlhotError(f"{what}: a keys state carries its lens as zero rows of F_k; the entry takes none")
+        m = proj.shape[0]
+        nb = {"cached": self.favor_keys_bytes, "long": self.favor_keys_long_bytes, "paged": self.favor_keys_paged_bytes}[form](T, H, Nc, d, m)
+        if not nb or state.dtype != torch.uint8 or state.numel() < nb:
+            raise MlhotError(f"{what}: the state is not this form's for T={T} H={H} Nc={Nc} d={d} m={m} "
+                             f"({state.numel()} bytes, {nb} needed; 0 = shape not served)")
+        _chk(q, v, proj, state, lens)
+        out = torch.empty(T, Nq, d * H, device=q.device)
+        idx = torch.empty(T, H, Nq, k, device=q.device, dtype=torch.int32)
+        wk = torch.empty(T, H, Nq, k, device=q.device)
+        ws = self._bytes(256, q)
+        head = (_ptr(q), _ptr(state), _ptr(v), _ptr(proj)) + (() if form == "cached" else (_ptr(lens),))
+        self._rc(fn(*head, T, H, Nq, Nc, d, m, _ptr(out), k, _ptr(idx), _ptr(wk), _ptr(ws), ws.numel(), _stream(q)), "mlhot_" + what)
+        return out, idx, wk
 
     def favor_mass_fold(self, part):
         """part [T,H,tiles,Nc] (the tile partials of favor_query_mass_fwd(fold=False), concatenated along the tile axis in target

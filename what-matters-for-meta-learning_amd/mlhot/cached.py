@@ -24,6 +24,7 @@
     mu, mass = mlhot.cached.predict(model, state, qry_x, attention_mass=True, target_weight=None)     # mass [T, 8, Nc slots]: attn summed over
                                                                     # the targets inside the query launch, attn never stored (6c-14)
     state, drop = mlhot.cached.prune(model, state, qry_x, keep)     # keep[t] slots with the largest mass stay, the rest go through evict
+    mu, idx, w = mlhot.cached.predict(model, state, qry_x, top_k=8) # [T, 8, Nq, k]: the k heaviest context slots per head and target (6c-15)
     ok, reason = mlhot.cached.supports(model)
     mu = mlhot.cached.sweep(model, ctx_x, ctx_y, qry_x, ks=None, route=None)      # [len(ks), T, Nq, y_dim]: every context prefix (6b-2)
     ok, reason = mlhot.cached.supports_sweep(model)
@@ -402,7 +403,8 @@ def select(model, states, picks):
     return context.select(_CachedContext(model) if isinstance(model, ResNetNP) else _Vanilla(model), states, picks)
 
 
-def predict(model, state, qry_x, chunk=None, route=None, return_attention=False, context_mask=None, attention_mass=False, target_weight=None):
+def predict(model, state, qry_x, chunk=None, route=None, return_attention=False, context_mask=None, attention_mass=False, target_weight=None,
+            top_k=None):
     """(state, target images [T, Nq, ...]) -> mu [T, Nq, y_dim] = `model(ctx, labels, targets, test=True)[0]` for the context the
     state was made from, any Nq >= 1.  `chunk` bounds the targets per launch sequence (and the encoder's activations with them).
     `route`: None picks "fused" where mlhot_np_query_supported says yes and "composed" otherwise; a test may force either.  The
@@ -439,10 +441,23 @@ def predict(model, state, qry_x, chunk=None, route=None, return_attention=False,
     return_attention=True's mu has.  `chunk` must be a multiple of 16: the chunks' tile partials are folded once behind the last
     chunk, so every such chunk size gives the same bits as chunk=None.  Served and routed exactly where return_attention=True is;
     summary, latent and empty states refuse in its words; return_attention=True and context_mask= do not combine with it.
-    `prune` chooses the slots to keep by this quantity."""
+    `prune` chooses the slots to keep by this quantity.
+
+    `top_k=k`, an integer in 1 .. 16 -> (mu, idx, w): idx int32 and w fp32 [T, 8, Nq, k], per head and target the k
+    stored shots the prediction rests on most and the share of the attention each holds - the valid slots ranked by FAVOR+'s
+    un-normalised score (descending, ties to the lower slot), w the very bits return_attention=True's attn has at [t, h, n, idx] -
+    selected inside the query launch, the paged form in its one walk over the pages, so attn [T, 8, Nq, Nc] is never stored.
+    Entries behind a task's ctx_len shots are idx = -1, w = 0.  The result is per target row: ANY `chunk` gives chunk=None's bits;
+    mu has the bits return_attention=True's mu has.  Slot indices are the state's slot order: after `evict` / `prune` / `concat`
+    they refer to the new state's.  Served and routed exactly where return_attention=True is; summary, latent and empty states and
+    models without attention refuse in its words; return_attention=True, context_mask= and attention_mass=True do not combine with
+    it; a forced "fused" / "fused_summary" route is a ValueError."""
     if isinstance(model, ResNetNP):
         if route is not None:
             raise ValueError("predict: route= belongs to the vanilla family")
+        if top_k is not None:
+            return model.predict(state, qry_x, chunk=chunk, return_attention=return_attention, context_mask=context_mask,
+                                 attention_mass=attention_mass, target_weight=target_weight, top_k=top_k)
         if attention_mass or target_weight is not None:
             return model.predict(state, qry_x, chunk=chunk, return_attention=return_attention, context_mask=context_mask,
                                  attention_mass=attention_mass, target_weight=target_weight)
@@ -451,8 +466,8 @@ def predict(model, state, qry_x, chunk=None, route=None, return_attention=False,
         if return_attention:
             return model.predict(state, qry_x, chunk=chunk, return_attention=True)
         return model.predict(state, qry_x, chunk=chunk)
-    return context.predict(_Vanilla(model, route, "attention_mass=True" if attention_mass else return_attention), state, qry_x, chunk,
-                           return_attention, context_mask, attention_mass, target_weight)
+    asks = "top_k=" if top_k is not None else "attention_mass=True" if attention_mass else return_attention
+    return context.predict(_Vanilla(model, route, asks), state, qry_x, chunk, return_attention, context_mask, attention_mass, target_weight, top_k)
 
 
 def prune(model, state, qry_x, keep, target_weight=None, chunk=None):
@@ -507,7 +522,7 @@ def composed_tail(params, x_qry, T, Nq, tanh, keys=None, vh=None, proj=None, z=N
 
     `weights` (with `keys`, the default FAVOR+ stage): -> (mu, w), w [T, 8, Nq, Nc] from favor_query(weights=True); mu's bits stay.
     `weights="mass"`: -> (mu, part), the tile partials [T, 8, ceil(Nq / 16), Nc] of favor_query(mass="tiles",
-    target_weight=); mu's bits stay."""
+    target_weight=); mu's bits stay.  `weights=("topk", k)`: -> (mu, [idx, wk]) of favor_query(topk=k); mu's bits stay."""
     def lin(sources, name, act="none"):
         return _rows(sources, params[name + ".weight"], params[name + ".bias"], act)
     K = 1 if prefixes is None else prefixes
@@ -517,8 +532,11 @@ def composed_tail(params, x_qry, T, Nq, tanh, keys=None, vh=None, proj=None, z=N
         qh = _rows([(x_qry, 1, 0)], w, b, "none").view(T, Nq, HEADS, -1)
         att = None
         if weights:
-            merged, att = (favor_query(qh, keys, vh, proj, mass="tiles", target_weight=target_weight) if weights == "mass"
-                           else favor_query(qh, keys, vh, proj, weights=True))
+            if isinstance(weights, tuple):
+                merged, *att = favor_query(qh, keys, vh, proj, topk=weights[1])
+            else:
+                merged, att = (favor_query(qh, keys, vh, proj, mass="tiles", target_weight=target_weight) if weights == "mass"
+                               else favor_query(qh, keys, vh, proj, weights=True))
             merged = merged.view(K * T * Nq, -1)
         else:
             merged = (favor_query(qh, keys, vh, proj) if favor is None else favor(qh)).view(K * T * Nq, -1)

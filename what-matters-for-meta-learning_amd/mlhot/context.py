@@ -20,7 +20,7 @@ import numbers
 import torch
 
 from mlhot import lib, ragged
-from mlhot.ops import GATHER_PARTS, PER_SHOT_ROUTES, LinearFunction, _c, favor_gather, favor_keys, favor_merge, target_weight_arg
+from mlhot.ops import GATHER_PARTS, PER_SHOT_ROUTES, LinearFunction, _c, favor_gather, favor_keys, favor_merge, target_weight_arg, topk_arg
 
 
 class ContextState:
@@ -563,7 +563,27 @@ def _refuse_mass(ad, state, chunk, return_attention, context_mask):
                          f"every chunk starts on a tile and the mass is the same bits for every chunk size, got {chunk}")
 
 
-def predict(ad, state, qry_x, chunk=None, return_attention=False, context_mask=None, attention_mass=False, target_weight=None):
+def _refuse_topk(ad, state, top_k, return_attention, context_mask, attention_mass):
+    """predict(top_k=): a k outside 1 .. 16, what it does not combine with, and the states without per-shot weights - in the read-out's
+    words.  Host checks only.  -> k as an int."""
+    k = topk_arg("predict", top_k)
+    if return_attention:
+        raise ValueError("predict: top_k= with return_attention=True - the top-k exists so that attn [T, H, Nq, Nc] is never stored; ask "
+                         "for one of the two (torch.topk of attn gives the same weights)")
+    if context_mask is not None:
+        raise ValueError("predict: top_k= with context_mask= - the masked read-outs have no reduced form; ask for return_attention=True "
+                         "with the mask and take torch.topk of it")
+    if attention_mass:
+        raise ValueError("predict: top_k= with attention_mass=True - each is one reduction of the read-out inside the query launch (over "
+                         "the slots, over the targets); ask for one per call")
+    try:
+        _refuse_attention(ad, state)
+    except ValueError as e:
+        raise ValueError(str(e).replace("return_attention=True", "top_k=")) from None
+    return k
+
+
+def predict(ad, state, qry_x, chunk=None, return_attention=False, context_mask=None, attention_mass=False, target_weight=None, top_k=None):
     """(state, target images [T, Nq, ...]) -> mu [T, Nq, y_dim] for the context the state was made from, any Nq >= 1.  `chunk` bounds
     the targets per launch sequence.  `return_attention`: -> (mu, attn), attn [T, H, Nq, Nc slots] FAVOR+'s weight of
     every context slot per head and target (mlhot.ops.favor_query(weights=True)), exact zeros at the slots behind a task's ctx_len,
@@ -578,7 +598,13 @@ def predict(ad, state, qry_x, chunk=None, return_attention=False, context_mask=N
     attn[t, :, n, :] (`target_weight` [T, Nq] finite and >= 0; None: the plain sum), reduced inside the query launch
     (mlhot.ops.favor_query(mass=)) - attn itself is never stored.  The chunks hand back their 16-row tile partials and ONE fold
     runs behind the last chunk, so the mass has the same bits for every chunk (a multiple of 16) and for chunk=None.  mu has the
-    bits of the call without it on the same route.  Refusals: _refuse_mass."""
+    bits of the call without it on the same route.  Refusals: _refuse_mass.
+
+    `top_k`: an integer k in 1 .. 16 -> (mu, idx, w), idx int32 and w fp32 [T, H, Nq, k]: per head and target the k
+    valid slots of largest un-normalised score (descending, ties to the lower slot) and their attention weights, the bits attn has
+    there, selected inside the query launch (mlhot.ops.favor_query(topk=)) - attn itself is never stored; -1 / 0 behind a task's
+    shots.  The result is per target row, so the chunks are concatenated along the target axis and ANY chunk gives chunk=None's
+    bits.  mu has the bits of the call without it on the same route.  Refusals: _refuse_topk."""
     _enter(ad, "predict", state, qry_x, "targets")
     Nq = qry_x.shape[1]
     if Nq < 1:
@@ -587,6 +613,15 @@ def predict(ad, state, qry_x, chunk=None, return_attention=False, context_mask=N
         raise ValueError(f"predict: chunk must be a positive number of targets, got {chunk}")
     if target_weight is not None and not attention_mass:
         raise ValueError("predict: target_weight= weighs the targets of attention_mass=True; without it there is nothing to weigh")
+    if top_k is not None:
+        k = _refuse_topk(ad, state, top_k, return_attention, context_mask, attention_mass)
+        ad.route(state, qry_x)
+        step = Nq if chunk is None else min(int(chunk), Nq)
+        with torch.no_grad():
+            res = [ad.predict_targets(state, qry_x[:, i:i + step], attention=("topk", k)) for i in range(0, Nq, step)]
+        if len(res) == 1:
+            return res[0][0], res[0][1][0], res[0][1][1]
+        return torch.cat([r[0] for r in res], dim=1), torch.cat([r[1][0] for r in res], dim=2), torch.cat([r[1][1] for r in res], dim=2)
     if attention_mass:
         _refuse_mass(ad, state, chunk, return_attention, context_mask)
         tw = target_weight_arg("predict", target_weight, state.T, Nq, qry_x.device, ValueError)

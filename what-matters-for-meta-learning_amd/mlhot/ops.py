@@ -588,6 +588,7 @@ def favor_prefixes_long(qh, kh, vh, proj, ks=None, lens=None):
 
 
 PER_SHOT_ROUTES = ("cached", "long", "paged")      # the states that keep F_k per slot: weights and masks can be read out of them
+TOPK_MAX = 16                                      # slots per row of the top-k read-out (csrc/favor_topk.h: one lane per kept slot)
 
 
 class FavorKeyState:
@@ -1016,7 +1017,14 @@ def target_weight_arg(what, tw, T, Nq, device, exc=MlhotError):
     return _c(tw.to(device=device, dtype=torch.float32))
 
 
-def favor_query(qh, state, vh, proj, weights=False, mask=None, mass=False, target_weight=None):
+def topk_arg(what, k, name="top_k", exc=ValueError):
+    """`top_k` of the top-k attention read-out: an integer in 1 .. 16 (a bool is none) -> int.  Host check."""
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= int(k) <= TOPK_MAX:
+        raise exc(f"{what}: {name} must be an integer in 1 .. {TOPK_MAX} (the kernels keep at most {TOPK_MAX} slots per row), got {k!r}")
+    return int(k)
+
+
+def favor_query(qh, state, vh, proj, weights=False, mask=None, mass=False, target_weight=None, topk=None):
     """FAVOR+ attention of q [T, Nq, H, d] against a favor_keys state and v [T, Nc, H, d] -> merged [T, Nq, d*H], any Nq >= 1 in
     one launch.  On the "cached" route the bits of a row do not depend on the other rows of the call (csrc/favor_cached.h), nor on
     the "long" route (favor_keys_long, csrc/favor_long.h: up to 256 slots in chunks of 32, weights=True included); the
@@ -1046,7 +1054,28 @@ def favor_query(qh, state, vh, proj, weights=False, mask=None, mass=False, targe
     1/16 of it.  With target_weight None the result is bit-equal to that fold of `weights=True`'s w; merged has the plain call's
     bits.  "cached", "long" and "paged" states, refused where `weights=True` is; exclusive with `weights=True` and `mask=`.
     `mass="tiles"` -> (merged, part [T, H, ceil(Nq / 16), Nc]): the tile partials, unfolded, for a caller that splits the targets at
-    multiples of 16 and folds once (mlhot.lib().favor_mass_fold)."""
+    multiples of 16 and folds once (mlhot.lib().favor_mass_fold).
+
+    `topk=k`, 1 <= k <= 16 -> (merged, idx int32 [T, H, Nq, k], wk fp32 [T, H, Nq, k]): per head and query row the k
+    valid slots with the largest un-normalised score S, descending, ties to the lower slot, and their weights wk = S / D - the bits
+    `weights=True` stores into w[t, h, n, idx] - selected INSIDE the query launch (mlhot_favor_query_topk_fwd / _long_topk_fwd /
+    _paged_topk_fwd), the paged form in its ONE walk over the pages; w is never stored.  Entries behind the task's valid slots are
+    idx = -1, wk = +0.  merged has the plain call's bits; every row's result is its own.  "cached", "long" and "paged" states,
+    refused where `weights=True` is; exclusive with `weights=True`, `mask=` and `mass=`."""
+    if topk is not None:
+        topk = topk_arg("favor_query", topk, "topk")
+        for on, name, why in ((weights, "weights=True", "the top-k exists so that w [T, H, Nq, Nc] is never stored; ask for one of the two"),
+                              (mask is not None, "mask=", "the masked read-outs have no reduced form; ask for weights=True with the mask"),
+                              (mass, "mass=", "each is one reduction of the read-out inside the launch; ask for one per call")):
+            if on:
+                raise ValueError(f"favor_query: topk= with {name} - {why}")
+        if isinstance(state, FavorKeyState) and state.route not in PER_SHOT_ROUTES:
+            if state.route == "summary":
+                raise MlhotError("favor_query: topk= - a summary state keeps no per-shot rows, so there is no weight per context shot to "
+                                 "read out (condition with the default form for at most 32 shots)")
+            T, Nc, H, d, m = state.dims
+            raise MlhotError(f"favor_query: topk= needs the cached kernels' envelope (Nc <= 32, d % 16 == 0, d <= 256, 16 <= m <= 1536), "
+                             f"got Nc={Nc} d={d} m={m}: mlhot_favor_fwd on the kept keys forms no per-shot weights")
     if mass:
         if weights:
             raise ValueError("favor_query: mass=True with weights=True - the mass exists so that w [T, H, Nq, Nc] is never stored; ask for one "
@@ -1096,6 +1125,8 @@ def favor_query(qh, state, vh, proj, weights=False, mask=None, mass=False, targe
     T, Nc, H, d, m = state.dims
     if tuple(vh.shape) != (T, Nc, H, d) or qh.dim() != 4 or (qh.shape[0], qh.shape[2], qh.shape[3]) != (T, H, d) or tuple(proj.shape) != (m, d):
         raise MlhotError(f"favor_query: the state was built for T={T} Nc={Nc} H={H} d={d} m={m}; got q {tuple(qh.shape)}, v {tuple(vh.shape)}, proj {tuple(proj.shape)}")
+    if topk is not None:
+        return lib().favor_query_topk_fwd(qh, state.buf, vh, proj, state.route, topk, lens=state.lens_dev)
     if mass:
         tw = target_weight_arg("favor_query", target_weight, T, qh.shape[1], qh.device)
         return lib().favor_query_mass_fwd(qh, state.buf, vh, proj, state.route, lens=state.lens_dev, tw=tw, fold=mass != "tiles")

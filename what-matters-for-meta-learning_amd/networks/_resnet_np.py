@@ -133,6 +133,8 @@ class _CachedContext:
         pass
 
     def predict_targets(self, state, qry_x, attention=False, mask_words=None, target_weight=None):
+        if isinstance(attention, tuple):     # ("topk", k) -> (mu, [idx, wk])
+            return self.model._predict_targets(state, qry_x.contiguous(), return_attention=attention)
         if attention == "mass":      # -> (mu, the tile partials of the attention mass)
             return self.model._predict_targets(state, qry_x.contiguous(), return_attention="mass", target_weight=target_weight)
         if mask_words is not None:
@@ -566,7 +568,8 @@ class ResNetNP(nn.Module):
             return self._heads(x_ctx[None], self._W_k)[0], self._heads(feats[None], self._W_v)[0]
         return self._latent_rows(feats)
 
-    def predict(self, state, batch_test_images, chunk=None, return_attention=False, context_mask=None, attention_mass=False, target_weight=None):
+    def predict(self, state, batch_test_images, chunk=None, return_attention=False, context_mask=None, attention_mass=False, target_weight=None,
+                top_k=None):
         """(ContextState, target images [T, Nq, ...]) -> mu [T, Nq, out] = `forward(ctx, labels, targets, test=True)[0]` for the
         context the state was made from, any Nq >= 1.  One run_trunks call does the target (attention models) and decoder passes;
         the query head projection, `_W`, `mu` and the decoder head go through mlhot.ops.linear_rows and the attention through
@@ -586,8 +589,14 @@ class ResNetNP(nn.Module):
         `attention_mass=True` -> (mu, mass): mass [T, heads, Nc slots] = attn summed over the targets, weighed by
         `target_weight` [T, Nq] (None: 1), reduced inside the favor_query launch so that attn is never stored; bit-equal to the
         documented fp32 fold of return_attention=True's attn, the same for every chunk that is a multiple of 16; mu has plain
-        predict's bits.  mlhot.cached.predict states the rest."""
-        return context.predict(_CachedContext(self), state, batch_test_images, chunk, return_attention, context_mask, attention_mass, target_weight)
+        predict's bits.  mlhot.cached.predict states the rest.
+
+        `top_k=k`, 1 <= k <= 16 -> (mu, idx, w), idx int32 and w fp32 [T, heads, Nq, k]: per head and target the k
+        heaviest context slots (by the un-normalised score, descending, ties to the lower slot) and their weights - attn's bits
+        there - selected inside the favor_query launch so that attn is never stored; -1 / 0 behind a task's shots; the same bits for
+        any chunk; mu has plain predict's bits.  mlhot.cached.predict states the rest."""
+        return context.predict(_CachedContext(self), state, batch_test_images, chunk, return_attention, context_mask, attention_mass, target_weight,
+                               top_k)
 
     def _predict_targets(self, state, batch_test_images, return_attention=False, mask_words=None, target_weight=None):
         self._refresh_arena()
@@ -617,7 +626,9 @@ class ResNetNP(nn.Module):
                     sample = _fold_linear([(sample, 1, 0)], self.mu, "none", G)
                     mu = self._fold_head(x_dec, sample, 1, G, Nq).transpose(0, 1).contiguous()
                     return (mu, attn) if return_attention else mu
-                if return_attention == "mass":
+                if isinstance(return_attention, tuple):
+                    merged, *attn = favor_query(qh, state.keys, state.vh, self.attn.projection_matrix, topk=return_attention[1])
+                elif return_attention == "mass":
                     merged, attn = favor_query(qh, state.keys, state.vh, self.attn.projection_matrix, mass="tiles", target_weight=target_weight)
                 elif return_attention:
                     merged, attn = favor_query(qh, state.keys, state.vh, self.attn.projection_matrix, weights=True)
