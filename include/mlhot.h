@@ -638,6 +638,36 @@ int mlhot_favor_query_paged_topk_fwd(const float* q, const void* state, const fl
                                      float* out, int k, int32_t* idx /* [T,H,Nq,k] */, float* wk /* [T,H,Nq,k] */,
                                      void* ws, size_t ws_bytes, void* stream);
 
+/* ---- shared targets: one set of query rows against every stored context (csrc/favor_shared.h) --------------------
+ * q[Nq,H,d] carries NO task axis: the same Nq rows are asked of all T tasks of the state.  mlhot_favor_query_shared_fwd serves a
+ * mlhot_favor_keys_fwd / _ragged_fwd state (Nc <= 32; no lens, like the entry it extends: a masked slot is a zero row of F_k and v is
+ * read there as mlhot_favor_query_fwd reads it - zero-fill it), mlhot_favor_query_long_shared_fwd a mlhot_favor_keys_long_fwd state
+ * (Nc <= 256, the SAME lens or NULL; rows n >= lens[t] of v are never read).  v[T,Nc,H,d], proj[m,d] as in the per-task entries.
+ * -> out[T,Nq,d*H] in mlhot_favor_fwd's merged order and, with w != NULL, w[T,H,Nq,Nc] = S / D as mlhot_favor_query_weights_fwd
+ *   defines it, columns n' >= lens[t] exactly 0.0f.  w == NULL means no read-out (unlike _weights_fwd: one entry serves both), and out
+ *   is BIT-EQUAL with and without it.  ONE launch for any Nq and T.
+ * A workgroup owns one (head, 16-row target tile) and a contiguous group of tasks: it forms the query features F_q ONCE - they read
+ *   the query row, proj and the row's own maximum, nothing of a task - keeps them in LDS and runs the per-task entry's own steps
+ *   against each task's F_k, lens[t] and v.  out and w are BIT-EQUAL to mlhot_favor_query_fwd / _weights_fwd / _long_fwd on q
+ *   replicated to [T,Nq,H,d], and carry their ROW-INVARIANCE guarantee.  No atomics; every store is a vector store.
+ * task_group: tasks per workgroup, held to 1 .. T; 0: the library picks it so that the grid ceil(T / task_group) H ceil(Nq / 16)
+ *   covers the 256 CUs about once.  A task's sums never see another task's: the bits of out and w do not depend on task_group.
+ * ws: mlhot_favor_query_shared_ws_bytes / _long_shared_ws_bytes (256, the token block: the kernels work in LDS alone - the per-task
+ *   kernels' 124 KB / 140 KB); 0 for a shape the entry does not serve.
+ * Envelope, alignment rules and error codes are those of the per-task entry each one extends (task_group < 0 is MLHOT_ERR_ARG); an
+ * unsupported shape returns MLHOT_ERR_UNSUPPORTED and writes nothing.  Forward only; GPU build only.  Added within ABI 8: bindings look the symbols up. */
+size_t mlhot_favor_query_shared_ws_bytes(int T, int H, int Nq, int Nc, int d, int m);
+size_t mlhot_favor_query_long_shared_ws_bytes(int T, int H, int Nq, int Nc, int d, int m);
+int mlhot_favor_query_shared_fwd(const float* q /* [Nq,H,d] */, const void* state, const float* v, const float* proj,
+                                 int T, int H, int Nq, int Nc, int d, int m, int task_group /* 0: the library's choice */,
+                                 float* out /* [T,Nq,d*H] */, float* w /* [T,H,Nq,Nc], or NULL */,
+                                 void* ws, size_t ws_bytes, void* stream);
+int mlhot_favor_query_long_shared_fwd(const float* q /* [Nq,H,d] */, const void* state, const float* v, const float* proj,
+                                      const int32_t* lens /* [T], device, or NULL */,
+                                      int T, int H, int Nq, int Nc, int d, int m, int task_group /* 0: the library's choice */,
+                                      float* out /* [T,Nq,d*H] */, float* w /* [T,H,Nq,Nc], or NULL */,
+                                      void* ws, size_t ws_bytes, void* stream);
+
 /* ---- cached contexts that let shots go: the per-shot rows moved by a plan (csrc/rows_compact.h) ------------------
  * mlhot_rows_compact: `sets` row sets, 1 <= sets <= 4, that share one plan.  Row set i is (src[i], dst[i], W[i]): fp32 rows of W[i]
  *   floats in [T][cap][W[i]]; src, dst and W are arrays of `sets` entries in HOST memory.  plan[T][cap] (int32, DEVICE memory, read by

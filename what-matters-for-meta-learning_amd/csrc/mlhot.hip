@@ -36,6 +36,7 @@
 #include "favor_paged.h"
 #include "favor_mass.h"
 #include "favor_topk.h"
+#include "favor_shared.h"
 #include "rows_compact.h"
 #include "rows_gather.h"
 #include "resnet_trunk.h"
@@ -461,6 +462,19 @@ int mlhot_favor_query_long_topk_fwd(const float* q, const void* state, const flo
 int mlhot_favor_query_paged_topk_fwd(const float* q, const void* state, const float* v, const float* proj, const int32_t* lens, int T, int H, int Nq,
                                      int Nc, int d, int m, float* out, int k, int32_t* idx, float* wk, void* ws, size_t ws_bytes, void* stream) {
   return favor_query_topk_launch("favor_query_paged_topk_fwd", 2, q, state, v, proj, lens, T, H, Nq, Nc, d, m, out, k, idx, wk, ws, ws_bytes, (hipStream_t)stream);
+}
+// shared targets: one set of query rows against every stored context, F_q formed once per (head, tile) (csrc/favor_shared.h)
+size_t mlhot_favor_query_shared_ws_bytes(int T, int H, int Nq, int Nc, int d, int m) { return favor_query_shared_ws_need(T, H, Nq, Nc, d, m); }
+size_t mlhot_favor_query_long_shared_ws_bytes(int T, int H, int Nq, int Nc, int d, int m) { return favor_query_long_shared_ws_need(T, H, Nq, Nc, d, m); }
+int mlhot_favor_query_shared_fwd(const float* q, const void* state, const float* v, const float* proj, int T, int H, int Nq, int Nc, int d, int m,
+                                 int task_group, float* out, float* w, void* ws, size_t ws_bytes, void* stream) {
+  return favor_query_shared_launch("favor_query_shared_fwd", false, q, state, v, proj, nullptr, T, H, Nq, Nc, d, m, task_group, out, w, ws, ws_bytes,
+                                   (hipStream_t)stream);
+}
+int mlhot_favor_query_long_shared_fwd(const float* q, const void* state, const float* v, const float* proj, const int32_t* lens, int T, int H, int Nq,
+                                      int Nc, int d, int m, int task_group, float* out, float* w, void* ws, size_t ws_bytes, void* stream) {
+  return favor_query_shared_launch("favor_query_long_shared_fwd", true, q, state, v, proj, lens, T, H, Nq, Nc, d, m, task_group, out, w, ws, ws_bytes,
+                                   (hipStream_t)stream);
 }
 // cached contexts that let shots go: the per-shot rows of up to 4 row sets moved by one plan, one launch (csrc/rows_compact.h)
 int mlhot_rows_compact(const float* const* src, float* const* dst, const int* W, int sets, const int32_t* plan, int T, int cap, void* stream) {

@@ -318,6 +318,11 @@ SIGNATURES = {
     "mlhot_favor_query_topk_fwd": (i, [P, P, P, P, i, i, i, i, i, i, P, i, P, P, P, z, P]),
     "mlhot_favor_query_long_topk_fwd": (i, [P, P, P, P, P, i, i, i, i, i, i, P, i, P, P, P, z, P]),
     "mlhot_favor_query_paged_topk_fwd": (i, [P, P, P, P, P, i, i, i, i, i, i, P, i, P, P, P, z, P]),
+    # shared targets: one set of query rows against every stored context
+    "mlhot_favor_query_shared_ws_bytes": (z, [i] * 6),
+    "mlhot_favor_query_long_shared_ws_bytes": (z, [i] * 6),
+    "mlhot_favor_query_shared_fwd": (i, [P, P, P, P, i, i, i, i, i, i, i, P, P, P, z, P]),
+    "mlhot_favor_query_long_shared_fwd": (i, [P, P, P, P, P, i, i, i, i, i, i, i, P, P, P, z, P]),
     # cached contexts that let shots go: the per-shot rows moved by a plan
     "mlhot_rows_compact": (i, [P, P, P, i, P, i, i, P]),
     # cached contexts joined or regrouped across states: per-shot rows gathered from several sources
@@ -1418,6 +1423,43 @@ class MlhotLib:
         head = (_ptr(q), _ptr(state), _ptr(v), _ptr(proj)) + (() if form == "cached" else (_ptr(lens),))
         self._rc(fn(*head, T, H, Nq, Nc, d, m, _ptr(out), k, _ptr(idx), _ptr(wk), _ptr(ws), ws.numel(), _stream(q)), "mlhot_" + what)
         return out, idx, wk
+
+    # ---- shared targets: one set of query rows against every stored context (csrc/favor_shared.h) ----
+    def favor_query_shared_fwd(self, q, state, v, proj, form, lens=None, weights=False, task_group=0):
+        """q [Nq,H,d] WITHOUT a task axis, a per-shot key state of `form` ("cached" | "long") for T tasks with its lens, v [T,Nc,H,d],
+        proj [m,d] -> out [T,Nq,d*H]; weights=True -> (out, w [T,H,Nq,Nc]).  ONE launch: the query features once per (head, 16 rows),
+        then the per-task entry's steps for each task of the workgroup's group of `task_group` tasks (0: the library picks).  out and
+        w have the bits of favor_query_fwd / _weights_fwd / _long_fwd on q expanded to [T,Nq,H,d], whatever task_group
+        (include/mlhot.h).  Forward only."""
+        what = {"cached": "favor_query_shared_fwd", "long": "favor_query_long_shared_fwd"}[form]
+        fn = self._fn(what, "mlhot_" + what)
+        if q.dtype != torch.float32 or q.dim() != 3:
+            raise MlhotError(f"{what}: q must be fp32 [Nq, H, d] - the targets are shared by the tasks - got {q.dtype} {tuple(q.shape)}")
+        if v.dtype != torch.float32 or v.dim() != 4:
+            raise MlhotError(f"{what}: v must be fp32 [T, Nc, H, d], got {v.dtype} {tuple(v.shape)}")
+        Nq, H, d = q.shape
+        T, Nc = v.shape[0], v.shape[1]
+        if tuple(v.shape) != (T, Nc, H, d) or proj.dtype != torch.float32 or proj.dim() != 2 or proj.shape[1] != d or Nq < 1:
+            raise MlhotError(f"{what}: q {tuple(q.shape)}, v {tuple(v.shape)}, proj {tuple(proj.shape)} do not fit together")
+        if any(t.device != q.device for t in (state, v, proj)):
+            raise MlhotError(f"{what}: q, state, v and proj must lie on one device")
+        if isinstance(task_group, bool) or not isinstance(task_group, int) or task_group < 0:
+            raise MlhotError(f"{what}: task_group must be an integer >= 0 (0: the library picks), got {task_group!r}")
+        self._long_lens(what, lens, T, q)
+        if form == "cached" and lens is not None:
+            raise MlhotError(f"{what}: a keys state carries its lens as zero rows of F_k; the entry takes none")
+        m = proj.shape[0]
+        nb = {"cached": self.favor_keys_bytes, "long": self.favor_keys_long_bytes}[form](T, H, Nc, d, m)
+        if not nb or state.dtype != torch.uint8 or state.numel() < nb:
+            raise MlhotError(f"{what}: the state is not this form's for T={T} H={H} Nc={Nc} d={d} m={m} "
+                             f"({state.numel()} bytes, {nb} needed; 0 = shape not served)")
+        _chk(q, v, proj, state, lens)
+        out = torch.empty(T, Nq, d * H, device=q.device)
+        w = torch.empty(T, H, Nq, Nc, device=q.device) if weights else None
+        ws = self._bytes(self._fn(what, "mlhot_" + what.replace("_fwd", "_ws_bytes"))(T, H, Nq, Nc, d, m), q)
+        head = (_ptr(q), _ptr(state), _ptr(v), _ptr(proj)) + (() if form == "cached" else (_ptr(lens),))
+        self._rc(fn(*head, T, H, Nq, Nc, d, m, task_group, _ptr(out), _ptr(w), _ptr(ws), ws.numel(), _stream(q)), "mlhot_" + what)
+        return (out, w) if weights else out
 
     def favor_mass_fold(self, part):
         """part [T,H,tiles,Nc] (the tile partials of favor_query_mass_fwd(fold=False), concatenated along the tile axis in target

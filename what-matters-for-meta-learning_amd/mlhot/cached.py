@@ -25,6 +25,8 @@
                                                                     # the targets inside the query launch, attn never stored (6c-14)
     state, drop = mlhot.cached.prune(model, state, qry_x, keep)     # keep[t] slots with the largest mass stay, the rest go through evict
     mu, idx, w = mlhot.cached.predict(model, state, qry_x, top_k=8) # [T, 8, Nq, k]: the k heaviest context slots per head and target (6c-15)
+    mu = mlhot.cached.predict(model, state, qry_x, shared_targets=True)   # qry_x [Nq, ...] without a task axis: one frame asked of all T
+                                                                    # stored contexts, encoded once, F_q formed once -> [T, Nq, y_dim] (6c-16)
     ok, reason = mlhot.cached.supports(model)
     mu = mlhot.cached.sweep(model, ctx_x, ctx_y, qry_x, ks=None, route=None)      # [len(ks), T, Nq, y_dim]: every context prefix (6b-2)
     ok, reason = mlhot.cached.supports_sweep(model)
@@ -228,6 +230,26 @@ class _Vanilla:
                              f"y_dim={self.dims.y_dim} m={self.dims.m_feat}); the composed route serves them")
         state.route = "fused_summary"
 
+    def route_shared(self, state, imgs):
+        """predict(shared_targets=True): the composed route, whose linear_rows sources broadcast the shared rows."""
+        if self.asked is not None and self.asked not in ROUTES:
+            raise ValueError(f"predict: route must be one of {ROUTES}, got {self.asked!r}")
+        if self.asked in ("fused", "fused_summary"):
+            raise ValueError(f'predict: shared_targets=True with route "{self.asked}" - the one-launch tails read one target set per task and '
+                             "stay as they are; shared targets run the composed route (linear_rows and favor_query(shared=True))")
+        _need_gpu(imgs)
+        self.dims = self.model._dims(state.Nc, 1)
+        state.route = "composed"
+
+    def predict_shared(self, state, imgs, attention=False):
+        model = self.model
+        x_qry = _encode(model, imgs)                 # [n, dim_w]: the n shared targets, once
+        params = {k: _c(p.detach()) for k, p in model.named_parameters()}
+        if state.kind != "attention":
+            return composed_tail(params, x_qry, state.T, imgs.shape[0], model.OUT_TANH, z=state.z, shared=True)
+        return composed_tail(params, x_qry, state.T, imgs.shape[0], model.OUT_TANH, keys=state.keys, vh=state.vh,
+                             proj=_c(model.attn.projection_matrix), wq=state.wq, weights=attention, shared=True)
+
     def predict_targets(self, state, qry_x, attention=False, mask_words=None, target_weight=None):
         model, T, Nq = self.model, qry_x.shape[0], qry_x.shape[1]
         x_qry = _encode(model, qry_x)
@@ -404,7 +426,7 @@ def select(model, states, picks):
 
 
 def predict(model, state, qry_x, chunk=None, route=None, return_attention=False, context_mask=None, attention_mass=False, target_weight=None,
-            top_k=None):
+            top_k=None, shared_targets=False):
     """(state, target images [T, Nq, ...]) -> mu [T, Nq, y_dim] = `model(ctx, labels, targets, test=True)[0]` for the context the
     state was made from, any Nq >= 1.  `chunk` bounds the targets per launch sequence (and the encoder's activations with them).
     `route`: None picks "fused" where mlhot_np_query_supported says yes and "composed" otherwise; a test may force either.  The
@@ -451,7 +473,28 @@ def predict(model, state, qry_x, chunk=None, route=None, return_attention=False,
     mu has the bits return_attention=True's mu has.  Slot indices are the state's slot order: after `evict` / `prune` / `concat`
     they refer to the new state's.  Served and routed exactly where return_attention=True is; summary, latent and empty states and
     models without attention refuse in its words; return_attention=True, context_mask= and attention_mass=True do not combine with
-    it; a forced "fused" / "fused_summary" route is a ValueError."""
+    it; a forced "fused" / "fused_summary" route is a ValueError.
+
+    `shared_targets=True`: `qry_x` is [Nq, ...] with NO task axis - one incoming frame or a set of probe images
+    asked of all T stored contexts - -> mu [T, Nq, y_dim] (and attn [T, 8, Nq, Nc slots] with return_attention=True).  The targets go
+    through the encoder (ResNetNP: the trunks) ONCE, as Nq images instead of T * Nq; the query-head Linear runs on Nq rows; the
+    attention is ONE launch that forms the FAVOR+ query features once per 16 targets for all tasks
+    (mlhot.ops.favor_query(shared=True)); only the Linears behind it see T * Nq rows, through linear_rows, whose sources
+    broadcast.  Against `predict` on `qry_x.expand(T, ...)` the result agrees to the kernels' tolerance (the attention itself to
+    the bit; the encoder's and the few-row Linears' bits may depend on the row count).  Served: per-shot states of form "keys" and
+    "long", latent states (z[t] against the shared rows) and empty states; the vanilla family runs the composed route.  `chunk`
+    bounds the targets per launch sequence; chunked equals unchunked to the bit.  Refused with ValueError before any launch:
+    `context_mask=`, `attention_mass=True`, `target_weight=`, `top_k=`, a "summary" or "paged" state, a `qry_x` that carries a
+    task axis, a forced "fused" / "fused_summary" route, and whatever plain predict refuses.  The default False is every call as
+    it was."""
+    if shared_targets:
+        if isinstance(model, ResNetNP):
+            if route is not None:
+                raise ValueError("predict: route= belongs to the vanilla family")
+            return model.predict(state, qry_x, chunk=chunk, return_attention=return_attention, context_mask=context_mask,
+                                 attention_mass=attention_mass, target_weight=target_weight, top_k=top_k, shared_targets=True)
+        return context.predict_shared(_Vanilla(model, route, return_attention), state, qry_x, chunk, return_attention, context_mask, attention_mass,
+                                      target_weight, top_k)
     if isinstance(model, ResNetNP):
         if route is not None:
             raise ValueError("predict: route= belongs to the vanilla family")
@@ -506,12 +549,19 @@ def _rows(sources, lin_w, lin_b, act):
     if (k0, k1, lin_w.shape[0]) not in _logged:
         _logged.add((k0, k1, lin_w.shape[0]))
         logging.getLogger(__name__).info("mlhot.cached.predict: no row-invariant kernel for a Linear [%d | %d] -> %d", k0, k1, lin_w.shape[0])
-    x = torch.cat([x.repeat_interleave(rep, dim=0) if rep > 1 else x for x, rep, _ in sources], dim=1)
+    rows = next(x.shape[0] * rep for x, rep, period in sources if period == 0)
+
+    def gathered(x, rep, period):                # a source that wraps before the last row (shared targets) is gathered by index
+        if period and period < rows:
+            idx = torch.arange(rows, device=x.device)
+            return x[(idx // rep) % period]
+        return x.repeat_interleave(rep, dim=0) if rep > 1 else x
+    x = torch.cat([gathered(*s) for s in sources], dim=1)
     return LinearFunction.apply(x, lin_w, lin_b, act)
 
 
 def composed_tail(params, x_qry, T, Nq, tanh, keys=None, vh=None, proj=None, z=None, wq=None, favor=None, prefixes=None, weights=False,
-                  target_weight=None):
+                  target_weight=None, shared=False):
     """The query tail from the existing row-invariant operators - the yardstick of the fused launch and the route for dimensions
     it does not serve.  params: state_dict key -> tensor; x_qry [T * Nq, dim_w]; attention: keys (FavorKeyState), vh, proj (wq: the
     stacked _W_q weight and bias, else stacked here); otherwise z [T, dim_z].  -> mu [T, Nq, y_dim].
@@ -522,9 +572,29 @@ def composed_tail(params, x_qry, T, Nq, tanh, keys=None, vh=None, proj=None, z=N
 
     `weights` (with `keys`, the default FAVOR+ stage): -> (mu, w), w [T, 8, Nq, Nc] from favor_query(weights=True); mu's bits stay.
     `weights="mass"`: -> (mu, part), the tile partials [T, 8, ceil(Nq / 16), Nc] of favor_query(mass="tiles",
-    target_weight=); mu's bits stay.  `weights=("topk", k)`: -> (mu, [idx, wk]) of favor_query(topk=k); mu's bits stay."""
+    target_weight=); mu's bits stay.  `weights=("topk", k)`: -> (mu, [idx, wk]) of favor_query(topk=k); mu's bits stay.
+
+    `shared=True`: x_qry is [Nq, dim_w], the encoder's rows of Nq targets shared by the T tasks.  The query-head
+    Linear runs on those Nq rows, the attention is favor_query(shared=True), and the Linears behind it run over the T * Nq rows
+    with x_qry wrapping every Nq.  With `keys` (weights False or True) or `z`; -> mu [T, Nq, y_dim] (and w [T, 8, Nq, Nc])."""
     def lin(sources, name, act="none"):
         return _rows(sources, params[name + ".weight"], params[name + ".bias"], act)
+    if shared:
+        att = None
+        if keys is not None:
+            w, b = wq if wq is not None else (torch.cat([params[f"_W_q.{i}.linear.weight"] for i in range(HEADS)]),
+                                              torch.cat([params[f"_W_q.{i}.linear.bias"] for i in range(HEADS)]))
+            qh = _rows([(x_qry, 1, 0)], w, b, "none").view(Nq, HEADS, -1)
+            merged = favor_query(qh, keys, vh, proj, weights=bool(weights), shared=True)
+            if weights:
+                merged, att = merged
+            zq = lin([(lin([(merged.view(T * Nq, -1), 1, 0)], "_W.linear"), 1, 0)], "r_to_z")
+            h = lin([(x_qry, 1, Nq), (zq, 1, 0)], "decoder0.0", "relu")
+        else:
+            h = lin([(x_qry, 1, Nq), (z, Nq, 0)], "decoder0.0", "relu")
+        h = lin([(h, 1, 0)], "decoder0.2", "relu")
+        mu = lin([(h, 1, 0)], "decoder0.4", "tanh" if tanh else "none").view(T, Nq, -1)
+        return (mu, att) if weights else mu
     K = 1 if prefixes is None else prefixes
     if keys is not None or favor is not None:
         w, b = wq if wq is not None else (torch.cat([params[f"_W_q.{i}.linear.weight"] for i in range(HEADS)]),

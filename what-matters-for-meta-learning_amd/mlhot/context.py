@@ -14,6 +14,8 @@ What differs per family comes in as an adapter `ad`, a small object with
     route(state, qry_x)                 predict's own checks and choices, behind the shared ones
     predict_targets(state, qry_x)       one launch sequence for the targets of one chunk -> mu [T, n, y_dim]; called with
                                         attention=True for predict(return_attention=True) -> (mu, attn [T, H, n, Nc])
+    route_shared(state, imgs)           route's part for predict(shared_targets=True)
+    predict_shared(state, imgs [n, C, H, W])        predict_targets for n targets WITHOUT a task axis, asked of all T tasks
 This module imports nothing from networks/: both families import it."""
 import numbers
 
@@ -581,6 +583,57 @@ def _refuse_topk(ad, state, top_k, return_attention, context_mask, attention_mas
     except ValueError as e:
         raise ValueError(str(e).replace("return_attention=True", "top_k=")) from None
     return k
+
+
+def _shared_images(model, qry_x):
+    """predict(shared_targets=True): qry_x [Nq, C, H, W] (or [Nq, H, W] for one channel) -> [Nq, C, H, W]; a tensor with a task axis,
+    or of another image shape, is a ValueError."""
+    C, H, W = model.img_channels, model.img_size[0], model.img_size[1]
+    if not isinstance(qry_x, torch.Tensor) or not (tuple(qry_x.shape[1:]) == (C, H, W) or (C == 1 and tuple(qry_x.shape[1:]) == (H, W))):
+        got = tuple(qry_x.shape) if isinstance(qry_x, torch.Tensor) else type(qry_x).__name__
+        raise ValueError(f"predict: shared_targets=True takes qry_x [Nq, {C}, {H}, {W}] with no task axis - the same targets are asked of "
+                         f"every task of the state - got {got}; targets of their own per task go through the call without shared_targets")
+    return qry_x.reshape(qry_x.shape[0], C, H, W)
+
+
+def predict_shared(ad, state, qry_x, chunk=None, return_attention=False, context_mask=None, attention_mass=False, target_weight=None, top_k=None):
+    """predict(shared_targets=True): (state, target images [Nq, ...] WITHOUT a task axis) -> mu [T, Nq, y_dim], the
+    prediction of every stored context of the state for the same Nq targets; return_attention=True -> (mu, attn [T, H, Nq, Nc slots]).
+    The targets go through the encoder / the trunks ONCE, as Nq images, the query-head Linear runs on Nq rows and the attention is
+    ONE launch that forms the query features once per 16 targets for all tasks (mlhot.ops.favor_query(shared=True)); only the
+    Linears behind it see T * Nq rows, through linear_rows, whose sources broadcast.  Latent and empty states are served: z[t]
+    against the shared target rows.  Per-shot states "keys" and "long".  Every refusal is a ValueError before any launch."""
+    what = "predict"
+    _own(ad, what, state)
+    for on, name in ((context_mask is not None, "context_mask="), (attention_mass, "attention_mass=True"), (target_weight is not None, "target_weight="),
+                     (top_k is not None, "top_k=")):
+        if on:
+            raise ValueError(f"predict: shared_targets=True with {name} - the shared-target launch forms the plain read-out alone (mu, and attn "
+                             "with return_attention=True); masks, the attention mass and the top-k run on per-task targets: expand qry_x "
+                             "to [T, Nq, ...] and call without shared_targets")
+    if state.form in ("summary", "paged"):
+        raise ValueError(f'predict: shared_targets=True serves per-shot states of form "keys" and "long" and latent states; this state is a '
+                         f'{state.form!r} state, for which no shared-target kernel is built - expand qry_x to [T, Nq, ...] and call '
+                         "without shared_targets")
+    if state.kind == "attention" and state.keys.route not in ("cached", "long"):
+        raise ValueError("predict: shared_targets=True needs the cached kernels' envelope (Nc <= 32 or form=\"long\", d % 16 == 0, d <= 256, "
+                         f"16 <= m <= 1536); this state's keys are kept {state.keys.route!r} (T, Nc, H, d, m = {state.keys.dims})")
+    imgs = _shared_images(ad.model, qry_x)
+    Nq = imgs.shape[0]
+    if Nq < 1:
+        raise ValueError("predict needs at least one target")
+    if chunk is not None and int(chunk) < 1:
+        raise ValueError(f"predict: chunk must be a positive number of targets, got {chunk}")
+    if return_attention:
+        _refuse_attention(ad, state)
+    ad.route_shared(state, imgs)
+    step = Nq if chunk is None else min(int(chunk), Nq)
+    with torch.no_grad():
+        if return_attention:
+            out, att = zip(*[ad.predict_shared(state, imgs[i:i + step], attention=True) for i in range(0, Nq, step)])
+            return (out[0], att[0]) if len(out) == 1 else (torch.cat(out, dim=1), torch.cat(att, dim=2))
+        out = [ad.predict_shared(state, imgs[i:i + step]) for i in range(0, Nq, step)]
+    return out[0] if len(out) == 1 else torch.cat(out, dim=1)
 
 
 def predict(ad, state, qry_x, chunk=None, return_attention=False, context_mask=None, attention_mass=False, target_weight=None, top_k=None):

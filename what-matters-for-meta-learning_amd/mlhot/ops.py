@@ -1024,7 +1024,36 @@ def topk_arg(what, k, name="top_k", exc=ValueError):
     return int(k)
 
 
-def favor_query(qh, state, vh, proj, weights=False, mask=None, mass=False, target_weight=None, topk=None):
+SHARED_ROUTES = ("cached", "long")                 # the states the shared-target query serves (csrc/favor_shared.h)
+
+
+def _favor_query_shared(qh, state, vh, proj, weights, mask, mass, target_weight, topk, task_group):
+    """favor_query(shared=True): the refusals, all on the host, then mlhot_favor_query_shared_fwd / _long_shared_fwd."""
+    for on, name in ((mask is not None, "mask="), (bool(mass), "mass="), (target_weight is not None, "target_weight="), (topk is not None, "topk=")):
+        if on:
+            raise MlhotError(f"favor_query: shared=True with {name} - the shared-target launch forms the plain read-out alone (out, and w "
+                             "with weights=True); expand the query rows to [T, Nq, H, d] and call without shared=True")
+    if not isinstance(state, FavorKeyState):
+        raise MlhotError("favor_query: state must come from favor_keys")
+    if state.route not in SHARED_ROUTES:
+        why = {"plain": "its keys lie outside the cached kernels' envelope and mlhot_favor_fwd takes one query set per task",
+               "summary": "it keeps sums over shots, and mlhot_favor_summary_query_fwd takes one query set per task",
+               "paged": "its query walks pages of 256 slots (csrc/favor_paged.h), for which no shared-target kernel is built"}.get(state.route, "")
+        raise MlhotError(f"favor_query: shared=True serves \"cached\" and \"long\" states; this state's route is {state.route!r} - {why}")
+    if isinstance(task_group, bool) or not isinstance(task_group, numbers.Integral) or task_group < 0:
+        raise MlhotError(f"favor_query: task_group must be an integer >= 0 (0: the library picks), got {task_group!r}")
+    _forward_only("favor_query", qh, vh, proj)
+    _need_gpu(qh, vh, proj)
+    qh, vh, proj = _c(qh.detach()), _c(vh.detach()), _c(proj.detach())
+    T, Nc, H, d, m = state.dims
+    if tuple(vh.shape) != (T, Nc, H, d) or qh.dim() != 3 or tuple(qh.shape[1:]) != (H, d) or tuple(proj.shape) != (m, d):
+        raise MlhotError(f"favor_query: shared=True takes q [Nq, H={H}, d={d}] without a task axis against the state built for T={T} Nc={Nc} "
+                         f"m={m}; got q {tuple(qh.shape)}, v {tuple(vh.shape)}, proj {tuple(proj.shape)}")
+    return lib().favor_query_shared_fwd(qh, state.buf, vh, proj, state.route, lens=state.lens_dev if state.route == "long" else None,
+                                        weights=bool(weights), task_group=int(task_group))
+
+
+def favor_query(qh, state, vh, proj, weights=False, mask=None, mass=False, target_weight=None, topk=None, shared=False, task_group=0):
     """FAVOR+ attention of q [T, Nq, H, d] against a favor_keys state and v [T, Nc, H, d] -> merged [T, Nq, d*H], any Nq >= 1 in
     one launch.  On the "cached" route the bits of a row do not depend on the other rows of the call (csrc/favor_cached.h), nor on
     the "long" route (favor_keys_long, csrc/favor_long.h: up to 256 slots in chunks of 32, weights=True included); the
@@ -1061,7 +1090,19 @@ def favor_query(qh, state, vh, proj, weights=False, mask=None, mass=False, targe
     `weights=True` stores into w[t, h, n, idx] - selected INSIDE the query launch (mlhot_favor_query_topk_fwd / _long_topk_fwd /
     _paged_topk_fwd), the paged form in its ONE walk over the pages; w is never stored.  Entries behind the task's valid slots are
     idx = -1, wk = +0.  merged has the plain call's bits; every row's result is its own.  "cached", "long" and "paged" states,
-    refused where `weights=True` is; exclusive with `weights=True`, `mask=` and `mass=`."""
+    refused where `weights=True` is; exclusive with `weights=True`, `mask=` and `mass=`.
+
+    `shared=True`: q is [Nq, H, d] WITHOUT a task axis - one frame, or one set of probe rows, asked of all T stored
+    contexts of the state -> merged [T, Nq, d*H] (and w [T, H, Nq, Nc] with weights=True) in ONE launch
+    (mlhot_favor_query_shared_fwd / _long_shared_fwd): the query features are formed once per (head, 16 rows) instead of once per
+    task, then the per-task kernel's own steps run against every task of the workgroup's group.  The bits are those of the call
+    on `q.expand(T, ...)`.  `task_group`: tasks per workgroup (0: the library picks so the grid covers the CUs about once); the
+    bits do not depend on it.  "cached" and "long" states only - a "plain", "summary" or "paged" state raises MlhotError naming the
+    state's route - and `mask=`, `mass=` and `topk=` do not combine with it.  Without it the call is the one it always was."""
+    if shared:
+        return _favor_query_shared(qh, state, vh, proj, weights, mask, mass, target_weight, topk, task_group)
+    if task_group != 0:
+        raise MlhotError("favor_query: task_group= groups the tasks of shared=True; without it every workgroup serves one task")
     if topk is not None:
         topk = topk_arg("favor_query", topk, "topk")
         for on, name, why in ((weights, "weights=True", "the top-k exists so that w [T, H, Nq, Nc] is never stored; ask for one of the two"),

@@ -132,6 +132,12 @@ class _CachedContext:
     def route(self, state, qry_x):
         pass
 
+    def route_shared(self, state, imgs):
+        pass
+
+    def predict_shared(self, state, imgs, attention=False):
+        return self.model._predict_shared(state, imgs.contiguous(), return_attention=bool(attention))
+
     def predict_targets(self, state, qry_x, attention=False, mask_words=None, target_weight=None):
         if isinstance(attention, tuple):     # ("topk", k) -> (mu, [idx, wk])
             return self.model._predict_targets(state, qry_x.contiguous(), return_attention=attention)
@@ -569,7 +575,7 @@ class ResNetNP(nn.Module):
         return self._latent_rows(feats)
 
     def predict(self, state, batch_test_images, chunk=None, return_attention=False, context_mask=None, attention_mass=False, target_weight=None,
-                top_k=None):
+                top_k=None, shared_targets=False):
         """(ContextState, target images [T, Nq, ...]) -> mu [T, Nq, out] = `forward(ctx, labels, targets, test=True)[0]` for the
         context the state was made from, any Nq >= 1.  One run_trunks call does the target (attention models) and decoder passes;
         the query head projection, `_W`, `mu` and the decoder head go through mlhot.ops.linear_rows and the attention through
@@ -594,9 +600,57 @@ class ResNetNP(nn.Module):
         `top_k=k`, 1 <= k <= 16 -> (mu, idx, w), idx int32 and w fp32 [T, heads, Nq, k]: per head and target the k
         heaviest context slots (by the un-normalised score, descending, ties to the lower slot) and their weights - attn's bits
         there - selected inside the favor_query launch so that attn is never stored; -1 / 0 behind a task's shots; the same bits for
-        any chunk; mu has plain predict's bits.  mlhot.cached.predict states the rest."""
+        any chunk; mu has plain predict's bits.  mlhot.cached.predict states the rest.
+
+        `shared_targets=True`: the target images are [Nq, ...] with NO task axis and are asked of all T stored
+        contexts -> mu [T, Nq, out] (and attn [T, heads, Nq, Nc slots]).  The target and decoder trunk passes run ONCE on the Nq
+        images, the query head projection on Nq rows, the attention is one favor_query(shared=True) launch, and only the few-row
+        Linears behind it (`_W`, `mu`, the decoder head) see T * Nq rows, the decoder features wrapping every Nq.  State forms
+        "keys" and "long", latent and empty states; masks, the attention mass and top-k refuse.  mlhot.cached.predict states the
+        rest."""
+        if shared_targets:
+            return context.predict_shared(_CachedContext(self), state, batch_test_images, chunk, return_attention, context_mask, attention_mass,
+                                          target_weight, top_k)
         return context.predict(_CachedContext(self), state, batch_test_images, chunk, return_attention, context_mask, attention_mass, target_weight,
                                top_k)
+
+    def _predict_shared(self, state, imgs, return_attention=False):
+        """_predict_targets for n target images [n, C, H, W] WITHOUT a task axis, asked of all T tasks: the trunk
+        passes and the query head projection see the n images once; favor_query(shared=True) answers for every task; `_W`, `mu` and
+        the decoder head run over the T * n rows, the decoder features wrapping every n.  -> mu [T, n, out] (and attn)."""
+        self._refresh_arena()
+        with torch.no_grad():
+            T, Nq = self.task_num, imgs.shape[0]
+            attend = state.kind == "attention"
+            jobs = ([self.img_encoder.trunk_job(imgs)] if attend else []) + [self.decoder.trunk_job(imgs)]
+            maps = run_trunks(jobs)
+            if maps is None:            # no weight-stationary kernels for this image size: the per-operator route
+                enc = self.img_encoder
+                dec_map = self.decoder.resnet.trunk(run_conv(self.decoder.conv1, imgs, relu=True), None)
+                enc_map = enc.resnet.trunk(run_conv(enc.conv1, imgs, relu=True), enc._taps()) if attend else None
+            else:
+                dec_map, enc_map = maps[-1], maps[0] if attend else None
+            # the encoder's features as rows [n, F]: ImageEncoder.features would fold them into [T, N, F], and n is no multiple of T
+            x_tgt = _aggregate_feature_map(enc_map, self.img_encoder.aggregate) if attend else None
+            x_dec = _aggregate_feature_map(dec_map, self.decoder.aggregate).reshape(Nq, -1)
+            fc = self.decoder.fc_mu
+
+            def head(sample, rep):
+                h = _fold_linear([(x_dec, 1, Nq), (sample, rep, 0)], fc[0], "relu", 1)
+                h = _fold_linear([(h, 1, 0)], fc[2], "relu", 1)
+                return _fold_linear([(h, 1, 0)], fc[4], "none", 1).view(T, Nq, -1)
+            if attend:
+                w, b = self._stack(self._W_q).tensors()
+                qh = _fold_linear([(x_tgt.reshape(Nq, -1), 1, 0)], _Stacked(w, b), "none", 1).view(Nq, self.N_HEADS, -1)
+                res = favor_query(qh, state.keys, state.vh, self.attn.projection_matrix, weights=return_attention, shared=True)
+                merged, attn = res if return_attention else (res, None)
+                sample = _fold_linear([(merged.reshape(T * Nq, -1), 1, 0)], self._W.linear, "none", 1)
+                sample = _fold_linear([(sample, 1, 0)], self.mu, "none", 1)
+                mu = head(sample, 1)
+                return (mu, attn) if return_attention else mu
+            if state.kind == "latent":
+                return head(state.z, Nq)
+            return head(torch.zeros(T * Nq, 256, device=imgs.device), 1)
 
     def _predict_targets(self, state, batch_test_images, return_attention=False, mask_words=None, target_weight=None):
         self._refresh_arena()
